@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the mvlm predict_one_file hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   N > 1, either form: `python bench.py --gpus N ...` alone starts its N ranks itself (fresh child processes under
   torch.distributed.run; the parent never touches the GPU and relays rank 0's JSON line), or an external
   `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...` (RANK set) runs as a rank.
@@ -18,8 +18,14 @@ With N GPUs the SAME 96 views are sharded 96/N per rank (strong scaling - BASELI
 before fusion; `--scaling weak` keeps 96 views per GPU instead.  Other BASELINE configurations:
 `--config dtu3d-rgb-64 | bu3dfe-depth-8 | dtu3d-geomdepth-96 | mediapipe-478x128`.
 
-roofline.traffic (HBM bytes per launch of the dominant kernel) is measured by the N = 1 invocation itself with three short
-rocprofv3 --pmc child passes after the timed region (each at most 90 s, 150 s together; the timed result is logged first) (live_counters: HBM bytes and MFMA-busy of the dominant kernel); --no-live-traffic / MVLM_BENCH_LIVE_TRAFFIC=0 quote the
+A plain run sets up, warms up, times the K steps and prints the line: `value` (views/s), `ms_per_step`, `dtype`.
+--dump-outputs DIR then writes what the last timed step returned (dump_outputs).  Everything else the line can carry
+is measured only with --full, after the timed region: per-kernel HIP events over K more steps (`roofline`,
+`roofline_rasteriser`), the opt-in fast precisions, ingest from disk, the CPU baseline and, at N > 1, `scaling_breakdown`.
+
+With --full, roofline.traffic (HBM bytes per launch of the dominant kernel) is measured by the N = 1 invocation itself with
+three short rocprofv3 --pmc child passes after the timed region (each at most 90 s, 150 s together; the timed result is logged
+first) (live_counters: HBM bytes and MFMA-busy of the dominant kernel); --no-live-traffic / MVLM_BENCH_LIVE_TRAFFIC=0 quote the
 committed profiles/rNN_traffic.json instead.
 
 Rank 0 prints ONE JSON line on stdout; everything else goes to stderr.
@@ -242,7 +248,7 @@ def live_counters(variant_name: str | None, argv: list[str]):
         out = tempfile.mkdtemp(prefix="mvlm_pmc_", dir="/tmp")
         env = dict(os.environ, MVLM_BENCH_NO_INGEST="1", MVLM_BENCH_CHILD="1", TMPDIR="/tmp")
         cmd = [exe, "--pmc", *counters, "--kernel-trace", "--output-format", "csv", "-d", out, "--", sys.executable,
-               str(Path(__file__).resolve())] + argv + ["--steps", "1", "--warmup", "0", "--cpu-views", "0", "--no-fast-mode"]
+               str(Path(__file__).resolve())] + argv + ["--steps", "1", "--warmup", "0", "--cpu-views", "0", "--no-fast-mode", "--full"]
         # A pass takes ~3 s; the timed result exists already and must not be lost to a stalled profiler: each pass gets at most
         # PASS_LIMIT seconds and all of them together BUDGET.  rocprofv3 and the python under it run in a session of their
         # own, so that a timeout ends BOTH (killing rocprofv3 alone would leave its python holding the GPU).
@@ -297,6 +303,16 @@ def live_counters(variant_name: str | None, argv: list[str]):
         gui = dom.get("GRBM_GUI_ACTIVE", 0.0) / 8
         res["mfma_busy"] = round(dom.get("SQ_VALU_MFMA_BUSY_CYCLES", 0.0) / (gui * 1024), 4) if gui > 0 else None
     return res
+
+
+def dump_outputs(directory: str, landmarks, error) -> None:
+    """--dump-outputs: what a caller of the timed path receives from its last step - predict_mesh_device's landmarks
+    [NL, 3] (in the mesh's own coordinates) and its mean RANSAC error - as float64 .npy files (a few KB)."""
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "landmarks.npy", np.asarray(landmarks, dtype=np.float64))
+    np.save(d / "ransac_error.npy", np.asarray([error], dtype=np.float64))
+    log(f"outputs of the last timed step written to {d}/: landmarks.npy {np.shape(landmarks)}, ransac_error.npy")
 
 
 def visible_gpus() -> int:
@@ -468,7 +484,14 @@ def main():
                     help="heatmap maxima (paulsenpredictor.py:112-158): the argmax pixel (default) or the 31x31 centroid around it - both fused")
     ap.add_argument("--cnn-execution", default="", help=argparse.SUPPRESS)  # "graphs,concurrency" for experiments, e.g. "1,0"
     ap.add_argument("--cpu-views", type=int, default=-1, help="views in the CPU-baseline sample (-1 = the whole workload, at most 96; 0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure per-kernel figures and rooflines, rocprofv3 counters, the opt-in "
+                         "fast precisions, ingest, the CPU baseline and (N > 1) the scaling breakdown")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # started as a plain process: the N ranks are this process's children; it never touches the GPU itself
@@ -664,7 +687,7 @@ def main():
     step_marks = [] if os.environ.get("MVLM_BENCH_STEP_TIMES") else None  # diagnostic: host time at the end of every timed step
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
         if profile_in_timed:
             collect()
         if step_marks is not None:
@@ -675,17 +698,19 @@ def main():
     if step_marks and rank == 0:
         log("timed steps, ms between their returns: " + " ".join(f"{1e3 * (b - a):.2f}" for a, b in zip([t0] + step_marks, step_marks))
             + f"; final wait {1e3 * (t0 + elapsed - step_marks[-1]):.2f}")
-    if not profile_in_timed and rank == 0:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last)
+    if args.full and not profile_in_timed and rank == 0:
         set_profiling(1)
-    if sharded:
+    if args.full and sharded:
         parallel.enable_timing(True)  # the all-gather and the draws broadcast of the steps below, per rank
-    if not profile_in_timed:
+    if args.full and not profile_in_timed:
         for _ in range(args.steps):  # every rank joins (collectives inside a step), rank 0 records
             step()
             if rank == 0:
                 collect()
     set_profiling(0)
-    collectives = parallel.timing_summary() if sharded else None
+    collectives = parallel.timing_summary() if args.full and sharded else None
     if sharded:
         parallel.enable_timing(False)
     # the same shard WITHOUT the sharded path (no collectives, this rank draws for itself), timed on rank 0 while the other
@@ -693,7 +718,7 @@ def main():
     # efficiency into "smaller batch per GPU" (single_gpu_shard_ms x N against the N = 1 step) and "cost of sharding"
     # (this rank's ms_per_step against single_gpu_shard_ms)
     single_gpu_shard_ms = None
-    if sharded and world > 1:
+    if args.full and sharded and world > 1:
         barrier()
         if rank == 0 and hi > lo:
             pipe.shard_views = False
@@ -720,7 +745,7 @@ def main():
 
     # ---- opt-in "fast" precision (bf16x3 split, mvlm_amd/csrc/conv_fast.hip): a separate figure, never `value` ----------
     fast_mode = fast16_mode = None
-    if not sharded and not fusion_only and not args.no_fast_mode:
+    if args.full and not sharded and not fusion_only and not args.no_fast_mode:
         p2 = pipe.predictor_2d
         lm_exact, _ = step()
         images = pipe._buffers["images"]
@@ -804,7 +829,7 @@ def main():
         live = None
         # (not when this process itself runs under a profiler: its preloaded tool library would be inherited by the children)
         profiled = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
-        if (world == 1 and not args.no_live_traffic and not os.environ.get("MVLM_BENCH_CHILD") and args.precision == "exact"
+        if (args.full and world == 1 and not args.no_live_traffic and not os.environ.get("MVLM_BENCH_CHILD") and args.precision == "exact"
                 and os.environ.get("MVLM_BENCH_LIVE_TRAFFIC", "1") != "0" and not profiled):
             child_args = ["--config", args.config, "--device-batch", str(args.device_batch), "--selection", args.selection]
             if args.views_total:
@@ -860,11 +885,11 @@ def main():
             roof, roof_r = roof_r, None
         log("stage seconds (last step):", {k: round(v, 5) for k, v in pipe.timings.items()})
         ingest = None
-        if not sharded and not fusion_only and not os.environ.get("MVLM_BENCH_NO_INGEST"):
+        if args.full and not sharded and not fusion_only and not os.environ.get("MVLM_BENCH_NO_INGEST"):
             ingest = ingest_figures(pipe, n_total)
         cpu = None
         n_cpu = min(n_total, 96) if args.cpu_views < 0 else min(args.cpu_views, n_total)
-        if n_cpu > 0 and not fusion_only and world == 1:  # the CPU baseline belongs to the N = 1 line only
+        if args.full and n_cpu > 0 and not fusion_only and world == 1:  # the CPU baseline belongs to the N = 1 line only
             sd = weights.synthetic_state_dict(nl, c, seed=0)
             cpu = cpu_baseline(mesh, poses, sd, arch.CHANNEL_SELECT[cfg.image_channels], n_cpu, n_total,
                                shading="geometry" if "geometry" in cfg.image_channels else "texture")
@@ -896,8 +921,9 @@ def main():
             "roofline": roof,
             "roofline_rasteriser": roof_r,
             "kernel_events": "HIP events live over the timed steps" if profile_in_timed else
-                             "HIP events over the same number of steps run right after the timed region (timed steps = product path, replayed launch graphs)",
-            "scaling_breakdown": None if not sharded else {
+                             "HIP events over the same number of steps run right after the timed region (timed steps = product path, replayed launch graphs)"
+                             if args.full else None,
+            "scaling_breakdown": None if not (args.full and sharded) else {
                 "per_rank_ms_per_step": {"min": round(min(per_rank_ms), 3), "max": round(max(per_rank_ms), 3),
                                          "all": [round(v, 3) for v in per_rank_ms]},
                 "all_gather_ms_per_step": None if collectives["all_gather"]["mean_ms"] is None else round(collectives["all_gather"]["mean_ms"], 4),

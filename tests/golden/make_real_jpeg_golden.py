@@ -28,7 +28,8 @@ def main():
         (OUT / f"{name}.jpg").chmod(0o644)
         rgb = np.asarray(Image.open(OUT / f"{name}.jpg").convert("RGB"))
         expected[name] = {"height": int(rgb.shape[0]), "width": int(rgb.shape[1]), "file_bytes": (OUT / f"{name}.jpg").stat().st_size,
-                          "sha256_rgb": hashlib.sha256(rgb.tobytes()).hexdigest()}
+                          "sha256_rgb": hashlib.sha256(rgb.tobytes()).hexdigest(),
+                          "sha256_file": hashlib.sha256((OUT / f"{name}.jpg").read_bytes()).hexdigest()}
         print(name, expected[name])
     (OUT / "expected.json").write_text(json.dumps(expected, indent=1) + "\n")
 

@@ -375,7 +375,7 @@ def test_bench_starts_its_own_ranks():
     over RCCL."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--cpu-views", "0", "--no-fast-mode", "--views-total", "16"],
+                        "--cpu-views", "0", "--no-fast-mode", "--views-total", "16", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=str(REPO),
                        env=dict(env, MVLM_BENCH_SHARE_GPU="1", MVLM_BENCH_NO_INGEST="1"))
     assert r.returncode == 0, r.stderr[-3000:]
@@ -402,3 +402,31 @@ def test_bench_refuses_more_gpus_than_visible():
                        capture_output=True, text=True, timeout=300, cwd=str(REPO), env=env)
     assert r.returncode != 0 and r.stdout.strip() == ""
     assert f"needs {n} visible GPUs" in r.stderr
+
+
+def test_plain_bench_run_dumps_its_last_timed_step(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full: the line carries the headline figures and none of
+    the extra measurements, and DIR holds the last timed step's landmarks and RANSAC error - the same arrays whatever the
+    step counts, so that two builds can be compared output for output."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MVLM_BENCH_SHARE_GPU")}
+    got = []
+    for steps, warmup in ((2, 1), (3, 0)):
+        out = tmp_path / f"out{steps}"
+        r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                            "--views-total", "8", "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=600, cwd=str(REPO), env=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout
+        rec = json.loads(lines[0])
+        assert rec["steps"] == steps and rec["warmup"] == warmup and rec["unit"] == "views/s" and rec["dtype"] == "f32"
+        assert rec["value"] == pytest.approx(8 * 1e3 / rec["ms_per_step"], rel=1e-2)
+        for key in ("roofline", "roofline_rasteriser", "kernel_events", "fast_mode", "fast16_mode", "cpu_baseline", "with_ingest",
+                    "scaling_breakdown"):
+            assert rec[key] is None, key
+        assert sorted(f.name for f in out.iterdir()) == ["landmarks.npy", "ransac_error.npy"]
+        lm, err = np.load(out / "landmarks.npy"), np.load(out / "ransac_error.npy")
+        assert lm.dtype == np.float64 and lm.shape == (84, 3) and np.isfinite(lm).all()
+        assert err.dtype == np.float64 and err.shape == (1,) and np.isfinite(err).all()
+        got.append((lm, err))
+    assert np.array_equal(got[0][0], got[1][0]) and np.array_equal(got[0][1], got[1][1])

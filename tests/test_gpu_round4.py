@@ -184,7 +184,7 @@ def test_bench_two_ranks_over_rccl():
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "MVLM_BENCH_SHARE_GPU")}
     r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--cpu-views", "0",
-                        "--no-fast-mode", "--views-total", "24"], capture_output=True, text=True, timeout=900, cwd=str(REPO),
+                        "--no-fast-mode", "--views-total", "24", "--full"], capture_output=True, text=True, timeout=900, cwd=str(REPO),
                        env=dict(env, MVLM_BENCH_NO_INGEST="1"))
     assert r.returncode == 0, r.stderr[-3000:]
     rec = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])

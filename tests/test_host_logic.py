@@ -249,15 +249,13 @@ def test_config_parser(tmp_path, dataset, mode, nl, c):
 
 def test_config_parser_reads_reference_files_when_present():
     """Every configs/*.json of the reference parses, and ``default_config(<stem>)`` reproduces each file's inference
-    keys one by one (view count, batch size, line filter, pose ranges, pre-align block, write_renderings)."""
+    keys one by one (view count, batch size, line filter, pose ranges, pre-align block, write_renderings).
+    The reference's 17 files are committed unchanged as data under tests/golden/reference_configs/."""
     import dataclasses
 
     from mvlm_amd import config
 
-    ref = Path("/root/reference/configs")
-    if not ref.exists():
-        pytest.skip("reference checkout not present")
-    files = sorted(ref.glob("*.json"))
+    files = sorted((REPO / "tests" / "golden" / "reference_configs").glob("*.json"))
     assert sorted(f.stem for f in files) == sorted(config.REFERENCE_CONFIGS)
     for f in files:
         cfg = config.load_config(f)
@@ -621,3 +619,14 @@ def test_bench_parent_refuses_without_enough_gpus():
                        capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 2 and r.stdout.strip() == ""
     assert "needs 2 visible GPUs" in r.stderr
+
+
+def test_bench_refuses_a_run_without_timed_steps():
+    """`--steps` is the number of timed steps that `ms_per_step` divides by: fewer than one is refused before any set-up."""
+    import subprocess
+    import sys
+
+    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "1", "--steps", "0", "--warmup", "0"],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and r.stdout.strip() == ""
+    assert "--steps must be at least 1" in r.stderr

@@ -3,7 +3,7 @@ tests/golden/jpeg/real/, tests/golden/make_real_jpeg_golden.py) - the only real 
 vtkJPEGReader path (src/mvlm/utils/utils3d.py:26-36).  Not written by Pillow's encoder, 3496 x 2275 ... 3562 x 2359, 4:2:0,
 2.2 MB of entropy-coded data without restart markers.
 
-CPU: oracle/jpeg.py == libjpeg-turbo (Pillow) on every one of them (all 15 where /root/reference exists, else the three).
+CPU: oracle/jpeg.py == libjpeg-turbo (Pillow) on each of the three committed files.
 -m gpu: the device decoder byte for byte, and the rasteriser with such a 24 MB non-power-of-two texture."""
 import ctypes as C
 import hashlib
@@ -21,7 +21,6 @@ from conftest import GOLDEN
 
 REAL = GOLDEN / "jpeg" / "real"
 EXPECTED = json.loads((REAL / "expected.json").read_text())
-REFERENCE = Path("/root/reference/assets/Normal-Emotion")
 
 
 def _pillow(data):
@@ -41,8 +40,8 @@ def _oracle_equals_pillow(path: str):
 
 
 def test_oracle_decodes_the_reference_textures_like_libjpeg():
-    files = sorted(REFERENCE.glob("*.jpg")) if REFERENCE.is_dir() else sorted(REAL.glob("*.jpg"))
-    assert len(files) in (15, 3)
+    files = sorted(REAL.glob("*.jpg"))
+    assert sorted(f.stem for f in files) == sorted(EXPECTED) and len(files) == 3
     workers = max(1, min(8, len(os.sched_getaffinity(0)), len(files)))      # ~18 s of pure-Python entropy decoding per file
     with ProcessPoolExecutor(workers) as pool:
         results = list(pool.map(_oracle_equals_pillow, [str(f) for f in files]))
@@ -56,8 +55,7 @@ def test_committed_textures_are_the_reference_files():
     for name, e in EXPECTED.items():
         data = (REAL / f"{name}.jpg").read_bytes()
         assert len(data) == e["file_bytes"]
-        if REFERENCE.is_dir():
-            assert data == (REFERENCE / f"{name}.jpg").read_bytes()
+        assert hashlib.sha256(data).hexdigest() == e["sha256_file"]                          # the reference's file, unchanged
         assert b"\xff\xc0" in data and b"\xff\xc2" not in data[:data.index(b"\xff\xda")]      # baseline, one scan
         assert not any(bytes([0xFF, 0xD0 + k]) in data for k in range(8))                       # no restart markers
 

@@ -13,15 +13,15 @@ mkdir -p $OUT
 cd $ROOT
 if [[ $PART == *a* ]]; then
 echo "== default bench" ; date
-timeout -k 10 900 python3 bench.py --steps 10 --warmup 3 > $OUT/${TAG}_bench_n1.json 2> $OUT/${TAG}_bench_n1.stderr.txt || exit 1
+timeout -k 10 900 python3 bench.py --full --steps 10 --warmup 3 > $OUT/${TAG}_bench_n1.json 2> $OUT/${TAG}_bench_n1.stderr.txt || exit 1
 export MVLM_BENCH_NO_INGEST=1 MVLM_BENCH_LIVE_TRAFFIC=0
 echo "== other configs" ; date
-timeout -k 10 300 python3 bench.py --config bu3dfe-depth-8 --steps 20 --warmup 5 --cpu-views 0 --no-fast-mode > $OUT/${TAG}_bench_b8views.json 2> $OUT/${TAG}_bench_b8views.stderr.txt || exit 1
-timeout -k 10 300 python3 bench.py --config dtu3d-rgb-64 --steps 10 --warmup 3 --cpu-views 0 --no-fast-mode > $OUT/${TAG}_bench_dtu3d_rgb_64views.json 2> /dev/null || exit 1
-timeout -k 10 300 python3 bench.py --config mediapipe-478x128 --steps 200 --warmup 5 --cpu-views 0 > $OUT/${TAG}_bench_mediapipe_478x128.json 2> /dev/null || exit 1
+timeout -k 10 300 python3 bench.py --full --config bu3dfe-depth-8 --steps 20 --warmup 5 --cpu-views 0 --no-fast-mode > $OUT/${TAG}_bench_b8views.json 2> $OUT/${TAG}_bench_b8views.stderr.txt || exit 1
+timeout -k 10 300 python3 bench.py --full --config dtu3d-rgb-64 --steps 10 --warmup 3 --cpu-views 0 --no-fast-mode > $OUT/${TAG}_bench_dtu3d_rgb_64views.json 2> /dev/null || exit 1
+timeout -k 10 300 python3 bench.py --full --config mediapipe-478x128 --steps 200 --warmup 5 --cpu-views 0 > $OUT/${TAG}_bench_mediapipe_478x128.json 2> /dev/null || exit 1
 echo "== one GPU's share of the headline configuration at N = 2 / 4 / 8 (48 / 24 / 12 of the 96 views)" ; date
 for v in 48 24 12; do
-  timeout -k 10 300 python3 bench.py --views-total $v --steps 20 --warmup 5 --cpu-views 0 --no-fast-mode > $OUT/${TAG}_bench_bu3dfe_rgbd_${v}views.json 2> /dev/null || exit 1
+  timeout -k 10 300 python3 bench.py --full --views-total $v --steps 20 --warmup 5 --cpu-views 0 --no-fast-mode > $OUT/${TAG}_bench_bu3dfe_rgbd_${v}views.json 2> /dev/null || exit 1
 done
 echo "== parity reports" ; date
 timeout -k 10 600 python3 tests/reports/parity_stats.py 8 > $OUT/${TAG}_parity_stats.txt 2>&1 || exit 1
@@ -35,15 +35,15 @@ timeout -k 10 300 python3 tests/reports/gl_contract_report.py > $OUT/${TAG}_gl_c
 timeout -k 10 300 python3 tests/reports/gl_sensitivity_report.py 2>&1 | grep -v amdgpu.ids > $OUT/${TAG}_gl_sensitivity.txt || exit 1
 timeout -k 10 300 python3 -m pytest tests/test_real_textures.py -m gpu -q -s -p no:cacheprovider 2>&1 | grep "synchronisation rounds\|passed\|failed" > $OUT/${TAG}_real_textures.txt || exit 1
 echo "== moment selection (fused) beside simple" ; date
-timeout -k 10 300 python3 bench.py --steps 10 --warmup 3 --cpu-views 0 --no-fast-mode --selection moment > $OUT/${TAG}_bench_moment_96views.json 2> /dev/null || exit 1
-timeout -k 10 300 python3 bench.py --config dtu3d-geomdepth-96 --views-total 12 --steps 20 --warmup 5 --cpu-views 0 --no-fast-mode --selection moment > $OUT/${TAG}_bench_moment_12views.json 2> /dev/null || exit 1
+timeout -k 10 300 python3 bench.py --full --steps 10 --warmup 3 --cpu-views 0 --no-fast-mode --selection moment > $OUT/${TAG}_bench_moment_96views.json 2> /dev/null || exit 1
+timeout -k 10 300 python3 bench.py --full --config dtu3d-geomdepth-96 --views-total 12 --steps 20 --warmup 5 --cpu-views 0 --no-fast-mode --selection moment > $OUT/${TAG}_bench_moment_12views.json 2> /dev/null || exit 1
 echo "== ingest segments, per-level tables" ; date
 timeout -k 10 300 python3 tools/ingest_segments.py > $OUT/${TAG}_ingest_segments.txt 2>&1 || exit 1  # (JPEG on the device and on the host)
 for v in 8 12; do
-  MVLM_BENCH_PER_LAYER=1 timeout -k 10 300 python3 bench.py --config dtu3d-geomdepth-96 --views-total $v --steps 20 --warmup 5 --cpu-views 0 --no-fast-mode > $OUT/${TAG}_bench_dtu3d_${v}views.json 2> $OUT/${TAG}_bench_dtu3d_${v}views.stderr.txt || exit 1
+  MVLM_BENCH_PER_LAYER=1 timeout -k 10 300 python3 bench.py --full --config dtu3d-geomdepth-96 --views-total $v --steps 20 --warmup 5 --cpu-views 0 --no-fast-mode > $OUT/${TAG}_bench_dtu3d_${v}views.json 2> $OUT/${TAG}_bench_dtu3d_${v}views.stderr.txt || exit 1
   python3 tools/per_level_table.py $OUT/${TAG}_bench_dtu3d_${v}views.stderr.txt > $OUT/${TAG}_per_level_${v}views.txt
 done
-MVLM_BENCH_PER_LAYER=1 timeout -k 10 300 python3 bench.py --steps 10 --warmup 3 --cpu-views 0 --no-fast-mode > /dev/null 2> $OUT/per_layer_96.err || exit 1
+MVLM_BENCH_PER_LAYER=1 timeout -k 10 300 python3 bench.py --full --steps 10 --warmup 3 --cpu-views 0 --no-fast-mode > /dev/null 2> $OUT/per_layer_96.err || exit 1
 python3 tools/per_level_table.py $OUT/per_layer_96.err > $OUT/${TAG}_per_level_96views.txt
 echo "== bench.py --gpus 5 as a plain process (five gloo ranks sharing this GPU: the box's process guard admits six processes), configs[2] / [3] / [4] at the 8-GPU shard sizes" ; date
 timeout -k 10 900 bash tools/rehearsal.sh $TAG > $OUT/rehearsal_log.txt 2>&1 || exit 1

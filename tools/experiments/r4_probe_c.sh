@@ -15,11 +15,11 @@ tail -15 $OUT/tests.log
 echo "pytest rc $rc"
 export MVLM_BENCH_NO_INGEST=1
 for v in 12 8; do
-  MVLM_BENCH_PER_LAYER=1 timeout -k 10 300 python3 bench.py --config dtu3d-geomdepth-96 --views-total $v --steps 20 --warmup 5 --cpu-views 0 --no-fast-mode > $OUT/bench_${v}views.json 2> $OUT/bench_${v}views.stderr.txt || exit 1
+  MVLM_BENCH_PER_LAYER=1 timeout -k 10 300 python3 bench.py --full --config dtu3d-geomdepth-96 --views-total $v --steps 20 --warmup 5 --cpu-views 0 --no-fast-mode > $OUT/bench_${v}views.json 2> $OUT/bench_${v}views.stderr.txt || exit 1
   python3 tools/per_level_table.py $OUT/bench_${v}views.stderr.txt > $OUT/per_level_${v}views.txt
   cat $OUT/per_level_${v}views.txt
 done
-MVLM_BENCH_PER_LAYER=1 timeout -k 10 400 python3 bench.py --steps 10 --warmup 3 --cpu-views 0 > $OUT/bench_96views.json 2> $OUT/bench_96views.stderr.txt || exit 1
+MVLM_BENCH_PER_LAYER=1 timeout -k 10 400 python3 bench.py --full --steps 10 --warmup 3 --cpu-views 0 > $OUT/bench_96views.json 2> $OUT/bench_96views.stderr.txt || exit 1
 python3 tools/per_level_table.py $OUT/bench_96views.stderr.txt > $OUT/per_level_96views.txt
 cat $OUT/per_level_96views.txt
 python3 -c "

@@ -12,5 +12,5 @@ for V in NONE NO_STAGING NO_LOADS NO_WRITES NO_BARRIER; do
   /opt/rocm/bin/hipcc $FLAGS $D -c conv_inst_g14.hip -o /tmp/conv_inst_g14_$V.o || exit 1
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o /tmp/libmvlm_$V.so /tmp/conv_inst_g14_$V.o $OTHERS || exit 1
   echo "== $V"
-  MVLM_HIP_LIB=/tmp/libmvlm_$V.so MVLM_BENCH_PER_LAYER=1 MVLM_BENCH_NO_INGEST=1 python3 $ROOT/bench.py --steps 5 --warmup 2 --cpu-views 0 --no-fast-mode 2>&1 >/dev/null | grep "conv11\|conv2x2"
+  MVLM_HIP_LIB=/tmp/libmvlm_$V.so MVLM_BENCH_PER_LAYER=1 MVLM_BENCH_NO_INGEST=1 python3 $ROOT/bench.py --full --steps 5 --warmup 2 --cpu-views 0 --no-fast-mode 2>&1 >/dev/null | grep "conv11\|conv2x2"
 done

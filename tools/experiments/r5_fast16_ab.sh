@@ -8,7 +8,7 @@ cd $ROOT
 export MVLM_BENCH_NO_INGEST=1
 for H in ${1:-0 1 3}; do
   for rep in 1 2; do
-    MVLM_FAST16_HALF_TILES=$H python3 bench.py --precision fast16 --steps 10 --warmup 3 --cpu-views 0 2>/tmp/err_$H.txt | python3 -c "
+    MVLM_FAST16_HALF_TILES=$H python3 bench.py --full --precision fast16 --steps 10 --warmup 3 --cpu-views 0 2>/tmp/err_$H.txt | python3 -c "
 import json,sys;r=json.loads(sys.stdin.read().strip().splitlines()[-1]);print('half_tiles=$H', r['value'], 'views/s', r['ms_per_step'], 'ms; f16 kernel', r['roofline']['achieved'], 'TF-eq over', r['roofline']['kernel_launches_per_step'], 'launches; conv ms', r['roofline']['conv_ms_per_step'])"
   done
 done

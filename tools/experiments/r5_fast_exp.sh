@@ -12,7 +12,7 @@ for V in ${1:-NONE SETPRIO}; do
   /opt/rocm/bin/hipcc $FLAGS $D -c conv_fast.hip -o /tmp/conv_fast_$V.o || exit 1
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o /tmp/libmvlm_$V.so /tmp/conv_fast_$V.o $OTHERS || exit 1
   for rep in 1 2; do
-  MVLM_HIP_LIB=/tmp/libmvlm_$V.so MVLM_BENCH_NO_INGEST=1 python3 $ROOT/bench.py --precision fast16 --steps 10 --warmup 3 --cpu-views 0 2>/dev/null | python3 -c "
+  MVLM_HIP_LIB=/tmp/libmvlm_$V.so MVLM_BENCH_NO_INGEST=1 python3 $ROOT/bench.py --full --precision fast16 --steps 10 --warmup 3 --cpu-views 0 2>/dev/null | python3 -c "
 import json,sys;r=json.loads(sys.stdin.read().strip().splitlines()[-1]);print('$V', r['value'], 'views/s', r['ms_per_step'], 'ms; f16 kernel', r['roofline']['achieved'], 'TF-eq, conv ms', r['roofline']['conv_ms_per_step'])"
   done
 done

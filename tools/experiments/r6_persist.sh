@@ -22,7 +22,7 @@ for mode in plain persist ablate; do
     persist) export MVLM_CONV_PERSIST=3 ;;
     ablate) export MVLM_CONV_PERSIST=3 MVLM_CONV_PERSIST_ABLATE_PROLOGUE=1 ;;
   esac
-  python3 bench.py --steps 10 --warmup 3 --cpu-views 0 --no-fast-mode --no-live-traffic > $OUT/bench_$mode.json 2> $OUT/bench_$mode.err
+  python3 bench.py --full --steps 10 --warmup 3 --cpu-views 0 --no-fast-mode --no-live-traffic > $OUT/bench_$mode.json 2> $OUT/bench_$mode.err
   echo "== $mode"; python3 -c "import json,sys; d=json.loads(open('$OUT/bench_$mode.json').read().strip().splitlines()[-1]); r=d['roofline']; print('views/s', d['value'], 'ms', d['ms_per_step'], 'dominant', r['kernel'], r['frac'], 'all conv', r['all_conv_frac'], 'conv ms', r['conv_ms_per_step'])"
   grep "launches/step" $OUT/bench_$mode.err | tail -14 | grep "c64_t8x32\|c128_t8x32\|c84\|c32_t16"
 done

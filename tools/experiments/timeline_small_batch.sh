@@ -3,7 +3,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/tl12
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp MVLM_BENCH_NO_INGEST=1
-rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --config dtu3d-geomdepth-96 --views-total 12 --steps 6 --warmup 3 --cpu-views 0 --no-fast-mode --no-kernel-profile > $OUT/bench.json 2> $OUT/bench.err
+rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --full --config dtu3d-geomdepth-96 --views-total 12 --steps 6 --warmup 3 --cpu-views 0 --no-fast-mode --no-kernel-profile > $OUT/bench.json 2> $OUT/bench.err
 f=$(find $OUT/trace -name '*kernel_trace.csv' | head -1)
 python3 $ROOT/tools/timeline_gaps.py $f 2000 > $OUT/gaps.txt 2>&1
 python3 - "$f" > $OUT/last_step.txt <<'PY'

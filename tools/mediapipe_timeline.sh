@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/mp_tl${1:-}
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp MVLM_BENCH_NO_INGEST=1
-rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --config mediapipe-478x128 --steps 20 --warmup 5 --cpu-views 0 --no-live-traffic --no-kernel-profile > $OUT/bench.json 2> $OUT/bench.err
+rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --full --config mediapipe-478x128 --steps 20 --warmup 5 --cpu-views 0 --no-live-traffic --no-kernel-profile > $OUT/bench.json 2> $OUT/bench.err
 k=$(find $OUT/trace -name '*kernel_trace.csv' | head -1)
 m=$(find $OUT/trace -name '*memory_copy_trace.csv' | head -1)
 python3 $ROOT/tools/timeline_steps.py "$k" "$m" 20 > $OUT/last_steps.txt 2>&1

@@ -17,7 +17,7 @@ export MVLM_BENCH_SHARE_GPU=1 MVLM_BENCH_NO_INGEST=1
 run() {  # name, bench arguments...
   local name=$1; shift
   local t0=$(date +%s.%N)
-  timeout -k 10 900 python3 bench.py --gpus 5 --steps 5 --warmup 2 --cpu-views 0 --no-fast-mode "$@" > $OUT/${TAG}_rehearsal_5ranks_$name.json 2> $OUT/$name.err || return 1
+  timeout -k 10 900 python3 bench.py --full --gpus 5 --steps 5 --warmup 2 --cpu-views 0 --no-fast-mode "$@" > $OUT/${TAG}_rehearsal_5ranks_$name.json 2> $OUT/$name.err || return 1
   local t1=$(date +%s.%N)
   python3 - "$OUT/${TAG}_rehearsal_5ranks_$name.json" "$t0" "$t1" <<'PY'
 import json, sys
