@@ -138,6 +138,13 @@ int mvlm_set_render_shading(mvlm_ctx* ctx, int shading);
  * (GL_SUBPIXEL_BITS; the reference's images depend on the OpenGL its VTK runs on, render3d.py:60-65).  8 (default) = what
  * GPUs report; 4 = the standard's minimum and the software OpenGL tests/golden/gl_raster.npz was drawn with.  4..8. */
 int mvlm_set_render_subpixel_bits(mvlm_ctx* ctx, int bits);
+/* The other rasterisation choice OpenGL leaves open: multisampling (vtkRenderWindow.MultiSamples, which the reference never
+ * sets, render3d.py:60-65, so its views follow the installed VTK's default).  0 (default) = one sample at the pixel centre, the
+ * contract every other test pins; 4 = four samples per pixel at the rotated-grid positions (3,6) (13,10) (6,13) (10,3) in
+ * 1/16 pixel from the lower-left corner, coverage and depth per sample, the colour evaluated once per pixel at its centre and
+ * resolved by pairwise rounding-up averages per byte, the depth byte from sample 0 - what the OpenGL behind
+ * tests/golden/gl_raster_msaa4.npz does.  Any other value is an error. */
+int mvlm_set_render_multisamples(mvlm_ctx* ctx, int samples);
 /* HIP-event timing of the render kernels (bench.py's rasteriser roofline): while enabled every mvlm_render
  * records one {n_views, n_verts, n_tris, ms}; get_profile waits for the stream, fills up to `cap` records,
  * clears them and returns the count (-1 on failure). */

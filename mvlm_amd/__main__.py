@@ -44,6 +44,9 @@ def main(argv=None) -> int:
     parser.add_argument("--seed", type=int, default=None,
                         help="seed of the global numpy RNG (poses for N != 8 views and the RANSAC draws come from it, as in the "
                              "reference, which never seeds it): makes a run reproducible")
+    parser.add_argument("--multisamples", type=int, choices=(0, 4), default=0,
+                        help="samples per pixel of the renderer: 0 = one at the pixel centre (default), 4 = multisampled views "
+                             "(for checkpoints trained on multisampled VTK renders; DESIGN.md 5.1)")
     args = parser.parse_args(argv)
     if args.out is None:
         args.out = args.path
@@ -76,6 +79,8 @@ def main(argv=None) -> int:
     from . import pipeline
 
     extra = {"precision": args.precision} if args.precision != "exact" else {}
+    if args.multisamples:
+        extra["render_multisamples"] = args.multisamples
     if args.config is not None:
         from . import config as mvlm_config
 

@@ -25,39 +25,9 @@
 // Neither fewer instructions (the 24-bit path below: 3 %) nor more loads in flight per thread (TPT / PPT: nothing) nor
 // keeping the keys in LDS with every survivor binned (built: 210 us - a cull pass, a survivor list, a fill pass and a
 // per-tile gather cost more than the plane they save) beat this structure; fewer bytes per vertex do.
-#include "common.h"
-#include "raster_math.h"
+#include "raster_common.h"
 
 namespace {
-
-constexpr int TILES = RM_TILES * RM_TILES;  // 256 per view
-
-// Workgroup -> (view, chunk of that view's work) so that every view is worked on by ONE XCD: consecutive block ids
-// go round-robin over the 8 XCDs, each with its own L2; a view's transformed vertices (0.8 MB), key plane (0.5 MB) and
-// bins then live in one L2 instead of being fetched by all eight (speed heuristic only: any placement is correct).
-// The grid holds ceil(n_views / 8) * 8 * chunks_per_view workgroups; surplus ones return at once.
-__device__ inline bool view_chunk(int chunks_per_view, int n_views, int* view, int* chunk) {
-    const int bid = blockIdx.x, xcd = bid & 7, j = bid >> 3;
-    *view = (j / chunks_per_view) * 8 + xcd;
-    *chunk = j % chunks_per_view;
-    return *view < n_views;
-}
-inline unsigned view_chunk_grid(int chunks_per_view, int n_views) { return unsigned((n_views + 7) / 8 * 8) * unsigned(chunks_per_view); }
-
-// a transformed vertex as stored (rm_vert without its padding word: a quarter less traffic on the largest scratch array)
-struct vert12 {
-    int32_t X, Y;
-    float z;
-};
-__device__ inline rm_vert load_vert(const vert12* __restrict__ p, int i) {
-    const vert12 v = p[i];
-    rm_vert o;
-    o.X = v.X;
-    o.Y = v.Y;
-    o.z = v.z;
-    o.pad = 0.f;
-    return o;
-}
 
 __global__ void transform_kernel(const float* __restrict__ verts, int n_verts, const double* __restrict__ rot,
                                  int n_views, int sub_bits, vert12* __restrict__ tv) {
@@ -88,21 +58,13 @@ __device__ inline rm_tri load_tri(const vert12* tvv, const int32_t* tris, int t)
 // |px - ax|, |py - ay| < 2^14: every product is below 2^28 and fits the full-rate 24-bit multiply (v_mul_i32_i24), every
 // edge value and the area are below 2^29.  The integers are THE SAME as rm_setup's / rm_cover's, so are the floats made
 // from them: a kernel may take either path per triangle and the image does not change by a bit (oracle/raster.c, the
-// tests' checker, knows only the 64-bit form).  Worth 3-5 % of a render.
-constexpr int RM_SMALL_EXTENT = 1 << 14;
-
+// tests' checker, knows only the 64-bit form).  Worth 3-5 % of a render.  (RM_SMALL_EXTENT, small_extent: raster_common.h)
 struct tri24 {
     int32_t X0, Y0, X1, Y1, X2, Y2;  // after the winding swap (vertices 1 and 2)
     float z0, z1, z2;
     float farea;
     int32_t swapped;
 };
-
-__device__ inline bool small_extent(const rm_vert& a, const rm_vert& b, const rm_vert& c) {
-    const int32_t minx = min(a.X, min(b.X, c.X)), maxx = max(a.X, max(b.X, c.X));
-    const int32_t miny = min(a.Y, min(b.Y, c.Y)), maxy = max(a.Y, max(b.Y, c.Y));
-    return maxx - minx < RM_SMALL_EXTENT && maxy - miny < RM_SMALL_EXTENT;
-}
 
 // rm_setup without the bounding box; false for a zero-area triangle
 __device__ inline bool setup24(rm_vert a, rm_vert b, rm_vert c, tri24* t) {
@@ -152,8 +114,6 @@ __device__ inline int cover24(const T* t, int i, int j, float* b0, float* b1, fl
     *b2 = float(w2) / t->farea;
     return 1;
 }
-
-constexpr int SMALL_PIXELS = 16;  // triangles covering at most this many pixel centres skip the bins
 
 // Classify every (view, triangle): cull / resolve small ones with atomics / count big ones.
 // Order of the tests: the pixel-centre box first (integer shifts: most triangles of a dense scan lie between pixel
@@ -258,7 +218,6 @@ __global__ __launch_bounds__(256) void classify_kernel(const vert12* __restrict_
 // Scatter the big triangles' ids into the per-tile lists (offsets from the scan).  FILL_WGS workgroups per view stride
 // over the view's big list: a grid sized for "every triangle is big" spent 11 us on dispatching 37 000 workgroups that
 // found nothing to do (a dense scan has a handful of big triangles per view).
-constexpr int FILL_WGS = 32;
 __global__ void bin_fill_kernel(const vert12* __restrict__ tv, const int32_t* __restrict__ tris, int n_verts,
                                 int n_tris, int n_views, const int* __restrict__ n_big,
                                 const int* __restrict__ big_list, const int* __restrict__ offsets,
@@ -419,8 +378,11 @@ extern "C" int mvlm_render(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* r
     auto* offsets = static_cast<int*>(ctx->get_scratch("raster.off", n_ctr * sizeof(int)));
     auto* bins = static_cast<int*>(ctx->get_scratch("raster.bins", size_t(n_views) * cap * sizeof(int)));
     auto* big_list = static_cast<int*>(ctx->get_scratch("raster.big", size_t(n_views) * T * sizeof(int)));
-    const size_t key_bytes = size_t(n_views) * RM_SIZE * RM_SIZE * sizeof(unsigned long long);
-    auto* keys = static_cast<unsigned long long*>(ctx->get_scratch("raster.keys", key_bytes));
+    // one key per pixel, or S per pixel in a plane of its own when multisampling (allocated only then)
+    const int S = ctx->render_multisamples;
+    const char* const key_name = S ? "raster.keys4" : "raster.keys";
+    const size_t key_bytes = size_t(n_views) * RM_SIZE * RM_SIZE * size_t(S ? S : 1) * sizeof(unsigned long long);
+    auto* keys = static_cast<unsigned long long*>(ctx->get_scratch(key_name, key_bytes));
     MVLM_REQUIRE(ctx, tv && rot && ctr && offsets && bins && big_list && keys, "render: scratch allocation failed");
     int* counts = ctr;
     int* cursors = ctr + n_ctr;
@@ -430,13 +392,17 @@ extern "C" int mvlm_render(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* r
                                        ctx->stream));
     MVLM_CHECK_HIP(ctx, hipMemsetAsync(ctr, 0, ctr_ints * sizeof(int), ctx->stream));
     // The key plane is EMPTY between renders (tile_kernel clears what it reads); it is filled here only when the buffer is new
-    // or a render did not run to its end.  `clean_cap` = the capacity it was last known clean at (a reallocation only grows it).
-    const size_t keys_cap = ctx->scratch["raster.keys"].second;
-    if (ctx->raster_keys_clean_cap != keys_cap)
+    // or a render did not run to its end.  `clean` = the buffer and capacity it was last known clean at: a buffer that
+    // get_scratch replaced (after a failed allocation, say) is filled even when its size is the old one.
+    mvlm_ctx::KeyPlaneState& clean = S ? ctx->raster_keys4_clean : ctx->raster_keys_clean;
+    const size_t keys_cap = ctx->scratch[key_name].second;
+    if (clean.ptr != keys || clean.cap != keys_cap)
         MVLM_CHECK_HIP(ctx, hipMemsetAsync(keys, 0xFF, keys_cap, ctx->stream));  // RM_KEY_EMPTY everywhere
-    ctx->raster_keys_clean_cap = 0;  // (until this call has enqueued its tile kernel)
-    if (!ctx->render_overflow_host)
+    clean = mvlm_ctx::KeyPlaneState{};  // (until this call has enqueued its tile kernel)
+    if (!ctx->render_overflow_host) {
         MVLM_CHECK_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->render_overflow_host), sizeof(int)));
+        *ctx->render_overflow_host = 0;  // (a render that fails before its tile kernel leaves no garbage for render_check)
+    }
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (ctx->render_profiling) {  // HIP events on the launch stream around the five kernels of this call
         if (ctx->render_event_cursor + 2 > ctx->render_events.size()) ctx->render_events.resize(ctx->render_event_cursor + 2, nullptr);
@@ -451,16 +417,24 @@ extern "C" int mvlm_render(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* r
     }
     hipLaunchKernelGGL(transform_kernel, dim3(view_chunk_grid((V + 255) / 256, n_views)), dim3(256), 0, ctx->stream,
                        mesh->verts, V, rot, n_views, ctx->render_subpixel_bits, tv);
-    hipLaunchKernelGGL(classify_kernel<CLASSIFY_TPT>, dim3(view_chunk_grid((T + 256 * CLASSIFY_TPT - 1) / (256 * CLASSIFY_TPT), n_views)), dim3(256), 0,
-                       ctx->stream, tv, mesh->tris, V, T, n_views, keys, counts, n_big, big_list);
-    hipLaunchKernelGGL(scan_kernel, dim3(n_views), dim3(TILES), 0, ctx->stream, counts, offsets, cap, overflow);
-    hipLaunchKernelGGL(bin_fill_kernel, dim3(view_chunk_grid(FILL_WGS, n_views)), dim3(256), 0, ctx->stream, tv,
-                       mesh->tris, V, T, n_views, n_big, big_list, offsets, cursors, bins, cap, overflow);
-    hipLaunchKernelGGL(tile_kernel, dim3(view_chunk_grid(TILES, n_views)), dim3(256), 0, ctx->stream, tv, mesh->tris,
-                       mesh->uvs, mesh->tex, mesh->tex_w, mesh->tex_h, V, counts, offsets, bins, cap, keys,
-                       ctx->render_shading, n_views, overflow, ctx->render_overflow_host, out_dev);
+    if (S == 0) {
+        hipLaunchKernelGGL(classify_kernel<CLASSIFY_TPT>, dim3(view_chunk_grid((T + 256 * CLASSIFY_TPT - 1) / (256 * CLASSIFY_TPT), n_views)), dim3(256), 0,
+                           ctx->stream, tv, mesh->tris, V, T, n_views, keys, counts, n_big, big_list);
+        hipLaunchKernelGGL(scan_kernel, dim3(n_views), dim3(TILES), 0, ctx->stream, counts, offsets, cap, overflow);
+        hipLaunchKernelGGL(bin_fill_kernel, dim3(view_chunk_grid(FILL_WGS, n_views)), dim3(256), 0, ctx->stream, tv,
+                           mesh->tris, V, T, n_views, n_big, big_list, offsets, cursors, bins, cap, overflow);
+        hipLaunchKernelGGL(tile_kernel, dim3(view_chunk_grid(TILES, n_views)), dim3(256), 0, ctx->stream, tv, mesh->tris,
+                           mesh->uvs, mesh->tex, mesh->tex_w, mesh->tex_h, V, counts, offsets, bins, cap, keys,
+                           ctx->render_shading, n_views, overflow, ctx->render_overflow_host, out_dev);
+    } else {  // S == 4 (mvlm_set_render_multisamples admits nothing else): the kernels of raster_ms.hip
+        raster_ms_classify(ctx->stream, S, tv, mesh->tris, V, T, n_views, keys, counts, n_big, big_list);
+        hipLaunchKernelGGL(scan_kernel, dim3(n_views), dim3(TILES), 0, ctx->stream, counts, offsets, cap, overflow);
+        raster_ms_bin_and_tile(ctx->stream, S, tv, mesh->tris, mesh->uvs, mesh->tex, mesh->tex_w, mesh->tex_h, V, T, n_views,
+                               n_big, big_list, counts, offsets, cursors, bins, cap, keys, ctx->render_shading, overflow,
+                               ctx->render_overflow_host, out_dev);
+    }
     MVLM_CHECK_HIP(ctx, hipGetLastError());
-    ctx->raster_keys_clean_cap = keys_cap;
+    clean = mvlm_ctx::KeyPlaneState{keys, keys_cap};
     if (e1) {
         MVLM_CHECK_HIP(ctx, hipEventRecord(e1, ctx->stream));
         ctx->render_prof.push_back({n_views, V, T, e0, e1});
@@ -522,6 +496,15 @@ extern "C" int mvlm_set_render_subpixel_bits(mvlm_ctx* ctx, int bits) {
     std::lock_guard<std::mutex> lk(ctx->mu);
     MVLM_REQUIRE(ctx, bits >= 4 && bits <= 8, "render: subpixel bits must be 4..8 (GL_SUBPIXEL_BITS of the OpenGL to match; 8 = GPUs)");
     ctx->render_subpixel_bits = bits;
+    return 0;
+}
+
+extern "C" int mvlm_set_render_multisamples(mvlm_ctx* ctx, int samples) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    MVLM_REQUIRE(ctx, samples == 0 || samples == 4,
+                 "render: multisamples must be 0 (one sample at the pixel centre, the default) or 4 (" + std::to_string(samples) +
+                     " given)");
+    ctx->render_multisamples = samples;
     return 0;
 }
 

@@ -1,0 +1,63 @@
+// Pieces of the multi-view rasteriser shared by its one-sample kernels (raster.hip) and its multisampled ones
+// (raster_ms.hip, an object of its own: tools/kernel_occupancy.py keeps a table of its kernels beside the main one).
+#ifndef MVLM_RASTER_COMMON_H
+#define MVLM_RASTER_COMMON_H
+
+#include "common.h"
+#include "raster_math.h"
+
+namespace {
+
+constexpr int TILES = RM_TILES * RM_TILES;  // 256 per view
+
+// Workgroup -> (view, chunk of that view's work) so that every view is worked on by ONE XCD: consecutive block ids
+// go round-robin over the 8 XCDs, each with its own L2; a view's transformed vertices (0.8 MB), key plane (0.5 MB) and
+// bins then live in one L2 instead of being fetched by all eight (speed heuristic only: any placement is correct).
+// The grid holds ceil(n_views / 8) * 8 * chunks_per_view workgroups; surplus ones return at once.
+__device__ inline bool view_chunk(int chunks_per_view, int n_views, int* view, int* chunk) {
+    const int bid = blockIdx.x, xcd = bid & 7, j = bid >> 3;
+    *view = (j / chunks_per_view) * 8 + xcd;
+    *chunk = j % chunks_per_view;
+    return *view < n_views;
+}
+inline unsigned view_chunk_grid(int chunks_per_view, int n_views) { return unsigned((n_views + 7) / 8 * 8) * unsigned(chunks_per_view); }
+
+// a transformed vertex as stored (rm_vert without its padding word: a quarter less traffic on the largest scratch array)
+struct vert12 {
+    int32_t X, Y;
+    float z;
+};
+__device__ inline rm_vert load_vert(const vert12* __restrict__ p, int i) {
+    const vert12 v = p[i];
+    rm_vert o;
+    o.X = v.X;
+    o.Y = v.Y;
+    o.z = v.z;
+    o.pad = 0.f;
+    return o;
+}
+
+// a triangle whose vertices lie within 2^14 steps of each other takes the 24-bit edge functions (raster.hip, "24-bit path")
+constexpr int RM_SMALL_EXTENT = 1 << 14;
+
+__device__ inline bool small_extent(const rm_vert& a, const rm_vert& b, const rm_vert& c) {
+    const int32_t minx = min(a.X, min(b.X, c.X)), maxx = max(a.X, max(b.X, c.X));
+    const int32_t miny = min(a.Y, min(b.Y, c.Y)), maxy = max(a.Y, max(b.Y, c.Y));
+    return maxx - minx < RM_SMALL_EXTENT && maxy - miny < RM_SMALL_EXTENT;
+}
+
+constexpr int SMALL_PIXELS = 16;  // triangles covering at most this many pixel centres skip the bins
+constexpr int FILL_WGS = 32;      // bin-fill workgroups per view (raster.hip, bin_fill_kernel)
+
+}  // namespace
+
+// The multisampled kernels of one mvlm_render at `samples` samples per pixel (raster_ms.hip); raster.hip launches the
+// transform before and the scan between them.  `tv` is the transformed-vertex scratch (vert12[n_views][n_verts]).
+void raster_ms_classify(hipStream_t stream, int samples, const void* tv, const int32_t* tris, int n_verts, int n_tris,
+                        int n_views, unsigned long long* keys, int* counts, int* n_big, int* big_list);
+void raster_ms_bin_and_tile(hipStream_t stream, int samples, const void* tv, const int32_t* tris, const float* uvs,
+                            const uint8_t* tex, int tex_w, int tex_h, int n_verts, int n_tris, int n_views, const int* n_big,
+                            const int* big_list, const int* counts, const int* offsets, int* cursors, int* bins, int cap,
+                            unsigned long long* keys, int shading, int* overflow, int* overflow_host, float* out);
+
+#endif

@@ -89,7 +89,7 @@ class Pipeline(abc.ABC):
     def __init__(self, render_image_stack: bool = False, offscreen: bool = True, n_views: int = 8,
                  render_image_folder: Path | None = None, visualize_rays: bool = False,
                  screenshot_folder: Path | None = None, device: int = 0, shard_views: bool = False,
-                 verbose: bool = True):
+                 verbose: bool = True, render_multisamples: int = 0):
         self.render_image_stack = render_image_stack
         self.render_image_folder = render_image_folder
         self.n_views = n_views
@@ -114,8 +114,9 @@ class Pipeline(abc.ABC):
 
             if torch.cuda.is_available():
                 torch.cuda.set_device(device)
+        # render_multisamples: samples per pixel of the renderer (HipRenderer3D.multisamples: 0 or 4)
         self.renderer_3d = HipRenderer3D(image_size=(256, 256), offscreen=offscreen, n_views=n_views, device=device,
-                                         verbose=verbose)
+                                         verbose=verbose, multisamples=render_multisamples)
         self.estimator_3d = HipEstimator3D(device=device, verbose=verbose)
         self.predictor_2d = None  # will be assigned externally
 

@@ -173,7 +173,7 @@ class HipRenderer3D:
                  min_x_angle: int = -40, max_x_angle: int = 40, min_y_angle: int = -80, max_y_angle: int = 80,
                  min_z_angle: int = -20, max_z_angle: int = 20, min_scale: float = 1.4, max_scale: float = 1.9,
                  min_tx: int = -20, max_tx: int = 20, min_ty: int = -20, max_ty: int = 20, device: int = 0,
-                 verbose: bool = True, shading: str = "texture", subpixel_bits: int = 8):
+                 verbose: bool = True, shading: str = "texture", subpixel_bits: int = 8, multisamples: int = 0):
         if tuple(image_size) != (256, 256):
             raise ValueError("the HIP renderer is built for 256x256 views (general_pipeline.py:57)")
         self.n_views = n_views
@@ -197,6 +197,9 @@ class HipRenderer3D:
         if subpixel_bits not in (4, 5, 6, 7, 8):
             raise ValueError("subpixel_bits must be 4..8")
         self.subpixel_bits = int(subpixel_bits)
+        # samples per pixel (vtkRenderWindow.MultiSamples, which the reference leaves to VTK's default): 0 = one at the pixel
+        # centre (the default contract), 4 = four, resolved like the OpenGL behind tests/golden/gl_raster_msaa4.npz
+        self.multisamples = multisamples
         # "pre-align" block of a Deep-MVLM config (utils/prealign.py; utils3d.py:465-503): applied to every mesh this
         # renderer loads, the mesh handle it returns carries the matrix (Mesh.to_original)
         self.pre_align: dict | None = None
@@ -204,6 +207,16 @@ class HipRenderer3D:
         # or "host" (libjpeg through Pillow at load time); the pixels are the same bytes either way
         self.texture_decode = "device"
         self.ctx = _lib.get_context(device)
+
+    @property
+    def multisamples(self) -> int:
+        return self._multisamples
+
+    @multisamples.setter
+    def multisamples(self, samples: int) -> None:
+        if isinstance(samples, bool) or samples not in (0, 4):
+            raise ValueError(f"multisamples must be 0 (one sample at the pixel centre) or 4, not {samples!r}")
+        self._multisamples = int(samples)
 
     # ---- pose table (render3d.py:79-112) ----------------------------------------------
     def random_transform(self, size=1):
@@ -238,10 +251,11 @@ class HipRenderer3D:
         rot = np.ascontiguousarray(view_rotations(transform_stack) if rot is None else rot, dtype=np.float64)
         handle = upload_mesh(self.ctx, mesh)
         self.ctx.bind_current_stream(torch, dev)
-        mode = (1 if self.shading == "geometry" else 0, self.subpixel_bits)
+        mode = (1 if self.shading == "geometry" else 0, self.subpixel_bits, self.multisamples)
         if getattr(self.ctx, "_render_mode", None) != mode:  # (renderers of one GPU share the context)
             self.ctx.check(self.ctx.lib.mvlm_set_render_shading(self.ctx.handle, mode[0]))
             self.ctx.check(self.ctx.lib.mvlm_set_render_subpixel_bits(self.ctx.handle, mode[1]))
+            self.ctx.check(self.ctx.lib.mvlm_set_render_multisamples(self.ctx.handle, mode[2]))
             self.ctx._render_mode = mode
         self.ctx.check(self.ctx.lib.mvlm_render(self.ctx.handle, handle, _lib.as_ptr(rot, C.c_double), n,
                                                 C.c_void_p(out.data_ptr())))

@@ -279,3 +279,157 @@ class GLReference:
         gl.glReadPixels(0, 0, s, s, GL_RED_INTEGER, GL_UNSIGNED_INT, zbits.ctypes.data_as(C.c_void_p))
         self.check("draw")
         return rgba[:, :, :3].copy(), zbits.view(np.float32)
+
+
+# ---- multisampled target (tools/make_gl_msaa_golden.py) --------------------------------------------------------------------
+GL_DRAW_FRAMEBUFFER = 0x8CA9
+GL_DEPTH_COMPONENT32F = 0x8CAC
+GL_TEXTURE_COMPARE_MODE, GL_NONE = 0x884C, 0
+
+RESOLVE_VERTEX_SHADER = b"""#version 300 es
+void main() {
+    vec2 p = vec2(float((gl_VertexID & 1) * 4 - 1), float((gl_VertexID & 2) * 2 - 1));   /* one triangle over the window */
+    gl_Position = vec4(p, 0.0, 1.0);
+}
+"""
+
+RESOLVE_FRAGMENT_SHADER = b"""#version 300 es
+precision highp float;
+precision highp int;
+uniform highp sampler2D depth_0;
+layout(location = 0) out uint depthBits;
+void main() {
+    depthBits = floatBitsToUint(texelFetch(depth_0, ivec2(gl_FragCoord.xy), 0).r);
+}
+"""
+
+
+class MultisampleTarget:
+    """VTK's multisampled offscreen frame (vtkOpenGLRenderWindow with MultiSamples > 0): RGBA8 + DEPTH_COMPONENT32F
+    renderbuffers with `samples` samples, resolved before the read-back the way VTK does (render3d.py:157-168): a blit to a
+    single-sample target, for colour (SetInputBufferTypeToRGB) and for depth (SetInputBufferTypeToZBuffer).  GLES 3.0 cannot
+    read a depth attachment, so the resolved depth (a DEPTH_COMPONENT32F texture) is read by a full-screen pass that writes
+    floatBitsToUint(texelFetch(..).r) into R32UI: the exact bits the blit left."""
+
+    def __init__(self, g: GLReference, samples: int):
+        self.g, self.samples = g, samples
+        gl, s = g.gl, g.size
+        rb = (C.c_uint * 4)()
+        gl.glGenRenderbuffers(4, rb)
+        gl.glBindRenderbuffer(GL_RENDERBUFFER, rb[0])
+        gl.glRenderbufferStorageMultisample(GL_RENDERBUFFER, samples, GL_RGBA8, s, s)
+        gl.glBindRenderbuffer(GL_RENDERBUFFER, rb[1])
+        gl.glRenderbufferStorageMultisample(GL_RENDERBUFFER, samples, GL_DEPTH_COMPONENT32F, s, s)
+        gl.glBindRenderbuffer(GL_RENDERBUFFER, rb[2])
+        gl.glRenderbufferStorage(GL_RENDERBUFFER, GL_RGBA8, s, s)
+        gl.glBindRenderbuffer(GL_RENDERBUFFER, rb[3])
+        gl.glRenderbufferStorage(GL_RENDERBUFFER, GL_R32UI, s, s)
+        dtex = C.c_uint()
+        gl.glGenTextures(1, C.byref(dtex))
+        gl.glActiveTexture(GL_TEXTURE0 + 1)
+        gl.glBindTexture(GL_TEXTURE_2D, dtex)
+        gl.glTexImage2D(GL_TEXTURE_2D, 0, GL_DEPTH_COMPONENT32F, s, s, 0, GL_DEPTH_COMPONENT, GL_FLOAT, None)
+        for k, v in ((GL_TEXTURE_MIN_FILTER, GL_NEAREST), (GL_TEXTURE_MAG_FILTER, GL_NEAREST), (GL_TEXTURE_COMPARE_MODE, GL_NONE)):
+            gl.glTexParameteri(GL_TEXTURE_2D, k, v)
+        gl.glActiveTexture(GL_TEXTURE0)
+        fbo = (C.c_uint * 3)()
+        gl.glGenFramebuffers(3, fbo)
+        self.ms_fbo, self.resolve_fbo, self.bits_fbo = fbo
+        gl.glBindFramebuffer(GL_FRAMEBUFFER, self.ms_fbo)
+        gl.glFramebufferRenderbuffer(GL_FRAMEBUFFER, GL_COLOR_ATTACHMENT0, GL_RENDERBUFFER, rb[0])
+        gl.glFramebufferRenderbuffer(GL_FRAMEBUFFER, GL_DEPTH_ATTACHMENT, GL_RENDERBUFFER, rb[1])
+        self._complete("multisampled")
+        gl.glBindFramebuffer(GL_FRAMEBUFFER, self.resolve_fbo)
+        gl.glFramebufferRenderbuffer(GL_FRAMEBUFFER, GL_COLOR_ATTACHMENT0, GL_RENDERBUFFER, rb[2])
+        gl.glFramebufferTexture2D(GL_FRAMEBUFFER, GL_DEPTH_ATTACHMENT, GL_TEXTURE_2D, dtex, 0)
+        self._complete("resolve")
+        gl.glBindFramebuffer(GL_FRAMEBUFFER, self.bits_fbo)
+        gl.glFramebufferRenderbuffer(GL_FRAMEBUFFER, GL_COLOR_ATTACHMENT0, GL_RENDERBUFFER, rb[3])
+        self._complete("depth bits")
+        self.info = {"samples": samples, "sample_buffers": self._samples_of(self.ms_fbo)}
+        # the read-back pass of the resolved depth
+        prog = gl.glCreateProgram()
+        gl.glAttachShader(prog, g._shader(GL_VERTEX_SHADER, RESOLVE_VERTEX_SHADER))
+        gl.glAttachShader(prog, g._shader(GL_FRAGMENT_SHADER, RESOLVE_FRAGMENT_SHADER))
+        gl.glLinkProgram(prog)
+        ok = C.c_int()
+        gl.glGetProgramiv(prog, GL_LINK_STATUS, C.byref(ok))
+        if not ok.value:
+            raise RuntimeError("resolve program: link failed")
+        gl.glUseProgram(prog)
+        gl.glUniform1i(gl.glGetUniformLocation(prog, b"depth_0"), 1)
+        self.depth_prog, self.depth_tex = prog, dtex
+        vao = C.c_uint()
+        gl.glGenVertexArrays(1, C.byref(vao))
+        self.empty_vao = vao
+        gl.glUseProgram(g.prog)
+        g.check("multisample target")
+
+    def _complete(self, what):
+        if self.g.gl.glCheckFramebufferStatus(GL_FRAMEBUFFER) != GL_FRAMEBUFFER_COMPLETE:
+            raise RuntimeError(f"{what} framebuffer incomplete")
+
+    def _samples_of(self, fbo):
+        self.g.gl.glBindFramebuffer(GL_FRAMEBUFFER, fbo)
+        return self.g._geti(GL_SAMPLES)
+
+    def draw(self, verts_view: np.ndarray):
+        """GLReference.draw into the multisampled frame, then the resolve -> (rgb u8 [256,256,3], z f32 [256,256]), GL rows
+        (row 0 = bottom); z is the resolved DEPTH_COMPONENT32F value (1.0 = the clear value)."""
+        g = self.g
+        gl, s = g.gl, g.size
+        gl.glBindFramebuffer(GL_FRAMEBUFFER, self.ms_fbo)
+        gl.glDrawBuffers(1, (C.c_uint * 1)(GL_COLOR_ATTACHMENT0))   # the shader's depth-bits output is discarded here
+        gl.glViewport(0, 0, s, s)
+        gl.glUseProgram(g.prog)
+        v = np.ascontiguousarray(verts_view, np.float32)
+        gl.glBindBuffer(GL_ARRAY_BUFFER, g.vbo_pos)
+        gl.glBufferData(GL_ARRAY_BUFFER, C.c_ssize_t(v.nbytes), v.ctypes.data_as(C.c_void_p), GL_STATIC_DRAW)
+        gl.glEnableVertexAttribArray(0)
+        gl.glVertexAttribPointer(0, 3, GL_FLOAT, 0, 0, None)
+        for cap in (GL_CULL_FACE, GL_BLEND, GL_DITHER, GL_SCISSOR_TEST):
+            gl.glDisable(cap)
+        gl.glEnable(GL_DEPTH_TEST)
+        gl.glDepthFunc(GL_LEQUAL)
+        gl.glDepthMask(1)
+        white = (C.c_float * 4)(1.0, 1.0, 1.0, 1.0)
+        one = C.c_float(1.0)
+        gl.glClearBufferfv(GL_COLOR, 0, white)
+        gl.glClearBufferfv(GL_DEPTH, 0, C.byref(one))
+        gl.glDrawElements(GL_TRIANGLES, g.n_idx, GL_UNSIGNED_INT, None)
+        gl.glBindFramebuffer(GL_READ_FRAMEBUFFER, self.ms_fbo)
+        gl.glBindFramebuffer(GL_DRAW_FRAMEBUFFER, self.resolve_fbo)
+        g.check("multisampled draw")
+        gl.glBlitFramebuffer(0, 0, s, s, 0, 0, s, s, GL_COLOR_BUFFER_BIT, GL_NEAREST)
+        g.check("colour resolve")
+        gl.glBindFramebuffer(GL_FRAMEBUFFER, self.resolve_fbo)
+        gl.glReadBuffer(GL_COLOR_ATTACHMENT0)
+        gl.glPixelStorei(GL_PACK_ALIGNMENT, 1)
+        rgba = np.empty((s, s, 4), np.uint8)
+        gl.glReadPixels(0, 0, s, s, GL_RGBA, GL_UNSIGNED_BYTE, rgba.ctypes.data_as(C.c_void_p))
+        g.check("colour read-back")
+        gl.glBindFramebuffer(GL_READ_FRAMEBUFFER, self.ms_fbo)
+        gl.glBindFramebuffer(GL_DRAW_FRAMEBUFFER, self.resolve_fbo)
+        gl.glBlitFramebuffer(0, 0, s, s, 0, 0, s, s, GL_DEPTH_BUFFER_BIT, GL_NEAREST)
+        self.depth_readable = gl.glGetError() == 0
+        if not self.depth_readable:     # this GL refuses a depth blit into a texture: the resolved depth cannot be read back
+            gl.glFinish()
+            return rgba[:, :, :3].copy(), None
+        # resolved depth -> R32UI through the full-screen pass (depth test off: every pixel is written)
+        gl.glBindFramebuffer(GL_FRAMEBUFFER, self.bits_fbo)
+        gl.glDrawBuffers(1, (C.c_uint * 1)(GL_COLOR_ATTACHMENT0))
+        gl.glDisable(GL_DEPTH_TEST)
+        gl.glUseProgram(self.depth_prog)
+        gl.glActiveTexture(GL_TEXTURE0 + 1)
+        gl.glBindTexture(GL_TEXTURE_2D, self.depth_tex)
+        gl.glActiveTexture(GL_TEXTURE0)
+        gl.glBindVertexArray(self.empty_vao)                      # (the mesh's attribute state stays in the default one)
+        gl.glDrawArrays(GL_TRIANGLES, 0, 3)
+        gl.glBindVertexArray(0)
+        gl.glFinish()
+        zbits = np.empty((s, s), np.uint32)
+        gl.glReadBuffer(GL_COLOR_ATTACHMENT0)
+        gl.glReadPixels(0, 0, s, s, GL_RED_INTEGER, GL_UNSIGNED_INT, zbits.ctypes.data_as(C.c_void_p))
+        gl.glUseProgram(g.prog)
+        g.check("multisampled draw")
+        return rgba[:, :, :3].copy(), zbits.view(np.float32)

@@ -2,13 +2,15 @@
 """Registers, spills and the waves per SIMD they allow, for every kernel of the built library objects.
 
     tools/kernel_occupancy.py            print the table
-    tools/kernel_occupancy.py --write    rewrite tests/golden/kernel_occupancy.json from the current build
+    tools/kernel_occupancy.py --write    rewrite tests/golden/kernel_occupancy.json (and kernel_occupancy_msaa.json) from the build
 
 A convolution tile's rate depends on how many workgroups a CU holds, i.e. on which side of 168 / 128 / 102 ... registers the
 compiler lands - and every epilogue kind compiled into a tile moves that number (round 4: two new kinds took the 80-row tile
 from 166 to 191 registers, three resident workgroups per CU to two, conv6 / conv10 of a 12-view pass from 541 to 713 us;
 no test saw it, the evidence pass did).  tests/test_host_logic.py::test_kernel_occupancy_table compares the build with the
-committed table: fewer waves per SIMD or more spilled registers than recorded fail, on the CPU, at build time."""
+committed table: fewer waves per SIMD or more spilled registers than recorded fail, on the CPU, at build time.  The multisampled
+rasteriser's kernels are built into an object directory of their own (build/msaa/) with a table of their own,
+tests/golden/kernel_occupancy_msaa.json, held to the same rule by tests/test_msaa_occupancy.py."""
 import json
 import re
 import subprocess
@@ -19,6 +21,8 @@ from pathlib import Path
 REPO = Path(__file__).resolve().parents[1]
 LLVM = Path("/opt/rocm/lib/llvm/bin")
 TABLE = REPO / "tests" / "golden" / "kernel_occupancy.json"
+MSAA_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_msaa.json"
+BUILD = REPO / "mvlm_amd" / "csrc" / "build"
 
 
 def waves_per_simd(vgprs: int) -> int:
@@ -52,18 +56,19 @@ def object_kernels(obj: Path) -> dict:
     return out
 
 
-def build_table() -> dict:
+def build_table(objdir: Path = BUILD) -> dict:
     table = {}
-    for obj in sorted((REPO / "mvlm_amd" / "csrc" / "build").glob("*.o")):
+    for obj in sorted(objdir.glob("*.o")):
         table.update(object_kernels(obj))
     return dict(sorted(table.items()))
 
 
 if __name__ == "__main__":
-    t = build_table()
-    if "--write" in sys.argv:
-        TABLE.write_text(json.dumps({k: {"waves_per_simd": v["waves_per_simd"], "spilled": v["spilled"]} for k, v in t.items()}, indent=1) + "\n")
-        print(f"{len(t)} kernels -> {TABLE}")
-    else:
-        for k, v in t.items():
-            print(f"{v['vgprs']:4d} regs  {v['waves_per_simd']} waves/SIMD  {v['spilled']:3d} spilled  {k}")
+    for table_path, objdir in ((TABLE, BUILD), (MSAA_TABLE, BUILD / "msaa")):
+        t = build_table(objdir)
+        if "--write" in sys.argv:
+            table_path.write_text(json.dumps({k: {"waves_per_simd": v["waves_per_simd"], "spilled": v["spilled"]} for k, v in t.items()}, indent=1) + "\n")
+            print(f"{len(t)} kernels -> {table_path}")
+        else:
+            for k, v in t.items():
+                print(f"{v['vgprs']:4d} regs  {v['waves_per_simd']} waves/SIMD  {v['spilled']:3d} spilled  {k}")
