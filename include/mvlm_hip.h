@@ -190,6 +190,18 @@ int mvlm_cnn_heatmaps(mvlm_ctx* ctx, const float* images_dev, int n_views, const
  * captures failed (those passes ran eagerly instead). */
 int mvlm_cnn_set_execution(mvlm_ctx* ctx, int graph_mode, int concurrency);
 int mvlm_cnn_set_pairing(mvlm_ctx* ctx, int mode);
+/* F(2,3) Winograd tiles on the exact path (csrc/conv_kernel.h: Cfg::WINO): the large stride-1 3x3 layers computed as four
+ * GEMMs over row-transformed inputs and load-time-transformed weights - fp32 in, fp32 accumulation on the same MFMA, 4
+ * multiplies per output pair where the direct form spends 6.  mode 0: never (the direct tiles only), 1 (default): where the
+ * measured table csrc/conv_tuned_wino.h lists the layer (shape, kind, device batch), 2: every layer a Winograd variant can
+ * serve (tests).  A new context takes its default from the environment variable MVLM_WINOGRAD (0 | 1 | 2).  Results differ
+ * from the direct tiles' in the last bits (another summation order).  Profile records of such a launch
+ * (mvlm_cnn_get_profile) count the FLOPs its MFMAs execute: 12 Cin Cout H W B, not 18.
+ * mvlm_pack_winograd_weights: the host transform mvlm_cnn_load applies, packed f32[9][cin_pad][cout_pad] (tap = ky * 3 + kx) ->
+ * f32[12][cin_pad][cout_pad] (slice t * 3 + kx; u0 = g0, u1 = (g0 + g1 + g2) / 2, u2 = (g0 - g1 + g2) / 2, u3 = g2 over ky,
+ * float64 arithmetic, one rounding). */
+int mvlm_cnn_set_winograd(mvlm_ctx* ctx, int mode);
+int mvlm_pack_winograd_weights(const float* w9_host, int cin_pad, int cout_pad, float* w12_host);
 int mvlm_cnn_execution_stats(mvlm_ctx* ctx, int64_t* eager_runs, int64_t* graph_captures, int64_t* graph_replays,
                              int64_t* graph_failures);
 /* OPT-IN reduced-cost arithmetic ("fast" precision, mvlm_amd/csrc/conv_fast.hip): the big 3x3 layers (input channels a

@@ -54,6 +54,7 @@ extern "C" void mvlm_ctx_destroy(mvlm_ctx* ctx) {
     if (ctx->cnn.blob) hipFree(ctx->cnn.blob);
     if (ctx->cnn.fast_blob) hipFree(ctx->cnn.fast_blob);
     if (ctx->cnn.fast16_blob) hipFree(ctx->cnn.fast16_blob);
+    if (ctx->cnn.wino_blob) hipFree(ctx->cnn.wino_blob);
     if (ctx->cnn.fast16_flag) hipFree(ctx->cnn.fast16_flag);
     if (ctx->switch_event) hipEventDestroy(ctx->switch_event);
     for (int i = 0; i < 2; ++i) {
@@ -531,6 +532,12 @@ extern "C" int mvlm_conv2d(mvlm_ctx* ctx, const float* x_dev, int batch, int cin
         for (int i = 0; i < n; ++i) blob[off + i] = src[i];
         return long(off);
     };
+    // the Winograd form beside it where such a tile could be chosen or forced
+    long ww_off = -1;
+    if (mvlm_conv_wino_serves_slot(ksize, cin_pad, cout_pad)) {
+        ww_off = long(push(size_t(12) * cin_pad * cout_pad));
+        mvlm_winograd_transform(blob.data() + w_off, cin_pad, cout_pad, blob.data() + ww_off);
+    }
     const long b_off = vec(bias_host, cout, cout_pad);
     const long ps_off = vec(pre_scale_host, cin, cin_pad), pt_off = vec(pre_shift_host, cin, cin_pad);
     const long qs_off = vec(post_scale_host, cout, cout_pad), qt_off = vec(post_shift_host, cout, cout_pad);
@@ -547,6 +554,7 @@ extern "C" int mvlm_conv2d(mvlm_ctx* ctx, const float* x_dev, int batch, int cin
     a.H = h;
     a.W = w;
     a.w = d + w_off;
+    a.w_wino = ww_off < 0 ? nullptr : d + ww_off;
     a.cout = cout;
     a.cout_pad = cout_pad;
     a.ksize = ksize;
@@ -578,7 +586,7 @@ extern "C" int mvlm_conv_bench(mvlm_ctx* ctx, int batch, int cin, int cout, int 
     const bool plain = (flags & 4) && !(flags & (1 | 2 | 8));
     const int cout_pad = (plain && (cout + 15) / 16 * 16 == 80) ? 80 : (plain && ksize == 3 && cout == 84) ? 84 : (cout + 31) / 32 * 32;
     const size_t px = size_t(batch) * size * size;
-    const size_t n_w = size_t(taps) * cin_pad * cout_pad, n_vec = size_t(cin_pad) * 2 + size_t(cout_pad) * 3;
+    const size_t n_w = size_t(ksize == 3 ? 12 : taps) * cin_pad * cout_pad, n_vec = size_t(cin_pad) * 2 + size_t(cout_pad) * 3;
     const size_t n_x = px * cin, n_y = px * cout;
     const size_t total = n_w + n_vec + n_x + 3 * n_y + 64;
     auto* base = static_cast<float*>(ctx->get_scratch("conv_bench", total * sizeof(float)));
@@ -598,6 +606,7 @@ extern "C" int mvlm_conv_bench(mvlm_ctx* ctx, int batch, int cin, int cout, int 
     a.B = batch;
     a.H = a.W = size;
     a.w = w;
+    if (mvlm_conv_wino_serves_slot(ksize, cin_pad, cout_pad)) a.w_wino = w;  // zero data: the transformed weights are zeros too
     a.cout = cout;
     a.cout_pad = cout_pad;
     a.ksize = ksize;

@@ -171,6 +171,7 @@ struct Exec {
         a.cin_pad = r[4];
         a.cout_pad = r[5];
         a.w = blob(r[6]);
+        a.w_wino = (size_t(slot) < st.wino_off.size() && st.wino_off[size_t(slot)] >= 0) ? st.wino_blob + st.wino_off[size_t(slot)] : nullptr;
         a.bias = blob(r[7]);
         a.pre_scale = blob(r[8]);
         a.pre_shift = blob(r[9]);
@@ -199,7 +200,11 @@ struct Exec {
         hipEventRecord(e0, ctx->cur_stream());
         return 0;
     }
-    static double conv_flops(const ConvArgs& a) { return 2.0 * a.cin * a.cout * a.ksize * a.ksize * double(a.H) * a.W * a.B * a.n_par; }
+    // the multiply-adds the launch's MFMAs execute: a Winograd tile spends 6 per output and input channel where a direct 3x3 spends 9
+    static double conv_flops(const ConvArgs& a, int variant = -1) {
+        const double taps = mvlm_conv_variant_is_wino(variant) ? 6.0 : double(a.ksize * a.ksize);
+        return 2.0 * a.cin * a.cout * taps * double(a.H) * a.W * a.B * a.n_par;
+    }
 
     // fill weights / BN / bias of `slot` into `a` and launch
     int conv(int slot, const Tensor& x, ConvArgs a, int S) {
@@ -221,7 +226,7 @@ struct Exec {
         }
         if (st.profiling) {
             hipEventRecord(e1, ctx->cur_stream());
-            ConvProfileRec rec{slot, variant, conv_flops(a), e0, e1};
+            ConvProfileRec rec{slot, variant, conv_flops(a, variant), e0, e1};
             const short sh[6] = {short(a.ksize), short(a.cin_pad), short(a.cout_pad), short(a.H), short(mvlm_conv_kind(a)), short(B > 32767 ? 32767 : B)};
             for (int k = 0; k < 6; ++k) rec.shape[k] = sh[k];
             st.prof.push_back(rec);
@@ -233,6 +238,9 @@ struct Exec {
     int pair_variant(int slot0, const Tensor& x0, ConvArgs a0, int S0, int slot1, const Tensor& x1, ConvArgs a1, int S1) {
         if (st.pairing == 0 || fill(slot0, x0, a0, S0) || fill(slot1, x1, a1, S1)) return -1;
         if (runs_fast(slot0, a0) || runs_fast(slot1, a1)) return -1;
+        // a layer routed to a Winograd tile (which has no two-problem form) leaves the pair: the table lists it only where
+        // its own launch beat the shared one
+        if (mvlm_conv_wino_variant(ctx, a0) >= 0 || mvlm_conv_wino_variant(ctx, a1) >= 0) return -1;
         return mvlm_conv_pair_variant(a0, a1, st.pairing);
     }
 
@@ -863,6 +871,12 @@ extern "C" int mvlm_cnn_load(mvlm_ctx* ctx, const float* blob_host, size_t n_flo
         (void)hipFree(st.fast16_blob);
         st.fast16_blob = nullptr;
     }
+    st.wino_off.clear();
+    st.wino_bytes = 0;
+    if (st.wino_blob) {
+        (void)hipFree(st.wino_blob);
+        st.wino_blob = nullptr;
+    }
     for (auto& g : st.graphs)
         if (g.exec) hipGraphExecDestroy(g.exec);  // captured launches point into the old weight blob
     st.graphs.clear();
@@ -887,6 +901,25 @@ extern "C" int mvlm_cnn_load(mvlm_ctx* ctx, const float* blob_host, size_t n_flo
                  "cnn_load: conv11 output channels != n_landmarks");
     MVLM_CHECK_HIP(ctx, hipMalloc(&st.blob, n_floats * sizeof(float)));
     MVLM_CHECK_HIP(ctx, hipMemcpy(st.blob, blob_host, n_floats * sizeof(float), hipMemcpyHostToDevice));
+    // The weights are fixed for the life of the model: the Winograd form of every 3x3 slot a Winograd tile can serve is
+    // made here, once (4/3 of those slots' weight bytes in a buffer of its own).
+    {
+        std::vector<float> wino;
+        st.wino_off.assign(size_t(n_slots), -1);
+        for (int s = 0; s < n_slots; ++s) {
+            const int32_t* r = &st.desc[size_t(s) * MVLM_CONV_DESC_INTS];
+            if (!r[0] || !mvlm_conv_wino_serves_slot(r[3], r[4], r[5])) continue;
+            const size_t off = wino.size();
+            wino.resize(off + size_t(12) * r[4] * r[5]);
+            mvlm_winograd_transform(blob_host + r[6], r[4], r[5], wino.data() + off);
+            st.wino_off[size_t(s)] = (long long)off;
+        }
+        if (!wino.empty()) {
+            MVLM_CHECK_HIP(ctx, hipMalloc(&st.wino_blob, wino.size() * sizeof(float)));
+            MVLM_CHECK_HIP(ctx, hipMemcpy(st.wino_blob, wino.data(), wino.size() * sizeof(float), hipMemcpyHostToDevice));
+            st.wino_bytes = wino.size() * sizeof(float);
+        }
+    }
     st.n_landmarks = n_landmarks;
     st.in_channels = in_channels;
     st.loaded = true;
@@ -961,6 +994,18 @@ extern "C" int mvlm_cnn_set_pairing(mvlm_ctx* ctx, int mode) {
         st.graphs.clear();
     }
     st.pairing = mode;
+    return 0;
+}
+
+extern "C" int mvlm_cnn_set_winograd(mvlm_ctx* ctx, int mode) {
+    MVLM_ENTER(ctx);
+    MVLM_REQUIRE(ctx, mode >= 0 && mode <= 2, "cnn_set_winograd: 0 never, 1 the measured table (default), 2 every layer a Winograd variant can serve");
+    if (mode != ctx->conv_winograd) {  // captured graphs encode the launches
+        for (auto& g : ctx->cnn.graphs)
+            if (g.exec) hipGraphExecDestroy(g.exec);
+        ctx->cnn.graphs.clear();
+    }
+    ctx->conv_winograd = mode;
     return 0;
 }
 

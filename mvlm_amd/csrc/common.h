@@ -4,6 +4,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <map>
 #include <mutex>
 #include <string>
@@ -126,6 +127,9 @@ struct ConvArgs {
     // -DMVLM_CONV_TIMING builds only (tools/conv_phase_timing.py): u64[4] = summed cycles of wave 0 in
     // prologue / K loop / epilogue, number of workgroups
     unsigned long long* timing = nullptr;
+    // the layer's weights in the Winograd tiles' form ([12][cin_pad][cout_pad], mvlm_pack_winograd_weights) where it has one:
+    // mvlm_launch_conv puts it in `w` when it routes the launch to such a tile
+    const float* w_wino = nullptr;
 };
 
 struct ConvProfileRec {
@@ -182,6 +186,10 @@ struct CnnState {
     std::vector<long long> fast16_off;
     std::vector<float> fast16_unscale;
     unsigned* fast16_flag = nullptr;         // device word: an f16x2 launch of the current pass met |x| >= 65504
+    // F(2,3) Winograd form of the 3x3 slots a Winograd tile can serve (exact path): transformed weights, float offset per slot (-1: none)
+    float* wino_blob = nullptr;
+    std::vector<long long> wino_off;
+    size_t wino_bytes = 0;
     std::vector<CnnGraphEntry> graphs;
     long graph_replays = 0, graph_captures = 0, eager_runs = 0, graph_failures = 0;
 };
@@ -240,6 +248,9 @@ struct mvlm_ctx {
     float* kparts_ws[2] = {nullptr, nullptr};      // split-K over workgroups: partial tiles, arrival counters
     unsigned* kparts_cnt[2] = {nullptr, nullptr};  // ([0] main launch stream, [1] the executor's side stream)
     int conv_force_variant = -1;            // >= 0: mvlm_conv_bench times exactly this kernel variant
+    // Winograd tiles on the exact path: 0 never, 1 where the measured table (conv_tuned_wino.h) has an entry, 2 every layer a
+    // Winograd variant can serve (tests); a new context takes MVLM_WINOGRAD from the environment (default 1)
+    int conv_winograd = [] { const char* e = getenv("MVLM_WINOGRAD"); return (e && e[0] >= '0' && e[0] <= '2' && !e[1]) ? e[0] - '0' : 1; }();
     std::vector<ConvOverride> conv_overrides;  // tools/tune_in_network.py: kernel variant per (shape, kind), before any table
     unsigned long long conv_attr_mask = 0;  // conv variants whose launch attributes are set on this ctx's device
     // a depth-key plane's buffer and capacity when it was last left all-EMPTY ({nullptr, 0}: not known clean); keyed on both,
@@ -340,6 +351,12 @@ bool mvlm_conv_in2_ok(const mvlm_ctx* ctx, const ConvArgs& a);  // this launch w
 bool mvlm_conv_can_pool(const mvlm_ctx* ctx, const ConvArgs& a);  // the variant this launch would use can also emit the 2x2 max-pooled tensor
 int mvlm_conv_kind(const ConvArgs& a);
 bool mvlm_conv_variant_can_pool(int variant);
+bool mvlm_conv_variant_is_wino(int variant);
+// the Winograd variant this launch is routed to (overrides, mode and table of the context), or -1: the direct tiles
+int mvlm_conv_wino_variant(const mvlm_ctx* ctx, const ConvArgs& a);
+bool mvlm_conv_wino_serves_slot(int ksize, int cin_pad, int cout_pad);  // a Winograd variant exists for these channels
+// host: packed [9][cin_pad][cout_pad] -> [12][cin_pad][cout_pad] (u_t per kx: t * 3 + kx), float64 arithmetic, one rounding
+void mvlm_winograd_transform(const float* w9, int cin_pad, int cout_pad, float* w12);
 // two independent convolutions in one grid (conv_kernel.h: conv_pair_kernel)
 constexpr int MVLM_CONV_PAIR_FLAG = 0x1000;  // variant code of a paired launch: flag | base id | lg(kparts0) << 8 | lg(kparts1) << 10
 int mvlm_conv_pair_variant(const ConvArgs& a0, const ConvArgs& a1, int mode);

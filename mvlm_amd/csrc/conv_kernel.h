@@ -32,15 +32,22 @@ __device__ __forceinline__ void static_for(F&& f) {
 // SPLITK: the four waves of a workgroup share ONE 32x32 output tile and each sums a quarter of
 // every K-chunk's channels (latency-bound tiny feature maps: 4x more workgroups, 4x shorter serial
 // K loop per wave); the partial sums are added in wave order through LDS, i.e. deterministically.
+// KS_ == 32 (WINO): a 3x3 convolution as F(2,3) Winograd along y.  Output rows 2p, 2p+1 come from the input rows
+// d0..d3 = 2p-1 .. 2p+2 (after BatchNorm + ReLU and the zero padding): the staged planes hold, per channel and row pair,
+// the four transformed rows v0 = d0 - d2, v1 = d1 + d2, v2 = d2 - d1, v3 = d1 - d3 ([cin][p][t][x]), the weight slice the
+// host-transformed columns u_t ([t * 3 + kx][cin][cout], 12 "taps").  Four GEMMs m_t over K = (kx, cin) - a tap is an x
+// offset only - and out[2p] = (m0 + m1) + m2, out[2p+1] = (m1 - m2) - m3 in the registers of one lane: 4 MFMAs per
+// output pair and (kx, cin) instead of 6, and the epilogue sees the register layout of the direct tile.
 template <int COUT_T_, int TW_, int TRI_, int NIMG_, int KS_, int CK_, bool SPLITK_ = false>
 struct Cfg {
-    static constexpr int COUT_T = COUT_T_, TW = TW_, TRI = TRI_, NIMG = NIMG_, KS = KS_, CK = CK_;
+    static constexpr bool WINO = KS_ == 32;
+    static constexpr int COUT_T = COUT_T_, TW = TW_, TRI = TRI_, NIMG = NIMG_, KS = WINO ? 3 : KS_, CK = CK_;
     static constexpr bool SPLITK = SPLITK_;
     static constexpr int CKW = SPLITK ? CK / 4 : CK;  // channels of a chunk one wave multiplies
-    static constexpr int TAPS = KS * KS;
+    static constexpr int TAPS = WINO ? 12 : KS * KS;
     static constexpr int HALO = KS == 1 ? 0 : 1;  // KS == 2: a 2x2 window inside the 3x3 halo tile
     static constexpr int PW = TW + 2 * HALO;
-    static constexpr int PH = TRI + 2 * HALO;
+    static constexpr int PH = WINO ? 2 * TRI : TRI + 2 * HALO;  // WINO: four transformed rows per output row pair
     static constexpr int PLANE = NIMG * PH * PW;  // floats per channel in sX
     static constexpr int PIX_T = TW * TRI * NIMG;
     static constexpr int XT = CK * PLANE;
@@ -58,14 +65,16 @@ struct Cfg {
     static constexpr bool HAS_AMAX = NIMG == 1 && TW == 32 && TRI == 8 && KS != 1 && (COUT_T == 80 || COUT_T == 96 || (COUT_T == 84 && KS == 2));
     static constexpr int NT = SPLITK ? PIX_T / 32 : PIX_T / 4 / 32;  // split-K: every wave multiplies all (one or two) 32-pixel columns
     static constexpr int NT16 = TAIL16 ? 2 * NT : 1;  // 16-pixel column groups of a wave
-    static constexpr int KSTEPS = TAPS * CKW / 2;
-    static constexpr int X_ITERS = (XT + 255) / 256;
+    static constexpr int KSTEPS = WINO ? 3 * CK / 2 : TAPS * CKW / 2;  // WINO: (kx, channel pair), four GEMMs per step
+    static constexpr int WP = PIX_T / 4 / 64;              // WINO: row pairs of a wave
+    static constexpr int WJOBS = CK * (TRI / 2) * PW;      // WINO: staging jobs of a chunk = (channel, row pair, x)
+    static constexpr int X_ITERS = WINO ? (WJOBS + 255) / 256 : (XT + 255) / 256;
     static constexpr int W_ITERS = (WT / 4 + 255) / 256;
     static constexpr int BN_MAXC = 256;  // pre-BN scale/shift of up to 256 input channels live in LDS
     static constexpr size_t LDS_BYTES = size_t(2 * STAGE + 2 * BN_MAXC) * 4;
     // accumulators + staged tile + operands: above ~200 registers the kernel is told it owns
     // the whole SIMD register file (one wave per SIMD) instead of spilling for occupancy
-    static constexpr int ACC_REGS = (COUT_T / 32) * (SPLITK ? PIX_T / 32 : TW * TRI * NIMG / 128) * 16 + (TAIL16 ? 4 * NT16 : 0) + (TAIL4 ? 4 : 0);
+    static constexpr int ACC_REGS = ((COUT_T / 32) * (SPLITK ? PIX_T / 32 : TW * TRI * NIMG / 128) * 16 + (TAIL16 ? 4 * NT16 : 0) + (TAIL4 ? 4 : 0)) * (WINO ? 2 : 1);
     // register budget per lane: 168 at three workgroups per CU, 256 at two
     // (four per CU = 128 registers makes the 64-accumulator tiles spill; measured slower)
     static constexpr int MIN_BLOCKS_PER_CU = (ACC_REGS <= 64 && TW * TRI * NIMG <= 256) ? 3 : 2;
@@ -78,15 +87,17 @@ struct Cfg {
     static constexpr bool POOL_SMALL = TW < 32 && TRI % 2 == 0 && COUT_T % 32 == 0;
     static constexpr bool CAN_POOL_ANY = POOL32 || POOL_SMALL;
     // the tile that also exists with a second input tensor added on the load (ConvArgs::in2): the dominant 128 x (8 x 32) tile
-    static constexpr bool HAS_IN2 = !SPLITK && COUT_T == 128 && TW == 32 && TRI == 8 && NIMG == 1 && KS == 3 && CK == 4;
+    static constexpr bool HAS_IN2 = !WINO && !SPLITK && COUT_T == 128 && TW == 32 && TRI == 8 && NIMG == 1 && KS == 3 && CK == 4;
     // variants that also exist as a two-problem launch (conv_pair_kernel): the tiles of the residual blocks' 3x3 convolutions
-    static constexpr bool PAIRABLE = KS == 3 && COUT_T % 32 == 0 && COUT_T != 96 && !(SPLITK && PIX_T != 32);
+    static constexpr bool PAIRABLE = !WINO && KS == 3 && COUT_T % 32 == 0 && COUT_T != 96 && !(SPLITK && PIX_T != 32);
     static_assert(SPLITK ? ((PIX_T == 32 || PIX_T == 64) && COUT_T == 32 && CK % 8 == 0) : (PIX_T % 128 == 0),
                   "pixel tile must split into 4 waves x 32-pixel MFMA columns (or be one or two columns for split-K)");
     static_assert(!TAIL4 || PIX_T == 256, "the 4-row strip gives every lane of a wave one pixel: 64 pixels per wave");
     static_assert(COUT_T % 32 == 0 || (TAIL16 && !SPLITK && CK == 4 && TW == 32 && NIMG == 1),
                   "cout tile must be a multiple of the 32-row MFMA tile (+ one 16-row strip on the 32-pixel-row tiles)");
     static_assert(CK % 2 == 0, "the f32 MFMA consumes two k values per step");
+    static_assert(!WINO || (!SPLITK && TW == 32 && NIMG == 1 && PIX_T % 256 == 0 && COUT_T % 32 == 0),
+                  "Winograd tiles: 32-pixel rows, one image, whole row pairs per wave, no strips");
     static_assert(LDS_BYTES <= 160 * 1024, "two stages must fit the CU's 160 KiB LDS");
 };
 
@@ -297,6 +308,198 @@ __device__ __forceinline__ void compute_chunk(const ConvArgs& a, const float* st
     });
 }
 
+
+// ---- F(2,3) Winograd tiles (Cfg::WINO) ----------------------------------------------------------------------------------
+// Staging job = one (channel, row pair, x) of a chunk: four loads (rows 2p-1 .. 2p+2), one BatchNorm pair, four LDS writes.
+template <class C>
+struct WinoStage {
+    static constexpr int N = C::WINO ? C::X_ITERS : 1;
+    unsigned base[N];  // offset of the job's first row at its x (channel = position in the chunk); wraps for y = -1, never used then
+    unsigned rows[N];  // bit r: row 2p - 1 + r and the column lie inside the image (0: no such job)
+    int lds[N];        // stage offset of the job's t = 0 value
+    float xw[N][4];
+};
+
+template <class C, int T, bool BN_FROM_GLOBAL = false>
+__device__ __forceinline__ void issue_item_wino(const ConvArgs& a, int cb, int tid, unsigned HWin, const float* sbn, WinoStage<C>& ws,
+                                                const unsigned (&woff_g)[C::W_ITERS], StageRegs<C>& r) {
+    if constexpr (T < C::X_ITERS) {
+        const int c = cb + (tid + T * 256) / ((C::TRI / 2) * C::PW);
+        const bool okc = c < a.cin;
+        const float* const base = a.in + size_t(cb < a.cin ? cb : 0) * HWin;  // wave-uniform
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const bool ok = okc && ((ws.rows[T] >> q) & 1u);
+            ws.xw[T][q] = base[ok ? ws.base[T] + unsigned(q * a.W) : 0u];  // unconditional: masked lanes read a valid element
+        }
+        if (a.pre_scale != nullptr) {
+            const int cc = c < a.cin_pad ? c : 0;
+            if constexpr (BN_FROM_GLOBAL) {
+                r.bn_s[T] = a.pre_scale[cc];
+                r.bn_t[T] = a.pre_shift[cc];
+            } else {
+                r.bn_s[T] = sbn[cc];
+                r.bn_t[T] = sbn[C::BN_MAXC + cc];
+            }
+        }
+    } else {
+        constexpr int I = T - C::X_ITERS;
+        const float* const base = a.w + size_t(cb) * a.cout_pad;  // wave-uniform
+        r.wv[I] = *reinterpret_cast<const f32x4*>(base + (woff_g[I] != INVALID_OFF ? woff_g[I] : 0u));
+    }
+}
+
+// BatchNorm + ReLU, zero padding AFTER the activation, the input transform, four LDS writes
+template <class C, int T>
+__device__ __forceinline__ void write_item_wino(const ConvArgs& a, int cb, int tid, float* st, const WinoStage<C>& ws, const StageRegs<C>& r) {
+    if constexpr (T < C::X_ITERS) {
+        const int e = tid + T * 256;
+        const bool okc = cb + e / ((C::TRI / 2) * C::PW) < a.cin;
+        float d[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            float v = ws.xw[T][q];
+            if (a.pre_scale != nullptr) v = fmaxf(fmaf(v, r.bn_s[T], r.bn_t[T]), 0.f);
+            d[q] = (okc && ((ws.rows[T] >> q) & 1u)) ? v : 0.f;
+        }
+        if (e < C::WJOBS) {
+            float* const p = st + ws.lds[T];
+            p[0] = d[0] - d[2];
+            p[C::PW] = d[1] + d[2];
+            p[2 * C::PW] = d[2] - d[1];
+            p[3 * C::PW] = d[1] - d[3];
+        }
+    } else {
+        constexpr int I = T - C::X_ITERS;
+        const int f = tid + I * 256;
+        if (f < C::WT / 4) reinterpret_cast<f32x4*>(st + C::XT_PAD)[f] = r.wv[I];
+    }
+}
+
+// The MFMAs of one K-chunk: k-steps (kx, channel pair) in a fixed order, per step the four GEMMs t = 0..3 of every row pair
+// of the wave on MT cout tiles; operands of the next step are fetched while this one's MFMAs issue, the next chunk's
+// staging rides in their shadow as in compute_chunk.
+template <class C, bool STAGE_NEXT>
+__device__ __forceinline__ void compute_chunk_wino(const ConvArgs& a, const float* st, float* st_next, int cb_next, int tid, unsigned HWin,
+                                                   const float* sbn, int woff, const int (&pixw)[4 * C::WP], WinoStage<C>& ws,
+                                                   const unsigned (&woff_g)[C::W_ITERS], StageRegs<C>& r, f32x16 (&acc)[C::MT][4 * C::WP]) {
+    constexpr int T_TOT = C::X_ITERS + C::W_ITERS;
+    constexpr int ISSUE_SPAN = C::KSTEPS / 2 > 0 ? C::KSTEPS / 2 : 1;
+    constexpr int WRITE_SPAN = ISSUE_SPAN;
+    constexpr int WRITE_START = C::KSTEPS - WRITE_SPAN;
+    constexpr int NQ = 4 * C::WP;
+    float av[2][4][C::MT], bv[2][NQ];
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int m = 0; m < C::MT; ++m) av[0][t][m] = st[woff + t * 3 * C::CK * C::COUT_T + m * 32];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) bv[0][q] = st[pixw[q]];
+    static_for<0, C::KSTEPS>([&](auto ksc) {
+        constexpr int ks = decltype(ksc)::value;
+        constexpr int nx = ks + 1;
+        if constexpr (nx < C::KSTEPS) {
+            constexpr int kx = nx / (C::CK / 2), cp = nx % (C::CK / 2);
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int m = 0; m < C::MT; ++m) av[nx & 1][t][m] = st[woff + ((t * 3 + kx) * C::CK + 2 * cp) * C::COUT_T + m * 32];
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) bv[nx & 1][q] = st[2 * cp * C::PLANE + pixw[q] + kx];
+        }
+        constexpr int LEAD = 2;
+        static_for<0, C::MT * NQ>([&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            constexpr int m = i / NQ, q = i % NQ;
+            if constexpr (i < LEAD) acc[m][q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[ks & 1][q & 3][m], bv[ks & 1][q], acc[m][q], 0, 0, 0);
+        });
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (STAGE_NEXT) {
+            static_for<0, T_TOT>([&](auto tc) {
+                constexpr int t = decltype(tc)::value;
+                if constexpr ((t * ISSUE_SPAN) / T_TOT == ks) issue_item_wino<C, t>(a, cb_next, tid, HWin, sbn, ws, woff_g, r);
+                if constexpr (WRITE_START + (t * WRITE_SPAN) / T_TOT == ks) write_item_wino<C, t>(a, cb_next, tid, st_next, ws, r);
+            });
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        __builtin_amdgcn_s_setprio(1);
+        static_for<0, C::MT * NQ>([&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            constexpr int m = i / NQ, q = i % NQ;
+            if constexpr (i >= LEAD) acc[m][q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[ks & 1][q & 3][m], bv[ks & 1][q], acc[m][q], 0, 0, 0);
+        });
+        __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_sched_barrier(0);
+    });
+}
+
+// The whole K loop of a Winograd tile and the output transform into the direct tile's accumulator layout
+// (acc[m][n]: n = output row of the wave, 32 pixels x 16 channel registers).
+template <class C>
+__device__ __forceinline__ void wino_main(const ConvArgs& a, float* smem, const int tid, const int y0, const int x0, const int b0,
+                                          const int co0, const unsigned HWin, const unsigned (&woff_g)[C::W_ITERS], const int woff,
+                                          f32x16 (&acc)[C::MT][C::NT]) {
+    const int lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
+    WinoStage<C> ws;
+    constexpr int JPC = (C::TRI / 2) * C::PW;  // jobs per channel
+#pragma unroll
+    for (int i = 0; i < C::X_ITERS; ++i) {
+        const int e = tid + i * 256;
+        const int c = e / JPC;
+        const int rem = e - c * JPC;
+        const int p = rem / C::PW;
+        const int xx = rem - p * C::PW;
+        const int y = y0 + 2 * p - 1, x = x0 + xx - 1;
+        const bool okx = e < C::WJOBS && x >= 0 && x < a.W && b0 < a.B;
+        unsigned rows = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) rows |= (okx && y + q >= 0 && y + q < a.H) ? (1u << q) : 0u;
+        ws.rows[i] = rows;
+        ws.base[i] = unsigned(b0 * a.in_ctot + a.in_coff + c) * HWin + unsigned(y * a.W + x);
+        ws.lds[i] = c * C::PLANE + p * 4 * C::PW + xx;
+    }
+    int pixw[4 * C::WP];
+#pragma unroll
+    for (int q = 0; q < 4 * C::WP; ++q) pixw[q] = ((wave * C::WP + (q >> 2)) * 4 + (q & 3)) * C::PW + l31 + half * C::PLANE;
+    f32x16 wacc[C::MT][4 * C::WP];
+#pragma unroll
+    for (int m = 0; m < C::MT; ++m)
+#pragma unroll
+        for (int q = 0; q < 4 * C::WP; ++q) wacc[m][q] = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float* sbn = smem + 2 * C::STAGE;
+    StageRegs<C> regs;
+    constexpr int T_TOT = C::X_ITERS + C::W_ITERS;
+    static_for<0, T_TOT>([&](auto tc) { issue_item_wino<C, decltype(tc)::value, true>(a, 0, tid, HWin, sbn, ws, woff_g, regs); });
+    if (a.pre_scale != nullptr) {
+        for (int i = tid; i < a.cin_pad; i += 256) {
+            sbn[i] = a.pre_scale[i];
+            sbn[C::BN_MAXC + i] = a.pre_shift[i];
+        }
+    }
+    static_for<0, T_TOT>([&](auto tc) { write_item_wino<C, decltype(tc)::value>(a, 0, tid, smem, ws, regs); });
+    __syncthreads();
+    int cur = 0;
+    for (int cb = C::CK; cb < a.cin_pad; cb += C::CK) {
+        compute_chunk_wino<C, true>(a, smem + cur * C::STAGE, smem + (cur ^ 1) * C::STAGE, cb, tid, HWin, sbn, woff, pixw, ws, woff_g, regs, wacc);
+        __syncthreads();  // next stage complete; everybody is done reading this one
+        cur ^= 1;
+    }
+    compute_chunk_wino<C, false>(a, smem + cur * C::STAGE, nullptr, 0, tid, HWin, sbn, woff, pixw, ws, woff_g, regs, wacc);
+    static_for<0, C::MT>([&](auto mc) {
+        constexpr int m = decltype(mc)::value;
+        static_for<0, C::WP>([&](auto pc) {
+            constexpr int p = decltype(pc)::value;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float m0 = wacc[m][4 * p][r], m1 = wacc[m][4 * p + 1][r], m2 = wacc[m][4 * p + 2][r], m3 = wacc[m][4 * p + 3][r];
+                acc[m][2 * p][r] = (m0 + m1) + m2;
+                acc[m][2 * p + 1][r] = (m1 - m2) - m3;
+            }
+        });
+    });
+    (void)co0;
+}
+
 // Software-pipelined main loop, one workgroup (4 waves, one per SIMD) per CU-resident tile:
 //   while the MFMAs of K-chunk c run out of LDS stage c&1, the global loads of chunk c+1 are
 //   in flight into registers; after the MFMAs they get their BatchNorm+ReLU and are written to
@@ -360,6 +563,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a_in, const int tiles_
 
 #if defined(MVLM_CONV_TIMING)
     const long long t_start = clock64();
+    long long t_loop = t_start;  // (Winograd tiles: the prologue is counted with the K loop)
 #endif
     const int H = a.H, W = a.W;
     const int Hin = a.up_in ? (H >> 1) : H, Win = a.up_in ? (W >> 1) : W;
@@ -484,34 +688,38 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a_in, const int tiles_
             }
         }
     }
-    static_for<0, T_TOT>([&](auto tc) { issue_item<C, decltype(tc)::value, true, IN2>(a, cb0, tid, HWin, sbn, goff, woff_g, regs, smem, goff2); });
-    if (a.pre_scale != nullptr) {
-        for (int i = tid; i < a.cin_pad; i += 256) {
-            sbn[i] = a.pre_scale[i];
-            sbn[C::BN_MAXC + i] = a.pre_shift[i];
+    if constexpr (C::WINO) {
+        wino_main<C>(a, smem, tid, y0, x0, b0, co0, HWin, woff_g, woff, acc);
+    } else {
+        static_for<0, T_TOT>([&](auto tc) { issue_item<C, decltype(tc)::value, true, IN2>(a, cb0, tid, HWin, sbn, goff, woff_g, regs, smem, goff2); });
+        if (a.pre_scale != nullptr) {
+            for (int i = tid; i < a.cin_pad; i += 256) {
+                sbn[i] = a.pre_scale[i];
+                sbn[C::BN_MAXC + i] = a.pre_shift[i];
+            }
         }
-    }
-    static_for<0, T_TOT>([&](auto tc) { write_item<C, decltype(tc)::value, IN2>(a, cb0, tid, smem, goff, regs); });
-    __syncthreads();
+        static_for<0, T_TOT>([&](auto tc) { write_item<C, decltype(tc)::value, IN2>(a, cb0, tid, smem, goff, regs); });
+        __syncthreads();
 
 #if defined(MVLM_CONV_TIMING)
-    const long long t_loop = clock64();
+        t_loop = clock64();
 #endif
-    int cur = 0;
-    for (int cb = cb0 + C::CK; cb < cb1; cb += C::CK) {
+        int cur = 0;
+        for (int cb = cb0 + C::CK; cb < cb1; cb += C::CK) {
 #if defined(MVLM_ABLATE_NO_STAGING)  // timing experiment only: wrong results
-        compute_chunk<C, false, AMAX, IN2>(a, smem + cur * C::STAGE, smem + (cur ^ 1) * C::STAGE, cb, tid, HWin, sbn, woff, pixoff,
-                                goff, woff_g, regs, acc, woff16, pixoff16, acc16, s4, goff2);
+            compute_chunk<C, false, AMAX, IN2>(a, smem + cur * C::STAGE, smem + (cur ^ 1) * C::STAGE, cb, tid, HWin, sbn, woff, pixoff,
+                                    goff, woff_g, regs, acc, woff16, pixoff16, acc16, s4, goff2);
 #else
-        compute_chunk<C, true, AMAX, IN2>(a, smem + cur * C::STAGE, smem + (cur ^ 1) * C::STAGE, cb, tid, HWin, sbn, woff, pixoff,
-                               goff, woff_g, regs, acc, woff16, pixoff16, acc16, s4, goff2);
+            compute_chunk<C, true, AMAX, IN2>(a, smem + cur * C::STAGE, smem + (cur ^ 1) * C::STAGE, cb, tid, HWin, sbn, woff, pixoff,
+                                   goff, woff_g, regs, acc, woff16, pixoff16, acc16, s4, goff2);
 #endif
 #if !defined(MVLM_ABLATE_NO_BARRIER)
-        __syncthreads();  // next stage complete; everybody is done reading this one
+            __syncthreads();  // next stage complete; everybody is done reading this one
 #endif
-        cur ^= 1;
+            cur ^= 1;
+        }
+        compute_chunk<C, false, AMAX, IN2>(a, smem + cur * C::STAGE, nullptr, 0, tid, HWin, sbn, woff, pixoff, goff, woff_g, regs, acc, woff16, pixoff16, acc16, s4, goff2);
     }
-    compute_chunk<C, false, AMAX, IN2>(a, smem + cur * C::STAGE, nullptr, 0, tid, HWin, sbn, woff, pixoff, goff, woff_g, regs, acc, woff16, pixoff16, acc16, s4, goff2);
 #if defined(MVLM_CONV_TIMING)
     const long long t_epi = clock64();
 #endif
@@ -1276,6 +1484,8 @@ int check_variant(mvlm_ctx* ctx, ConvArgs& a, ConvGrid& g) {
     MVLM_REQUIRE(ctx, a.ksize == C::KS, "conv: kernel variant built for another kernel size");
     MVLM_REQUIRE(ctx, !a.in2 || (C::HAS_IN2 && !a.up_in && !a.amax_val && a.in_coff == 0 && a.in2_ctot >= a.cin && !(a.H & 1) && !(a.W & 1) && a.kparts <= 1),
                  "conv: a second input tensor (upsample + skip on the load) is served by the 128-channel 8x32 tile only");
+    MVLM_REQUIRE(ctx, !C::WINO || (!a.up_in && !a.in2 && !a.amax_val && a.up_out != 2 && a.n_par == 1 && a.kparts <= 1),
+                 "conv: the Winograd tiles serve plain, pooling and scattering 3x3 layers (no upsampled / second input, no fused argmax, no K parts)");
     MVLM_REQUIRE(ctx, a.W % C::TW == 0 && a.H % C::TRI == 0, "conv: spatial size not a multiple of the tile");
     MVLM_REQUIRE(ctx, !C::SPLITK || a.cin_pad % 32 == 0, "conv: split-K tiles need 32-channel chunks");
     MVLM_REQUIRE(ctx, !(C::SPLITK && C::NT > 1) || (a.kparts <= 1 && !a.amax_val), "conv: the two-column split-K tiles have no K-parts / argmax form");

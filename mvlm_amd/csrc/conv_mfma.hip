@@ -29,6 +29,12 @@
 //   (paulsenpredictor.py:273), the hourglass "upsample + skip add" (:334-359) as a 2x2
 //   scatter, and for the last layer the per-(view, landmark) argmax
 //   (paulsenpredictor.py:123) so the [N,NL,256,256] heatmaps never reach HBM.
+//
+//   The large stride-1 3x3 layers also exist as F(2,3) Winograd along y (conv_kernel.h: Cfg::WINO, variants conv3x3w_*):
+//   row pairs of transformed inputs x load-time-transformed weights, four GEMMs over K = (kx, cin), 4 MFMAs per output pair
+//   where the direct form spends 6 - same instruction, fp32 in and out.  mvlm_conv_wino_variant() routes a launch there where
+//   the measured table conv_tuned_wino.h says it is faster (mvlm_cnn_set_winograd / MVLM_WINOGRAD: 0 never, 1 table, 2 always).
+//   A profile record of such a launch counts the FLOPs its MFMAs execute (12 Cin Cout H W B, not 18).
 #include <cstdlib>
 #include <string>
 #include <vector>
@@ -39,6 +45,7 @@
 #include "conv_tuned.h"
 #include "conv_tuned_net.h"
 #include "conv_pair_tuned.h"
+#include "conv_tuned_wino.h"
 #include <map>
 #include <mutex>
 #include <algorithm>
@@ -131,7 +138,74 @@ int pick_variant(const mvlm_ctx* ctx, const ConvArgs& a, bool rules_only = false
     return it->variant;
 }
 
+// The Winograd variant that can serve this launch at all (shape and features), or -1.
+int wino_candidate(const ConvArgs& a) {
+    if (a.ksize != 3 || a.up_in || a.in2 || a.amax_val || a.up_out == 2 || a.n_par != 1 || a.H != a.W) return -1;
+    int found = -1;
+#define X(id, name, ...)                                                                                             \
+    {                                                                                                                \
+        using V = __VA_ARGS__;                                                                                       \
+        if (found < 0 && a.W % V::TW == 0 && a.H % V::TRI == 0 && a.cout_pad % V::COUT_T == 0 && a.cin_pad % V::CK == 0 && \
+            a.cin_pad <= V::BN_MAXC)                                                                                 \
+            found = id;                                                                                              \
+    }
+    MVLM_CONV_VARIANTS_W0(X)
+#undef X
+    return found;
+}
+
 }  // namespace
+
+bool mvlm_conv_variant_is_wino(int v) {
+    if (v < 0 || v >= 256) return false;
+    switch (v) {
+#define X(id, name, ...) \
+    case id:             \
+        return true;
+        MVLM_CONV_VARIANTS_W0(X)
+#undef X
+    }
+    return false;
+}
+
+bool mvlm_conv_wino_serves_slot(int ksize, int cin_pad, int cout_pad) {
+    if (ksize != 3) return false;
+#define X(id, name, ...)                                                  \
+    {                                                                     \
+        using V = __VA_ARGS__;                                            \
+        if (cout_pad % V::COUT_T == 0 && cin_pad % V::CK == 0) return true; \
+    }
+    MVLM_CONV_VARIANTS_W0(X)
+#undef X
+    return false;
+}
+
+// Winograd routing of the exact path, a pure function of (shape, kind, batch) and the context's settings: a tuning override
+// that names a Winograd variant first; then mode 0 never, 2 wherever a variant can serve, 1 the measured table
+// (conv_tuned_wino.h: the Winograd launch beat what runs otherwise from `min_batch` views per device batch on).
+int mvlm_conv_wino_variant(const mvlm_ctx* ctx, const ConvArgs& a) {
+    const int cand = wino_candidate(a);
+    if (cand < 0) return -1;
+    const int kind = mvlm_conv_kind(a);
+    if (ctx)
+        for (const ConvOverride& o : ctx->conv_overrides)
+            if (o.ksize == a.ksize && o.cin_pad == a.cin_pad && o.cout_pad == a.cout_pad && o.size == a.H && o.kind == kind)
+                return mvlm_conv_variant_is_wino(o.variant) ? o.variant : -1;
+    const int mode = ctx ? ctx->conv_winograd : 1;
+    if (mode == 0) return -1;
+    if (mode == 2) return cand;
+    for (int i = 0; i < MVLM_CONV_TUNED_WINO_N; ++i) {
+        const ConvTunedWino& e = MVLM_CONV_TUNED_WINO[i];
+        if (e.cin_pad == a.cin_pad && e.cout_pad == a.cout_pad && e.size == a.H && e.kind == kind && a.B >= e.min_batch) return e.variant;
+    }
+    return -1;
+}
+
+// the variant a launch runs on: the Winograd routing first, the direct tiles' tables and rules otherwise
+static int route_variant(const mvlm_ctx* ctx, const ConvArgs& a) {
+    const int w = mvlm_conv_wino_variant(ctx, a);
+    return w >= 0 ? w : pick_variant(ctx, a);
+}
 
 // Variant ids >= 256 are a split-K variant (low byte) whose input channels are divided over 2 / 4 / 8 workgroups per
 // output tile (id = base + 256 log2(parts)); the partial tiles meet in a per-context workspace (one per launch stream).
@@ -187,7 +261,7 @@ const char* mvlm_conv_variant_name_impl(int v) {
 bool mvlm_conv_in2_ok(const mvlm_ctx* ctx, const ConvArgs& a) {
     if (a.ksize != 3 || a.up_in || a.up_out || a.amax_val || a.in_coff != 0 || (a.H & 1) || a.H != a.W) return false;
     if (ctx && ctx->conv_force_variant != -1) return false;
-    return pick_variant(ctx, a) == 0;
+    return route_variant(ctx, a) == 0;  // (a Winograd tile has no second-input form)
 }
 
 int mvlm_conv_kind(const ConvArgs& a) { return a.up_out == 1 ? 1 : ((a.pool_out || a.pool_hint) ? 2 : 0); }
@@ -197,7 +271,7 @@ bool mvlm_conv_can_pool(const mvlm_ctx* ctx, const ConvArgs& a_in) {
     ConvArgs a = a_in;
     a.pool_hint = 1;
     if (ctx && ctx->conv_force_variant >= 0) return mvlm_conv_variant_can_pool(ctx->conv_force_variant);
-    switch (pick_variant(ctx, a) & 255) {
+    switch (route_variant(ctx, a) & 255) {
 #define X(id, name, ...)                                                                                   \
     case id: {                                                                                             \
         using V = __VA_ARGS__;                                                                             \
@@ -327,8 +401,11 @@ int mvlm_launch_conv(mvlm_ctx* ctx, const ConvArgs& a, int* variant_out) {
     MVLM_REQUIRE(ctx, !a.out || px * a.out_ctot * (a.up_out ? 4 : 1) < lim, "conv: output exceeds 32-bit element offsets");
     MVLM_REQUIRE(ctx, a.up_out != 1 || px * a.skip_ctot * 4 < lim, "conv: skip tensor exceeds 32-bit element offsets");
     // conv_force_variant (mvlm_conv_bench only): >= 0 that variant, -2 the rules without the tuned table
-    const int v = ctx->conv_force_variant >= 0 ? ctx->conv_force_variant : pick_variant(ctx, a, ctx->conv_force_variant == -2);
+    const int v = ctx->conv_force_variant >= 0 ? ctx->conv_force_variant
+                  : ctx->conv_force_variant == -2 ? pick_variant(ctx, a, true) : route_variant(ctx, a);
     MVLM_REQUIRE(ctx, v >= 0, "conv: no kernel variant for this shape");
+    const bool wino = mvlm_conv_variant_is_wino(v);
+    MVLM_REQUIRE(ctx, !wino || a.w_wino, "conv: a Winograd tile needs the layer's transformed weights (mvlm_pack_winograd_weights)");
     MVLM_REQUIRE(ctx, !a.in2 || v == 0, "conv: a second input tensor needs the 128-channel 8x32 tile (ask mvlm_conv_in2_ok first)");
     MVLM_REQUIRE(ctx, !a.in2 || px / 4 * a.in2_ctot < lim, "conv: second input exceeds 32-bit element offsets");
     MVLM_REQUIRE(ctx, !a.pool_out || mvlm_conv_variant_can_pool(v), "conv: this shape's kernel variant cannot emit the pooled tensor");
@@ -338,6 +415,7 @@ int mvlm_launch_conv(mvlm_ctx* ctx, const ConvArgs& a, int* variant_out) {
     MVLM_REQUIRE(ctx, v < 1024, "conv: unknown kernel variant");
     ConvArgs b = a;
     b.kparts = 1 << (v >> 8);
+    if (wino) b.w = a.w_wino;
     switch (v & 255) {
 #define X(id, name, ...) \
     case id:             \
@@ -361,6 +439,7 @@ extern "C" int mvlm_conv_variant_serves(int variant, int ksize, int cin_pad, int
     case id: {                                                                                                               \
         using V = __VA_ARGS__;                                                                                               \
         if (V::KS != 3 || V::TAIL16 || V::COUT_T == 96) return 0;                                                            \
+        if (V::WINO && cin_pad > V::BN_MAXC) return 0;                                                                       \
         if (size % V::TW != 0 || size % V::TRI != 0 || cout_pad % V::COUT_T != 0 || cin_pad % V::CK != 0) return 0;          \
         if (V::SPLITK && cin_pad % 32 != 0) return 0;                                                                        \
         if (parts > 1 && (!V::SPLITK || V::PIX_T != 32 || cin_pad % (parts * V::CK) != 0)) return 0;                         \
@@ -393,5 +472,26 @@ extern "C" int mvlm_conv_set_override(mvlm_ctx* ctx, int ksize, int cin_pad, int
     for (auto& g : ctx->cnn.graphs)
         if (g.exec) hipGraphExecDestroy(g.exec);
     ctx->cnn.graphs.clear();
+    return 0;
+}
+
+// ---- Winograd weights -----------------------------------------------------------------------------------------------------
+// Filter column g0, g1, g2 (ky = 0, 1, 2) of every (kx, cin, cout) -> u0 = g0, u1 = (g0 + g1 + g2) / 2, u2 = (g0 - g1 + g2) / 2,
+// u3 = g2, in float64 from the fp32 weights, rounded once.  Slice t * 3 + kx of the result is u_t at kx; padded channels stay zero.
+void mvlm_winograd_transform(const float* w9, int cin_pad, int cout_pad, float* w12) {
+    const size_t n = size_t(cin_pad) * cout_pad;
+    for (int kx = 0; kx < 3; ++kx)
+        for (size_t i = 0; i < n; ++i) {
+            const double g0 = w9[size_t(kx) * n + i], g1 = w9[size_t(3 + kx) * n + i], g2 = w9[size_t(6 + kx) * n + i];
+            w12[size_t(kx) * n + i] = float(g0);
+            w12[size_t(3 + kx) * n + i] = float((g0 + g1 + g2) * 0.5);
+            w12[size_t(6 + kx) * n + i] = float((g0 - g1 + g2) * 0.5);
+            w12[size_t(9 + kx) * n + i] = float(g2);
+        }
+}
+
+extern "C" int mvlm_pack_winograd_weights(const float* w9_host, int cin_pad, int cout_pad, float* w12_host) {
+    if (!w9_host || !w12_host || cin_pad <= 0 || cout_pad <= 0) return 1;
+    mvlm_winograd_transform(w9_host, cin_pad, cout_pad, w12_host);
     return 0;
 }

@@ -63,7 +63,12 @@
     X(30, "conv3x3_sk16_t8x8", Cfg<32, 8, 8, 1, 3, 16, true>) \
     X(31, "conv3x3_sk8_t8x8", Cfg<32, 8, 8, 1, 3, 8, true>) \
     X(32, "conv3x3_sk16_t4x16", Cfg<32, 16, 4, 1, 3, 16, true>)
+// F(2,3) Winograd along y (KS parameter 32 = "3x3 as F(2,3)", conv_kernel.h: Cfg::WINO): 4 MFMAs per output pair and
+// (kx, cin) instead of 6 on transformed rows and host-transformed weights ([12][cin_pad][cout_pad]).  Instantiated in
+// conv_inst_w0.hip, built into build/wino/ (occupancy table tests/golden/kernel_occupancy_wino.json).
+#define MVLM_CONV_VARIANTS_W0(X) \
+    X(40, "conv3x3w_c64_t8x32", Cfg<64, 32, 8, 1, 32, 4>)
 #define MVLM_CONV_VARIANTS(X) \
-    MVLM_CONV_VARIANTS_G0(X) MVLM_CONV_VARIANTS_G1(X) MVLM_CONV_VARIANTS_G2(X) MVLM_CONV_VARIANTS_G3(X) MVLM_CONV_VARIANTS_G4(X) MVLM_CONV_VARIANTS_G5(X) MVLM_CONV_VARIANTS_G6(X) MVLM_CONV_VARIANTS_G7(X) MVLM_CONV_VARIANTS_G8(X) MVLM_CONV_VARIANTS_G9(X) MVLM_CONV_VARIANTS_G10(X) MVLM_CONV_VARIANTS_G11(X) MVLM_CONV_VARIANTS_G12(X) MVLM_CONV_VARIANTS_G13(X) MVLM_CONV_VARIANTS_G14(X) MVLM_CONV_VARIANTS_G15(X)
+    MVLM_CONV_VARIANTS_G0(X) MVLM_CONV_VARIANTS_G1(X) MVLM_CONV_VARIANTS_G2(X) MVLM_CONV_VARIANTS_G3(X) MVLM_CONV_VARIANTS_G4(X) MVLM_CONV_VARIANTS_G5(X) MVLM_CONV_VARIANTS_G6(X) MVLM_CONV_VARIANTS_G7(X) MVLM_CONV_VARIANTS_G8(X) MVLM_CONV_VARIANTS_G9(X) MVLM_CONV_VARIANTS_G10(X) MVLM_CONV_VARIANTS_G11(X) MVLM_CONV_VARIANTS_G12(X) MVLM_CONV_VARIANTS_G13(X) MVLM_CONV_VARIANTS_G14(X) MVLM_CONV_VARIANTS_G15(X) MVLM_CONV_VARIANTS_W0(X)
 #define MVLM_CONV_N_GROUPS 16
 #endif

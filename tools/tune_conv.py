@@ -20,7 +20,6 @@ from pathlib import Path
 REPO = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(REPO))
 
-N_VARIANTS = 33
 # tiles that fold several images into one MFMA column are only used at the level they were written for
 NATIVE_WIDTH = {"conv3x3_c32_t8x8x2": 8, "conv3x3_c32_t4x4x8": 4, "conv3x3_sk_t4x4x2": 4, "conv3x3_sk16_t4x4x2": 4, "conv3x3_sk8_t4x4x2": 4}
 HEADER = REPO / "mvlm_amd" / "csrc" / "conv_tuned.h"
@@ -53,10 +52,13 @@ def main():
             users = shapes.setdefault(key, [])
             if s.name not in users:
                 users.append(s.name)
-    names = {v: lib.mvlm_conv_variant_name(v).decode() for v in range(N_VARIANTS)}
+    # the base ids the library names (the split-operand kernels' 61 / 62 aside)
+    # (the Winograd tiles, conv3x3w_*, are tuned in the network only: tools/tune_in_network.py --winograd)
+    names = {v: lib.mvlm_conv_variant_name(v).decode() for v in range(61)
+             if lib.mvlm_conv_variant_name(v).decode() != "?" and not lib.mvlm_conv_variant_name(v).decode().startswith("conv3x3w_")}
     # split-K tiles with the input channels divided over 2 / 4 workgroups per output tile (id + 256 log2(parts)): they
     # only pay at the 8x8 / 4x4 levels of small batches (measured: slower from 16x16 up)
-    kpart_ids = [v + 256 * lg for v in range(N_VARIANTS) if names[v].startswith("conv3x3_sk") for lg in (1, 2)]
+    kpart_ids = [v + 256 * lg for v in names if names[v].startswith("conv3x3_sk") for lg in (1, 2)]
     names.update({v: lib.mvlm_conv_variant_name(v).decode() for v in kpart_ids})
     table = []
     for batch in [int(b) for b in args.batches.split(",")]:
@@ -68,7 +70,7 @@ def main():
                 continue
             auto_v, auto_ms = used.value, ms.value
             res = {}
-            for v in list(range(N_VARIANTS)) + (kpart_ids if k == 3 and size <= 8 and batch <= 32 else []):
+            for v in sorted(names) + (kpart_ids if k == 3 and size <= 8 and batch <= 32 else []):
                 if names[v] == "?" or not names[v].startswith(f"conv{k}x{k}") or NATIVE_WIDTH.get(names[v].split("_k")[0], size) != size:
                     continue
                 rc = lib.mvlm_conv_bench(ctx.handle, batch, cin, cout, k, size, flags, v, args.iters, C.byref(ms), C.byref(used))

@@ -21,7 +21,6 @@ from pathlib import Path
 REPO = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(REPO))
 HEADER = REPO / "mvlm_amd" / "csrc" / "conv_pair_tuned.h"
-N_VARIANTS = 33
 # (cin, cout, flags) of a 256-channel residual block's conv1 / conv2 / conv3 (flags: 1 pre-BN, 2 residual + raw copy)
 CONVS = [(256, 128, 3), (128, 64, 3), (64, 64, 3)]
 SIZES = [128, 64, 32, 16, 8]
@@ -39,7 +38,7 @@ def main():
 
     ctx = _lib.get_context(0)
     lib = ctx.lib
-    names = {v: lib.mvlm_conv_variant_name(v).decode() for v in range(N_VARIANTS)}
+    names = {v: lib.mvlm_conv_variant_name(v).decode() for v in range(61) if lib.mvlm_conv_variant_name(v).decode() != "?"}
     base_ids = [v for v, n in names.items() if n.startswith("conv3x3_") and "c80" not in n and "c84" not in n and "c96" not in n]
     table = []
     for batch in [int(b) for b in args.batches.split(",")]:

@@ -12,6 +12,12 @@ kernels, which a pool-capable tile makes unnecessary) are summed.  One sweep of 
 first; winners that beat the current choice by more than 2 % stay in place for the keys after them.
 
 usage: python tools/tune_in_network.py [--batches 8,12,...] [--write-header] [--out gpurun_out/conv_net_tune.json]
+
+--winograd: the table of the Winograd tiles (conv_tuned_wino.h) instead.  Per batch, starting from the direct path (mode 0),
+every (shape, kind) a Winograd variant can serve is switched to it alone, largest first; the launches that CHANGED against the
+pass before it (the layer's own, the pair launch it left, a second-input form it ended) are summed on both sides, and the key
+stays switched where the new launches are faster by more than --min-gain.  An entry names the smallest tuned batch from which
+the key won at every tuned batch above it.
 """
 from __future__ import annotations
 
@@ -28,8 +34,17 @@ import numpy as np
 REPO = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(REPO))
 HEADER = REPO / "mvlm_amd" / "csrc" / "conv_tuned_net.h"
-N_VARIANTS = 33
+WINO_HEADER = REPO / "mvlm_amd" / "csrc" / "conv_tuned_wino.h"
 CAP = 1024
+
+
+def variant_ids(lib):
+    """the base ids the library names (mvlm_conv_variant_name), the split-operand kernels' 61 / 62 aside"""
+    return [v for v in range(61) if lib.mvlm_conv_variant_name(v).decode() != "?"]
+
+
+def wino_ids(lib):
+    return [v for v in variant_ids(lib) if lib.mvlm_conv_variant_name(v).decode().startswith("conv3x3w_")]
 
 
 def profile_pass(pred, images, out, passes):
@@ -66,7 +81,10 @@ def main():
     ap.add_argument("--passes", type=int, default=3)
     ap.add_argument("--min-gain", type=float, default=0.02)
     ap.add_argument("--max-size", type=int, default=256, help="only keys of feature maps up to this size (re-tuning the small levels)")
+    ap.add_argument("--winograd", action="store_true", help="tune the Winograd tiles' table (conv_tuned_wino.h) instead")
     args = ap.parse_args()
+    if args.winograd:
+        return tune_winograd(args)
 
     import torch
 
@@ -78,7 +96,7 @@ def main():
         name, mode = net.split(":")
         pred = (DTU3DPredictor if name == "dtu3d" else BU3DFEPredictor)(image_mode=mode, weights="synthetic:0", verbose=False)
         ctx, lib = pred.ctx, pred.ctx.lib
-        names = {v: lib.mvlm_conv_variant_name(v).decode() for v in range(N_VARIANTS)}
+        ids = [v for v in variant_ids(lib) if v not in wino_ids(lib)]  # (the Winograd tiles have a table of their own: --winograd)
         nl = pred.get_lm_count()
         for batch in [int(b) for b in args.batches.split(",")]:
             rs = np.random.RandomState(batch)
@@ -102,9 +120,9 @@ def main():
                 if (key, batch) in seen_keys:
                     continue
                 seen_keys.add((key, batch))
-                cands = [v for v in range(N_VARIANTS) if lib.mvlm_conv_variant_serves(v, *key)]
+                cands = [v for v in ids if lib.mvlm_conv_variant_serves(v, *key)]
                 if key[3] <= 8 and batch <= 32:
-                    cands += [v + 256 * lg for v in range(N_VARIANTS) for lg in (1, 2) if lib.mvlm_conv_variant_serves(v + 256 * lg, *key)]
+                    cands += [v + 256 * lg for v in ids for lg in (1, 2) if lib.mvlm_conv_variant_serves(v + 256 * lg, *key)]
                 cur = current[key]
                 if len(cands) < 2:
                     continue
@@ -142,6 +160,137 @@ def main():
     Path(args.out).write_text(json.dumps(rows, indent=0))
     if args.write_header:
         write_header(rows, args.merge)
+
+
+def min_records(runs):
+    """per launch of a pass the quietest of the passes' timings (the launch sequence of a configuration is fixed)"""
+    assert all(len(r) == len(runs[0]) for r in runs)
+    return [(runs[0][i][0], runs[0][i][1], min(r[i][2] for r in runs), runs[0][i][3]) for i in range(len(runs[0]))]
+
+
+def changed_us(before, after):
+    """sum of the launches of `before` that `after` does not have with the same (slot, variant), and the other way round"""
+    from collections import Counter
+
+    cb, ca = Counter((s, v) for s, v, _, _ in before), Counter((s, v) for s, v, _, _ in after)
+    common = cb & ca
+
+    def rest(recs):
+        left, tot, rows = Counter(common), 0.0, []
+        for s, v, t, sh in recs:
+            if left[(s, v)] > 0:
+                left[(s, v)] -= 1
+            else:
+                tot += t
+                rows.append((s, v, round(t, 1)))
+        return tot, rows
+
+    return rest(before), rest(after)
+
+
+def tune_winograd(args):
+    import torch
+
+    from mvlm_amd.prediction import BU3DFEPredictor, DTU3DPredictor
+
+    rows = []
+    batches = sorted((int(b) for b in args.batches.split(",")), reverse=True)
+    for net in args.nets.split(","):
+        name, mode = net.split(":")
+        pred = (DTU3DPredictor if name == "dtu3d" else BU3DFEPredictor)(image_mode=mode, weights="synthetic:0", verbose=False)
+        ctx, lib = pred.ctx, pred.ctx.lib
+        wids = wino_ids(lib)
+        nl = pred.get_lm_count()
+        ctx.check(lib.mvlm_cnn_set_winograd(ctx.handle, 0))
+        for batch in batches:
+            rs = np.random.RandomState(batch)
+            images = torch.from_numpy(rs.rand(batch, 256, 256, 4).astype(np.float32)).cuda()
+            out = torch.empty((nl, batch, 3), dtype=torch.float32, device="cuda")
+            pred.set_execution(graphs=False)
+            ctx.check(lib.mvlm_conv_set_override(ctx.handle, 0, 0, 0, 0, 0, -1))
+            pred.predict_device(images, out=out)
+            ctx.check(lib.mvlm_cnn_set_profiling(ctx.handle, 1))
+            state = min_records(profile_pass(pred, images, out, args.passes))
+            total0 = sum(t for _, _, t, _ in state)
+            keys = defaultdict(float)
+            # which (shape, kind) keys exist: one pass with everything servable switched
+            ctx.check(lib.mvlm_cnn_set_winograd(ctx.handle, 2))
+            everything = min_records(profile_pass(pred, images, out, 1))
+            ctx.check(lib.mvlm_cnn_set_winograd(ctx.handle, 0))
+            for s, v, t, sh in everything:
+                if s >= 0 and v in wids:
+                    keys[sh[:5]] += t
+            for key in sorted(keys, key=lambda k: -keys[k]):
+                best = None
+                for v in wids:
+                    if not lib.mvlm_conv_variant_serves(v, *key):
+                        continue
+                    ctx.check(lib.mvlm_conv_set_override(ctx.handle, *key, v))
+                    cand = min_records(profile_pass(pred, images, out, args.passes))
+                    (us0, rows0), (us1, rows1) = changed_us(state, cand)
+                    if best is None or us1 < best[2]:
+                        best = (v, us0, us1, rows0, rows1, cand)
+                    ctx.check(lib.mvlm_conv_set_override(ctx.handle, *key, -1))
+                if best is None:
+                    continue
+                v, us0, us1, rows0, rows1, cand = best
+                win = us1 < (1.0 - args.min_gain) * us0
+                if win:
+                    ctx.check(lib.mvlm_conv_set_override(ctx.handle, *key, v))
+                    state = cand
+                rows.append(dict(net=net, batch=batch, key=list(key), variant=v, name=lib.mvlm_conv_variant_name(v).decode(),
+                                 direct_us=round(us0, 1), winograd_us=round(us1, 1), kept=bool(win), direct=rows0, winograd=rows1))
+                print(f"{net} B{batch:3d} {key[1]:3d}->{key[2]:3d} @{key[3]:3d} kind {key[4]}  direct {us0:9.1f} us ({len(rows0)} launches)  "
+                      f"{lib.mvlm_conv_variant_name(v).decode()} {us1:9.1f} us ({len(rows1)} launches)  {us0 / us1:5.2f}x{'  <-- kept' if win else ''}", flush=True)
+            total1 = sum(t for _, _, t, _ in state)
+            ctx.check(lib.mvlm_cnn_set_profiling(ctx.handle, 0))
+            print(f"== {net} batch {batch}: conv kernels of a pass {total0 / 1e3:.3f} ms -> {total1 / 1e3:.3f} ms", flush=True)
+            rows.append(dict(net=net, batch=batch, summary=True, before_us=round(total0, 1), after_us=round(total1, 1)))
+            del images, out
+        ctx.check(lib.mvlm_conv_set_override(ctx.handle, 0, 0, 0, 0, 0, -1))
+        del pred
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(args.out).write_text(json.dumps(rows, indent=0))
+    if args.write_header:
+        write_wino_header(rows, batches, Path(args.out).parent)
+
+
+def write_wino_header(rows, batches, copy_dir=None):
+    """entry = the smallest tuned batch from which the key was kept at every tuned batch above it, in every net that has it"""
+    kept = defaultdict(dict)  # key -> batch -> (all nets kept, variant, note)
+    for r in rows:
+        if r.get("summary"):
+            continue
+        k, b = tuple(r["key"]), r["batch"]
+        ok, v, note = kept[k].get(b, (True, r["variant"], ""))
+        kept[k][b] = (ok and r["kept"] and v == r["variant"], v, note + f" B{b} {r['direct_us']} -> {r['winograd_us']} us [{r['net']}]")
+    lines = ["// GENERATED by tools/tune_in_network.py --winograd --write-header on an MI355X: 3x3 layers that run faster on a Winograd tile",
+             "// than on what the direct path launches for them (its pair launches and second-input forms included), timed INSIDE a forward",
+             "// pass of the landmark network.  {cin_pad, cout_pad, size, kind, min_batch, variant}: from min_batch views per device batch on.",
+             f"// Tuned at {', '.join(str(b) for b in sorted(batches, reverse=True))} views per device batch ({', '.join(sorted({r['net'] for r in rows}))}): min_batch is the smallest of these from which",
+             "// the key won at every tuned batch above it; the note gives the timings at that batch.",
+             "#ifndef MVLM_CONV_TUNED_WINO_H", "#define MVLM_CONV_TUNED_WINO_H",
+             "struct ConvTunedWino { short cin_pad, cout_pad, size, kind, min_batch, variant; };",
+             "static const ConvTunedWino MVLM_CONV_TUNED_WINO[] = {"]
+    n = 0
+    for k in sorted(kept):
+        min_batch, variant, note = None, None, ""
+        for b in sorted(kept[k], reverse=True):
+            ok, v, nt = kept[k][b]
+            if not ok or (variant is not None and v != variant):
+                break
+            min_batch, variant, note = b, v, nt
+        if min_batch is not None:
+            lines.append(f"    {{{k[1]}, {k[2]}, {k[3]}, {k[4]}, {min_batch}, {variant}}},  //{note}")
+            n += 1
+    if n == 0:
+        lines.append("    {0, 0, 0, 0, 0, -1},")
+    lines += ["};", f"static const int MVLM_CONV_TUNED_WINO_N = {n};", "#endif", ""]
+    WINO_HEADER.write_text("\n".join(lines))
+    if copy_dir is not None:  # a copy beside the tuner's JSON (--out)
+        Path(copy_dir).mkdir(parents=True, exist_ok=True)
+        (Path(copy_dir) / "conv_tuned_wino.h").write_text("\n".join(lines))
+    print(f"wrote {WINO_HEADER} ({n} entries)")
 
 
 def write_header(rows, merge=False):
