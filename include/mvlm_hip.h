@@ -72,6 +72,11 @@ int mvlm_obj_info(const mvlm_obj* obj, int64_t* n_verts, int64_t* n_tris, int* h
 /* copies into caller arrays sized from mvlm_obj_info: verts f32[V,3], uvs f32[V,2] (may be NULL),
  * tris i32[T,3] */
 int mvlm_obj_copy(const mvlm_obj* obj, float* verts, float* uvs, int32_t* tris);
+/* per-point colours, where the file carries them (.ply uchar red green blue / diffuse_*, .vtk POINT_DATA COLOR_SCALARS with 3
+ * or 4 components, .obj "v x y z r g b" on every v line): *has = 1, and rgb u8[V,3] receives them (a duplicated point keeps
+ * its colour).  mvlm_obj_copy_colors on a mesh without colours returns MVLM_OBJ_ERR_EMPTY. */
+int mvlm_obj_has_colors(const mvlm_obj* obj, int* has);
+int mvlm_obj_copy_colors(const mvlm_obj* obj, uint8_t* rgb);
 void mvlm_obj_free(mvlm_obj* obj);
 /* The reference's legacy multi-format reader (Utils3D.multi_read_surface, utils3d.py:389-423) by file extension:
  * .obj (as above), .ply (ASCII / binary), .stl (ASCII / binary, coincident points merged like vtkSTLReader),
@@ -90,6 +95,13 @@ int mvlm_mesh_read(const char* path, mvlm_obj** out, char* err, int err_len);
 int mvlm_mesh_upload(mvlm_ctx* ctx, const float* verts_host, const float* uvs_host, int n_verts,
                      const int32_t* tris_host, int n_tris, const uint8_t* tex_host, int tex_h, int tex_w,
                      mvlm_mesh** out);
+/* Per-vertex colours, rgb_host u8[V,3], for a mesh made by any mvlm_mesh_upload* entry (n_verts must be the mesh's count).
+ * They shade the RGB planes when the render's shading is 0 (unlit) and the mesh has NO usable texture (no uvs or no texture
+ * image): per channel the plane through vertex 0 of c / 255, clamped to [0,1], then converted through 16-bit fixed point like
+ * the OpenGL the contract is pinned to (rm_color_u8, DESIGN.md 5.1: round-to-nearest but for values within 1/512 of k + 1/2).
+ * A mesh with a texture and uvs renders with its texture alone (VTK would multiply texel and colour: not built); geometry shading and the
+ * depth plane never see colours.  Same staging, copy stream and ready event as the mesh upload; may run on a reader thread. */
+int mvlm_mesh_upload_colors(mvlm_ctx* ctx, mvlm_mesh* mesh, const uint8_t* rgb_host, int n_verts);
 void mvlm_mesh_free(mvlm_ctx* ctx, mvlm_mesh* mesh);
 
 /* ---- JPEG texture decoded on the device (replaces vtkJPEGReader in obj_to_actor, utils3d.py:28-34 / :42-48, and in

@@ -34,9 +34,12 @@ SIGNATURES = {
     "mvlm_mesh_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p), C.c_char_p, C.c_int]),
     "mvlm_obj_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     "mvlm_obj_copy": (C.c_int, [C.c_void_p, c_float_p, c_float_p, c_int32_p]),
+    "mvlm_obj_has_colors": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "mvlm_obj_copy_colors": (C.c_int, [C.c_void_p, c_uint8_p]),
     "mvlm_obj_free": (None, [C.c_void_p]),
     "mvlm_mesh_upload": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_int, c_int32_p, C.c_int, c_uint8_p,
                                    C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "mvlm_mesh_upload_colors": (C.c_int, [C.c_void_p, C.c_void_p, c_uint8_p, C.c_int]),
     "mvlm_mesh_free": (None, [C.c_void_p, C.c_void_p]),
     "mvlm_jpeg_info": (C.c_int, [c_uint8_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_int]),
     "mvlm_mesh_upload_jpeg": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_int, c_int32_p, C.c_int, c_uint8_p, C.c_size_t,

@@ -455,18 +455,90 @@ extern "C" int mvlm_mesh_upload_texture(mvlm_ctx* ctx, const float* verts_host, 
     return rc;
 }
 
+// Per-vertex colours for a mesh that any of the upload entries above made: rgb_host u8[V,3] -> u8[V,4] (r g b 255) on the
+// device, through the pinned staging and the upload stream like the mesh itself; the mesh's ready event is recorded again
+// behind the copy, so whatever renders the mesh afterwards waits for the colours too.  May run on a reader thread.  The buffer
+// comes from the mesh pool and is written in full - a recycled one keeps nothing of its previous owner - and a mesh that
+// never had this call has no colours, whatever its buffers held before.  A second call replaces the colours.
+extern "C" int mvlm_mesh_upload_colors(mvlm_ctx* ctx, mvlm_mesh* m, const uint8_t* rgb_host, int n_verts) {
+    MVLM_REQUIRE(ctx, m && rgb_host, "mesh_upload_colors: null pointer");
+    MVLM_REQUIRE(ctx, n_verts == m->n_verts, "mesh_upload_colors: " + std::to_string(n_verts) + " colours for a mesh of " +
+                                                  std::to_string(m->n_verts) + " points");
+    const size_t bytes = size_t(n_verts) * 4;
+    std::lock_guard<std::mutex> upload_lock(ctx->upload_mu);
+    MVLM_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->upload_stream) MVLM_CHECK_HIP(ctx, hipStreamCreateWithFlags(&ctx->upload_stream, hipStreamNonBlocking));
+    const int slot = ctx->upload_stage_next;
+    ctx->upload_stage_next ^= 1;
+    if (ctx->upload_stage_done[slot]) MVLM_CHECK_HIP(ctx, hipEventSynchronize(ctx->upload_stage_done[slot]));
+    if (ctx->upload_stage_cap[slot] < bytes) {
+        if (ctx->upload_stage[slot]) (void)hipHostFree(ctx->upload_stage[slot]);
+        ctx->upload_stage[slot] = nullptr;
+        ctx->upload_stage_cap[slot] = 0;
+        const size_t cap = (bytes + (size_t(4) << 20)) / (size_t(4) << 20) * (size_t(4) << 20);
+        MVLM_CHECK_HIP(ctx, hipHostMalloc(&ctx->upload_stage[slot], cap, hipHostMallocDefault));
+        ctx->upload_stage_cap[slot] = cap;
+    }
+    auto* stage = static_cast<unsigned char*>(ctx->upload_stage[slot]);
+    for (size_t i = 0; i < size_t(n_verts); ++i) {
+        stage[4 * i] = rgb_host[3 * i];
+        stage[4 * i + 1] = rgb_host[3 * i + 1];
+        stage[4 * i + 2] = rgb_host[3 * i + 2];
+        stage[4 * i + 3] = 255;
+    }
+    std::lock_guard<std::mutex> lock(ctx->mu);  // pool, events, the mesh's fields: shared with the launch entry points
+    bool ok = true;
+    void* dst = m->colors;
+    if (dst) {  // replacing: a render that was enqueued with the old colours reads them first
+        hipEvent_t e = ctx->take_event();
+        ok = e && hipEventRecord(e, ctx->stream) == hipSuccess && hipStreamWaitEvent(ctx->upload_stream, e, 0) == hipSuccess;
+        if (e) ctx->event_free.push_back(e);
+    } else {
+        size_t cap = 0;
+        hipEvent_t waited = nullptr;
+        ok = take_upload_buffer(ctx, bytes, bytes, &dst, &cap, &waited);
+        if (ok) {
+            m->cap[4] = cap;
+            m->waited[4] = waited;
+        } else if (dst) {  // (the pool's buffer could not be waited for: back to the allocator)
+            (void)hipFree(dst);
+            if (waited) ctx->event_free.push_back(waited);
+            dst = nullptr;
+        }
+    }
+    ok = ok && hipMemcpyAsync(dst, stage, bytes, hipMemcpyHostToDevice, ctx->upload_stream) == hipSuccess;
+    if (ok) {
+        if (!ctx->upload_stage_done[slot]) ctx->upload_stage_done[slot] = ctx->take_event();
+        if (!m->ready) m->ready = ctx->take_event();
+        ok = ctx->upload_stage_done[slot] && m->ready &&
+             hipEventRecord(ctx->upload_stage_done[slot], ctx->upload_stream) == hipSuccess &&
+             hipEventRecord(m->ready, ctx->upload_stream) == hipSuccess;
+    }
+    if (!ok) (void)hipStreamSynchronize(ctx->upload_stream);  // (whatever was enqueued has left the staging slot)
+    if (dst && !m->colors && !ok) {  // the new buffer stays out of the mesh
+        (void)hipFree(dst);
+        if (m->waited[4]) ctx->event_free.push_back(m->waited[4]);
+        m->cap[4] = 0;
+        m->waited[4] = nullptr;
+        dst = nullptr;
+    }
+    if (ok) m->colors = static_cast<uint8_t*>(dst);
+    MVLM_REQUIRE(ctx, ok, "mesh_upload_colors: device allocation / copy failed");
+    return 0;
+}
+
 // Buffers go back to the context's pool together with an event on the launch stream: whatever was enqueued for this
 // mesh before the free may still read them.  ctx == NULL (or a pool that is full): plain hipFree (which waits for the device).
 extern "C" void mvlm_mesh_free(mvlm_ctx* ctx, mvlm_mesh* m) {
     if (!m) return;
-    void* bufs[4] = {m->verts, m->uvs, m->tris, m->tex};
+    void* bufs[5] = {m->verts, m->uvs, m->tris, m->tex, m->colors};
     constexpr size_t POOL_MAX_BYTES = size_t(1) << 30;
     constexpr size_t POOL_MAX_ENTRIES = 32;
-    hipEvent_t spare[5] = {m->ready, m->waited[0], m->waited[1], m->waited[2], m->waited[3]};
+    hipEvent_t spare[6] = {m->ready, m->waited[0], m->waited[1], m->waited[2], m->waited[3], m->waited[4]};
     if (ctx) {
         std::lock_guard<std::mutex> lock(ctx->mu);
         (void)hipSetDevice(ctx->device);
-        for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < 5; ++i)
             if (bufs[i] && m->cap[i] && ctx->mesh_pool.size() < POOL_MAX_ENTRIES &&
                 ctx->mesh_pool_bytes + m->cap[i] <= POOL_MAX_BYTES) {
                 hipEvent_t ev = ctx->take_event();

@@ -199,12 +199,14 @@ struct mvlm_mesh {
     float* uvs = nullptr;     // [V,2] or null
     int32_t* tris = nullptr;  // [T,3]
     uint8_t* tex = nullptr;   // [H,W,3] or null
+    uint8_t* colors = nullptr;  // [V,4] per-vertex r g b 255 (one aligned 4-byte load per vertex) or null: mvlm_mesh_upload_colors
     int n_verts = 0, n_tris = 0, tex_h = 0, tex_w = 0;
     unsigned long long uid = 0;  // unique per upload (an address can be recycled): key of per-mesh derived data a context keeps
-    size_t cap[4] = {0, 0, 0, 0};  // allocation sizes of verts / uvs / tris / tex (for the ctx's mesh pool)
-    // recorded on the context's upload stream behind the four host-to-device copies; every consumer's stream waits for it
+    size_t cap[5] = {0, 0, 0, 0, 0};  // allocation sizes of verts / uvs / tris / tex / colors (for the ctx's mesh pool)
+    // recorded on the context's upload stream behind the host-to-device copies (again behind the colours' copy, when they
+    // follow); every consumer's stream waits for it
     hipEvent_t ready = nullptr;
-    hipEvent_t waited[4] = {nullptr, nullptr, nullptr, nullptr};  // "previous owner is done" events of recycled buffers
+    hipEvent_t waited[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // "previous owner is done" events of recycled buffers
 };
 
 struct RenderProfileRec {

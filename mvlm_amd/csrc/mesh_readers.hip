@@ -5,15 +5,18 @@
 // texture coordinate per point where the file has them, polygons as triangle fans - the same mvlm_obj
 // handle the OBJ reader fills (obj_reader.hip), so upload, render and snap do not care about the source.
 //
-//   .ply  ASCII and binary little/big endian; element vertex with x y z (+ s t | u v | texture_u texture_v),
-//         element face with a list property (vertex_indices | vertex_index); other elements / properties skipped
+//   .ply  ASCII and binary little/big endian; element vertex with x y z (+ s t | u v | texture_u texture_v, + uchar
+//         red green blue | diffuse_red diffuse_green diffuse_blue: per-point colours; another type: no colours; an alpha
+//         is skipped), element face with a list property (vertex_indices | vertex_index); other elements / properties skipped
 //   .stl  ASCII and binary; vtkSTLReader merges coincident points (Merging is on by default): vertices with
 //         bit-identical coordinates share one point, numbered in order of first appearance
 //   .vtk  legacy POLYDATA, ASCII and BINARY (big endian): POINTS, POLYGONS, TRIANGLE_STRIPS,
-//         POINT_DATA TEXTURE_COORDINATES <name> 2 <type>; the 5.x OFFSETS / CONNECTIVITY form of POLYGONS too
+//         POINT_DATA TEXTURE_COORDINATES <name> 2 <type> and COLOR_SCALARS <name> 3|4 (per-point colours: bytes in a
+//         BINARY file, floats in [0,1] in an ASCII one); the 5.x OFFSETS / CONNECTIVITY form of POLYGONS too
 //   .wrl  VRML 2.0 IndexedFaceSet: Coordinate point [], coordIndex [], TextureCoordinate point [],
 //         texCoordIndex [] (a point used with several texture coordinates is duplicated, like OBJ corners);
-//         the last IndexedFaceSet of the file wins (utils3d.py:401: GetActors().GetLastActor())
+//         the last IndexedFaceSet of the file wins (utils3d.py:401: GetActors().GetLastActor()); Color nodes are not read
+// STL's merged points and VRML carry no colours.
 // Malformed input returns an error code and a message, never undefined behaviour: every count is checked
 // against the bytes that are really there (tests/test_mesh_readers.py runs this file under ASan + UBSan).
 #include <cctype>
@@ -249,10 +252,12 @@ int read_ply(const std::vector<char>& data, mvlm_obj* o, std::string* msg) {
     if (!header_done || format < 0) { *msg = "incomplete PLY header"; return MVLM_OBJ_ERR_SYNTAX; }
     const bool swap = format != 0 && ((format == 1) != host_is_little_endian());
     std::vector<float> uv;
+    std::vector<uint8_t> col;
     std::vector<long long> ids;
     for (const PlyElem& e : elems) {
         const bool is_vertex = e.name == "vertex", is_face = e.name == "face";
         int ix = -1, iy = -1, iz = -1, iu = -1, iv = -1, ilist = -1;
+        int irgb[3] = {-1, -1, -1}, idiffuse[3] = {-1, -1, -1};
         for (int k = 0; k < int(e.props.size()); ++k) {
             const std::string& n = e.props[size_t(k)].name;
             if (is_vertex && !e.props[size_t(k)].is_list) {
@@ -261,19 +266,33 @@ int read_ply(const std::vector<char>& data, mvlm_obj* o, std::string* msg) {
                 else if (n == "z") iz = k;
                 else if (n == "s" || n == "u" || n == "texture_u") iu = k;
                 else if (n == "t" || n == "v" || n == "texture_v") iv = k;
+                else if (n == "red") irgb[0] = k;
+                else if (n == "green") irgb[1] = k;
+                else if (n == "blue") irgb[2] = k;
+                else if (n == "diffuse_red") idiffuse[0] = k;
+                else if (n == "diffuse_green") idiffuse[1] = k;
+                else if (n == "diffuse_blue") idiffuse[2] = k;
             }
             if (is_face && e.props[size_t(k)].is_list && (n == "vertex_indices" || n == "vertex_index")) ilist = k;
         }
         if (is_vertex && (ix < 0 || iy < 0 || iz < 0)) { *msg = "PLY vertex element without x y z"; return MVLM_OBJ_ERR_SYNTAX; }
         const bool want_uv = is_vertex && iu >= 0 && iv >= 0;
+        // per-point colours: red green blue (or the diffuse_ names), all three of type uchar - a float or 16-bit colour
+        // has no agreed scale and means "no colours", not an error
+        if (irgb[0] < 0 || irgb[1] < 0 || irgb[2] < 0)
+            for (int k = 0; k < 3; ++k) irgb[k] = idiffuse[k];
+        bool want_col = is_vertex;
+        for (int k = 0; k < 3; ++k) want_col = want_col && irgb[k] >= 0 && e.props[size_t(irgb[k])].type == P_U8;
         if (is_vertex) {
             // a count the file cannot possibly hold must not drive an allocation
             if (e.count > int64_t(data.size())) { *msg = "PLY vertex count exceeds the file size"; return MVLM_OBJ_ERR_SYNTAX; }
             o->verts.reserve(size_t(e.count) * 3);
             if (want_uv) uv.reserve(size_t(e.count) * 2);
+            if (want_col) col.reserve(size_t(e.count) * 3);
         }
         for (long long r = 0; r < e.count; ++r) {
             double vals[5] = {0, 0, 0, 0, 0};
+            uint8_t rgb[3] = {0, 0, 0};
             for (int k = 0; k < int(e.props.size()); ++k) {
                 const PlyProp& pr = e.props[size_t(k)];
                 long long n = 1;
@@ -307,6 +326,8 @@ int read_ply(const std::vector<char>& data, mvlm_obj* o, std::string* msg) {
                         else if (k == iz) vals[2] = v;
                         else if (k == iu) vals[3] = v;
                         else if (k == iv) vals[4] = v;
+                        else if (want_col && (k == irgb[0] || k == irgb[1] || k == irgb[2]))  // (uchar: 0..255 in a binary file)
+                            rgb[k == irgb[0] ? 0 : k == irgb[1] ? 1 : 2] = uint8_t(v >= 255.0 ? 255 : v > 0.0 ? int(v) : 0);
                     }
                 }
             }
@@ -318,6 +339,7 @@ int read_ply(const std::vector<char>& data, mvlm_obj* o, std::string* msg) {
                     uv.push_back(float(vals[3]));
                     uv.push_back(float(vals[4]));
                 }
+                if (want_col) col.insert(col.end(), rgb, rgb + 3);
             } else if (is_face && ilist >= 0 && ids.size() >= 3) {
                 for (long long id : ids)
                     if (id < 0 || id >= MAX_ELEMS) { *msg = "PLY face references a vertex that does not exist"; return MVLM_OBJ_ERR_INDEX; }
@@ -326,6 +348,7 @@ int read_ply(const std::vector<char>& data, mvlm_obj* o, std::string* msg) {
         }
     }
     o->uvs.swap(uv);
+    o->colors.swap(col);
     return 0;
 }
 
@@ -555,6 +578,26 @@ int read_vtk(const std::vector<char>& data, mvlm_obj* o, std::string* msg) {
                 }
             }
         }
+        // per-point colours: "COLOR_SCALARS <name> <nValues>", then nValues numbers per point - unsigned bytes in a BINARY
+        // file, floats in [0,1] in an ASCII one (mvlm_color_byte); 3 (rgb) or 4 (rgba, the alpha dropped) components are
+        // colours, another count is read past
+        else if (kw == "color_scalars" && point_data) {
+            std::string name;
+            long long nc;
+            if (!sc.word(&name) || !sc.integer(&nc) || nc < 1 || nc > 4 || n_points < 0 ||
+                !vtk_values(&sc, binary, binary ? "unsigned_char" : "double", n_points * nc, &vals)) {
+                *msg = "bad VTK COLOR_SCALARS";
+                return MVLM_OBJ_ERR_SYNTAX;
+            }
+            if (nc >= 3) {
+                o->colors.resize(size_t(n_points) * 3);
+                for (long long i = 0; i < n_points; ++i)
+                    for (int k = 0; k < 3; ++k) {
+                        const double v = vals[size_t(i * nc + k)];
+                        o->colors[size_t(i) * 3 + size_t(k)] = binary ? uint8_t(v) : mvlm_color_byte(v);
+                    }
+            }
+        }
         // every other keyword (VERTICES, LINES, SCALARS, NORMALS, ...): its values are skipped as tokens, which is
         // safe for ASCII; an unknown BINARY block would desynchronise the scan, so stop at the first one
         else if (binary && (kw == "vertices" || kw == "lines" || kw == "scalars" || kw == "normals" || kw == "vectors" ||
@@ -747,6 +790,7 @@ extern "C" int mvlm_mesh_read(const char* path, mvlm_obj** out, char* err, int e
         rc = MVLM_OBJ_ERR_INDEX;
     }
     if (!rc && !o->uvs.empty() && o->uvs.size() != size_t(n_points) * 2) o->uvs.clear();  // partial texture coordinates: none
+    if (!rc && !o->colors.empty() && o->colors.size() != size_t(n_points) * 3) o->colors.clear();  // (likewise)
     if (rc) {
         delete o;
         set_err(err, err_len, std::string("File ") + path + ": " + msg);

@@ -1,7 +1,8 @@
 // Wavefront OBJ ingest on the host (no device code): what obj_to_actor gets out of vtkOBJReader
 // (reference src/mvlm/utils/utils3d.py:16-24) - float32 points, one texture coordinate per point
 // (a point is duplicated when it is used with several `vt` indices), polygons as triangle fans,
-// `.mtl` / normals / groups ignored.  A 100k-triangle scan is ~6 MB of text; this reader is what
+// `.mtl` / normals / groups ignored; "v x y z r g b" (MeshLab, Artec: floats in [0,1]) gives per-point colours when EVERY
+// v line carries them - "v x y z w" stays a point with a weight that is dropped.  A 100k-triangle scan is ~6 MB of text; this reader is what
 // keeps file ingest (tens of ms) below the GPU time of the views it feeds.
 //
 // The corner numbering is the contract with mvlm_amd/utils/mesh_io.py:_parse_obj (the pure-Python
@@ -160,6 +161,7 @@ struct Chunk {
     const char* begin = nullptr;
     const char* end = nullptr;
     std::vector<float> pos, tex;
+    std::vector<uint8_t> col;       // r g b of the v lines that carry six numbers (all of them, or the file has no colours)
     std::vector<long long> cv, ct;  // raw indices as written (1-based or negative), ct = NO_TEX when absent
     std::vector<Face> faces;
     long lines = 0;
@@ -245,6 +247,12 @@ void parse_chunk(Chunk* c) {
             if (!parse_double(tok_s[i], tok_e[i], &v[i])) return syntax("could not convert string to float");
         std::vector<float>& dst = is_v ? c->pos : c->tex;
         for (int i = 0; i < need; ++i) dst.push_back(float(v[i]));
+        if (is_v && ntok >= 6) {  // "v x y z r g b": numbers that do not parse make it a line without a colour
+            double rgb[3];
+            if (parse_double(tok_s[3], tok_e[3], &rgb[0]) && parse_double(tok_s[4], tok_e[4], &rgb[1]) &&
+                parse_double(tok_s[5], tok_e[5], &rgb[2]))
+                for (int i = 0; i < 3; ++i) c->col.push_back(mvlm_color_byte(rgb[i]));
+        }
     }
     c->lines = line_no;
 }
@@ -400,8 +408,12 @@ extern "C" int mvlm_obj_read(const char* path, mvlm_obj** out, char* err, int er
         return MVLM_OBJ_ERR_EMPTY;
     }
     std::vector<float> pos(size_t(n_pos) * 3), tex(size_t(n_tex) * 2);
+    bool has_col = true;  // every v line of the file has a colour
+    for (const Chunk& c : chunks) has_col = has_col && c.col.size() == c.pos.size();
+    std::vector<uint8_t> col(has_col ? size_t(n_pos) * 3 : 0);
     for (int k = 0; k < n_chunks; ++k) {
         const Chunk& c = chunks[size_t(k)];
+        if (has_col && !c.col.empty()) memcpy(&col[size_t(pos_base[size_t(k)]) * 3], c.col.data(), c.col.size());
         if (!c.pos.empty()) memcpy(&pos[size_t(pos_base[size_t(k)]) * 3], c.pos.data(), c.pos.size() * sizeof(float));
         if (!c.tex.empty()) memcpy(&tex[size_t(tex_base[size_t(k)]) * 2], c.tex.data(), c.tex.size() * sizeof(float));
     }
@@ -410,6 +422,7 @@ extern "C" int mvlm_obj_read(const char* path, mvlm_obj** out, char* err, int er
     o->n_positions = n_pos;
     if (n_fan == 0) {  // a point cloud: keep the points, nothing to render or to snap to
         o->verts.swap(pos);
+        o->colors.swap(col);
         *out = o;
         return 0;
     }
@@ -461,6 +474,7 @@ extern "C" int mvlm_obj_read(const char* path, mvlm_obj** out, char* err, int er
     lap("corners");
     const size_t nc = corner_v.size();
     o->verts.resize(nc * 3);
+    if (has_col) o->colors.resize(nc * 3);  // a point duplicated for a second `vt` keeps its colour
     bool any_uv = false;
     for (size_t i = 0; i < nc; ++i) {
         const long long vi = corner_v[i];
@@ -470,6 +484,7 @@ extern "C" int mvlm_obj_read(const char* path, mvlm_obj** out, char* err, int er
             return MVLM_OBJ_ERR_INDEX;
         }
         memcpy(&o->verts[i * 3], &pos[size_t(vi) * 3], 3 * sizeof(float));
+        if (has_col) memcpy(&o->colors[i * 3], &col[size_t(vi) * 3], 3);
         any_uv |= corner_t[i] >= 0;
     }
     if (n_tex > 0 && any_uv) {
@@ -501,6 +516,19 @@ extern "C" int mvlm_obj_copy(const mvlm_obj* obj, float* verts, float* uvs, int3
     if (verts && !obj->verts.empty()) memcpy(verts, obj->verts.data(), obj->verts.size() * sizeof(float));
     if (uvs && !obj->uvs.empty()) memcpy(uvs, obj->uvs.data(), obj->uvs.size() * sizeof(float));
     if (tris && !obj->tris.empty()) memcpy(tris, obj->tris.data(), obj->tris.size() * sizeof(int32_t));
+    return 0;
+}
+
+extern "C" int mvlm_obj_has_colors(const mvlm_obj* obj, int* has) {
+    if (!obj || !has) return MVLM_OBJ_ERR_ARGS;
+    *has = !obj->colors.empty() && obj->colors.size() == obj->verts.size() ? 1 : 0;
+    return 0;
+}
+
+extern "C" int mvlm_obj_copy_colors(const mvlm_obj* obj, uint8_t* rgb) {
+    if (!obj || !rgb) return MVLM_OBJ_ERR_ARGS;
+    if (obj->colors.empty() || obj->colors.size() != obj->verts.size()) return MVLM_OBJ_ERR_EMPTY;
+    memcpy(rgb, obj->colors.data(), obj->colors.size());
     return 0;
 }
 

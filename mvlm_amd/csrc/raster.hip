@@ -15,8 +15,9 @@
 //                  small triangles left, stages the tile's big-triangle list through LDS in
 //                  chunks of 256 set-up triangles (each thread sets one up), every pixel walks
 //                  the chunk (LDS broadcast reads) and keeps the winning key in a register;
-//                  then shades (nearest texel, unlit) and writes its RGBD texel; a tile row is
-//                  256 contiguous bytes of the [N,256,256,4] f32 stack.
+//                  then shades (nearest texel, unlit - or, for a mesh with per-vertex colours and no
+//                  texture, the interpolated colour: raster_vc.hip) and writes its RGBD texel; a tile row
+//                  is 256 contiguous bytes of the [N,256,256,4] f32 stack.
 // The key (depth bits << 32 | ~triangle id) makes the result independent of the order in which
 // atomics and tiles run: least depth wins, the later-drawn triangle wins ties (GL_LEQUAL).
 // Bandwidth-bound on its REAL traffic, measured (round 4): 0.74 GB through the L2s per 96 views at
@@ -25,7 +26,7 @@
 // Neither fewer instructions (the 24-bit path below: 3 %) nor more loads in flight per thread (TPT / PPT: nothing) nor
 // keeping the keys in LDS with every survivor binned (built: 210 us - a cull pass, a survivor list, a fill pass and a
 // per-tile gather cost more than the plane they save) beat this structure; fewer bytes per vertex do.
-#include "raster_common.h"
+#include "raster_tile.h"
 
 namespace {
 
@@ -50,70 +51,7 @@ __device__ inline rm_tri load_tri(const vert12* tvv, const int32_t* tris, int t)
     return rm_setup(load_vert(tvv, a), load_vert(tvv, b), load_vert(tvv, c));
 }
 
-// ---- 24-bit path ---------------------------------------------------------------------------------------------------------
-// rm_setup / rm_cover evaluate the area and the three edge functions in 64-bit integers (window coordinates reach
-// +-2^22 sub-pixel steps), and a 64-bit or a full 32-bit integer multiply runs at a quarter of the vector rate.  A
-// triangle whose vertices lie within 2^14 steps (64 pixels) of each other
-// in x and in y - every triangle of a dense scan - has |dx|, |dy| < 2^14 and, for a pixel centre inside its bounding box,
-// |px - ax|, |py - ay| < 2^14: every product is below 2^28 and fits the full-rate 24-bit multiply (v_mul_i32_i24), every
-// edge value and the area are below 2^29.  The integers are THE SAME as rm_setup's / rm_cover's, so are the floats made
-// from them: a kernel may take either path per triangle and the image does not change by a bit (oracle/raster.c, the
-// tests' checker, knows only the 64-bit form).  Worth 3-5 % of a render.  (RM_SMALL_EXTENT, small_extent: raster_common.h)
-struct tri24 {
-    int32_t X0, Y0, X1, Y1, X2, Y2;  // after the winding swap (vertices 1 and 2)
-    float z0, z1, z2;
-    float farea;
-    int32_t swapped;
-};
-
-// rm_setup without the bounding box; false for a zero-area triangle
-__device__ inline bool setup24(rm_vert a, rm_vert b, rm_vert c, tri24* t) {
-    int32_t area = __mul24(b.X - a.X, c.Y - a.Y) - __mul24(b.Y - a.Y, c.X - a.X);
-    t->swapped = 0;
-    if (area < 0) {
-        const rm_vert s = b;
-        b = c;
-        c = s;
-        area = -area;
-        t->swapped = 1;
-    }
-    t->X0 = a.X; t->Y0 = a.Y; t->X1 = b.X; t->Y1 = b.Y; t->X2 = c.X; t->Y2 = c.Y;
-    t->z0 = a.z; t->z1 = b.z; t->z2 = c.z;
-    t->farea = float(area);
-    return area != 0;
-}
-
-// the geometry plane's shade (rm_geometry_u8 reads the swapped vertices and depths only)
-__device__ inline int geometry24(const tri24* t) {
-    rm_tri r = {};
-    r.X0 = t->X0; r.Y0 = t->Y0; r.X1 = t->X1; r.Y1 = t->Y1; r.X2 = t->X2; r.Y2 = t->Y2;
-    r.z0 = t->z0; r.z1 = t->z1; r.z2 = t->z2;
-    return rm_geometry_u8(&r);
-}
-
-__device__ inline int edge24(int32_t ax, int32_t ay, int32_t bx, int32_t by, int32_t px, int32_t py, int32_t* w) {
-    const int32_t dx = bx - ax, dy = by - ay;
-    const int32_t e = __mul24(dx, py - ay) - __mul24(dy, px - ax);
-    *w = e;
-    if (e > 0) return 1;
-    if (e < 0) return 0;
-    return RM_OWNS(dx, dy);
-}
-
-// rm_cover for a pixel centre inside the triangle's bounding box (T: tri24, or an rm_tri of small extent)
-template <class T>
-__device__ inline int cover24(const T* t, int i, int j, float* b0, float* b1, float* b2) {
-    const int32_t px = i * RM_SUB + RM_HALF, py = j * RM_SUB + RM_HALF;
-    int32_t w0, w1, w2;
-    const int in0 = edge24(t->X1, t->Y1, t->X2, t->Y2, px, py, &w0);
-    const int in1 = edge24(t->X2, t->Y2, t->X0, t->Y0, px, py, &w1);
-    const int in2 = edge24(t->X0, t->Y0, t->X1, t->Y1, px, py, &w2);
-    if (!(in0 && in1 && in2)) return 0;
-    *b0 = float(w0) / t->farea;
-    *b1 = float(w1) / t->farea;
-    *b2 = float(w2) / t->farea;
-    return 1;
-}
+// (the 24-bit edge functions - tri24, setup24, cover24 - that classify_one shares with the tile stage: raster_tile.h)
 
 // Classify every (view, triangle): cull / resolve small ones with atomics / count big ones.
 // Order of the tests: the pixel-centre box first (integer shifts: most triangles of a dense scan lie between pixel
@@ -258,10 +196,7 @@ __global__ void scan_kernel(const int* __restrict__ counts, int* __restrict__ of
     if (t == TILES - 1 && s[t] > cap) *overflow = 1;
 }
 
-// One workgroup per (view, 16x16-pixel tile), one thread per pixel.  More pixels per thread with the loads of a stage
-// (key, triangle, vertices and texture coordinates, texel) in flight together were built and measured (2 and 4 pixels:
-// 161 / 163 us per render against 164): the kernel does not wait for latency, it moves its bytes at the rate the memory
-// system gives - without the texel fetch 43 of its 76 us, without any shading 37 = key plane in, pixels out at 4 TB/s.
+// The tile stage (raster_tile.h: tile_body) without per-vertex colours; raster_vc.hip holds the coloured form.
 __global__ __launch_bounds__(256) void tile_kernel(const vert12* __restrict__ tv, const int32_t* __restrict__ tris,
                                                    const float* __restrict__ uvs, const uint8_t* __restrict__ tex,
                                                    int tex_w, int tex_h, int n_verts, const int* __restrict__ counts,
@@ -269,95 +204,8 @@ __global__ __launch_bounds__(256) void tile_kernel(const vert12* __restrict__ tv
                                                    int cap, unsigned long long* __restrict__ keys,
                                                    int shading, int n_views, const int* __restrict__ overflow,
                                                    int* __restrict__ overflow_host, float* __restrict__ out) {
-    __shared__ rm_tri s_tri[256];  // (valid == 2: small extent, the 24-bit edge functions apply)
-    __shared__ int s_id[256];
-    int view, tile;
-    if (!view_chunk(TILES, n_views, &view, &tile)) return;
-    const int vt = view * TILES + tile;
-    const int tid = threadIdx.x;
-    const int i = (tile % RM_TILES) * RM_TILE + (tid & (RM_TILE - 1));
-    const int j = (tile / RM_TILES) * RM_TILE + (tid >> 4);
-    const vert12* const tvv = tv + size_t(view) * n_verts;
-    const int n = min(counts[vt], cap - offsets[vt]);
-    const int* const list = bins + size_t(view) * cap + offsets[vt];
-
-    unsigned long long* const key_slot = keys + (size_t(view) * RM_SIZE + j) * RM_SIZE + i;
-    uint64_t best = *key_slot;  // what the small triangles left
-    // The key plane is handed back EMPTY: this kernel reads every slot of the rendered views exactly once, so it also clears
-    // what classify dirtied - instead of a 67 MB fill in front of every render (14 us + a launch gap at 128 views)
-    if (best != RM_KEY_EMPTY) *key_slot = RM_KEY_EMPTY;
-    // and the first workgroup carries the overflow flag of the kernels before it to the host's pinned word (no copy node)
-    if (blockIdx.x == 0 && tid == 0) {
-        __atomic_store_n(overflow_host, *overflow, __ATOMIC_RELAXED);
-        __threadfence_system();
-    }
-
-    // ---- phase B: every pixel walks the tile's big triangles, set up into LDS a chunk at a time ----
-    for (int base = 0; base < n; base += 256) {
-        const int m = min(256, n - base);
-        __syncthreads();
-        if (tid < m) {
-            const int t = list[base + tid];
-            const rm_vert a = load_vert(tvv, tris[3 * t]), b = load_vert(tvv, tris[3 * t + 1]), c = load_vert(tvv, tris[3 * t + 2]);
-            rm_tri tr = rm_setup(a, b, c);
-            if (tr.valid && small_extent(a, b, c)) tr.valid = 2;
-            s_id[tid] = t;
-            s_tri[tid] = tr;
-        }
-        __syncthreads();
-        for (int k = 0; k < m; ++k) {
-            const rm_tri* t = &s_tri[k];
-            if (i < t->ix0 || i > t->ix1 || j < t->iy0 || j > t->iy1) continue;
-            float b0, b1, b2;
-            if (!(t->valid == 2 ? cover24(t, i, j, &b0, &b1, &b2) : rm_cover(t, i, j, &b0, &b1, &b2))) continue;
-            const float z = rm_interp(b0, b1, b2, t->z0, t->z1, t->z2);
-            if (!(z >= 0.0f && z <= 1.0f)) continue;  // near / far clip (render3d.py:136)
-            const uint64_t key = rm_key(z, uint32_t(s_id[k]));
-            best = key < best ? key : best;
-        }
-    }
-
-    // ---- phase C: shade the winner ----
-    float4 px = make_float4(1.f, 1.f, 1.f, float(rm_depth_u8(1.0f)) / 255.0f);  // white background, far plane
-    if (best != RM_KEY_EMPTY) {
-        const int t = int(rm_key_tri(best));
-        int a = tris[3 * t], b = tris[3 * t + 1], c = tris[3 * t + 2];
-        const rm_vert va = load_vert(tvv, a), vb = load_vert(tvv, b), vc = load_vert(tvv, c);
-        // the winner's barycentric weights at this pixel (it is covered: inside the triangle's box)
-        float b0 = 0.f, b1 = 0.f, b2 = 0.f;
-        bool swapped;
-        float r = 255.f, g = 255.f, bl = 255.f;
-        if (small_extent(va, vb, vc)) {
-            tri24 tr;
-            setup24(va, vb, vc, &tr);
-            swapped = tr.swapped != 0;
-            cover24(&tr, i, j, &b0, &b1, &b2);
-            if (shading == 1) r = g = bl = float(geometry24(&tr));
-        } else {
-            const rm_tri tr = rm_setup(va, vb, vc);
-            swapped = tr.swapped != 0;
-            rm_cover(&tr, i, j, &b0, &b1, &b2);
-            if (shading == 1) r = g = bl = float(rm_geometry_u8(&tr));
-        }
-        if (swapped) {
-            const int s = b;
-            b = c;
-            c = s;
-        }
-        if (shading != 1 && tex && uvs) {
-            const float u = rm_interp(b0, b1, b2, uvs[2 * a], uvs[2 * b], uvs[2 * c]);
-            const float v = rm_interp(b0, b1, b2, uvs[2 * a + 1], uvs[2 * b + 1], uvs[2 * c + 1]);
-            // one (unaligned) 4-byte load per texel: the buffer carries 4 spare bytes behind the last one (api.hip)
-            uint32_t rgb;
-            __builtin_memcpy(&rgb, tex + size_t(rm_texel(u, v, tex_w, tex_h)) * 3, 4);
-            r = float(rgb & 255u);
-            g = float((rgb >> 8) & 255u);
-            bl = float((rgb >> 16) & 255u);
-        }
-        px = make_float4(r / 255.0f, g / 255.0f, bl / 255.0f, float(rm_depth_u8(rm_key_z(best))) / 255.0f);
-    }
-    // np.flip(axis=1): GL row j (bottom-up) is image row 255 - j (render3d.py:177)
-    reinterpret_cast<float4*>(out)[(size_t(view) * RM_SIZE + (RM_SIZE - 1 - j)) * RM_SIZE + i] = px;
+    tile_body<false>(tv, tris, uvs, tex, tex_w, tex_h, nullptr, n_verts, counts, offsets, bins, cap, keys, shading, n_views,
+                     overflow, overflow_host, out);
 }
 
 }  // namespace
@@ -380,6 +228,8 @@ extern "C" int mvlm_render(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* r
     auto* big_list = static_cast<int*>(ctx->get_scratch("raster.big", size_t(n_views) * T * sizeof(int)));
     // one key per pixel, or S per pixel in a plane of its own when multisampling (allocated only then)
     const int S = ctx->render_multisamples;
+    // per-vertex colours shade the RGB planes of the unlit render of a mesh without a usable texture
+    const uint8_t* const vcol = ctx->render_shading == 0 && mesh->colors && !(mesh->tex && mesh->uvs) ? mesh->colors : nullptr;
     const char* const key_name = S ? "raster.keys4" : "raster.keys";
     const size_t key_bytes = size_t(n_views) * RM_SIZE * RM_SIZE * size_t(S ? S : 1) * sizeof(unsigned long long);
     auto* keys = static_cast<unsigned long long*>(ctx->get_scratch(key_name, key_bytes));
@@ -423,15 +273,19 @@ extern "C" int mvlm_render(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* r
         hipLaunchKernelGGL(scan_kernel, dim3(n_views), dim3(TILES), 0, ctx->stream, counts, offsets, cap, overflow);
         hipLaunchKernelGGL(bin_fill_kernel, dim3(view_chunk_grid(FILL_WGS, n_views)), dim3(256), 0, ctx->stream, tv,
                            mesh->tris, V, T, n_views, n_big, big_list, offsets, cursors, bins, cap, overflow);
-        hipLaunchKernelGGL(tile_kernel, dim3(view_chunk_grid(TILES, n_views)), dim3(256), 0, ctx->stream, tv, mesh->tris,
-                           mesh->uvs, mesh->tex, mesh->tex_w, mesh->tex_h, V, counts, offsets, bins, cap, keys,
-                           ctx->render_shading, n_views, overflow, ctx->render_overflow_host, out_dev);
+        if (vcol)
+            raster_vc_tile(ctx->stream, 0, tv, mesh->tris, vcol, V, n_views, counts, offsets, bins, cap, keys, ctx->render_shading,
+                           overflow, ctx->render_overflow_host, out_dev);
+        else
+            hipLaunchKernelGGL(tile_kernel, dim3(view_chunk_grid(TILES, n_views)), dim3(256), 0, ctx->stream, tv, mesh->tris,
+                               mesh->uvs, mesh->tex, mesh->tex_w, mesh->tex_h, V, counts, offsets, bins, cap, keys,
+                               ctx->render_shading, n_views, overflow, ctx->render_overflow_host, out_dev);
     } else {  // S == 4 (mvlm_set_render_multisamples admits nothing else): the kernels of raster_ms.hip
         raster_ms_classify(ctx->stream, S, tv, mesh->tris, V, T, n_views, keys, counts, n_big, big_list);
         hipLaunchKernelGGL(scan_kernel, dim3(n_views), dim3(TILES), 0, ctx->stream, counts, offsets, cap, overflow);
         raster_ms_bin_and_tile(ctx->stream, S, tv, mesh->tris, mesh->uvs, mesh->tex, mesh->tex_w, mesh->tex_h, V, T, n_views,
                                n_big, big_list, counts, offsets, cursors, bins, cap, keys, ctx->render_shading, overflow,
-                               ctx->render_overflow_host, out_dev);
+                               ctx->render_overflow_host, out_dev, vcol);
     }
     MVLM_CHECK_HIP(ctx, hipGetLastError());
     clean = mvlm_ctx::KeyPlaneState{keys, keys_cap};

@@ -1,5 +1,6 @@
-// Pieces of the multi-view rasteriser shared by its one-sample kernels (raster.hip) and its multisampled ones
-// (raster_ms.hip, an object of its own: tools/kernel_occupancy.py keeps a table of its kernels beside the main one).
+// Pieces of the multi-view rasteriser shared by its one-sample kernels (raster.hip), its multisampled ones (raster_ms.hip)
+// and the per-vertex-colour tile kernels (raster_vc.hip) - the latter two objects of their own: tools/kernel_occupancy.py
+// keeps a table of each one's kernels beside the main one.  The tile stage's bodies: raster_tile.h.
 #ifndef MVLM_RASTER_COMMON_H
 #define MVLM_RASTER_COMMON_H
 
@@ -53,11 +54,18 @@ constexpr int FILL_WGS = 32;      // bin-fill workgroups per view (raster.hip, b
 
 // The multisampled kernels of one mvlm_render at `samples` samples per pixel (raster_ms.hip); raster.hip launches the
 // transform before and the scan between them.  `tv` is the transformed-vertex scratch (vert12[n_views][n_verts]).
+// `colors` (u8[V,4] on the device, or null): the tile stage is raster_vc_tile's, shading with the per-vertex colours.
 void raster_ms_classify(hipStream_t stream, int samples, const void* tv, const int32_t* tris, int n_verts, int n_tris,
                         int n_views, unsigned long long* keys, int* counts, int* n_big, int* big_list);
 void raster_ms_bin_and_tile(hipStream_t stream, int samples, const void* tv, const int32_t* tris, const float* uvs,
                             const uint8_t* tex, int tex_w, int tex_h, int n_verts, int n_tris, int n_views, const int* n_big,
                             const int* big_list, const int* counts, const int* offsets, int* cursors, int* bins, int cap,
-                            unsigned long long* keys, int shading, int* overflow, int* overflow_host, float* out);
+                            unsigned long long* keys, int shading, int* overflow, int* overflow_host, float* out,
+                            const uint8_t* colors);
+// The tile stage with per-vertex colours (raster_vc.hip), at `samples` = 0 (one sample, in place of raster.hip's tile_kernel)
+// or 4 (in place of tile_ms_kernel, behind raster_ms.hip's bin fill).
+void raster_vc_tile(hipStream_t stream, int samples, const void* tv, const int32_t* tris, const uint8_t* colors, int n_verts,
+                    int n_views, const int* counts, const int* offsets, const int* bins, int cap, unsigned long long* keys,
+                    int shading, const int* overflow, int* overflow_host, float* out);
 
 #endif

@@ -183,6 +183,17 @@ RM_FN int rm_geometry_u8(const rm_tri* t) {
     return (int)(s * 255.0f + 0.5f);
 }
 
+/* an interpolated per-vertex colour channel (0..1) -> its byte: clamped (a multisampled pixel evaluates the plane at its
+ * centre, which may lie outside the triangle), then the conversion of the OpenGL of tests/golden/gl_raster_vcolor.npz, read off
+ * its two probes: through 16-bit fixed point, c16 = trunc(65535 f), byte = (c16 - (c16 >> 8) + 128) >> 8.
+ * That is round-to-nearest with the boundary between k and k + 1 moved by 1/512 of a code value: down for k < 128, up for
+ * k >= 128 (an exact k + 1/2 goes up below 128, down from 128 on).  c / 255 comes back as c for every byte c. */
+RM_FN int rm_color_u8(float f) {
+    f = f < 0.0f ? 0.0f : (f > 1.0f ? 1.0f : f);
+    const int c16 = (int)(f * 65535.0f);
+    return (c16 - (c16 >> 8) + 128) >> 8;
+}
+
 /* nearest texel with GL_REPEAT wrapping; image rows are stored top row first while
  * v = 0 is the bottom of the image (vtkJPEGReader / OBJ convention) */
 RM_FN int rm_texel(float u, float v, int tw, int th) {

@@ -1,4 +1,4 @@
-"""Mesh ingest on the host: Wavefront OBJ + same-stem JPEG texture.
+"""Mesh ingest on the host: Wavefront OBJ + same-stem JPEG texture (+ per-point colours where the file carries them).
 
 Mirrors what ``obj_to_actor`` obtains from vtkOBJReader / vtkJPEGReader
 (reference src/mvlm/utils/utils3d.py:10-85): geometry as float32 points, one
@@ -36,6 +36,10 @@ class Mesh:
     # The texture as the bytes of its JPEG file, not decoded yet (load_obj / load_mesh with decode="device").  The renderer's
     # upload hands them to the device decoder (mvlm_mesh_upload_jpeg); ``texture`` decodes them with libjpeg on first use.
     texture_jpeg: bytes | None = field(default=None, repr=False)
+    # [V,3] uint8, one RGB triple per point (.ply red green blue, .vtk COLOR_SCALARS, .obj "v x y z r g b").  They shade the
+    # RGB planes of the unlit render when the mesh has no usable texture (no uvs or no texture image); a textured mesh
+    # renders with its texture alone, geometry shading and the depth plane never see them.
+    colors: np.ndarray | None = None
 
     @property
     def n_verts(self) -> int:
@@ -76,8 +80,16 @@ def decode_texture_bytes(data: bytes):
         return None
 
 
+def _color_byte(f: float) -> int:
+    """A colour channel written as a float in [0,1] -> its byte (mesh_obj.h: mvlm_color_byte): clamped, rounded to nearest."""
+    if not f > 0.0:  # (NaN too)
+        return 0
+    return 255 if f >= 1.0 else int(255.0 * f + 0.5)
+
+
 def _parse_obj(text: str):
     pos: list[tuple[float, float, float]] = []
+    col: list[tuple[int, int, int]] = []  # of the v lines that carry "r g b" behind x y z
     tex: list[tuple[float, float]] = []
     corners: dict[tuple[int, int], int] = {}
     out_v: list[int] = []
@@ -92,6 +104,11 @@ def _parse_obj(text: str):
         tag = parts[0]
         if tag == "v" and len(parts) >= 4:
             pos.append((float(parts[1]), float(parts[2]), float(parts[3])))
+            if len(parts) >= 7:
+                try:
+                    col.append(tuple(_color_byte(float(p)) for p in parts[4:7]))
+                except ValueError:  # numbers that do not parse: a line without a colour
+                    pass
         elif tag == "vt" and len(parts) >= 3:
             tex.append((float(parts[1]), float(parts[2])))
         elif tag == "f" and len(parts) >= 4:
@@ -113,7 +130,7 @@ def _parse_obj(text: str):
                 ids.append(idx)
             for k in range(1, len(ids) - 1):  # polygon -> fan
                 tris.append((ids[0], ids[k], ids[k + 1]))
-    return pos, tex, out_v, out_t, tris
+    return pos, tex, out_v, out_t, tris, (col if len(col) == len(pos) else None)  # colours: on every v line or none
 
 
 def _read_texture(jpg: Path):
@@ -150,20 +167,25 @@ def _read_obj_native(path: Path, any_format: bool = False):
         uvs = np.empty((nv.value, 2), np.float32) if has_uv.value else None
         lib.mvlm_obj_copy(handle, _lib.as_ptr(verts, C.c_float), _lib.as_ptr(uvs, C.c_float) if uvs is not None else None,
                           _lib.as_ptr(tris, C.c_int32))
+        has_col = C.c_int(0)
+        lib.mvlm_obj_has_colors(handle, C.byref(has_col))
+        colors = np.empty((nv.value, 3), np.uint8) if has_col.value else None
+        if colors is not None and lib.mvlm_obj_copy_colors(handle, _lib.as_ptr(colors, C.c_uint8)) != 0:
+            colors = None
     finally:
         lib.mvlm_obj_free(handle)
-    return verts, tris, uvs
+    return verts, tris, uvs, colors
 
 
 def _read_obj_python(path: Path):
     """The same rules in plain Python (the statement tests check the native reader against)."""
-    pos, tex, out_v, out_t, tris = _parse_obj(path.read_text(errors="replace"))
+    pos, tex, out_v, out_t, tris, col = _parse_obj(path.read_text(errors="replace"))
     if len(pos) == 0:
         raise ValueError(f"File {path} does not contain any points.")  # utils3d.py:20-21
     pos_a = np.asarray(pos, dtype=np.float32).reshape(-1, 3)
     if len(tris) == 0:
         # a point cloud: keep the points, nothing to render or to snap to
-        return pos_a, np.zeros((0, 3), np.int32), None
+        return pos_a, np.zeros((0, 3), np.int32), None, None if col is None else np.asarray(col, np.uint8).reshape(-1, 3)
     v_idx = np.asarray(out_v, dtype=np.int64)
     if v_idx.min() < 0 or v_idx.max() >= len(pos):
         raise ValueError(f"File {path} references a vertex that does not exist.")
@@ -174,7 +196,8 @@ def _read_obj_python(path: Path):
         tex_a = np.asarray(tex, dtype=np.float32).reshape(-1, 2)
         safe = np.clip(t_idx, 0, len(tex) - 1)
         uvs = np.where((t_idx >= 0)[:, None], tex_a[safe], np.float32(0)).astype(np.float32)
-    return np.ascontiguousarray(verts), np.asarray(tris, dtype=np.int32).reshape(-1, 3), uvs
+    colors = None if col is None else np.ascontiguousarray(np.asarray(col, np.uint8).reshape(-1, 3)[v_idx])
+    return np.ascontiguousarray(verts), np.asarray(tris, dtype=np.int32).reshape(-1, 3), uvs, colors
 
 
 def load_obj(path: Union[Path, str], load_texture: bool = True, reader: str = "native", decode: str = "device") -> Mesh:
@@ -206,16 +229,16 @@ def load_obj(path: Union[Path, str], load_texture: bool = True, reader: str = "n
             tex_job.start()
     try:
         if reader == "native":
-            verts, tris, uvs = _read_obj_native(path)
+            verts, tris, uvs, colors = _read_obj_native(path)
         elif reader == "python":
-            verts, tris, uvs = _read_obj_python(path)
+            verts, tris, uvs, colors = _read_obj_python(path)
         else:
             raise ValueError(f"unknown OBJ reader: {reader}")
     finally:
         if tex_job is not None:
             tex_job.join()
     texture = box[0] if (tex_job is not None and uvs is not None) else None  # utils3d.py:26: only with tcoords
-    return Mesh(verts, tris, uvs, texture, path, texture_jpeg=jpeg_bytes if uvs is not None else None)
+    return Mesh(verts, tris, uvs, texture, path, texture_jpeg=jpeg_bytes if uvs is not None else None, colors=colors)
 
 
 SURFACE_SUFFIXES = (".obj", ".wrl", ".vtk", ".stl", ".ply")  # Utils3D.multi_read_surface, utils3d.py:389-423
@@ -268,19 +291,25 @@ def load_mesh(path: Union[Path, str], load_texture: bool = True, texture_file_na
             tex_job = threading.Thread(target=lambda: box.__setitem__(0, _read_texture(tex_path)), daemon=True)
             tex_job.start()
     try:
-        verts, tris, uvs = _read_obj_native(path, any_format=True)
+        verts, tris, uvs, colors = _read_obj_native(path, any_format=True)
     finally:
         if tex_job is not None:
             tex_job.join()
     texture = box[0] if uvs is not None else None
-    return Mesh(verts, tris, uvs, texture, path, texture_jpeg=jpeg_bytes if uvs is not None else None)
+    return Mesh(verts, tris, uvs, texture, path, texture_jpeg=jpeg_bytes if uvs is not None else None, colors=colors)
 
 
 def write_obj(path: Union[Path, str], verts: np.ndarray, tris: np.ndarray, uvs: np.ndarray | None = None,
-              texture: np.ndarray | None = None, jpeg_quality: int = 95) -> None:
-    """Small writer used by the synthetic-mesh generator and the tests."""
+              texture: np.ndarray | None = None, jpeg_quality: int = 95, colors: np.ndarray | None = None) -> None:
+    """Small writer used by the synthetic-mesh generator and the tests.  ``colors`` (uint8 [V,3]): written as
+    ``v x y z r g b`` with r g b = c / 255, which the readers turn back into the same bytes."""
     path = Path(path)
-    lines = [f"v {x:.6f} {y:.6f} {z:.6f}" for x, y, z in np.asarray(verts, dtype=np.float64)]
+    if colors is None:
+        lines = [f"v {x:.6f} {y:.6f} {z:.6f}" for x, y, z in np.asarray(verts, dtype=np.float64)]
+    else:
+        rgb = np.asarray(colors, dtype=np.uint8).reshape(-1, 3).astype(np.float64) / 255.0
+        lines = [f"v {x:.6f} {y:.6f} {z:.6f} {r:.6f} {g:.6f} {b:.6f}"
+                 for (x, y, z), (r, g, b) in zip(np.asarray(verts, dtype=np.float64), rgb)]
     if uvs is not None:
         lines += [f"vt {u:.6f} {v:.6f}" for u, v in np.asarray(uvs, dtype=np.float64)]
         lines += [f"f {a + 1}/{a + 1} {b + 1}/{b + 1} {c + 1}/{c + 1}" for a, b, c in np.asarray(tris)]

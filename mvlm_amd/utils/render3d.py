@@ -126,7 +126,18 @@ def upload_mesh(ctx: "_lib.Context", mesh: Mesh) -> C.c_void_p:
             except Exception:  # noqa: BLE001
                 pass
 
-    mesh._device[key] = (handle, _Owner(ctx, handle))
+    owner = _Owner(ctx, handle)
+    # Per-point colours follow when the render can use them: the mesh has no usable texture (with one it renders with the
+    # texture alone) and the consumer reads an RGB plane (_colors_wanted: HipRenderer3D.load_mesh(load_texture=False)).
+    textured = uvs is not None and (mesh.texture_jpeg is not None or getattr(mesh, "_texture", None) is not None
+                                    or ahead is not None)
+    send_colors = mesh.colors is not None and not textured and getattr(mesh, "_colors_wanted", True)
+    if send_colors:
+        colors = np.ascontiguousarray(mesh.colors, dtype=np.uint8)
+        if colors.shape != (mesh.n_verts, 3):
+            raise ValueError(f"mesh colours must be uint8 [V,3] with V = {mesh.n_verts}, not {colors.shape}")
+        ctx.check(ctx.lib.mvlm_mesh_upload_colors(ctx.handle, handle, _lib.as_ptr(colors, C.c_uint8), mesh.n_verts), ValueError)
+    mesh._device[key] = (handle, owner, send_colors)  # (the third entry: were colours uploaded with it?)
     return handle
 
 
@@ -311,15 +322,18 @@ class HipRenderer3D:
 
     def load_mesh(self, file_name: Path, load_texture: bool = True) -> Mesh:
         """OBJ (+ texture) from disk, through the ``pre_align`` block when one is set.
-        ``load_texture=False`` leaves the JPEG alone (not even read), and the consumer of a depth / geometry model's views
-        reads no texture-shaded plane.  It is
+        ``load_texture=False`` leaves the JPEG alone (not even read) and keeps per-point colours off the device, and the
+        consumer of a depth / geometry model's views reads no texture-shaded plane.  It is
         an argument of the call, decided by the caller that knows the consumer (``Pipeline._texture_needed``) - the
         renderer keeps no such state, so its public entry points load the texture like the reference (utils3d.py:26-36)."""
         from .prealign import aligned
 
         jpg = Path(file_name).with_suffix(".jpg")
         if not (load_texture and self.texture_decode == "device" and jpg.exists()):
-            return aligned(load_obj(file_name, load_texture=load_texture, decode=self.texture_decode), self.pre_align)
+            mesh = load_obj(file_name, load_texture=load_texture, decode=self.texture_decode)
+            if not load_texture:
+                mesh._colors_wanted = False  # nobody reads an RGB plane: per-point colours are not uploaded either
+            return aligned(mesh, self.pre_align)
         # The texture is decoded on the device by a second thread (read the .jpg, unstuff, GPU decode: 1.8 ms at 2048^2)
         # while this one parses the geometry (2.7 ms): the scan is ready when the slower of the two is.
         import threading

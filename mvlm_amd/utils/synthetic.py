@@ -12,8 +12,9 @@ import numpy as np
 from .mesh_io import Mesh, write_obj
 
 
-def face_like_mesh(grid: int = 224, tex_size: int = 512, seed: int = 0) -> Mesh:
-    """(grid x grid) vertex height field -> 2*(grid-1)^2 triangles (224 -> 99 458)."""
+def face_like_mesh(grid: int = 224, tex_size: int = 512, seed: int = 0, vertex_colors: bool = False) -> Mesh:
+    """(grid x grid) vertex height field -> 2*(grid-1)^2 triangles (224 -> 99 458).  ``vertex_colors``: the mesh also
+    carries ``colors``, its texture's texel at each vertex's uv (a renderer shows them once ``uvs`` / ``texture`` are gone)."""
     rs = np.random.RandomState(seed)
     lin = np.linspace(-100.0, 100.0, grid)
     x, y = np.meshgrid(lin, lin)
@@ -36,14 +37,23 @@ def face_like_mesh(grid: int = 224, tex_size: int = 512, seed: int = 0) -> Mesh:
     tex[..., 2] = 110 + 30 * np.sin((xx + yy) / 11.0)
     tex += rs.randint(-12, 13, size=tex.shape)
     texture = np.clip(tex, 0, 255).astype(np.uint8)
-    return Mesh(verts, tris, uvs, texture, None)
+    colors = None
+    if vertex_colors:  # the nearest texel, rows top first while v = 0 is the bottom (raster_math.h: rm_texel)
+        tx = np.clip((uvs[:, 0] * tex_size).astype(np.int64), 0, tex_size - 1)
+        ty = np.clip((uvs[:, 1] * tex_size).astype(np.int64), 0, tex_size - 1)
+        colors = np.ascontiguousarray(texture[tex_size - 1 - ty, tx])
+    return Mesh(verts, tris, uvs, texture, None, colors=colors)
 
 
-def write_face_like_obj(path, grid: int = 224, tex_size: int = 512, seed: int = 0) -> Path:
-    """Write the synthetic mesh as ``<path>`` (+ same-stem .jpg texture)."""
+def write_face_like_obj(path, grid: int = 224, tex_size: int = 512, seed: int = 0, vertex_colors: bool = False) -> Path:
+    """Write the synthetic mesh as ``<path>`` (+ same-stem .jpg texture) - or, with ``vertex_colors``, as a coloured
+    ``v x y z r g b`` file without texture coordinates and without a texture."""
     path = Path(path)
-    m = face_like_mesh(grid, tex_size, seed)
-    write_obj(path, m.verts, m.tris, m.uvs, m.texture)
+    m = face_like_mesh(grid, tex_size, seed, vertex_colors=vertex_colors)
+    if vertex_colors:
+        write_obj(path, m.verts, m.tris, colors=m.colors)
+    else:
+        write_obj(path, m.verts, m.tris, m.uvs, m.texture)
     return path
 
 
@@ -57,4 +67,4 @@ def unaligned_copy(mesh: Mesh, pre_align: dict, offset=(3.0, -2.0, 1.5)) -> Mesh
     v = mesh.verts.astype(np.float64) @ np.linalg.inv(m[:3, :3]).T
     if pre_align.get("align_center_of_mass", False):
         v = v + np.asarray(offset, dtype=np.float64)
-    return Mesh(v.astype(np.float32), mesh.tris, mesh.uvs, mesh.texture, None)
+    return Mesh(v.astype(np.float32), mesh.tris, mesh.uvs, mesh.texture, None, colors=mesh.colors)

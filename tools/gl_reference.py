@@ -2,7 +2,8 @@
 
 BUILD-CONTAINER TOOL (like tools/make_golden.py): it needs an EGL + GLES 3.0 implementation; the image has one, SwiftShader
 (software, conformant), shipped inside the `kaleido` wheel.  Nothing of the product, the tests or the bench imports this file;
-tools/make_gl_golden.py uses it to write tests/golden/gl_raster.npz.
+tools/make_gl_golden.py uses it to write tests/golden/gl_raster.npz (make_gl_msaa_golden.py and make_gl_vcolor_golden.py
+their fixtures).
 
 What is drawn follows the reference's calls, not this repository's contract (that is the point of the exercise):
   * camera: position (0, 0, 500), focal point origin, view-up +y, parallel projection, parallel scale 150, clipping range
@@ -14,6 +15,11 @@ What is drawn follows the reference's calls, not this repository's contract (tha
   * material: colour (1,1,1), ambient 1, diffuse 0 (utils3d.py:61-64) -> unlit; texture GL_NEAREST (SetInterpolate(0), :32),
     GL_REPEAT (vtkTexture's default), no mipmaps; image row 0 at the BOTTOM (vtkJPEGReader hands VTK's lower-left origin), so
     the texture is uploaded bottom row first and t = v;
+  * point colours (a mesh read by vtkPLYReader / vtkPolyDataReader carries an unsigned-char array on its points, and
+    vtkPolyDataMapper's ScalarVisibility is on by default): the mapper hands the array to OpenGL as a normalised
+    GL_UNSIGNED_BYTE vec4 vertex attribute and passes it through a varying; with ambient 1 / diffuse 0 the fragment is the
+    interpolated colour.  Drawn here for a mesh that is not textured (texel x colour, VTK's product for one that is, is
+    outside the contract);
   * read-back: RGB as bytes (vtkWindowToImageFilter RGB), Z as float.  GLES 3.0 cannot read a depth attachment back, so every
     fragment also writes floatBitsToUint(gl_FragCoord.z) into an R32UI colour attachment (exact bits, core ES 3.0): the float
     window depth BEFORE the depth buffer's quantisation.  The 24-bit value a GL_DEPTH_COMPONENT read would return is derived
@@ -64,10 +70,13 @@ GL_READ_FRAMEBUFFER = 0x8CA8
 VERTEX_SHADER = b"""#version 300 es
 layout(location = 0) in vec3 vertexMC;
 layout(location = 1) in vec2 tcoordMC;
+layout(location = 2) in vec4 scalarColor;
 uniform mat4 MCDCMatrix;
 out vec2 tcoordVC;
+out vec4 vertexColorVSOutput;
 void main() {
     tcoordVC = tcoordMC;
+    vertexColorVSOutput = scalarColor;
     gl_Position = MCDCMatrix * vec4(vertexMC, 1.0);
 }
 """
@@ -77,12 +86,15 @@ precision highp float;
 precision highp int;
 uniform sampler2D texture_0;
 uniform int textured;
+uniform int coloured;
 in vec2 tcoordVC;
+in vec4 vertexColorVSOutput;
 layout(location = 0) out vec4 fragColour;
 layout(location = 1) out uint fragDepthBits;
 void main() {
     vec4 ambient = vec4(1.0, 1.0, 1.0, 1.0);                  /* colour (1,1,1) x ambient 1, diffuse 0 */
     if (textured != 0) ambient = ambient * texture(texture_0, tcoordVC);
+    else if (coloured != 0) ambient = vec4(vertexColorVSOutput.rgb, 1.0);   /* the point scalars replace the ambient colour */
     fragColour = ambient;
     fragDepthBits = floatBitsToUint(gl_FragCoord.z);
 }
@@ -213,10 +225,12 @@ class GLReference:
                               np.ascontiguousarray(m.T).ctypes.data_as(C.POINTER(C.c_float)))
         gl.glUniform1i(gl.glGetUniformLocation(prog, b"texture_0"), 0)
         self.u_textured = gl.glGetUniformLocation(prog, b"textured")
+        self.u_coloured = gl.glGetUniformLocation(prog, b"coloured")
         self.prog = prog
 
-    def set_mesh(self, uvs, tris, texture) -> None:
-        """Index buffer, texture coordinates and the texture: per mesh, as in the reference (obj_to_actor)."""
+    def set_mesh(self, uvs, tris, texture, colors=None) -> None:
+        """Index buffer, texture coordinates and the texture: per mesh, as in the reference (obj_to_actor).  `colors` (u8 [V,3]):
+        the mesh's point scalars, drawn when it is not textured."""
         gl = self.gl
         self.n_idx = int(np.asarray(tris).size)
         idx = np.ascontiguousarray(tris, np.uint32)
@@ -246,6 +260,20 @@ class GLReference:
                 gl.glTexParameteri(GL_TEXTURE_2D, k, v)
         else:
             gl.glDisableVertexAttribArray(1)
+        coloured = colors is not None and not textured
+        gl.glUniform1i(self.u_coloured, 1 if coloured else 0)
+        if coloured:
+            rgba = np.full((len(colors), 4), 255, np.uint8)
+            rgba[:, :3] = np.asarray(colors, np.uint8)
+            vbo = C.c_uint()
+            gl.glGenBuffers(1, C.byref(vbo))
+            gl.glBindBuffer(GL_ARRAY_BUFFER, vbo)
+            gl.glBufferData(GL_ARRAY_BUFFER, C.c_ssize_t(rgba.nbytes), rgba.ctypes.data_as(C.c_void_p), GL_STATIC_DRAW)
+            gl.glEnableVertexAttribArray(2)
+            gl.glVertexAttribPointer(2, 4, GL_UNSIGNED_BYTE, 1, 0, None)     # normalised: c / 255
+        else:
+            gl.glDisableVertexAttribArray(2)
+            gl.glVertexAttrib4f(2, C.c_float(1.0), C.c_float(1.0), C.c_float(1.0), C.c_float(1.0))
         self.check("set_mesh")
 
     def draw(self, verts_view: np.ndarray):

@@ -3,7 +3,7 @@
 
     tools/kernel_occupancy.py            print the table
     tools/kernel_occupancy.py --write    rewrite tests/golden/kernel_occupancy.json (and kernel_occupancy_msaa.json,
-                                         kernel_occupancy_wino.json) from the build
+                                         kernel_occupancy_vcolor.json, kernel_occupancy_wino.json) from the build
 
 A convolution tile's rate depends on how many workgroups a CU holds, i.e. on which side of 168 / 128 / 102 ... registers the
 compiler lands - and every epilogue kind compiled into a tile moves that number (round 4: two new kinds took the 80-row tile
@@ -11,7 +11,8 @@ from 166 to 191 registers, three resident workgroups per CU to two, conv6 / conv
 no test saw it, the evidence pass did).  tests/test_host_logic.py::test_kernel_occupancy_table compares the build with the
 committed table: fewer waves per SIMD or more spilled registers than recorded fail, on the CPU, at build time.  The multisampled
 rasteriser's kernels are built into an object directory of their own (build/msaa/) with a table of their own,
-tests/golden/kernel_occupancy_msaa.json, held to the same rule by tests/test_msaa_occupancy.py; so are the Winograd convolution
+tests/golden/kernel_occupancy_msaa.json, held to the same rule by tests/test_msaa_occupancy.py; so are the tile kernels that
+shade with per-vertex colours (build/vcolor/, kernel_occupancy_vcolor.json, tests/test_vcolor_occupancy.py) and the Winograd convolution
 tiles (build/wino/, tests/golden/kernel_occupancy_wino.json, tests/test_winograd_occupancy.py)."""
 import json
 import re
@@ -24,6 +25,7 @@ REPO = Path(__file__).resolve().parents[1]
 LLVM = Path("/opt/rocm/lib/llvm/bin")
 TABLE = REPO / "tests" / "golden" / "kernel_occupancy.json"
 MSAA_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_msaa.json"
+VCOLOR_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_vcolor.json"
 WINO_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_wino.json"
 BUILD = REPO / "mvlm_amd" / "csrc" / "build"
 
@@ -67,7 +69,8 @@ def build_table(objdir: Path = BUILD) -> dict:
 
 
 if __name__ == "__main__":
-    for table_path, objdir in ((TABLE, BUILD), (MSAA_TABLE, BUILD / "msaa"), (WINO_TABLE, BUILD / "wino")):
+    for table_path, objdir in ((TABLE, BUILD), (MSAA_TABLE, BUILD / "msaa"), (VCOLOR_TABLE, BUILD / "vcolor"),
+                                (WINO_TABLE, BUILD / "wino")):
         t = build_table(objdir)
         if "--write" in sys.argv:
             table_path.write_text(json.dumps({k: {"waves_per_simd": v["waves_per_simd"], "spilled": v["spilled"]} for k, v in t.items()}, indent=1) + "\n")
