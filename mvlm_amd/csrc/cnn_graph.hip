@@ -227,8 +227,9 @@ struct Exec {
         if (st.profiling) {
             hipEventRecord(e1, ctx->cur_stream());
             ConvProfileRec rec{slot, variant, conv_flops(a, variant), e0, e1};
-            const short sh[6] = {short(a.ksize), short(a.cin_pad), short(a.cout_pad), short(a.H), short(mvlm_conv_kind(a)), short(B > 32767 ? 32767 : B)};
-            for (int k = 0; k < 6; ++k) rec.shape[k] = sh[k];
+            const ConvKey key = mvlm_conv_key(a);
+            const short shape[6] = {key.ksize, key.cin_pad, key.cout_pad, key.size, key.kind, key.batch};
+            for (int i = 0; i < 6; ++i) rec.shape[i] = shape[i];
             st.prof.push_back(rec);
         }
         return 0;

@@ -146,6 +146,10 @@ struct ConvOverride {
     short ksize, cin_pad, cout_pad, size, kind;
     int variant;
 };
+// What the dispatcher looks a launch up by (conv_mfma.hip: mvlm_conv_key); also the shape[6] of a profile record.
+struct ConvKey {
+    short ksize, cin_pad, cout_pad, size, kind, batch;  // batch: clamped to the 16-bit field of the measured tables
+};
 
 // one captured forward pass (hipGraph) of the network for a fixed set of buffers and shapes
 struct CnnGraphEntry {
@@ -352,6 +356,7 @@ int mvlm_launch_conv(mvlm_ctx* ctx, const ConvArgs& a, int* variant_out);
 bool mvlm_conv_in2_ok(const mvlm_ctx* ctx, const ConvArgs& a);  // this launch would run on the tile that can add ConvArgs::in2 on its load
 bool mvlm_conv_can_pool(const mvlm_ctx* ctx, const ConvArgs& a);  // the variant this launch would use can also emit the 2x2 max-pooled tensor
 int mvlm_conv_kind(const ConvArgs& a);
+ConvKey mvlm_conv_key(const ConvArgs& a);
 bool mvlm_conv_variant_can_pool(int variant);
 bool mvlm_conv_variant_is_wino(int variant);
 // the Winograd variant this launch is routed to (overrides, mode and table of the context), or -1: the direct tiles

@@ -35,20 +35,32 @@
 //   where the direct form spends 6 - same instruction, fp32 in and out.  mvlm_conv_wino_variant() routes a launch there where
 //   the measured table conv_tuned_wino.h says it is faster (mvlm_cnn_set_winograd / MVLM_WINOGRAD: 0 never, 1 table, 2 always).
 //   A profile record of such a launch counts the FLOPs its MFMAs execute (12 Cin Cout H W B, not 18).
+//
+// How a launch finds its kernel.  Every variant of conv_variants.h has one row in VARIANTS below (tile geometry, features,
+// launchers); tile_fits() is the one statement of "this tile divides this layer".  A launch is looked up by its ConvKey
+// (ksize, cin_pad, cout_pad, size, kind, batch), in this order:
+//   1. a tuning override of the context for the key's shape and kind (mvlm_conv_set_override),
+//   2. the Winograd routing (mode 0 never, 2 wherever a Winograd tile can serve, 1 the measured table conv_tuned_wino.h),
+//   3. the in-network table conv_tuned_net.h, 4. the single-layer table conv_tuned.h - both by the entry of the smallest
+//      tuned batch >= the launch's, 5. the rules (pick_variant_rules).
+// Launches with a fused argmax, an upsampled input or a parity output and the 2x2 layers go straight to the rules: one
+// kernel can serve them.  Every decision is pinned by tests/golden/conv_routing.txt (tests/test_conv_routing_cpu.py).
+#include <algorithm>
+#include <array>
 #include <cstdlib>
+#include <map>
+#include <mutex>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "common.h"
-#include "conv_kernel.h"   // Cfg<> (tile geometry) for the compile-time queries below; kernels are not instantiated here
+#include "conv_kernel.h"   // Cfg<> (tile geometry) for the variant table below; kernels are not instantiated here
 #include "conv_variants.h"
 #include "conv_tuned.h"
 #include "conv_tuned_net.h"
 #include "conv_pair_tuned.h"
 #include "conv_tuned_wino.h"
-#include <map>
-#include <mutex>
-#include <algorithm>
 
 // one launcher per variant, defined in conv_inst_g*.hip
 #define X(id, name, ...)                                         \
@@ -58,6 +70,67 @@ MVLM_CONV_VARIANTS(X)
 #undef X
 
 namespace {
+
+// ---- the variant table ------------------------------------------------------------------------------------------------------
+struct ConvVariantInfo {
+    int id;
+    const char* name;
+    int KS, TW, TRI, NIMG, COUT_T, CK, PIX_T, NT, BN_MAXC;
+    bool SPLITK, WINO, TAIL16, PAIRABLE, CAN_POOL_ANY, HAS_IN2;
+    int (*launch)(mvlm_ctx*, const ConvArgs&);
+    int (*launch_pair)(mvlm_ctx*, const ConvArgs&, const ConvArgs&);
+};
+constexpr int MAX_VARIANT_ID = 64;  // base ids live in the low byte of a variant code; the table is indexed by them
+
+template <int ID, class V>
+constexpr ConvVariantInfo variant_info(const char* name, int (*launch)(mvlm_ctx*, const ConvArgs&),
+                                       int (*launch_pair)(mvlm_ctx*, const ConvArgs&, const ConvArgs&)) {
+    static_assert(ID >= 0 && ID < MAX_VARIANT_ID, "conv variant ids are below 64");
+    return {ID, name, V::KS, V::TW, V::TRI, V::NIMG, V::COUT_T, V::CK, V::PIX_T, V::NT, V::BN_MAXC,
+            V::SPLITK, V::WINO, V::TAIL16, V::PAIRABLE, V::CAN_POOL_ANY, V::HAS_IN2, launch, launch_pair};
+}
+
+constexpr ConvVariantInfo VARIANTS[] = {
+#define X(id, name, ...) variant_info<id, __VA_ARGS__>(name, mvlm_conv_launch_##id, mvlm_conv_pair_launch_##id),
+    MVLM_CONV_VARIANTS(X)
+#undef X
+};
+
+// the variant of this base id, or null
+const ConvVariantInfo* conv_variant(int id) {
+    static const std::array<const ConvVariantInfo*, MAX_VARIANT_ID> by_id = [] {
+        std::array<const ConvVariantInfo*, MAX_VARIANT_ID> t{};
+        for (const ConvVariantInfo& v : VARIANTS) t[size_t(v.id)] = &v;
+        return t;
+    }();
+    return id >= 0 && id < MAX_VARIANT_ID ? by_id[size_t(id)] : nullptr;
+}
+
+// Does the tile divide this layer?  Every "can this variant serve ..." question is this plus the caller's own conditions.
+// (check_variant<C> in conv_kernel.h states the same once more at the launch, as the last line of defence.)
+bool tile_fits(const ConvVariantInfo& t, int ksize, int cin_pad, int cout_pad, int H, int W) {
+    return ksize == t.KS && W % t.TW == 0 && H % t.TRI == 0 && cout_pad % t.COUT_T == 0 && cin_pad % t.CK == 0 &&
+           (!t.SPLITK || cin_pad % 32 == 0);
+}
+
+// ---- keys and measured tables -----------------------------------------------------------------------------------------------
+// The entry of the smallest tuned batch >= `batch` among those whose leading fields `lead_of(entry)` (a tuple, in the
+// table's sort order) equal `lead`, or null.  The tables are sorted by (leading fields, batch).
+template <class E, class Lead, class LeadOf>
+const E* tuned_entry(const E* table, int n, const Lead& lead, short batch, LeadOf lead_of) {
+    const E* end = table + n;
+    const E* it = std::lower_bound(table, end, std::make_pair(lead, batch),
+                                   [&](const E& e, const std::pair<Lead, short>& key) { return std::make_pair(lead_of(e), e.batch) < key; });
+    return it != end && lead_of(*it) == lead ? it : nullptr;
+}
+
+// the tuning override of this context for the key's shape and kind, or null
+const ConvOverride* find_override(const mvlm_ctx* ctx, const ConvKey& k) {
+    if (ctx)
+        for (const ConvOverride& o : ctx->conv_overrides)
+            if (o.ksize == k.ksize && o.cin_pad == k.cin_pad && o.cout_pad == k.cout_pad && o.size == k.size && o.kind == k.kind) return &o;
+    return nullptr;
+}
 
 // level holds at most this many pixels in total -> latency-bound launch, split-K tiles
 constexpr long SPLITK_MAX_PIXELS = 8192;
@@ -93,90 +166,51 @@ int pick_variant_rules(const ConvArgs& a) {
     return -1;
 }
 
-// Measured choice first, the rules otherwise.  Order: a tuning override of this context (tools/tune_in_network.py), the
-// in-network table (conv_tuned_net.h: every layer kind timed INSIDE a forward pass on real activations - a launch whose
-// tensors come from HBM behind other layers ranks the tiles differently from one that re-reads them out of the MALL),
-// the single-layer table (conv_tuned.h: mvlm_conv_bench on idle data, plain layers only).  The fused argmax / upsampling
-// launches have one kernel that can serve them.
+// The direct tiles' choice: measured first, the rules otherwise.  Order: a tuning override of this context
+// (tools/tune_in_network.py), the in-network table (conv_tuned_net.h: every layer kind timed INSIDE a forward pass on real
+// activations - a launch whose tensors come from HBM behind other layers ranks the tiles differently from one that re-reads
+// them out of the MALL), the single-layer table (conv_tuned.h: mvlm_conv_bench on idle data, plain layers only).  The fused
+// argmax / upsampling launches have one kernel that can serve them.
 int pick_variant(const mvlm_ctx* ctx, const ConvArgs& a, bool rules_only = false) {
     const int by_rule = pick_variant_rules(a);
     if (rules_only || a.amax_val || a.up_in || a.up_out == 2 || a.ksize == 2 || a.H != a.W) return by_rule;
-    const int kind = mvlm_conv_kind(a);
-    if (ctx)
-        for (const ConvOverride& o : ctx->conv_overrides)
-            if (o.ksize == a.ksize && o.cin_pad == a.cin_pad && o.cout_pad == a.cout_pad && o.size == a.H && o.kind == kind) return o.variant;
-    const short batch = short(a.B > 32767 ? 32767 : a.B);
-    if (MVLM_CONV_TUNED_NET_N > 0) {
-        const ConvTunedNet key = {short(a.ksize), short(a.cin_pad), short(a.cout_pad), short(a.H), short(kind), batch, 0};
-        auto less = [](const ConvTunedNet& x, const ConvTunedNet& y) {
-            if (x.ksize != y.ksize) return x.ksize < y.ksize;
-            if (x.cin_pad != y.cin_pad) return x.cin_pad < y.cin_pad;
-            if (x.cout_pad != y.cout_pad) return x.cout_pad < y.cout_pad;
-            if (x.size != y.size) return x.size < y.size;
-            if (x.kind != y.kind) return x.kind < y.kind;
-            return x.batch < y.batch;
-        };
-        const ConvTunedNet* end = MVLM_CONV_TUNED_NET + MVLM_CONV_TUNED_NET_N;
-        const ConvTunedNet* it = std::lower_bound(MVLM_CONV_TUNED_NET, end, key, less);  // smallest tuned batch >= B of this (shape, kind)
-        if (it != end && it->ksize == key.ksize && it->cin_pad == key.cin_pad && it->cout_pad == key.cout_pad && it->size == key.size &&
-            it->kind == key.kind)
-            return it->variant;
-    }
-    if (MVLM_CONV_TUNED_N == 0) return by_rule;
-    const ConvTuned key = {short(a.ksize), short(a.cin_pad), short(a.cout_pad), short(a.H), batch, 0};
-    auto less = [](const ConvTuned& x, const ConvTuned& y) {
-        if (x.ksize != y.ksize) return x.ksize < y.ksize;
-        if (x.cin_pad != y.cin_pad) return x.cin_pad < y.cin_pad;
-        if (x.cout_pad != y.cout_pad) return x.cout_pad < y.cout_pad;
-        if (x.size != y.size) return x.size < y.size;
-        return x.batch < y.batch;
-    };
-    const ConvTuned* end = MVLM_CONV_TUNED + MVLM_CONV_TUNED_N;
-    const ConvTuned* it = std::lower_bound(MVLM_CONV_TUNED, end, key, less);  // smallest tuned batch >= B of this shape
-    if (it == end || it->ksize != key.ksize || it->cin_pad != key.cin_pad || it->cout_pad != key.cout_pad || it->size != key.size)
-        return by_rule;
-    return it->variant;
+    const ConvKey k = mvlm_conv_key(a);
+    if (const ConvOverride* o = find_override(ctx, k)) return o->variant;
+    const auto shape = std::make_tuple(k.ksize, k.cin_pad, k.cout_pad, k.size);
+    if (const ConvTunedNet* e = tuned_entry(MVLM_CONV_TUNED_NET, MVLM_CONV_TUNED_NET_N, std::tuple_cat(shape, std::make_tuple(k.kind)), k.batch,
+                                            [](const ConvTunedNet& e) { return std::make_tuple(e.ksize, e.cin_pad, e.cout_pad, e.size, e.kind); }))
+        return e->variant;
+    if (const ConvTuned* e = tuned_entry(MVLM_CONV_TUNED, MVLM_CONV_TUNED_N, shape, k.batch,
+                                         [](const ConvTuned& e) { return std::make_tuple(e.ksize, e.cin_pad, e.cout_pad, e.size); }))
+        return e->variant;
+    return by_rule;
 }
 
 // The Winograd variant that can serve this launch at all (shape and features), or -1.
 int wino_candidate(const ConvArgs& a) {
     if (a.ksize != 3 || a.up_in || a.in2 || a.amax_val || a.up_out == 2 || a.n_par != 1 || a.H != a.W) return -1;
-    int found = -1;
-#define X(id, name, ...)                                                                                             \
-    {                                                                                                                \
-        using V = __VA_ARGS__;                                                                                       \
-        if (found < 0 && a.W % V::TW == 0 && a.H % V::TRI == 0 && a.cout_pad % V::COUT_T == 0 && a.cin_pad % V::CK == 0 && \
-            a.cin_pad <= V::BN_MAXC)                                                                                 \
-            found = id;                                                                                              \
-    }
-    MVLM_CONV_VARIANTS_W0(X)
-#undef X
-    return found;
+    // (cin_pad <= BN_MAXC: the pre-BN parameters must fit the LDS; asked whether or not this layer has a pre-BN)
+    for (const ConvVariantInfo& t : VARIANTS)
+        if (t.WINO && tile_fits(t, a.ksize, a.cin_pad, a.cout_pad, a.H, a.W) && a.cin_pad <= t.BN_MAXC) return t.id;
+    return -1;
 }
 
 }  // namespace
 
+ConvKey mvlm_conv_key(const ConvArgs& a) {
+    return {short(a.ksize), short(a.cin_pad), short(a.cout_pad), short(a.H), short(mvlm_conv_kind(a)), short(a.B > 32767 ? 32767 : a.B)};
+}
+
 bool mvlm_conv_variant_is_wino(int v) {
-    if (v < 0 || v >= 256) return false;
-    switch (v) {
-#define X(id, name, ...) \
-    case id:             \
-        return true;
-        MVLM_CONV_VARIANTS_W0(X)
-#undef X
-    }
-    return false;
+    const ConvVariantInfo* t = conv_variant(v);
+    return t && t->WINO;
 }
 
 bool mvlm_conv_wino_serves_slot(int ksize, int cin_pad, int cout_pad) {
-    if (ksize != 3) return false;
-#define X(id, name, ...)                                                  \
-    {                                                                     \
-        using V = __VA_ARGS__;                                            \
-        if (cout_pad % V::COUT_T == 0 && cin_pad % V::CK == 0) return true; \
-    }
-    MVLM_CONV_VARIANTS_W0(X)
-#undef X
+    // a slot has channels but no size yet: asked at the tile's own size.  No cin_pad <= BN_MAXC here (historical: a wider
+    // slot gets transformed weights that no launch is routed to).
+    for (const ConvVariantInfo& t : VARIANTS)
+        if (t.WINO && tile_fits(t, ksize, cin_pad, cout_pad, t.TRI, t.TW)) return true;
     return false;
 }
 
@@ -186,17 +220,14 @@ bool mvlm_conv_wino_serves_slot(int ksize, int cin_pad, int cout_pad) {
 int mvlm_conv_wino_variant(const mvlm_ctx* ctx, const ConvArgs& a) {
     const int cand = wino_candidate(a);
     if (cand < 0) return -1;
-    const int kind = mvlm_conv_kind(a);
-    if (ctx)
-        for (const ConvOverride& o : ctx->conv_overrides)
-            if (o.ksize == a.ksize && o.cin_pad == a.cin_pad && o.cout_pad == a.cout_pad && o.size == a.H && o.kind == kind)
-                return mvlm_conv_variant_is_wino(o.variant) ? o.variant : -1;
+    const ConvKey k = mvlm_conv_key(a);
+    if (const ConvOverride* o = find_override(ctx, k)) return mvlm_conv_variant_is_wino(o->variant) ? o->variant : -1;
     const int mode = ctx ? ctx->conv_winograd : 1;
     if (mode == 0) return -1;
     if (mode == 2) return cand;
     for (int i = 0; i < MVLM_CONV_TUNED_WINO_N; ++i) {
         const ConvTunedWino& e = MVLM_CONV_TUNED_WINO[i];
-        if (e.cin_pad == a.cin_pad && e.cout_pad == a.cout_pad && e.size == a.H && e.kind == kind && a.B >= e.min_batch) return e.variant;
+        if (e.cin_pad == k.cin_pad && e.cout_pad == k.cout_pad && e.size == k.size && e.kind == k.kind && k.batch >= e.min_batch) return e.variant;
     }
     return -1;
 }
@@ -245,14 +276,8 @@ const char* mvlm_conv_variant_name_impl(int v) {
         }
         return it->second.c_str();
     }
-    switch (v) {
-#define X(id, name, ...) \
-    case id:             \
-        return name;
-        MVLM_CONV_VARIANTS(X)
-#undef X
-    }
-    return "?";
+    const ConvVariantInfo* t = conv_variant(v);
+    return t ? t->name : "?";
 }
 
 // Would the dispatcher run this layer on the tile that can add a second, half-resolution input tensor on its load
@@ -261,7 +286,7 @@ const char* mvlm_conv_variant_name_impl(int v) {
 bool mvlm_conv_in2_ok(const mvlm_ctx* ctx, const ConvArgs& a) {
     if (a.ksize != 3 || a.up_in || a.up_out || a.amax_val || a.in_coff != 0 || (a.H & 1) || a.H != a.W) return false;
     if (ctx && ctx->conv_force_variant != -1) return false;
-    return route_variant(ctx, a) == 0;  // (a Winograd tile has no second-input form)
+    return route_variant(ctx, a) == 0;  // (the one variant with HAS_IN2; a Winograd tile has no second-input form)
 }
 
 int mvlm_conv_kind(const ConvArgs& a) { return a.up_out == 1 ? 1 : ((a.pool_out || a.pool_hint) ? 2 : 0); }
@@ -270,46 +295,20 @@ bool mvlm_conv_can_pool(const mvlm_ctx* ctx, const ConvArgs& a_in) {
     if (a_in.up_out || a_in.amax_val || (a_in.H & 1) || (a_in.W & 1)) return false;
     ConvArgs a = a_in;
     a.pool_hint = 1;
-    if (ctx && ctx->conv_force_variant >= 0) return mvlm_conv_variant_can_pool(ctx->conv_force_variant);
-    switch (route_variant(ctx, a) & 255) {
-#define X(id, name, ...)                                                                                   \
-    case id: {                                                                                             \
-        using V = __VA_ARGS__;                                                                             \
-        return V::CAN_POOL_ANY;                                                                            \
-    }
-        MVLM_CONV_VARIANTS(X)
-#undef X
-    }
-    return false;
+    return mvlm_conv_variant_can_pool((ctx && ctx->conv_force_variant >= 0) ? ctx->conv_force_variant : route_variant(ctx, a));
 }
 
 bool mvlm_conv_variant_can_pool(int v) {
-    switch (v & 255) {
-#define X(id, name, ...)                                                                                   \
-    case id: {                                                                                             \
-        using V = __VA_ARGS__;                                                                             \
-        return V::CAN_POOL_ANY;                                                                            \
-    }
-        MVLM_CONV_VARIANTS(X)
-#undef X
-    }
-    return false;
+    const ConvVariantInfo* t = conv_variant(v & 255);
+    return t && t->CAN_POOL_ANY;
 }
 
 namespace {
 // can variant `v` (base id) serve this problem, and does it exist as a two-problem kernel?
+// (no cin_pad <= BN_MAXC: the launch checks it where the layer has a pre-BN, as for every direct tile)
 bool pair_variant_serves(int v, const ConvArgs& a) {
-    switch (v) {
-#define X(id, name, ...)                                                                                                \
-    case id: {                                                                                                          \
-        using V = __VA_ARGS__;                                                                                          \
-        return V::PAIRABLE && a.ksize == V::KS && a.W % V::TW == 0 && a.H % V::TRI == 0 && a.cout_pad % V::COUT_T == 0 && \
-               a.cin_pad % V::CK == 0 && (!V::SPLITK || a.cin_pad % 32 == 0);                                           \
-    }
-        MVLM_CONV_VARIANTS(X)
-#undef X
-    }
-    return false;
+    const ConvVariantInfo* t = conv_variant(v);
+    return t && t->PAIRABLE && tile_fits(*t, a.ksize, a.cin_pad, a.cout_pad, a.H, a.W);
 }
 }  // namespace
 
@@ -322,30 +321,20 @@ int mvlm_conv_pair_variant(const ConvArgs& a0, const ConvArgs& a1, int mode) {
     for (const ConvArgs* a : {&a0, &a1})
         if (a->ksize != 3 || a->amax_val || a->up_in || a->up_out == 2 || a->n_par != 1 || a->H != a->W) return -1;
     if (a0.B != a1.B) return -1;
-    int v = -1;
     if (mode == 2) {
         for (int cand : {pick_variant(nullptr, a0), pick_variant(nullptr, a1), pick_variant_rules(a0), pick_variant_rules(a1)}) {
             if (cand < 0) continue;
             const int base = cand & 255, lg = cand >> 8;
-            if (pair_variant_serves(base, a0) && pair_variant_serves(base, a1)) {
-                v = base | (lg << 8) | (lg << 10);
-                break;
-            }
+            if (pair_variant_serves(base, a0) && pair_variant_serves(base, a1)) return base | (lg << 8) | (lg << 10) | MVLM_CONV_PAIR_FLAG;
         }
-        return v < 0 ? -1 : (v | MVLM_CONV_PAIR_FLAG);
+        return -1;
     }
-    if (MVLM_CONV_PAIR_TUNED_N == 0 || a0.cin_pad != a1.cin_pad || a0.cout_pad != a1.cout_pad || a0.H != 2 * a1.H) return -1;
-    const ConvPairTuned key = {short(a0.cin_pad), short(a0.cout_pad), short(a0.H), short(a0.B > 32767 ? 32767 : a0.B), 0};
-    auto less = [](const ConvPairTuned& x, const ConvPairTuned& y) {
-        if (x.cin_pad != y.cin_pad) return x.cin_pad < y.cin_pad;
-        if (x.cout_pad != y.cout_pad) return x.cout_pad < y.cout_pad;
-        if (x.size != y.size) return x.size < y.size;
-        return x.batch < y.batch;
-    };
-    const ConvPairTuned* end = MVLM_CONV_PAIR_TUNED + MVLM_CONV_PAIR_TUNED_N;
-    const ConvPairTuned* it = std::lower_bound(MVLM_CONV_PAIR_TUNED, end, key, less);  // smallest tuned batch >= B of this pair shape
-    if (it == end || it->cin_pad != key.cin_pad || it->cout_pad != key.cout_pad || it->size != key.size || it->variant < 0) return -1;
-    v = it->variant;
+    if (a0.cin_pad != a1.cin_pad || a0.cout_pad != a1.cout_pad || a0.H != 2 * a1.H) return -1;
+    const ConvKey k = mvlm_conv_key(a0);
+    const ConvPairTuned* e = tuned_entry(MVLM_CONV_PAIR_TUNED, MVLM_CONV_PAIR_TUNED_N, std::make_tuple(k.cin_pad, k.cout_pad, k.size), k.batch,
+                                         [](const ConvPairTuned& e) { return std::make_tuple(e.cin_pad, e.cout_pad, e.size); });
+    if (!e || e->variant < 0) return -1;
+    const int v = e->variant;
     if (!pair_variant_serves(v & 255, a0) || !pair_variant_serves(v & 255, a1)) return -1;
     // The table was measured without the pool kernel that follows a block whose tiles cannot emit the pooled tensor.  Since
     // round 5 every pairable tile but the one-row split-K tiles (t1x32) pools in its epilogue; for those, keep the pair only
@@ -372,14 +361,8 @@ int mvlm_launch_conv_pair(mvlm_ctx* ctx, const ConvArgs& a0, const ConvArgs& a1,
     }
     b[0].kparts = 1 << ((pair_variant >> 8) & 3);
     b[1].kparts = 1 << ((pair_variant >> 10) & 3);
-    switch (pair_variant & 255) {
-#define X(id, name, ...) \
-    case id:             \
-        return mvlm_conv_pair_launch_##id(ctx, b[0], b[1]);
-        MVLM_CONV_VARIANTS(X)
-#undef X
-    }
-    return ctx->fail("conv: unreachable variant");
+    const ConvVariantInfo* t = conv_variant(pair_variant & 255);
+    return t ? t->launch_pair(ctx, b[0], b[1]) : ctx->fail("conv: unreachable variant");
 }
 
 int mvlm_conv_amax_parts(int H, int W) {
@@ -393,6 +376,7 @@ int mvlm_launch_conv(mvlm_ctx* ctx, const ConvArgs& a, int* variant_out) {
     MVLM_REQUIRE(ctx, !a.up_in || (a.H % 2 == 0), "conv: upsampled input needs even size");
     MVLM_REQUIRE(ctx, a.up_out != 1 || a.skip, "conv: up_out needs a skip tensor");
     MVLM_REQUIRE(ctx, a.ksize != 2 || ((a.sub_y | a.sub_x) & ~1) == 0, "conv: 2x2 window offset must be 0 or 1");
+    // (a failed check's message ends in the source text of its condition, so these stay spelled out here and in the pair launch)
     const double px = double(a.B) * a.H * a.W, lim = 4294967295.0;
     MVLM_REQUIRE(ctx, px * a.in_ctot < lim, "conv: input tensor exceeds 32-bit element offsets (lower the batch)");
     MVLM_REQUIRE(ctx, !a.out_raw || px * a.raw_ctot < lim, "conv: raw output exceeds 32-bit element offsets");
@@ -416,14 +400,8 @@ int mvlm_launch_conv(mvlm_ctx* ctx, const ConvArgs& a, int* variant_out) {
     ConvArgs b = a;
     b.kparts = 1 << (v >> 8);
     if (wino) b.w = a.w_wino;
-    switch (v & 255) {
-#define X(id, name, ...) \
-    case id:             \
-        return mvlm_conv_launch_##id(ctx, b);
-        MVLM_CONV_VARIANTS(X)
-#undef X
-    }
-    return ctx->fail("conv: unreachable variant");
+    const ConvVariantInfo* t = conv_variant(v & 255);
+    return t ? t->launch(ctx, b) : ctx->fail("conv: unreachable variant");
 }
 
 
@@ -433,22 +411,13 @@ int mvlm_launch_conv(mvlm_ctx* ctx, const ConvArgs& a, int* variant_out) {
 // serve conv6 / conv10 only)
 extern "C" int mvlm_conv_variant_serves(int variant, int ksize, int cin_pad, int cout_pad, int size, int kind) {
     if (variant < 0 || variant >= 1024 || ksize != 3 || kind < 0 || kind > 2) return 0;
+    const ConvVariantInfo* t = conv_variant(variant & 255);
+    if (!t || !tile_fits(*t, ksize, cin_pad, cout_pad, size, size)) return 0;
     const int parts = 1 << (variant >> 8);
-    switch (variant & 255) {
-#define X(id, name, ...)                                                                                                     \
-    case id: {                                                                                                               \
-        using V = __VA_ARGS__;                                                                                               \
-        if (V::KS != 3 || V::TAIL16 || V::COUT_T == 96) return 0;                                                            \
-        if (V::WINO && cin_pad > V::BN_MAXC) return 0;                                                                       \
-        if (size % V::TW != 0 || size % V::TRI != 0 || cout_pad % V::COUT_T != 0 || cin_pad % V::CK != 0) return 0;          \
-        if (V::SPLITK && cin_pad % 32 != 0) return 0;                                                                        \
-        if (parts > 1 && (!V::SPLITK || V::PIX_T != 32 || cin_pad % (parts * V::CK) != 0)) return 0;                         \
-        return 1;                                                                                                            \
-    }
-        MVLM_CONV_VARIANTS(X)
-#undef X
-    }
-    return 0;
+    const bool residual_block_tile = !t->TAIL16 && t->COUT_T != 96;                // (the 80-, 84- and 96-row tiles serve the last layers only)
+    const bool bn_fits = !t->WINO || cin_pad <= t->BN_MAXC;                         // (as wino_candidate; the direct tiles check it at the launch)
+    const bool parts_ok = parts == 1 || (t->SPLITK && t->PIX_T == 32 && cin_pad % (parts * t->CK) == 0);
+    return residual_block_tile && bn_fits && parts_ok;
 }
 
 // kernel variant for every launch of this (shape, kind) on this context, ahead of all tables; variant < 0 removes the
@@ -459,14 +428,13 @@ extern "C" int mvlm_conv_set_override(mvlm_ctx* ctx, int ksize, int cin_pad, int
     if (ksize == 0) {
         ov.clear();
     } else {
-        for (size_t i = 0; i < ov.size();)
-            if (ov[i].ksize == ksize && ov[i].cin_pad == cin_pad && ov[i].cout_pad == cout_pad && ov[i].size == size && ov[i].kind == kind)
-                ov.erase(ov.begin() + long(i));
-            else
-                ++i;
+        const ConvKey k = {short(ksize), short(cin_pad), short(cout_pad), short(size), short(kind), 0};
+        // (an argument beyond the entries' 16-bit fields matches none of them)
+        const bool fits = k.ksize == ksize && k.cin_pad == cin_pad && k.cout_pad == cout_pad && k.size == size && k.kind == kind;
+        while (const ConvOverride* o = fits ? find_override(ctx, k) : nullptr) ov.erase(ov.begin() + (o - ov.data()));
         if (variant >= 0) {
             MVLM_REQUIRE(ctx, mvlm_conv_variant_serves(variant, ksize, cin_pad, cout_pad, size, kind), "conv_set_override: the variant cannot serve this shape");
-            ov.push_back({short(ksize), short(cin_pad), short(cout_pad), short(size), short(kind), variant});
+            ov.push_back({k.ksize, k.cin_pad, k.cout_pad, k.size, k.kind, variant});
         }
     }
     for (auto& g : ctx->cnn.graphs)

@@ -1,0 +1,476 @@
+// Prints what the convolution dispatcher (mvlm_amd/csrc/conv_mfma.hip) decides, as a text table, without a GPU.
+// Built by tests/test_conv_routing_cpu.py: this file and conv_mfma.hip are compiled host-only and linked without the kernels'
+// translation units and without the HIP runtime.  The launchers mvlm_conv_launch_<id> / mvlm_conv_pair_launch_<id> are stubs
+// that record which one was reached and what it was given; the few HIP calls the dispatcher's entry points make are stubs
+// that succeed.  No data pointer is ever dereferenced: they all point at one dummy float.
+// The output (tests/golden/conv_routing.txt) is run-length encoded over the batch axis (BATCHES) and grouped: one line
+//   <what> {<case> <case> ...} | <batches> <result>, <batches> <result>, ...
+// for all cases of <what> (context states, input channels, launch features ...) that decide alike at every batch.
+#include <cstdio>
+#include <functional>
+#include <map>
+#include <set>
+#include <string>
+#include <tuple>
+#include <vector>
+
+#include "../../mvlm_amd/csrc/common.h"
+#include "../../mvlm_amd/csrc/conv_variants.h"
+#include "../../mvlm_amd/csrc/conv_tuned.h"
+#include "../../mvlm_amd/csrc/conv_tuned_net.h"
+#include "../../mvlm_amd/csrc/conv_pair_tuned.h"
+#include "../../mvlm_amd/csrc/conv_tuned_wino.h"
+
+// ---- stubs ------------------------------------------------------------------------------------------------------------------
+hipError_t hipSetDevice(int) { return hipSuccess; }
+const char* hipGetErrorString(hipError_t) { return "hip stub"; }
+hipError_t hipGetLastError() { return hipSuccess; }
+hipError_t hipMalloc(void**, size_t) { return hipErrorOutOfMemory; }
+hipError_t hipMemset(void*, int, size_t) { return hipSuccess; }
+hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
+hipError_t hipGraphExecDestroy(hipGraphExec_t) { return hipSuccess; }
+
+namespace {
+struct Reached {
+    int id = -1, kparts0 = 0, kparts1 = 0;
+    const float* w = nullptr;
+} g_reached;
+}  // namespace
+
+#define X(id, name, ...)                                                                    \
+    int mvlm_conv_launch_##id(mvlm_ctx*, const ConvArgs& a) {                               \
+        g_reached = {id, a.kparts, 0, a.w};                                                 \
+        return 0;                                                                           \
+    }                                                                                       \
+    int mvlm_conv_pair_launch_##id(mvlm_ctx*, const ConvArgs& a0, const ConvArgs& a1) {     \
+        g_reached = {id, a0.kparts, a1.kparts, a0.w};                                       \
+        return 0;                                                                           \
+    }
+MVLM_CONV_VARIANTS(X)
+#undef X
+
+namespace {
+
+float g_dummy, g_dummy_wino;
+int g_dummy_int;
+
+std::vector<int> batches() {
+    std::vector<int> b;
+    for (int i = 1; i <= 130; ++i) b.push_back(i);
+    b.push_back(40000);  // beyond the tables' 16-bit batch field: the clamp
+    return b;
+}
+const std::vector<int> BATCHES = batches();
+
+// error messages, numbered in order of first appearance; the legend is printed last
+std::vector<std::string> g_errors;
+std::string error_token(const std::string& e) {
+    size_t i = 0;
+    while (i < g_errors.size() && g_errors[i] != e) ++i;
+    if (i == g_errors.size()) g_errors.push_back(e);
+    return "E" + std::to_string(i + 1);
+}
+
+// "<first>-<last> <result>, ..." over BATCHES
+std::string runs(const std::function<std::string(int)>& result_at) {
+    std::string out, cur;
+    int first = 0, last = 0;
+    auto flush = [&] { out += (out.empty() ? "" : ", ") + std::to_string(first) + (last != first ? "-" + std::to_string(last) : "") + " " + cur; };
+    for (int b : BATCHES) {
+        const std::string r = result_at(b);
+        if (first && r == cur) {
+            last = b;
+            continue;
+        }
+        if (first) flush();
+        cur = r;
+        first = last = b;
+    }
+    flush();
+    return out;
+}
+
+// rows (what, case, result) printed as one line per group of cases of a `what` with equal results, in order of appearance
+struct Grouped {
+    std::vector<std::string> order;
+    std::map<std::string, std::vector<std::pair<std::string, std::string>>> rows;
+    void add(const std::string& what, const std::string& which, const std::string& result) {
+        if (!rows.count(what)) order.push_back(what);
+        rows[what].push_back({which, result});
+    }
+    void print() {
+        for (const std::string& what : order) {
+            const auto& r = rows[what];
+            std::vector<bool> done(r.size(), false);
+            for (size_t i = 0; i < r.size(); ++i) {
+                if (done[i]) continue;
+                std::string cases;
+                for (size_t j = i; j < r.size(); ++j)
+                    if (r[j].second == r[i].second) {
+                        done[j] = true;
+                        cases += (cases.empty() ? "" : " ") + r[j].first;
+                    }
+                std::printf("%s {%s} | %s\n", what.c_str(), cases.c_str(), r[i].second.c_str());
+            }
+        }
+        order.clear();
+        rows.clear();
+    }
+};
+
+using Shape = std::tuple<int, int, int, int>;  // ksize, cin_pad, cout_pad, size
+
+std::string shape_label(const Shape& s) {
+    char buf[64];
+    std::snprintf(buf, sizeof buf, "k%d %d>%d @%d", std::get<0>(s), std::get<1>(s), std::get<2>(s), std::get<3>(s));
+    return buf;
+}
+
+// kind 0 plain, 1 scatter into the skip tensor, 2 the pooled tensor is wanted
+ConvArgs make_args(const Shape& s, int kind, int batch) {
+    ConvArgs a;
+    a.ksize = std::get<0>(s);
+    a.cin = a.cin_pad = a.in_ctot = std::get<1>(s);
+    a.cout = a.cout_pad = a.out_ctot = std::get<2>(s);
+    a.H = a.W = std::get<3>(s);
+    a.B = batch;
+    a.in = a.w = &g_dummy;
+    a.w_wino = &g_dummy_wino;
+    a.out = &g_dummy;
+    if (kind == 1) {
+        a.up_out = 1;
+        a.skip = &g_dummy;
+        a.skip_ctot = a.cout_pad;
+    }
+    if (kind == 2) {
+        a.pool_hint = 1;
+        a.pool_ctot = a.cout_pad;
+    }
+    return a;
+}
+
+// One launch as a token: "<variant_out>" when mvlm_launch_conv succeeded, "E<n>" (+ "@<variant_out>" if it was set) when not,
+// then a letter per query that says yes: p mvlm_conv_can_pool, i mvlm_conv_in2_ok, w mvlm_conv_wino_variant >= 0 (+ its id
+// where that is not variant_out), s the stub received w_wino as its weights.  A successful launch must reach stub
+// variant_out & 255 with kparts 1 << (variant_out >> 8); otherwise "!<stub>/<kparts>" follows.
+// pool_as_asked: give the launch a pooled output exactly where mvlm_conv_can_pool allows one, as the network does
+std::string single(mvlm_ctx& ctx, ConvArgs a, bool pool_as_asked = true) {
+    const int pool = mvlm_conv_can_pool(&ctx, a), in2 = mvlm_conv_in2_ok(&ctx, a), wino = mvlm_conv_wino_variant(&ctx, a);
+    if (pool_as_asked && a.pool_hint && pool) a.pool_out = &g_dummy;
+    g_reached = Reached();
+    ctx.err.clear();
+    int v = -9;
+    const int rc = mvlm_launch_conv(&ctx, a, &v);
+    std::string t = rc ? error_token(ctx.err) + (v != -9 ? "@" + std::to_string(v) : "") : std::to_string(v);
+    if (pool) t += "p";
+    if (in2) t += "i";
+    if (wino >= 0) t += wino == v ? "w" : "w" + std::to_string(wino);
+    if (g_reached.w == &g_dummy_wino) t += "s";
+    if (rc ? g_reached.id != -1 : (g_reached.id != (v & 255) || g_reached.kparts0 != 1 << (v >> 8)))
+        t += "!" + std::to_string(g_reached.id) + "/" + std::to_string(g_reached.kparts0);
+    return t;
+}
+
+// "-" no pair, else the pair's variant code; a failed launch adds " E<n>"; the stub must be code & 255 and the kparts
+// 1 << (code >> 8 & 3), 1 << (code >> 10 & 3), otherwise "!<stub>/<kparts0>/<kparts1>" follows
+std::string pair_launch(mvlm_ctx& ctx, const ConvArgs& a0, const ConvArgs& a1, int pv) {
+    g_reached = Reached();
+    ctx.err.clear();
+    const int rc = mvlm_launch_conv_pair(&ctx, a0, a1, pv);
+    std::string t = std::to_string(pv) + (rc ? " " + error_token(ctx.err) : "");
+    if (rc ? g_reached.id != -1 : (g_reached.id != (pv & 255) || g_reached.kparts0 != 1 << ((pv >> 8) & 3) || g_reached.kparts1 != 1 << ((pv >> 10) & 3)))
+        t += "!" + std::to_string(g_reached.id) + "/" + std::to_string(g_reached.kparts0) + "/" + std::to_string(g_reached.kparts1);
+    return t;
+}
+std::string pair(mvlm_ctx& ctx, ConvArgs a0, ConvArgs a1, int mode) {
+    const int pv = mvlm_conv_pair_variant(a0, a1, mode);
+    if (pv < 0) return "-";
+    for (ConvArgs* a : {&a0, &a1})  // the pooled output where the pair's tile can emit it, as the network does
+        if (a->pool_hint && mvlm_conv_variant_can_pool(pv)) a->pool_out = &g_dummy;
+    return pair_launch(ctx, a0, a1, pv);
+}
+
+struct State {
+    const char* name;
+    int winograd, force;
+};
+void set_state(mvlm_ctx& ctx, const State& st) {
+    ctx.conv_winograd = st.winograd;
+    ctx.conv_force_variant = st.force;
+}
+const State DEFAULT_STATE = {"w1", 1, -1};
+
+// every shape in every kind under this state
+void singles(mvlm_ctx& ctx, Grouped& g, const std::vector<Shape>& shapes, const State& st) {
+    set_state(ctx, st);
+    for (const Shape& s : shapes)
+        for (int kind = 0; kind < 3; ++kind)
+            g.add(shape_label(s) + " kind" + std::to_string(kind), st.name, runs([&](int b) { return single(ctx, make_args(s, kind, b)); }));
+    set_state(ctx, DEFAULT_STATE);
+}
+
+// launch features beyond the kind, for the fixed list
+const char* const FEATURES[] = {"plain", "kind1", "amax", "up_in", "up_out2", "up_out2x4", "in2", "pool_out", "no_w_wino"};
+ConvArgs feature_args(const Shape& s, int feature, int batch) {
+    ConvArgs a = make_args(s, feature == 1 ? 1 : 0, batch);
+    switch (feature) {
+    case 2:
+        a.amax_val = &g_dummy;
+        a.amax_idx = &g_dummy_int;
+        a.out = nullptr;
+        break;
+    case 3: a.up_in = 1; break;
+    case 4:
+    case 5:
+        a.up_out = 2;
+        a.sub_y = 1;
+        a.n_par = feature == 5 ? 4 : 1;
+        break;
+    case 6:
+        a.in2 = &g_dummy;
+        a.in2_ctot = a.cin_pad;
+        break;
+    case 7:  // the pooled output whether or not the tile can emit it
+        a.pool_hint = 1;
+        a.pool_out = &g_dummy;
+        a.pool_ctot = a.cout_pad;
+        break;
+    case 8: a.w_wino = nullptr; break;
+    }
+    return a;
+}
+
+}  // namespace
+
+int main() {
+    mvlm_ctx ctx;
+    set_state(ctx, DEFAULT_STATE);
+    Grouped g;
+
+    // every shape of the four tuned tables (the pair table's at both of its sizes)
+    std::set<Shape> table_set;
+    for (int i = 0; i < MVLM_CONV_TUNED_N; ++i) {
+        const ConvTuned& e = MVLM_CONV_TUNED[i];
+        table_set.insert({e.ksize, e.cin_pad, e.cout_pad, e.size});
+    }
+    for (int i = 0; i < MVLM_CONV_TUNED_NET_N; ++i) {
+        const ConvTunedNet& e = MVLM_CONV_TUNED_NET[i];
+        table_set.insert({e.ksize, e.cin_pad, e.cout_pad, e.size});
+    }
+    std::set<std::tuple<int, int, int>> pair_set;
+    for (int i = 0; i < MVLM_CONV_PAIR_TUNED_N; ++i) {
+        const ConvPairTuned& e = MVLM_CONV_PAIR_TUNED[i];
+        pair_set.insert({e.cin_pad, e.cout_pad, e.size});
+        table_set.insert({3, e.cin_pad, e.cout_pad, e.size});
+        table_set.insert({3, e.cin_pad, e.cout_pad, e.size / 2});
+    }
+    for (int i = 0; i < MVLM_CONV_TUNED_WINO_N; ++i) {
+        const ConvTunedWino& e = MVLM_CONV_TUNED_WINO[i];
+        table_set.insert({3, e.cin_pad, e.cout_pad, e.size});
+    }
+    const std::vector<Shape> table_shapes(table_set.begin(), table_set.end());
+
+
+    std::printf("# single launches.  Result of a launch: <variant_out> or E<n>[@<variant_out>], then p = can_pool, i = in2_ok, w[<id>] = routed to a\n"
+                "# Winograd variant, s = the weights were swapped for w_wino.  Context states: w<m> Winograd mode m; rules conv_force_variant -2;\n"
+                "# force10 conv_force_variant 10; ov<v> after mvlm_conv_set_override(3, 128, 64, 64, kind 0, v)\n");
+    std::printf("# -- shapes of the tuned tables: <shape> <kind> {states}\n");
+    for (const State& st : {State{"w0", 0, -1}, DEFAULT_STATE, State{"w2", 2, -1}, State{"rules", 1, -2}}) singles(ctx, g, table_shapes, st);
+    g.print();
+
+    const int couts[] = {32, 64, 80, 84, 96, 128}, sizes[] = {4, 8, 16, 32, 64, 128, 256}, cins[] = {4, 16, 32, 64, 128, 256, 320};
+    const State fixed_states[] = {State{"w0", 0, -1}, DEFAULT_STATE, State{"w2", 2, -1}, State{"rules", 1, -2}};
+    std::printf("# -- fixed list, plain 3x3 layers: k3 *><cout_pad> @<size> {<state>:<cin_pad>}\n");
+    for (const State& st : fixed_states) {
+        set_state(ctx, st);
+        for (int co : couts)
+            for (int s : sizes)
+                for (int ci : cins)
+                    g.add("k3 *>" + std::to_string(co) + " @" + std::to_string(s), std::string(st.name) + ":" + std::to_string(ci),
+                          runs([&](int b) { return single(ctx, feature_args(Shape{3, ci, co, s}, 0, b)); }));
+    }
+    g.print();
+    std::printf("# -- fixed list, 1x1, 2x2 and the launch features at 128 input channels: <shape> {<state>:<feature>}\n");
+    for (const State& st : fixed_states) {
+        if (st.winograd == 0) continue;  // (mode 0 on these channels: the plain layers above and the tables' shapes)
+        set_state(ctx, st);
+        for (int ks : {1, 2, 3})
+            for (int co : couts)
+                for (int s : {16, 32, 128})
+                    for (int f = ks == 3 ? 1 : 0; f < 9; ++f) {
+                        // (the plain 3x3 layers are above; 1x1 and 2x2 do not look at the Winograd mode)
+                        if (ks != 3 && st.winograd == 2) continue;
+                        if (ks == 1 && f != 0 && f != 1 && f != 7) continue;
+                        if (ks == 2 && (f == 1 || f == 3 || f == 7 || f == 8)) continue;
+                        const Shape sh{ks, 128, co, s};
+                        g.add(shape_label(sh), std::string(st.name) + ":" + FEATURES[f], runs([&](int b) { return single(ctx, feature_args(sh, f, b), false); }));
+                    }
+    }
+    set_state(ctx, DEFAULT_STATE);
+    g.print();
+
+    std::printf("# -- a forced variant and tuning overrides: 128>64 shapes of the tables from 64x64 on\n");
+    std::vector<Shape> ov_shapes;
+    for (const Shape& s : table_shapes)
+        if (std::get<1>(s) == 128 && std::get<2>(s) == 64 && std::get<3>(s) >= 64) ov_shapes.push_back(s);
+    singles(ctx, g, ov_shapes, {"force10", 1, 10});
+    for (int variant : {9, 40, -1, 0, 265}) {
+        ctx.err.clear();
+        const int rc = mvlm_conv_set_override(&ctx, 3, 128, 64, 64, 0, variant);
+        std::printf("set_override %d -> %d%s, %d entries\n", variant, rc, rc ? (" " + error_token(ctx.err)).c_str() : "", int(ctx.conv_overrides.size()));
+        singles(ctx, g, ov_shapes, {("ov" + std::to_string(variant)).c_str(), 1, -1});
+        // an argument beyond the entries' 16-bit fields (65600 = 65536 + 64) names no entry: nothing is removed
+        if (variant == 40) std::printf("set_override -1 at size 65600 -> %d, %d entries\n", mvlm_conv_set_override(&ctx, 3, 128, 64, 65600, 0, -1), int(ctx.conv_overrides.size()));
+    }
+    std::printf("set_override clear -> %d", mvlm_conv_set_override(&ctx, 0, 0, 0, 0, 0, 0));
+    std::printf(", %d entries\n", int(ctx.conv_overrides.size()));
+    g.print();
+
+    std::printf("# -- 32-bit element offsets and the other launch checks: k3 128>128 @256 B40, one field changed\n");
+    {
+        const Shape sh{3, 128, 128, 256};
+        const int big = 2048;
+        using Change = std::function<void(ConvArgs&)>;
+        auto check = [&](const char* what, const Shape& shape, int kind, const Change& change) {
+            ConvArgs a = make_args(shape, kind, 40);
+            change(a);
+            std::printf("check %s | %s\n", what, single(ctx, a, false).c_str());
+        };
+        check("none", sh, 0, [](ConvArgs&) {});
+        check("in_ctot", sh, 0, [&](ConvArgs& a) { a.in_ctot = big; });
+        check("raw_ctot", sh, 0, [&](ConvArgs& a) { a.out_raw = &g_dummy, a.raw_ctot = big; });
+        check("res1_ctot", sh, 0, [&](ConvArgs& a) { a.res1 = &g_dummy, a.res1_ctot = big; });
+        check("res2_ctot", sh, 0, [&](ConvArgs& a) { a.res2 = &g_dummy, a.res2_ctot = big; });
+        check("out_ctot", sh, 0, [&](ConvArgs& a) { a.out_ctot = big; });
+        check("out_ctot up_out", sh, 1, [&](ConvArgs& a) { a.out_ctot = big / 4; });
+        check("skip_ctot", sh, 1, [&](ConvArgs& a) { a.skip_ctot = big / 4; });
+        check("in2_ctot", sh, 0, [&](ConvArgs& a) { a.in2 = &g_dummy, a.in2_ctot = big * 4; });
+        check("pool_ctot", sh, 2, [&](ConvArgs& a) { a.pool_out = &g_dummy, a.pool_ctot = big * 4; });
+        check("null in", sh, 0, [](ConvArgs& a) { a.in = nullptr; });
+        check("not square", sh, 0, [](ConvArgs& a) { a.W = 128; });
+        check("odd up_in", Shape{3, 128, 128, 33}, 0, [](ConvArgs& a) { a.up_in = 1; });
+        check("no skip", sh, 1, [](ConvArgs& a) { a.skip = nullptr; });
+        check("sub_x", Shape{2, 128, 96, 256}, 0, [](ConvArgs& a) { a.sub_x = 2; });
+        check("no output", sh, 0, [](ConvArgs& a) { a.out = nullptr; });
+        for (int force : {1024 + 15, 63, 256 + 15}) {
+            ctx.conv_force_variant = force;
+            check(("force " + std::to_string(force)).c_str(), sh, 0, [](ConvArgs&) {});
+        }
+        ctx.conv_force_variant = -1;
+
+        // pairs: problem 0 as above with one field changed, problem 1 the same layer at half the size
+        const int pv = MVLM_CONV_PAIR_FLAG | 0, pv_sk = MVLM_CONV_PAIR_FLAG | 15 | (1 << 8) | (2 << 10);
+        auto check_pair = [&](const char* what, int pair_variant, int kind, const Change& change) {
+            ConvArgs a0 = make_args(sh, kind, 40), a1 = make_args(Shape{3, 128, 128, 128}, 0, 40);
+            change(a0);
+            std::printf("check pair %s | %s\n", what, pair_launch(ctx, a0, a1, pair_variant).c_str());
+        };
+        check_pair("none", pv, 0, [](ConvArgs&) {});
+        check_pair("split-K", pv_sk, 0, [](ConvArgs&) {});
+        check_pair("not a pair variant", 0, 0, [](ConvArgs&) {});
+        check_pair("beyond the pair codes", 2 * MVLM_CONV_PAIR_FLAG, 0, [](ConvArgs&) {});
+        check_pair("unknown base", MVLM_CONV_PAIR_FLAG | 63, 0, [](ConvArgs&) {});
+        check_pair("in_ctot", pv, 0, [&](ConvArgs& a) { a.in_ctot = big; });
+        check_pair("raw_ctot", pv, 0, [&](ConvArgs& a) { a.out_raw = &g_dummy, a.raw_ctot = big; });
+        check_pair("res1_ctot", pv, 0, [&](ConvArgs& a) { a.res1 = &g_dummy, a.res1_ctot = big; });
+        check_pair("res2_ctot", pv, 0, [&](ConvArgs& a) { a.res2 = &g_dummy, a.res2_ctot = big; });
+        check_pair("out_ctot", pv, 0, [&](ConvArgs& a) { a.out_ctot = big; });
+        check_pair("kind 1", pv, 1, [](ConvArgs&) {});
+        check_pair("out_ctot up_out", pv, 1, [&](ConvArgs& a) { a.out_ctot = big / 4; });
+        check_pair("skip_ctot", pv, 1, [&](ConvArgs& a) { a.skip_ctot = big / 4; });
+        check_pair("pooled", pv, 2, [](ConvArgs& a) { a.pool_out = &g_dummy; });
+        check_pair("pooled on a tile that cannot", pv_sk, 2, [](ConvArgs& a) { a.pool_out = &g_dummy; });
+        check_pair("pool_ctot", pv, 2, [&](ConvArgs& a) { a.pool_out = &g_dummy, a.pool_ctot = big * 4; });
+        check_pair("in2 (not among a pair's tensors)", pv, 0, [&](ConvArgs& a) { a.in2 = &g_dummy, a.in2_ctot = big * 4; });
+        check_pair("up_in", pv, 0, [](ConvArgs& a) { a.up_in = 1; });
+        check_pair("no output", pv, 0, [](ConvArgs& a) { a.out = nullptr; });
+        check_pair("null w", pv, 0, [](ConvArgs& a) { a.w = nullptr; });
+    }
+
+    std::printf("# pairs: <cin_pad>><cout_pad> @<size>+@<size/2> {p<mode>h<pool_hint of problem 0 + 2 * of problem 1>} | <batches> <pair variant code or ->\n");
+    {
+        std::vector<std::tuple<int, int, int>> pair_shapes(pair_set.begin(), pair_set.end());
+        pair_shapes.push_back({64, 96, 64});   // no pair variant serves these two
+        pair_shapes.push_back({128, 80, 128});
+        for (int mode = 0; mode < 3; ++mode)
+            for (const auto& p : pair_shapes)
+                for (int hint = 0; hint < 4; ++hint) {
+                    const int ci = std::get<0>(p), co = std::get<1>(p), s = std::get<2>(p);
+                    char what[96];
+                    std::snprintf(what, sizeof what, "pair %d>%d @%d+@%d", ci, co, s, s / 2);
+                    g.add(what, "p" + std::to_string(mode) + "h" + std::to_string(hint), runs([&](int b) {
+                        return pair(ctx, make_args(Shape{3, ci, co, s}, (hint & 1) ? 2 : 0, b), make_args(Shape{3, ci, co, s / 2}, (hint & 2) ? 2 : 0, b), mode);
+                    }));
+                }
+        g.print();
+    }
+
+    std::printf("# mvlm_conv_variant_serves: k<ksize> *><cout_pad> @<size> {<cin_pad>:<kinds of -1..3 with this answer>} | the ids of -1..1023 that serve\n");
+    {
+        std::vector<Shape> shapes = table_shapes;
+        for (int co : couts)
+            for (int s : sizes)
+                for (int ci : cins) shapes.push_back(Shape{3, ci, co, s});
+        for (const Shape& s : shapes) {
+            Grouped kinds;  // the kinds of this shape with equal answers
+            for (int kind = -1; kind <= 3; ++kind) {
+                std::string ids;
+                for (int v = -1; v < 1024; ++v)
+                    if (mvlm_conv_variant_serves(v, std::get<0>(s), std::get<1>(s), std::get<2>(s), std::get<3>(s), kind)) ids += " " + std::to_string(v);
+                kinds.add(ids, std::to_string(kind), "");
+            }
+            for (const std::string& ids : kinds.order) {
+                std::string which;
+                for (const auto& k : kinds.rows[ids]) which += (which.empty() ? "" : ",") + k.first;
+                char what[64];
+                std::snprintf(what, sizeof what, "serves k%d *>%d @%d", std::get<0>(s), std::get<2>(s), std::get<3>(s));
+                g.add(what, std::to_string(std::get<1>(s)) + ":" + which, ids.empty() ? "none" : ids.substr(1));
+            }
+        }
+        g.print();
+    }
+
+    std::printf("# variant ids -1..255: <first>-<last> | name is_wino can_pool\n");
+    {
+        auto describe = [](int v) {
+            return std::string(mvlm_conv_variant_name_impl(v)) + " " + std::to_string(int(mvlm_conv_variant_is_wino(v))) + " " +
+                   std::to_string(int(mvlm_conv_variant_can_pool(v)));
+        };
+        std::string cur;
+        int first = -1;
+        for (int v = -1; v <= 256; ++v) {
+            const std::string d = v <= 255 ? describe(v) : std::string();
+            if (v > -1 && d == cur) continue;
+            if (v > -1) std::printf("id %d-%d | %s\n", first, v - 1, cur.c_str());
+            cur = d;
+            first = v;
+        }
+        // 256..1100: "<name of id & 255>_k<1 << (id >> 8 & 3)>", never Winograd, pools as id & 255 does; the exceptions are listed
+        int exceptions = 0;
+        for (int v = 256; v <= 1100; ++v) {
+            const std::string name = std::string(mvlm_conv_variant_name_impl(v & 255)) + "_k" + std::to_string(1 << ((v >> 8) & 3));
+            if (name != mvlm_conv_variant_name_impl(v) || mvlm_conv_variant_is_wino(v) || mvlm_conv_variant_can_pool(v) != mvlm_conv_variant_can_pool(v & 255)) {
+                std::printf("id %d | %s\n", v, describe(v).c_str());
+                ++exceptions;
+            }
+        }
+        std::printf("ids 256-1100 | <name of id & 255>_k<1 << (id >> 8 & 3)> 0 <can_pool of id & 255>, %d exceptions\n", exceptions);
+        const int P = MVLM_CONV_PAIR_FLAG;
+        for (int v : {260, 527, 808, 1063, P | 0, P | 10, P | 15 | (1 << 8) | (2 << 10), P | 13 | (3 << 10), P | 40, P | 63, 2 * P | 10})
+            std::printf("id %d | %s\n", v, describe(v).c_str());
+    }
+
+    std::printf("# mvlm_conv_wino_serves_slot: k<ksize> {cin_pad} | the cout_pad it serves\n");
+    for (int ks : {1, 2, 3})
+        for (int ci : {3, 4, 6, 16, 32, 64, 76, 84, 128, 256, 320}) {
+            std::string cos;
+            for (int co : {32, 64, 80, 84, 96, 128, 192, 256})
+                if (mvlm_conv_wino_serves_slot(ks, ci, co)) cos += " " + std::to_string(co);
+            g.add("slot k" + std::to_string(ks), std::to_string(ci), cos.empty() ? "none" : cos.substr(1));
+        }
+    g.print();
+
+    std::printf("# error messages\n");
+    for (size_t i = 0; i < g_errors.size(); ++i) std::printf("E%d: %s\n", int(i) + 1, g_errors[i].c_str());
+    return 0;
+}
