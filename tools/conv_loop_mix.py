@@ -1,0 +1,134 @@
+#!/usr/bin/env python3
+"""Instruction mix of the steady-state K loop of every convolution kernel of the built library objects.
+
+    tools/conv_loop_mix.py            print the table
+    tools/conv_loop_mix.py --write    rewrite tests/golden/conv_loop_mix_wino.json (the Winograd kernels' rows) from the build
+
+A convolution tile is compute-bound by construction: what it loses against the matrix peak is time its waves spend issuing
+anything but MFMAs inside the K loop (addresses, staging arithmetic, LDS traffic, waits, branches).  The ratio of those to the
+MFMAs can be read off the object file, before any GPU time is spent.  The steady-state loop of a kernel is the innermost
+backward branch whose body holds MFMAs and a barrier (the loop over K-chunks); where a kernel has several, the one with the most
+MFMAs.  Instructions are classed by the prefix of their mnemonic.  tests/test_winograd_loop_mix.py holds the Winograd kernel
+to the committed row."""
+import json
+import re
+import subprocess
+import sys
+import tempfile
+from pathlib import Path
+
+REPO = Path(__file__).resolve().parents[1]
+LLVM = Path("/opt/rocm/lib/llvm/bin")
+BUILD = REPO / "mvlm_amd" / "csrc" / "build"
+WINO_TABLE = REPO / "tests" / "golden" / "conv_loop_mix_wino.json"
+CLASSES = ("valu", "lds_read", "lds_write", "global_load", "scalar", "wait", "other")
+MFMAS_PER_CHUNK_WINO = 48  # a 4-channel group of the 64 x (8 x 32) Winograd tile: 6 k-steps x 2 cout tiles x 4 GEMMs
+
+_INSN = re.compile(r"^\s*([a-z][a-z0-9_]+)\s.*//\s*([0-9A-Fa-f]+):")
+_SYM = re.compile(r"^([0-9a-f]+) <(\S+)>:")
+
+
+def classify(mn: str) -> str:
+    if mn.startswith(("v_mfma", "v_smfmac")):
+        return "mfma"
+    if mn.startswith("s_barrier"):
+        return "barrier"
+    if mn.startswith("s_waitcnt"):
+        return "wait"
+    if mn.startswith("ds_"):
+        return "lds_read" if mn.startswith(("ds_read", "ds_load")) else "lds_write" if mn.startswith(("ds_write", "ds_store")) else "other"
+    if mn.startswith(("global_load", "buffer_load", "flat_load")):
+        return "global_load"
+    if mn.startswith("s_"):
+        return "scalar"
+    if mn.startswith("v_"):
+        return "valu"
+    return "other"
+
+
+def code_objects(obj: Path, td: Path):
+    fat = td / "fat.bin"
+    subprocess.run([str(LLVM / "llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", str(obj), str(fat)], check=True)
+    data = fat.read_bytes()
+    i = n = 0
+    while True:
+        j = data.find(b"\x7fELF", i)
+        if j < 0:
+            return
+        k = data.find(b"\x7fELF", j + 4)
+        elf = td / f"co{n}.elf"
+        elf.write_bytes(data[j:k if k > 0 else len(data)])
+        yield elf
+        n += 1
+        i = j + 4
+
+
+def kernel_listings(elf: Path) -> dict:
+    """kernel symbol -> [(address, mnemonic, branch target or None)]"""
+    text = subprocess.run([str(LLVM / "llvm-objdump"), "-d", "--no-show-raw-insn", str(elf)], capture_output=True, text=True).stdout
+    out, cur, base = {}, None, 0
+    for line in text.splitlines():
+        m = _SYM.match(line)
+        if m:
+            base, cur = int(m.group(1), 16), out.setdefault(m.group(2), [])
+            continue
+        m = _INSN.match(line)
+        if not m or cur is None:
+            continue
+        mn, addr = m.group(1), int(m.group(2), 16)
+        target = None
+        if mn.startswith(("s_cbranch", "s_branch")):
+            t = re.search(r"<[^>]*\+0x([0-9a-fA-F]+)>", line)
+            target = base + int(t.group(1), 16) if t else base if re.search(r"<[^+>]+>\s*$", line.split("//")[0]) else None
+        cur.append((addr, mn, target))
+    return out
+
+
+def loop_mix(insns) -> dict | None:
+    """The steady-state loop: among the backward branches whose body holds MFMAs and a barrier and no other such loop, the
+    one with the most MFMAs."""
+    addr_index = {a: i for i, (a, _, _) in enumerate(insns)}
+    loops = []
+    for i, (a, mn, t) in enumerate(insns):
+        if t is not None and t <= a and t in addr_index:
+            body = insns[addr_index[t]:i + 1]
+            kinds = [classify(m) for _, m, _ in body]
+            if "mfma" in kinds and "barrier" in kinds:
+                loops.append((addr_index[t], i, kinds))
+    inner = [l for l in loops if not any(o is not l and l[0] <= o[0] and o[1] <= l[1] for o in loops)]
+    if not inner:
+        return None
+    _, _, kinds = max(inner, key=lambda l: l[2].count("mfma"))
+    row = {"mfma": kinds.count("mfma"), "barriers": kinds.count("barrier")}
+    row.update({c: kinds.count(c) for c in CLASSES})
+    row["non_mfma"] = sum(row[c] for c in CLASSES) + row["barriers"]
+    row["non_mfma_per_mfma"] = round(row["non_mfma"] / row["mfma"], 3)
+    return row
+
+
+def build_table(objdir: Path = BUILD) -> dict:
+    table = {}
+    with tempfile.TemporaryDirectory() as td:
+        for obj in sorted(objdir.glob("conv_inst_*.o")):
+            for elf in code_objects(obj, Path(td)):
+                for name, insns in kernel_listings(elf).items():
+                    if "conv_mfma_kernel" not in name and "conv_pair_kernel" not in name:
+                        continue
+                    row = loop_mix(insns)
+                    if row:
+                        table[name] = row
+    return dict(sorted(table.items()))
+
+
+if __name__ == "__main__":
+    wino = build_table(BUILD / "wino")
+    if "--write" in sys.argv:
+        WINO_TABLE.write_text(json.dumps(wino, indent=1) + "\n")
+        print(f"{len(wino)} kernels -> {WINO_TABLE}")
+    else:
+        hdr = f"{'mfma':>5s} {'other':>6s} {'/mfma':>6s} {'barr':>5s} " + " ".join(f"{c:>11s}" for c in CLASSES)
+        print(hdr + "  kernel")
+        for objdir in (BUILD, BUILD / "wino"):
+            for k, v in build_table(objdir).items():
+                print(f"{v['mfma']:5d} {v['non_mfma']:6d} {v['non_mfma_per_mfma']:6.2f} {v['barriers']:5d} " +
+                      " ".join(f"{v[c]:11d}" for c in CLASSES) + f"  {k}")

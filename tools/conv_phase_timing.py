@@ -26,10 +26,14 @@ CASES = [  # name, cin, cout, size, k, batch, pre-BN, residual, bias+post-BN  (M
     ("block conv1  256->128 @ 64 (c128)", 256, 128, 64, 3, 64, True, True, False),
     ("resample 1x1  64->128 @256", 64, 128, 256, 1, 64, True, False, False),
     ("conv6        256-> 73 @128 (c80)", 256, 73, 128, 3, 64, False, False, False),
+    # the F(2,3) Winograd tile (variant 40, conv3x3w_c64_t8x32), forced: its own prologue / K loop / epilogue split
+    ("winograd     256->128 @128 (w64)", 256, 128, 128, 3, 64, True, True, False, 40),
+    ("winograd     128-> 64 @128 (w64)", 128, 64, 128, 3, 64, True, True, False, 40),
+    ("winograd      64-> 64 @ 64 (w64)", 64, 64, 64, 3, 64, True, True, False, 40),
 ]
 
 
-SMALL = [  # the latency-bound levels of a 12-view batch (MVLM_PHASE_CASES=small)
+SMALL = [  # the latency-bound levels of a 12-view batch (MVLM_PHASE_CASES=small; MVLM_PHASE_CASES=winograd: the forced Winograd cases alone)
     ("block conv1  256->128 @ 32 B12", 256, 128, 32, 3, 12, True, True, False),
     ("block conv2  128-> 64 @ 32 B12", 128, 64, 32, 3, 12, True, True, False),
     ("block conv1  256->128 @ 16 B12", 256, 128, 16, 3, 12, True, True, False),
@@ -55,7 +59,9 @@ def main():
     rs = np.random.RandomState(0)
     f = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
     print(f"{'layer':40s} {'ms':>7s} {'TFLOP/s':>8s} | per workgroup, wave 0: prologue / K loop / epilogue (cycles, share)")
-    for name, cin, cout, size, k, batch, pre, res, post in CASES:
+    if os.environ.get("MVLM_PHASE_CASES") == "winograd":
+        CASES = [c for c in CASES if len(c) > 9]
+    for name, cin, cout, size, k, batch, pre, res, post, *forced in CASES:
         batch = int(os.environ.get("MVLM_PHASE_BATCH", batch))
         x = torch.randn(batch, cin, size, size, device="cuda")
         y = torch.empty(batch, cout, size, size, device="cuda")
@@ -71,9 +77,15 @@ def main():
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ctx.set_stream(torch.cuda.current_stream().cuda_stream)
             e0.record()
-            ctx.check(ctx.lib.mvlm_conv2d(ctx.handle, C.c_void_p(x.data_ptr()), batch, cin, size, size, f(w), cout, k, f(b),
-                                          f(ps), f(pt), f(qs), f(qt), C.c_void_p(r.data_ptr()) if res else None, 0,
-                                          C.c_void_p(y.data_ptr())))
+            if forced:
+                ctx.check(ctx.lib.mvlm_conv_force_variant(ctx.handle, forced[0]))
+            try:
+                ctx.check(ctx.lib.mvlm_conv2d(ctx.handle, C.c_void_p(x.data_ptr()), batch, cin, size, size, f(w), cout, k, f(b),
+                                              f(ps), f(pt), f(qs), f(qt), C.c_void_p(r.data_ptr()) if res else None, 0,
+                                              C.c_void_p(y.data_ptr())))
+            finally:
+                if forced:
+                    ctx.check(ctx.lib.mvlm_conv_force_variant(ctx.handle, -1))
             e1.record()
             torch.cuda.synchronize()
             times.append(e0.elapsed_time(e1))
