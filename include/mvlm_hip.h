@@ -315,10 +315,36 @@ int mvlm_consensus_solve(mvlm_ctx* ctx, const double* starts_dev, const double* 
                          const int32_t* count_dev, const int32_t* draws_dev, int n_views, int n_landmarks,
                          double* out_dev, double* err_dev);
 
+/* Opt-in quality report of the consensus.  One wavefront per landmark repeats mvlm_consensus_solve on the same inputs
+ * (out_dev f64[NL,3] and err_dev f64[NL] are that call's, bit for bit) and writes what the solve decides and drops:
+ *   counts_dev i32[NL,4]  k (surviving lines), n_inliers (squared distance < 100 to the 8-draw sample fit; 0 where k < 3),
+ *                         n_used (lines of the final fit), branch (0: k < 3, plain least squares; 1: refit on the inliers;
+ *                         2: "RANSAC failed", all lines, error 1e8)
+ *   stats_dev f64[NL,MVLM_REPORT_STATS]  rms = sqrt(mean d2) and max_dist = sqrt(max d2) over the used lines, measured to
+ *                         the final point (NaN where n_used == 0); sigma2 = sum d2 / (2 n_used - 3) (NaN where 2 n_used <= 3);
+ *                         cov = sigma2 pinv(A), A = sum over the used lines of (I - n n^T), as xx yy zz xy xz yz
+ *   dist2_dev f64[NL,N]   squared distance of EVERY view's ray to the final point (estimator3d.py:109-111)
+ *   flags_dev u8[NL,N]    MVLM_VIEW_KEPT | _DRAWN | _INLIER | _USED */
+#define MVLM_REPORT_STATS 9
+#define MVLM_VIEW_KEPT 1
+#define MVLM_VIEW_DRAWN 2
+#define MVLM_VIEW_INLIER 4
+#define MVLM_VIEW_USED 8
+int mvlm_consensus_report(mvlm_ctx* ctx, const double* starts_dev, const double* ends_dev, const uint8_t* mask_dev,
+                          const int32_t* draws_dev, int n_views, int n_landmarks, double* out_dev, double* err_dev,
+                          double* stats_dev, int32_t* counts_dev, double* dist2_dev, uint8_t* flags_dev);
+
 /* ---- surface snap (replaces estimator3d.py:252-285) ------------------------------ */
 /* pts_dev f64[NL,3] -> out_dev f64[NL,3]: closest point on the triangle surface */
 int mvlm_project_to_surface(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* pts_dev, int n_points,
                             double* out_dev);
+
+/* The snap with its attachment: snapped_dev f64[n,3] is mvlm_project_to_surface's output, bit for bit; tri_dev i32[n] the
+ * triangle that holds it (lowest id on ties; -1 for a landmark without a finite distance, which is passed through);
+ * bary_dev f64[n,3] its weights of the triangle's corners, from the same Voronoi walk (NaN where tri is -1); uv_dev f64[n,2]
+ * the mesh's texture coordinates interpolated with them (NaN when the mesh has none). */
+int mvlm_surface_attach(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* pts_dev, int n_points, double* snapped_dev,
+                        int32_t* tri_dev, double* bary_dev, double* uv_dev);
 
 /* ---- ray clipping / depth unprojection (replaces visualization/ray_visualizer.py:172-192) */
 /* starts_dev, ends_dev f64[R,3] (e.g. the [NL,N,3] arrays of mvlm_estimate_lines) -> new_ends_dev f64[R,3]:

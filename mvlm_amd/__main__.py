@@ -2,7 +2,8 @@
 
 Same behaviour as the reference's ``main.py`` (:9-67): collect ``*.obj`` files, run every
 available pipeline over them and write ``<stem>_<pipeline>.txt`` (comma-separated [NL,3]
-landmarks, ``np.savetxt(..., delimiter=",")``, main.py:62).  Only the pipelines whose 2-D
+landmarks, ``np.savetxt(..., delimiter=",")``, main.py:62; with ``--report`` also ``<stem>_<pipeline>_report.csv``, the
+per-landmark quality report of mvlm_amd/utils/report.py).  Only the pipelines whose 2-D
 predictor this build ships are looped ("bu3dfe", "dtu3d"); the viewer flags of the reference
 (``--visualize-iter`` / ``--visualize-img``) need VTK and are not available.
 """
@@ -21,7 +22,7 @@ def shard_files(files, rank: int, world: int):
     return [f for i, f in enumerate(files) if i % world == rank]
 
 
-def main(argv=None) -> int:
+def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(prog="python -m mvlm_amd")
     parser.add_argument("-p", "--path", type=str, required=True)
     parser.add_argument("-o", "--out", type=str, required=False)
@@ -47,7 +48,15 @@ def main(argv=None) -> int:
     parser.add_argument("--multisamples", type=int, choices=(0, 4), default=0,
                         help="samples per pixel of the renderer: 0 = one at the pixel centre (default), 4 = multisampled views "
                              "(for checkpoints trained on multisampled VTK renders; DESIGN.md 5.1)")
-    args = parser.parse_args(argv)
+    parser.add_argument("--report", action="store_true",
+                        help="write <stem>_<pipeline>_report.csv beside every landmark file: one row per landmark with the surviving "
+                             "views, inliers, RANSAC branch, ray spread, snap distance, triangle, barycentric weights and uv "
+                             "(lengths in the space the network sees; x,y,z in file coordinates; INTEGRATION.md)")
+    return parser
+
+
+def main(argv=None) -> int:
+    args = build_parser().parse_args(argv)
     if args.out is None:
         args.out = args.path
     input_path, path_to_out = Path(args.path), Path(args.out)
@@ -81,6 +90,8 @@ def main(argv=None) -> int:
     extra = {"precision": args.precision} if args.precision != "exact" else {}
     if args.multisamples:
         extra["render_multisamples"] = args.multisamples
+    if args.report:
+        extra["landmark_report"] = True
     if args.config is not None:
         from . import config as mvlm_config
 
@@ -104,6 +115,8 @@ def main(argv=None) -> int:
                 print(f"Landmarks for {file} could not be predicted -> skipping file [{file.stem}] for pipeline {pname}")
                 continue
             np.savetxt((path_to_out / f"{file.stem}_{pname}.txt").as_posix(), landmarks, delimiter=",")
+            if args.report:
+                dm.last_report.to_csv(path_to_out / f"{file.stem}_{pname}_report.csv")
     return 0
 
 

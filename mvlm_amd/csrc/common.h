@@ -384,6 +384,11 @@ int mvlm_launch_conv_fast(mvlm_ctx* ctx, const ConvArgs& a, const unsigned short
 constexpr int MVLM_CONV_VARIANT_FAST = 62;    // id reported for launches of the bf16x3 kernel
 constexpr int MVLM_CONV_VARIANT_FAST16 = 61;  // ... of the f16x2 kernel
 
+// surface.hip: passes 0 and 1 of the surface snap (bound, de-indexed triangles, per-chunk winners in the context's scratch)
+// for an entry point that holds the context; its final kernel follows (mvlm_project_to_surface, mvlm_surface_attach)
+int mvlm_project_partials(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* pts_dev, int n_points, int* n_chunks_out,
+                          const double** part_d_out, const int** part_t_out);
+
 // small kernels (misc.hip)
 int mvlm_launch_pack_input(mvlm_ctx* ctx, const float* images, int n, const int* sel4, int c, float* out);
 int mvlm_launch_maxpool2(mvlm_ctx* ctx, const float* in, int planes, int H, int W, float* out);

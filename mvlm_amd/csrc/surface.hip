@@ -7,39 +7,9 @@
 #include <algorithm>
 
 #include "common.h"
+#include "surface_math.h"
 
 namespace {
-
-struct V3 {
-    double x, y, z;
-};
-__device__ inline V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ inline double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ inline V3 madd(V3 a, V3 d, double t) { return {a.x + t * d.x, a.y + t * d.y, a.z + t * d.z}; }
-
-// closest point on triangle (a,b,c) to p: walk the Voronoi regions (vertex, edge, face)
-__device__ V3 closest_on_triangle(V3 p, V3 a, V3 b, V3 c) {
-    const V3 ab = sub(b, a), ac = sub(c, a), ap = sub(p, a);
-    const double d1 = dot(ab, ap), d2 = dot(ac, ap);
-    if (d1 <= 0 && d2 <= 0) return a;
-    const V3 bp = sub(p, b);
-    const double d3 = dot(ab, bp), d4 = dot(ac, bp);
-    if (d3 >= 0 && d4 <= d3) return b;
-    const double vc = d1 * d4 - d3 * d2;
-    // (d1 - d3 = |ab|^2: a triangle with a == b is the segment ac - vtkCleanPolyData turns it into a line cell - and belongs
-    //  to the edge-ac branch below, not to a 0 / 0 here)
-    if (vc <= 0 && d1 >= 0 && d3 <= 0 && d1 > d3) return madd(a, ab, d1 / (d1 - d3));
-    const V3 cp = sub(p, c);
-    const double d5 = dot(ab, cp), d6 = dot(ac, cp);
-    if (d6 >= 0 && d5 <= d6) return c;
-    const double vb = d5 * d2 - d1 * d6;
-    if (vb <= 0 && d2 >= 0 && d6 <= 0) return madd(a, ac, d2 / (d2 - d6));
-    const double va = d3 * d6 - d5 * d4;
-    if (va <= 0 && (d4 - d3) >= 0 && (d5 - d6) >= 0) return madd(b, sub(c, b), (d4 - d3) / ((d4 - d3) + (d5 - d6)));
-    const double denom = 1.0 / (va + vb + vc);
-    const double v = vb * denom, w = vc * denom;
-    return {a.x + ab.x * v + ac.x * w, a.y + ab.y * v + ac.y * w, a.z + ab.z * v + ac.z * w};
-}
 
 // Pass 0: an upper bound on every landmark's squared distance to the surface.  The nearest vertex THAT A TRIANGLE USES
 // (vert_tri[v] = lowest id of a triangle with corner v, filled by project_soup_kernel; VERT_UNUSED = a stray point of the
@@ -422,11 +392,11 @@ extern "C" int mvlm_clip_rays_to_mesh(mvlm_ctx* ctx, const mvlm_mesh* mesh, cons
     return 0;
 }
 
-extern "C" int mvlm_project_to_surface(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* pts_dev, int n_points,
-                                       double* out_dev) {
-    MVLM_ENTER(ctx);
-    MVLM_REQUIRE(ctx, mesh && pts_dev && out_dev && n_points > 0, "project_to_surface: bad arguments");
-    MVLM_REQUIRE(ctx, mesh->n_tris > 0, "project_to_surface: empty mesh");
+// Passes 0 and 1 of the snap for an entry point that has validated its arguments and holds the context: bound, de-indexed
+// triangles and the per-chunk winners part_d / part_t [n_points][n_chunks] in the context's scratch.  The caller's final
+// kernel picks the winner (mvlm_project_to_surface: project_final_kernel; mvlm_surface_attach: attach_final_kernel).
+int mvlm_project_partials(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* pts_dev, int n_points, int* n_chunks_out,
+                          const double** part_d_out, const int** part_t_out) {
     if (mvlm_mesh_wait_ready(ctx, mesh, ctx->stream)) return 1;
     // pieces of PROJECT_CHUNK triangles, n_sub of them per workgroup: as many as leave >= ~768 workgroups (3 per CU)
     const int n_pieces = (mesh->n_tris + PROJECT_CHUNK - 1) / PROJECT_CHUNK, n_groups = (n_points + PROJECT_GROUP - 1) / PROJECT_GROUP;
@@ -458,6 +428,22 @@ extern "C" int mvlm_project_to_surface(mvlm_ctx* ctx, const mvlm_mesh* mesh, con
                        vert_tri, pts_dev, n_points, cand_d, cand_v, ub);
     hipLaunchKernelGGL(project_partial_kernel, dim3(n_chunks, n_groups), dim3(256), 0, ctx->stream, soup, mesh->n_tris, pts_dev,
                        n_points, ub, n_chunks, n_sub, part_d, part_t);
+    MVLM_CHECK_HIP(ctx, hipGetLastError());
+    *n_chunks_out = n_chunks;
+    *part_d_out = part_d;
+    *part_t_out = part_t;
+    return 0;
+}
+
+extern "C" int mvlm_project_to_surface(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* pts_dev, int n_points,
+                                       double* out_dev) {
+    MVLM_ENTER(ctx);
+    MVLM_REQUIRE(ctx, mesh && pts_dev && out_dev && n_points > 0, "project_to_surface: bad arguments");
+    MVLM_REQUIRE(ctx, mesh->n_tris > 0, "project_to_surface: empty mesh");
+    int n_chunks = 0;
+    const double* part_d = nullptr;
+    const int* part_t = nullptr;
+    if (mvlm_project_partials(ctx, mesh, pts_dev, n_points, &n_chunks, &part_d, &part_t)) return 1;
     hipLaunchKernelGGL(project_final_kernel, dim3(n_points), dim3(64), 0, ctx->stream, mesh->verts, mesh->tris, pts_dev,
                        n_chunks, part_d, part_t, out_dev);
     MVLM_CHECK_HIP(ctx, hipGetLastError());

@@ -28,6 +28,7 @@ from ..prediction.paulsenpredictor import HipPaulsenModel
 from ..utils.estimator3d import HipEstimator3D
 from ..utils.hostmem import retain_freed_host_memory
 from ..utils.render3d import HipRenderer3D
+from ..utils.report import LandmarkReport, ReportLayout
 
 __all__ = ["Pipeline"]
 
@@ -89,7 +90,7 @@ class Pipeline(abc.ABC):
     def __init__(self, render_image_stack: bool = False, offscreen: bool = True, n_views: int = 8,
                  render_image_folder: Path | None = None, visualize_rays: bool = False,
                  screenshot_folder: Path | None = None, device: int = 0, shard_views: bool = False,
-                 verbose: bool = True, render_multisamples: int = 0):
+                 verbose: bool = True, render_multisamples: int = 0, landmark_report: bool = False):
         self.render_image_stack = render_image_stack
         self.render_image_folder = render_image_folder
         self.n_views = n_views
@@ -101,6 +102,12 @@ class Pipeline(abc.ABC):
         self.timings: dict[str, float] = {}
         self._timer = StageTimer(self.timings, self._say)
         self.last_error: float | None = None
+        # landmark_report: every prediction leaves a LandmarkReport (mvlm_amd/utils/report.py) in ``last_report``: per
+        # landmark the surviving views, inliers, RANSAC branch, ray spread, covariance, snap distance and triangle.  Its
+        # lengths are in the space the network sees (the pre-aligned model space); only its ``landmarks`` are in file
+        # coordinates.  Off (the default): nothing of it is launched, allocated or copied.
+        self.landmark_report = bool(landmark_report)
+        self.last_report = None
         self._rays = None  # (mesh, starts, ends) of the current call when visualize_rays is set
         self._buffers: dict = {}
         self._lock = threading.RLock()  # see _serialised
@@ -328,7 +335,14 @@ class Pipeline(abc.ABC):
             rot_dev = e3.upload_rotations_async(rot)
         # landmarks f64[NL,3] | error f64[NL] | survivor counts i32[NL] in ONE buffer: one device-to-host copy per mesh,
         # into pinned memory, enqueued right behind the last kernel
-        pack = self._buffer_bytes("result", nl_all * (24 + 8 + 4))
+        base_bytes, report_bytes = nl_all * (24 + 8 + 4), 0
+        layout = rviews = None
+        if self.landmark_report:
+            # the report rides behind the result in the same buffer (8-byte aligned): still one copy per mesh.  Room for all
+            # views: should a detector's ``valid`` mask drop some, the smaller layout made below fits
+            base_bytes = (base_bytes + 7) // 8 * 8
+            report_bytes = ReportLayout(nl_all, n_total).nbytes
+        pack = self._buffer_bytes("result", base_bytes + report_bytes)
         pack_host, pack_np = self._pinned_bytes("result_host", int(pack.numel()))
         snap_view = pack[: nl_all * 24].view(torch.float64).view(nl_all, 3)
         err_view = pack[nl_all * 24: nl_all * 32].view(torch.float64)
@@ -336,6 +350,7 @@ class Pipeline(abc.ABC):
         if self.render_image_stack and images is not None:
             self.visualize_image_stack(images.cpu().numpy(), mesh.path or Path("mesh.obj"), first_index=lo)
 
+        kept_views = None  # positions in the pose table of the views a detector's ``valid`` mask left (None: all)
         valid = None  # host bool [views of this rank]: a detector's "nothing found in this view" (None: all valid)
         with tm.stage("prediction"):
             if images is not None and isinstance(p2, HipPaulsenModel):
@@ -363,6 +378,7 @@ class Pipeline(abc.ABC):
             transform_stack = transform_stack[keep]
             rot_dev = e3.upload_rotations_async(rot[keep])
             n_total = int(len(keep))
+            kept_views = keep
             if plan is not None:  # sharded: the draws planned for all views are void - plan again for the views that remain
                 np.random.set_state(plan["rng_state"])
                 plan = e3.plan_draws(nl_all, n_total, draws_fn)
@@ -378,24 +394,39 @@ class Pipeline(abc.ABC):
         with tm.stage("consensus"):
             if self.visualize_rays:
                 self._rays = (mesh, starts.cpu().numpy(), ends.cpu().numpy())
+            if self.landmark_report:
+                layout = ReportLayout(nl_all, n_total)
+                rviews = layout.device_views(pack[base_bytes: base_bytes + layout.nbytes])
+                rviews["scores"].copy_(maxima[:, :, 2])
+            # (with a report, every solve - the one verify may repeat too - is followed by the report kernel)
             out, err, verify = e3.consensus_device(maxima, starts, ends, deferred=True, plan=plan, err_out=err_view,
-                                                   count_out=count_view)
+                                                   count_out=count_view, report=rviews)
+
+        def snap():
+            e3.project_device(mesh, out, out=snap_view)
+            if rviews is not None:  # behind the snap: the same search once more, leaving triangle, weights and uv
+                e3.attach_device(mesh, out, views=rviews)
 
         with tm.stage("project"):
             # the snap is enqueued before anything is fetched: one wait and one copy per mesh, at the end
-            e3.project_device(mesh, out, out=snap_view)
+            snap()
             stream = torch.cuda.current_stream(dev_t)
             pack_host.copy_(pack, non_blocking=True)
             stream.synchronize()
             host = pack_np
             if verify(counts=host[nl_all * 32: nl_all * 36].view(np.int32)):
                 # the RANSAC draws had to be repeated for other survivor counts (tied / NaN scores, absolute mode)
-                e3.project_device(mesh, out, out=snap_view)
+                snap()
                 pack_host.copy_(pack, non_blocking=True)
                 stream.synchronize()
             landmarks = host[: nl_all * 24].view(np.float64).reshape(nl_all, 3).copy()
             error = e3.mean_error(host[nl_all * 24: nl_all * 32].view(np.float64))
             r3.check()  # deferred renderer status (the stream has been waited for above)
+            if layout is not None:
+                # (model space; _predict_fused maps ``landmarks`` back to the file's coordinates.  Should the fp16 range guard
+                # below repeat the scan, the repeated pass leaves its own report here.)
+                self.last_report = LandmarkReport(layout.host_arrays(host[base_bytes: base_bytes + layout.nbytes]),
+                                                  landmarks=landmarks, view_indices=kept_views)
         asked16 = getattr(p2, "configured_precision", getattr(p2, "precision", None)) == "fast16"
         if asked16:
             # an activation beyond fp16's range somewhere in the network (the kernel raised the context's flag; the maxima of
@@ -421,6 +452,8 @@ class Pipeline(abc.ABC):
             return False  # the fp16 range guard (and its fallback) works scan by scan
         if (self.shard_views and parallel.is_distributed()) or self.render_image_stack or self.visualize_rays:
             return False
+        if self.landmark_report:
+            return False  # one report per scan, made by the scan's own pass
         n = int(self.renderer_3d.n_views)
         return e3.expected_counts(p2.get_lm_count(), n) is not None and n_scans * n <= (p2.device_batch or 128)
 
@@ -433,7 +466,9 @@ class Pipeline(abc.ABC):
         of scan 1, poses of scan 2, ... - the draws being the speculative ones of ``plan_draws``; if a scan's survivor
         counts differ from the expectation (tied / NaN scores), that scan's draws are repeated from the saved RNG
         state and the scans after it are processed one by one from there.  Returns [(landmarks, error), ...]; falls back
-        to the loop when the scans cannot share a pass (``_groupable``)."""
+        to the loop when the scans cannot share a pass (``_groupable``).  With ``landmark_report`` the scans always go one
+        by one and ``last_report`` is the LAST scan's when this returns: a caller that wants every scan's report uses
+        ``predict_files`` (one report per yielded scan) or calls ``predict_mesh_device`` per mesh."""
         import torch
 
         from ..utils.render3d import view_rotations
@@ -448,7 +483,7 @@ class Pipeline(abc.ABC):
             out = []
             for m in meshes:
                 landmarks, err = self.predict_mesh_device(m, pose_fn())
-                out.append((self._to_original(m, landmarks), err))
+                out.append((self._report_landmarks(self._to_original(m, landmarks)), err))
             return out
         nl, n = p2.get_lm_count(), int(r3.n_views)
         per = (nl * 36 + 7) // 8 * 8
@@ -627,7 +662,13 @@ class Pipeline(abc.ABC):
         self.timings["load"] = time.perf_counter() - t0
         self._dump_pre_aligned(mesh, file_name)
         landmarks, _ = self.predict_mesh_device(mesh, poses)
-        return self._to_original(mesh, landmarks)
+        return self._report_landmarks(self._to_original(mesh, landmarks))
+
+    def _report_landmarks(self, landmarks):
+        """The last report's ``landmarks`` are what the caller gets: the file's coordinates."""
+        if self.landmark_report and self.last_report is not None and landmarks is not None:
+            self.last_report.landmarks = np.array(landmarks, dtype=np.float64)
+        return landmarks
 
     def _dump_pre_aligned(self, mesh, file_name):
         """``pre-align.write_pre_aligned`` (utils3d.py:489-494): the transformed surface as a legacy .vtk file."""
@@ -658,16 +699,33 @@ class Pipeline(abc.ABC):
             lines_s, lines_e = self.estimator_3d.estimate_landmark_lines(image_stack, landmark_stack, transform_stack)
         if self.visualize_rays:
             self._rays = (pd, np.asarray(lines_s), np.asarray(lines_e))
+        arrays = None
+        if self.landmark_report and not (callable(getattr(self.estimator_3d, "estimate_landmarks_from_lines_report", None))
+                                         and callable(getattr(self.estimator_3d, "attach_landmarks_to_surface", None))):
+            raise ValueError("landmark_report needs an estimator with estimate_landmarks_from_lines_report and "
+                             "attach_landmarks_to_surface (HipEstimator3D)")
         with tm.stage("consensus"):
-            landmarks, error = self.estimator_3d.estimate_landmarks_from_lines(landmark_stack, lines_s, lines_e)
+            if self.landmark_report:
+                landmarks, error, arrays = self.estimator_3d.estimate_landmarks_from_lines_report(landmark_stack, lines_s, lines_e)
+            else:
+                landmarks, error = self.estimator_3d.estimate_landmarks_from_lines(landmark_stack, lines_s, lines_e)
         with tm.stage("project"):
-            landmarks = self.estimator_3d.project_landmarks_to_surface(pd, landmarks)
+            if arrays is not None:
+                arrays.update(self.estimator_3d.attach_landmarks_to_surface(pd, landmarks))
+                landmarks = arrays["snapped"]
+            else:
+                landmarks = self.estimator_3d.project_landmarks_to_surface(pd, landmarks)
         self._say("Landmarks [Error]: ", f"{error:08.6f}", " mm")
         self.last_error = error
         self._dump_pre_aligned(pd, file_name)
         # a mesh handle that went through the config's pre-align block carries its matrix: results go back to
         # the file's coordinates (the rays kept for visualisation stay in the aligned space, with the mesh handle)
-        return self._to_original(pd, landmarks)
+        landmarks = self._to_original(pd, landmarks)
+        if arrays is not None:
+            kept = np.asarray(valid)
+            self.last_report = LandmarkReport(arrays, landmarks=landmarks,
+                                              view_indices=np.nonzero(kept)[0] if kept.dtype == bool else kept)
+        return landmarks
 
     def visualize_image_stack(self, image_stack: np.ndarray, file_name: Path, first_index: int = 0):
         """PNG dump of the rendered views (general_pipeline.py:133-146)."""

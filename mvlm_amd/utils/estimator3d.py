@@ -17,6 +17,7 @@ import numpy as np
 from .. import _lib
 from .mesh_io import Mesh
 from .render3d import upload_mesh, view_rotations
+from .report import ReportLayout
 
 __all__ = ["HipEstimator3D"]
 
@@ -179,7 +180,7 @@ class HipEstimator3D:
         return plan
 
     def consensus_device(self, landmarks_dev, starts, ends, draws_fn=None, deferred: bool = False, plan=None,
-                         err_out=None, count_out=None):
+                         err_out=None, count_out=None, report=None):
         """Filter + one-shot RANSAC + LSQ on device.  ``draws_fn(counts) -> int32[NL,8]`` replaces the local
         RNG draw (the sharded pipeline broadcasts rank 0's).  Returns (landmarks f64[NL,3] tensor,
         per-landmark error f64[NL] tensor, counts int32[NL] numpy).
@@ -190,7 +191,8 @@ class HipEstimator3D:
         them and the solve IN PLACE and returns True: the caller must then redo the work it had enqueued on the
         landmarks.  ``plan``: the result of ``plan_draws`` made before the step's GPU work (default: planned here).
         ``err_out`` / ``count_out``: device tensors (f64[NL] / i32[NL]) to write into, e.g. views of one buffer the
-        caller fetches with a single copy."""
+        caller fetches with a single copy.  ``report``: the device views of a ``ReportLayout``; every solve - the one
+        ``verify`` repeats included - is then followed by ``report_device`` on the same mask and draws."""
         torch, dev = self._torch()
         if self.mode not in _MODES:
             raise ValueError(f"Unknown mode for line matching in Estimator: {self.mode}")
@@ -212,6 +214,8 @@ class HipEstimator3D:
                 self.ctx.handle, C.c_void_p(starts.data_ptr()), C.c_void_p(ends.data_ptr()), C.c_void_p(mask.data_ptr()),
                 C.c_void_p(count.data_ptr()), C.c_void_p(draws_dev.data_ptr()), n, nl, C.c_void_p(out.data_ptr()),
                 C.c_void_p(err.data_ptr())))
+            if report is not None:
+                self.report_device(starts, ends, mask, draws_dev, views=report)
 
         def draw_and_solve(counts):
             draws = np.ascontiguousarray((draws_fn or self.draw_ransac_indices)(counts), dtype=np.int32)
@@ -249,6 +253,38 @@ class HipEstimator3D:
             return out, err, verify
         verify()
         return out, err, state["counts"]
+
+    def report_device(self, starts, ends, mask, draws_dev, views=None):
+        """The consensus once more with its quality report (mvlm_consensus_report): starts / ends f64[NL,N,3], mask
+        u8[NL,N] and draws i32[NL,8] on the device, as ``consensus_device`` hands them to the solve.  Returns the device
+        views of a ``ReportLayout`` (``views``: those of the caller's buffer) with ``raw``, ``error``, ``stats``, ``counts``,
+        ``view_dist2`` and ``view_flags`` written; ``raw`` and ``error`` are the solve's, bit for bit."""
+        torch, dev = self._torch()
+        nl, n = int(starts.shape[0]), int(starts.shape[1])
+        if views is None:
+            layout = ReportLayout(nl, n)
+            views = layout.device_views(torch.zeros(layout.nbytes, dtype=torch.uint8, device=dev))
+        self.ctx.check(self.ctx.lib.mvlm_consensus_report(
+            self.ctx.handle, C.c_void_p(starts.data_ptr()), C.c_void_p(ends.data_ptr()), C.c_void_p(mask.data_ptr()),
+            C.c_void_p(draws_dev.data_ptr()), n, nl, C.c_void_p(views["raw"].data_ptr()), C.c_void_p(views["error"].data_ptr()),
+            C.c_void_p(views["stats"].data_ptr()), C.c_void_p(views["counts"].data_ptr()),
+            C.c_void_p(views["view_dist2"].data_ptr()), C.c_void_p(views["view_flags"].data_ptr())))
+        return views
+
+    def attach_device(self, mesh: Mesh, pts, views=None):
+        """The snap with its attachment (mvlm_surface_attach): pts f64[n,3] on the device -> {"snapped" f64[n,3] (what
+        ``project_device`` gives, bit for bit), "tri" i32[n], "bary" f64[n,3], "uv" f64[n,2]} device tensors (``views``:
+        a dict that holds them already, e.g. the device views of a ``ReportLayout``)."""
+        torch, dev = self._torch()
+        n = int(pts.shape[0])
+        if views is None:
+            views = {"snapped": torch.empty((n, 3), dtype=torch.float64, device=dev), "tri": torch.empty((n,), dtype=torch.int32, device=dev),
+                     "bary": torch.empty((n, 3), dtype=torch.float64, device=dev), "uv": torch.empty((n, 2), dtype=torch.float64, device=dev)}
+        handle = upload_mesh(self.ctx, mesh)
+        self.ctx.check(self.ctx.lib.mvlm_surface_attach(
+            self.ctx.handle, handle, C.c_void_p(pts.data_ptr()), n, C.c_void_p(views["snapped"].data_ptr()),
+            C.c_void_p(views["tri"].data_ptr()), C.c_void_p(views["bary"].data_ptr()), C.c_void_p(views["uv"].data_ptr())))
+        return views
 
     def project_device(self, mesh: Mesh, landmarks_dev, out=None):
         torch, dev = self._torch()
@@ -309,6 +345,29 @@ class HipEstimator3D:
         e = torch.from_numpy(np.ascontiguousarray(lines_e, dtype=np.float64)).to(dev)
         out, err, _ = self.consensus_device(lms, s, e)
         return out.cpu().numpy(), self.mean_error(err.cpu().numpy())
+
+    # ---- the same two steps with the landmark report (Pipeline(..., landmark_report=True) on the slot protocol) --------
+    def estimate_landmarks_from_lines_report(self, landmark_stack, lines_s, lines_e):
+        """``estimate_landmarks_from_lines`` (same landmarks, same error, same use of the global RNG) -> (landmarks, error,
+        the arrays of a ``ReportLayout`` as numpy, with the consensus's part and ``scores`` filled)."""
+        torch, dev = self._torch()
+        lms = torch.from_numpy(np.ascontiguousarray(landmark_stack, dtype=np.float32)).to(dev)
+        s = torch.from_numpy(np.ascontiguousarray(lines_s, dtype=np.float64)).to(dev)
+        e = torch.from_numpy(np.ascontiguousarray(lines_e, dtype=np.float64)).to(dev)
+        layout = ReportLayout(int(lms.shape[0]), int(lms.shape[1]))
+        buf = torch.zeros(layout.nbytes, dtype=torch.uint8, device=dev)
+        views = layout.device_views(buf)
+        out, err, _ = self.consensus_device(lms, s, e, report=views)
+        views["scores"].copy_(lms[:, :, 2])
+        return out.cpu().numpy(), self.mean_error(err.cpu().numpy()), layout.host_arrays(buf.cpu().numpy())
+
+    def attach_landmarks_to_surface(self, pd, landmarks) -> dict:
+        """``project_landmarks_to_surface`` with the attachment: {"snapped", "tri", "bary", "uv"} as numpy."""
+        if not isinstance(pd, Mesh):
+            raise TypeError("attach_landmarks_to_surface expects the Mesh handle returned by multiview_render")
+        torch, dev = self._torch()
+        pts = torch.from_numpy(np.ascontiguousarray(landmarks, dtype=np.float64)).to(dev)
+        return {k: v.cpu().numpy() for k, v in self.attach_device(pd, pts).items()}
 
     def project_landmarks_to_surface(self, pd, landmarks):
         if not isinstance(pd, Mesh):
