@@ -214,6 +214,17 @@ int mvlm_cnn_set_pairing(mvlm_ctx* ctx, int mode);
  * float64 arithmetic, one rounding). */
 int mvlm_cnn_set_winograd(mvlm_ctx* ctx, int mode);
 int mvlm_pack_winograd_weights(const float* w9_host, int cin_pad, int cout_pad, float* w12_host);
+/* The F(4,3) Winograd tile (csrc/conv_kernel.h: Cfg::WINO4, variant conv3x3q_c32_t16x32): four output rows from six transformed
+ * input rows and six GEMMs on the points 0, 1, -1, 2, -1/2, inf - 6 multiplies per four outputs where F(2,3) spends 8 and the
+ * direct form 12, fp32 in and fp32 accumulation on the same MFMA.  It is consulted ahead of the F(2,3) table while the Winograd
+ * mode is not 0.  mode 0: never, 1 (default): where the measured table csrc/conv_tuned_wino4.h lists the layer and the Winograd
+ * mode is 1, 2: every layer the tile can serve (tests).  A new context takes MVLM_WINOGRAD4 (0 | 1 | 2) from the environment.
+ * Profile records of such a launch count 9 Cin Cout H W B FLOPs.
+ * mvlm_pack_winograd4_weights: f32[9][cin_pad][cout_pad] -> f32[18][cin_pad][cout_pad] (slice t * 3 + kx; u0 = g0,
+ * u1 = -(g0 + g1 + g2) / 3, u2 = (g0 - g1 + g2) / 3, u3 = (g0 + 2 g1 + 4 g2) / 15, u4 = (-16 g0 + 8 g1 - 4 g2) / 15, u5 = g2 over
+ * ky, float64 arithmetic, one rounding). */
+int mvlm_cnn_set_winograd4(mvlm_ctx* ctx, int mode);
+int mvlm_pack_winograd4_weights(const float* w9_host, int cin_pad, int cout_pad, float* w18_host);
 int mvlm_cnn_execution_stats(mvlm_ctx* ctx, int64_t* eager_runs, int64_t* graph_captures, int64_t* graph_replays,
                              int64_t* graph_failures);
 /* OPT-IN reduced-cost arithmetic ("fast" precision, mvlm_amd/csrc/conv_fast.hip): the big 3x3 layers (input channels a

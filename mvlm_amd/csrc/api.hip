@@ -55,6 +55,7 @@ extern "C" void mvlm_ctx_destroy(mvlm_ctx* ctx) {
     if (ctx->cnn.fast_blob) hipFree(ctx->cnn.fast_blob);
     if (ctx->cnn.fast16_blob) hipFree(ctx->cnn.fast16_blob);
     if (ctx->cnn.wino_blob) hipFree(ctx->cnn.wino_blob);
+    if (ctx->cnn.wino4_blob) hipFree(ctx->cnn.wino4_blob);
     if (ctx->cnn.fast16_flag) hipFree(ctx->cnn.fast16_flag);
     if (ctx->switch_event) hipEventDestroy(ctx->switch_event);
     for (int i = 0; i < 2; ++i) {
@@ -610,6 +611,11 @@ extern "C" int mvlm_conv2d(mvlm_ctx* ctx, const float* x_dev, int batch, int cin
         ww_off = long(push(size_t(12) * cin_pad * cout_pad));
         mvlm_winograd_transform(blob.data() + w_off, cin_pad, cout_pad, blob.data() + ww_off);
     }
+    long ww4_off = -1;
+    if (mvlm_conv_wino4_serves_slot(ksize, cin_pad, cout_pad)) {
+        ww4_off = long(push(size_t(18) * cin_pad * cout_pad));
+        mvlm_winograd4_transform(blob.data() + w_off, cin_pad, cout_pad, blob.data() + ww4_off);
+    }
     const long b_off = vec(bias_host, cout, cout_pad);
     const long ps_off = vec(pre_scale_host, cin, cin_pad), pt_off = vec(pre_shift_host, cin, cin_pad);
     const long qs_off = vec(post_scale_host, cout, cout_pad), qt_off = vec(post_shift_host, cout, cout_pad);
@@ -627,6 +633,7 @@ extern "C" int mvlm_conv2d(mvlm_ctx* ctx, const float* x_dev, int batch, int cin
     a.W = w;
     a.w = d + w_off;
     a.w_wino = ww_off < 0 ? nullptr : d + ww_off;
+    a.w_wino4 = ww4_off < 0 ? nullptr : d + ww4_off;
     a.cout = cout;
     a.cout_pad = cout_pad;
     a.ksize = ksize;
@@ -658,7 +665,7 @@ extern "C" int mvlm_conv_bench(mvlm_ctx* ctx, int batch, int cin, int cout, int 
     const bool plain = (flags & 4) && !(flags & (1 | 2 | 8));
     const int cout_pad = (plain && (cout + 15) / 16 * 16 == 80) ? 80 : (plain && ksize == 3 && cout == 84) ? 84 : (cout + 31) / 32 * 32;
     const size_t px = size_t(batch) * size * size;
-    const size_t n_w = size_t(ksize == 3 ? 12 : taps) * cin_pad * cout_pad, n_vec = size_t(cin_pad) * 2 + size_t(cout_pad) * 3;
+    const size_t n_w = size_t(ksize == 3 ? 18 : taps) * cin_pad * cout_pad, n_vec = size_t(cin_pad) * 2 + size_t(cout_pad) * 3;
     const size_t n_x = px * cin, n_y = px * cout;
     const size_t total = n_w + n_vec + n_x + 3 * n_y + 64;
     auto* base = static_cast<float*>(ctx->get_scratch("conv_bench", total * sizeof(float)));
@@ -679,6 +686,7 @@ extern "C" int mvlm_conv_bench(mvlm_ctx* ctx, int batch, int cin, int cout, int 
     a.H = a.W = size;
     a.w = w;
     if (mvlm_conv_wino_serves_slot(ksize, cin_pad, cout_pad)) a.w_wino = w;  // zero data: the transformed weights are zeros too
+    if (mvlm_conv_wino4_serves_slot(ksize, cin_pad, cout_pad)) a.w_wino4 = w;
     a.cout = cout;
     a.cout_pad = cout_pad;
     a.ksize = ksize;

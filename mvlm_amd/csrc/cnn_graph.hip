@@ -172,6 +172,7 @@ struct Exec {
         a.cout_pad = r[5];
         a.w = blob(r[6]);
         a.w_wino = (size_t(slot) < st.wino_off.size() && st.wino_off[size_t(slot)] >= 0) ? st.wino_blob + st.wino_off[size_t(slot)] : nullptr;
+        a.w_wino4 = (size_t(slot) < st.wino4_off.size() && st.wino4_off[size_t(slot)] >= 0) ? st.wino4_blob + st.wino4_off[size_t(slot)] : nullptr;
         a.bias = blob(r[7]);
         a.pre_scale = blob(r[8]);
         a.pre_shift = blob(r[9]);
@@ -200,9 +201,10 @@ struct Exec {
         hipEventRecord(e0, ctx->cur_stream());
         return 0;
     }
-    // the multiply-adds the launch's MFMAs execute: a Winograd tile spends 6 per output and input channel where a direct 3x3 spends 9
+    // the multiply-adds the launch's MFMAs execute: an F(2,3) Winograd tile spends 6 per output and input channel, the F(4,3) tile 4.5,
+    // where a direct 3x3 spends 9
     static double conv_flops(const ConvArgs& a, int variant = -1) {
-        const double taps = mvlm_conv_variant_is_wino(variant) ? 6.0 : double(a.ksize * a.ksize);
+        const double taps = mvlm_conv_variant_is_wino(variant) ? 6.0 : mvlm_conv_variant_is_wino4(variant) ? 4.5 : double(a.ksize * a.ksize);
         return 2.0 * a.cin * a.cout * taps * double(a.H) * a.W * a.B * a.n_par;
     }
 
@@ -878,6 +880,12 @@ extern "C" int mvlm_cnn_load(mvlm_ctx* ctx, const float* blob_host, size_t n_flo
         (void)hipFree(st.wino_blob);
         st.wino_blob = nullptr;
     }
+    st.wino4_off.clear();
+    st.wino4_bytes = 0;
+    if (st.wino4_blob) {
+        (void)hipFree(st.wino4_blob);
+        st.wino4_blob = nullptr;
+    }
     for (auto& g : st.graphs)
         if (g.exec) hipGraphExecDestroy(g.exec);  // captured launches point into the old weight blob
     st.graphs.clear();
@@ -919,6 +927,23 @@ extern "C" int mvlm_cnn_load(mvlm_ctx* ctx, const float* blob_host, size_t n_flo
             MVLM_CHECK_HIP(ctx, hipMalloc(&st.wino_blob, wino.size() * sizeof(float)));
             MVLM_CHECK_HIP(ctx, hipMemcpy(st.wino_blob, wino.data(), wino.size() * sizeof(float), hipMemcpyHostToDevice));
             st.wino_bytes = wino.size() * sizeof(float);
+        }
+    }
+    {  // likewise the F(4,3) form of the slots its tile can serve (twice those slots' weight bytes)
+        std::vector<float> wino4;
+        st.wino4_off.assign(size_t(n_slots), -1);
+        for (int s = 0; s < n_slots; ++s) {
+            const int32_t* r = &st.desc[size_t(s) * MVLM_CONV_DESC_INTS];
+            if (!r[0] || !mvlm_conv_wino4_serves_slot(r[3], r[4], r[5])) continue;
+            const size_t off = wino4.size();
+            wino4.resize(off + size_t(18) * r[4] * r[5]);
+            mvlm_winograd4_transform(blob_host + r[6], r[4], r[5], wino4.data() + off);
+            st.wino4_off[size_t(s)] = (long long)off;
+        }
+        if (!wino4.empty()) {
+            MVLM_CHECK_HIP(ctx, hipMalloc(&st.wino4_blob, wino4.size() * sizeof(float)));
+            MVLM_CHECK_HIP(ctx, hipMemcpy(st.wino4_blob, wino4.data(), wino4.size() * sizeof(float), hipMemcpyHostToDevice));
+            st.wino4_bytes = wino4.size() * sizeof(float);
         }
     }
     st.n_landmarks = n_landmarks;
@@ -1007,6 +1032,18 @@ extern "C" int mvlm_cnn_set_winograd(mvlm_ctx* ctx, int mode) {
         ctx->cnn.graphs.clear();
     }
     ctx->conv_winograd = mode;
+    return 0;
+}
+
+extern "C" int mvlm_cnn_set_winograd4(mvlm_ctx* ctx, int mode) {
+    MVLM_ENTER(ctx);
+    MVLM_REQUIRE(ctx, mode >= 0 && mode <= 2, "cnn_set_winograd4: 0 never, 1 the measured table (default), 2 every layer the F(4,3) Winograd tile can serve");
+    if (mode != ctx->conv_winograd4) {  // captured graphs encode the launches
+        for (auto& g : ctx->cnn.graphs)
+            if (g.exec) hipGraphExecDestroy(g.exec);
+        ctx->cnn.graphs.clear();
+    }
+    ctx->conv_winograd4 = mode;
     return 0;
 }
 

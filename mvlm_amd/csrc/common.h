@@ -122,8 +122,12 @@ struct ConvArgs {
     float* pool_out = nullptr;
     int pool_ctot = 0, pool_coff = 0;
     float fast_unscale = 1.f;  // f16x2 kernel only: inverse of the power-of-two scale its packed weights carry
+    int pool_hint = 0;  // the caller wants the pooled tensor too (set for the variant choice, before pool_out is decided; host only)
     unsigned* fast_ovf = nullptr;  // f16x2 kernel only: set to 1 when an activation lies outside fp16's range
-    int pool_hint = 0;  // the caller wants the pooled tensor too (set for the variant choice, before pool_out is decided)
+    // the layer's weights in the F(4,3) Winograd tile's form ([18][cin_pad][cout_pad], mvlm_pack_winograd4_weights) where it has
+    // one (host only, as w_wino below).  It sits where pool_hint and its padding were: the struct is a kernel argument, and
+    // every field a kernel reads keeps its offset (see the static_assert below).
+    const float* w_wino4 = nullptr;
     // -DMVLM_CONV_TIMING builds only (tools/conv_phase_timing.py): u64[4] = summed cycles of wave 0 in
     // prologue / K loop / epilogue, number of workgroups
     unsigned long long* timing = nullptr;
@@ -131,6 +135,8 @@ struct ConvArgs {
     // mvlm_launch_conv puts it in `w` when it routes the launch to such a tile
     const float* w_wino = nullptr;
 };
+static_assert(sizeof(ConvArgs) == 360 && offsetof(ConvArgs, fast_ovf) == 328 && offsetof(ConvArgs, timing) == 344,
+              "ConvArgs is passed to the kernels by value: moving a field changes the device code of every convolution kernel");
 
 struct ConvProfileRec {
     int slot, variant;
@@ -194,6 +200,10 @@ struct CnnState {
     float* wino_blob = nullptr;
     std::vector<long long> wino_off;
     size_t wino_bytes = 0;
+    // likewise the F(4,3) form ([18][cin_pad][cout_pad]) of the slots the F(4,3) tile can serve
+    float* wino4_blob = nullptr;
+    std::vector<long long> wino4_off;
+    size_t wino4_bytes = 0;
     std::vector<CnnGraphEntry> graphs;
     long graph_replays = 0, graph_captures = 0, eager_runs = 0, graph_failures = 0;
 };
@@ -257,8 +267,12 @@ struct mvlm_ctx {
     // Winograd tiles on the exact path: 0 never, 1 where the measured table (conv_tuned_wino.h) has an entry, 2 every layer a
     // Winograd variant can serve (tests); a new context takes MVLM_WINOGRAD from the environment (default 1)
     int conv_winograd = [] { const char* e = getenv("MVLM_WINOGRAD"); return (e && e[0] >= '0' && e[0] <= '2' && !e[1]) ? e[0] - '0' : 1; }();
+    // the F(4,3) Winograd tile, where Winograd mode is not 0 and the launch carries ConvArgs::w_wino4: 0 never, 1 where the measured
+    // table (conv_tuned_wino4.h) has an entry and Winograd mode is 1, 2 every layer the tile can serve (tests); MVLM_WINOGRAD4 (default 1)
+    int conv_winograd4 = [] { const char* e = getenv("MVLM_WINOGRAD4"); return (e && e[0] >= '0' && e[0] <= '2' && !e[1]) ? e[0] - '0' : 1; }();
     std::vector<ConvOverride> conv_overrides;  // tools/tune_in_network.py: kernel variant per (shape, kind), before any table
     unsigned long long conv_attr_mask = 0;  // conv variants whose launch attributes are set on this ctx's device
+    bool conv_wino4_attr_set = false;       // likewise the F(4,3) Winograd tile (MVLM_CONV_VARIANT_WINO4: not a base id, no bit of the mask)
     // a depth-key plane's buffer and capacity when it was last left all-EMPTY ({nullptr, 0}: not known clean); keyed on both,
     // so a buffer that get_scratch replaced by one of the same size is filled again
     struct KeyPlaneState {
@@ -358,12 +372,16 @@ bool mvlm_conv_can_pool(const mvlm_ctx* ctx, const ConvArgs& a);  // the variant
 int mvlm_conv_kind(const ConvArgs& a);
 ConvKey mvlm_conv_key(const ConvArgs& a);
 bool mvlm_conv_variant_can_pool(int variant);
-bool mvlm_conv_variant_is_wino(int variant);
+bool mvlm_conv_variant_is_wino(int variant);   // an F(2,3) Winograd tile (reads ConvArgs::w_wino)
+bool mvlm_conv_variant_is_wino4(int variant);  // the F(4,3) Winograd tile (reads ConvArgs::w_wino4)
 // the Winograd variant this launch is routed to (overrides, mode and table of the context), or -1: the direct tiles
 int mvlm_conv_wino_variant(const mvlm_ctx* ctx, const ConvArgs& a);
 bool mvlm_conv_wino_serves_slot(int ksize, int cin_pad, int cout_pad);  // a Winograd variant exists for these channels
 // host: packed [9][cin_pad][cout_pad] -> [12][cin_pad][cout_pad] (u_t per kx: t * 3 + kx), float64 arithmetic, one rounding
 void mvlm_winograd_transform(const float* w9, int cin_pad, int cout_pad, float* w12);
+bool mvlm_conv_wino4_serves_slot(int ksize, int cin_pad, int cout_pad);  // the F(4,3) tile can serve these channels
+// host: packed [9][cin_pad][cout_pad] -> [18][cin_pad][cout_pad] (u_t per kx: t * 3 + kx), float64 arithmetic, one rounding
+void mvlm_winograd4_transform(const float* w9, int cin_pad, int cout_pad, float* w18);
 // two independent convolutions in one grid (conv_kernel.h: conv_pair_kernel)
 constexpr int MVLM_CONV_PAIR_FLAG = 0x1000;  // variant code of a paired launch: flag | base id | lg(kparts0) << 8 | lg(kparts1) << 10
 int mvlm_conv_pair_variant(const ConvArgs& a0, const ConvArgs& a1, int mode);
@@ -381,6 +399,8 @@ inline bool mvlm_fast_channels_ok(int cin, int cout) {
 }
 bool mvlm_conv_fast_ok(const ConvArgs& a, int splits);  // splits: 3 = bf16x3 ("fast"), 2 = f16x2 ("fast16")
 int mvlm_launch_conv_fast(mvlm_ctx* ctx, const ConvArgs& a, const unsigned short* wq_dev, int splits = 3, float unscale = 1.f);
+// the F(4,3) Winograd tile (conv3x3q_c32_t16x32): a code beyond the base ids and their K-part forms (0..1023) and below the pair flag
+constexpr int MVLM_CONV_VARIANT_WINO4 = 2048;
 constexpr int MVLM_CONV_VARIANT_FAST = 62;    // id reported for launches of the bf16x3 kernel
 constexpr int MVLM_CONV_VARIANT_FAST16 = 61;  // ... of the f16x2 kernel
 

@@ -39,16 +39,22 @@ __device__ __forceinline__ void static_for(F&& f) {
 // host-transformed columns u_t ([t * 3 + kx][cin][cout], 12 "taps").  Four GEMMs m_t over K = (kx, cin) - a tap is an x
 // offset only - and out[2p] = (m0 + m1) + m2, out[2p+1] = (m1 - m2) - m3 in the registers of one lane: 4 MFMAs per
 // output pair and (kx, cin) instead of 6, and the epilogue sees the register layout of the direct tile.
+// KS_ == 34 (WINO4): a 3x3 convolution as F(4,3) Winograd along y on the points 0, 1, -1, 2, -1/2, inf.  Output rows 4q .. 4q+3
+// come from the input rows d0..d5 = 4q-1 .. 4q+4: six transformed rows v_t per channel and row quad, six host-transformed weight
+// columns u_t ([t * 3 + kx][cin][cout], 18 "taps"), six GEMMs m_t over K = (kx, cin) and the output transform in the registers
+// of one lane - 6 MFMAs per four output rows and (kx, cin) where F(2,3) spends 8 and the direct form 12 (see "F(4,3) Winograd
+// tiles" below for the transforms and the fixed order of their sums).
 template <int COUT_T_, int TW_, int TRI_, int NIMG_, int KS_, int CK_, bool SPLITK_ = false>
 struct Cfg {
     static constexpr bool WINO = KS_ == 32;
-    static constexpr int COUT_T = COUT_T_, TW = TW_, TRI = TRI_, NIMG = NIMG_, KS = WINO ? 3 : KS_, CK = CK_;
+    static constexpr bool WINO4 = KS_ == 34;
+    static constexpr int COUT_T = COUT_T_, TW = TW_, TRI = TRI_, NIMG = NIMG_, KS = (WINO || WINO4) ? 3 : KS_, CK = CK_;
     static constexpr bool SPLITK = SPLITK_;
     static constexpr int CKW = SPLITK ? CK / 4 : CK;  // channels of a chunk one wave multiplies
-    static constexpr int TAPS = WINO ? 12 : KS * KS;
+    static constexpr int TAPS = WINO4 ? 18 : WINO ? 12 : KS * KS;
     static constexpr int HALO = KS == 1 ? 0 : 1;  // KS == 2: a 2x2 window inside the 3x3 halo tile
     static constexpr int PW = TW + 2 * HALO;
-    static constexpr int PH = WINO ? 2 * TRI : TRI + 2 * HALO;  // WINO: four transformed rows per output row pair
+    static constexpr int PH = WINO4 ? 6 * TRI / 4 : WINO ? 2 * TRI : TRI + 2 * HALO;  // WINO: four transformed rows per output row pair, WINO4: six per row quad
     static constexpr int PLANE = NIMG * PH * PW;  // floats per channel in sX
     static constexpr int PIX_T = TW * TRI * NIMG;
     static constexpr int XT = CK * PLANE;
@@ -66,16 +72,16 @@ struct Cfg {
     static constexpr bool HAS_AMAX = NIMG == 1 && TW == 32 && TRI == 8 && KS != 1 && (COUT_T == 80 || COUT_T == 96 || (COUT_T == 84 && KS == 2));
     static constexpr int NT = SPLITK ? PIX_T / 32 : PIX_T / 4 / 32;  // split-K: every wave multiplies all (one or two) 32-pixel columns
     static constexpr int NT16 = TAIL16 ? 2 * NT : 1;  // 16-pixel column groups of a wave
-    static constexpr int KSTEPS = WINO ? 3 * CK / 2 : TAPS * CKW / 2;  // WINO: (kx, channel pair), four GEMMs per step
+    static constexpr int KSTEPS = (WINO || WINO4) ? 3 * CK / 2 : TAPS * CKW / 2;  // WINO: (kx, channel pair), four GEMMs per step (WINO4: six)
     static constexpr int WP = PIX_T / 4 / 64;              // WINO: row pairs of a wave
-    static constexpr int WJOBS = CK * (TRI / 2) * PW;      // WINO: staging jobs of a chunk = (channel, row pair, x)
-    static constexpr int X_ITERS = WINO ? (WJOBS + 255) / 256 : (XT + 255) / 256;
+    static constexpr int WJOBS = CK * (WINO4 ? TRI / 4 : TRI / 2) * PW;  // WINO: staging jobs of a chunk = (channel, row pair, x); WINO4: (channel, row quad, x)
+    static constexpr int X_ITERS = (WINO || WINO4) ? (WJOBS + 255) / 256 : (XT + 255) / 256;
     static constexpr int W_ITERS = (WT / 4 + 255) / 256;
     static constexpr int BN_MAXC = 256;  // pre-BN scale/shift of up to 256 input channels live in LDS
     static constexpr size_t LDS_BYTES = size_t(2 * STAGE + 2 * BN_MAXC) * 4;
     // accumulators + staged tile + operands: above ~200 registers the kernel is told it owns
     // the whole SIMD register file (one wave per SIMD) instead of spilling for occupancy
-    static constexpr int ACC_REGS = ((COUT_T / 32) * (SPLITK ? PIX_T / 32 : TW * TRI * NIMG / 128) * 16 + (TAIL16 ? 4 * NT16 : 0) + (TAIL4 ? 4 : 0)) * (WINO ? 2 : 1);
+    static constexpr int ACC_REGS = ((COUT_T / 32) * (SPLITK ? PIX_T / 32 : TW * TRI * NIMG / 128) * 16 + (TAIL16 ? 4 * NT16 : 0) + (TAIL4 ? 4 : 0)) * (WINO ? 4 : WINO4 ? 3 : 2) / 2;
     // register budget per lane: 168 at three workgroups per CU, 256 at two
     // (four per CU = 128 registers makes the 64-accumulator tiles spill; measured slower)
     static constexpr int MIN_BLOCKS_PER_CU = (ACC_REGS <= 64 && TW * TRI * NIMG <= 256) ? 3 : 2;
@@ -88,9 +94,9 @@ struct Cfg {
     static constexpr bool POOL_SMALL = TW < 32 && TRI % 2 == 0 && COUT_T % 32 == 0;
     static constexpr bool CAN_POOL_ANY = POOL32 || POOL_SMALL;
     // the tile that also exists with a second input tensor added on the load (ConvArgs::in2): the dominant 128 x (8 x 32) tile
-    static constexpr bool HAS_IN2 = !WINO && !SPLITK && COUT_T == 128 && TW == 32 && TRI == 8 && NIMG == 1 && KS == 3 && CK == 4;
+    static constexpr bool HAS_IN2 = !WINO && !WINO4 && !SPLITK && COUT_T == 128 && TW == 32 && TRI == 8 && NIMG == 1 && KS == 3 && CK == 4;
     // variants that also exist as a two-problem launch (conv_pair_kernel): the tiles of the residual blocks' 3x3 convolutions
-    static constexpr bool PAIRABLE = !WINO && KS == 3 && COUT_T % 32 == 0 && COUT_T != 96 && !(SPLITK && PIX_T != 32);
+    static constexpr bool PAIRABLE = !WINO && !WINO4 && KS == 3 && COUT_T % 32 == 0 && COUT_T != 96 && !(SPLITK && PIX_T != 32);
     static_assert(SPLITK ? ((PIX_T == 32 || PIX_T == 64) && COUT_T == 32 && CK % 8 == 0) : (PIX_T % 128 == 0),
                   "pixel tile must split into 4 waves x 32-pixel MFMA columns (or be one or two columns for split-K)");
     static_assert(!TAIL4 || PIX_T == 256, "the 4-row strip gives every lane of a wave one pixel: 64 pixels per wave");
@@ -99,6 +105,8 @@ struct Cfg {
     static_assert(CK % 2 == 0, "the f32 MFMA consumes two k values per step");
     static_assert(!WINO || (!SPLITK && TW == 32 && NIMG == 1 && PIX_T % 256 == 0 && COUT_T % 32 == 0),
                   "Winograd tiles: 32-pixel rows, one image, whole row pairs per wave, no strips");
+    static_assert(!WINO4 || (!SPLITK && TW == 32 && NIMG == 1 && PIX_T == 512 && COUT_T == 32),
+                  "F(4,3) Winograd tile: 32-pixel rows, one image, one row quad per wave, one 32-row cout tile");
     static_assert(LDS_BYTES <= 160 * 1024, "two stages must fit the CU's 160 KiB LDS");
 };
 
@@ -637,6 +645,318 @@ __device__ __forceinline__ void wino_main(const ConvArgs& a, float* smem, const 
     (void)t_loop;
 }
 
+// ---- F(4,3) Winograd tiles (Cfg::WINO4) ---------------------------------------------------------------------------------
+// The tile of conv3x3_c32_t16x32 (32 cout x 16 rows x 32 pixels, one row quad per wave) with the structure of the F(2,3)
+// tiles above.  Quad q covers output rows 4q .. 4q+3 and reads d0..d5 = rows 4q-1 .. 4q+4 (after BatchNorm + ReLU and the
+// zero padding).  All coefficients are dyadic, so every product is exact and only the sums round; they are summed left to
+// right as written, each step one fused multiply-add (= the exact product, added with one rounding):
+//   v0 = d0 + 1.5 d1 - 2 d2 - 1.5 d3 + d4      v1 = -d1 - 2.5 d2 - 0.5 d3 + d4      v2 = d1 + 0.5 d2 - 2.5 d3 + d4
+//   v3 = -d2 - 0.5 d1 + 0.5 d3 + d4            v4 = -d2 + 2 d1 - 2 d3 + d4          v5 = d1 + 1.5 d2 - 2 d3 - 1.5 d4 + d5
+// weights (host, float64, rounded once: mvlm_winograd4_transform):
+//   u0 = g0, u1 = -(g0 + g1 + g2) / 3, u2 = (g0 - g1 + g2) / 3, u3 = (g0 + 2 g1 + 4 g2) / 15, u4 = (-16 g0 + 8 g1 - 4 g2) / 15, u5 = g2
+// six GEMMs m_t = sum over (kx, cin) of u_t v_t, and with s = m1 + m2, d = m1 - m2:
+//   o0 = (m0 + s) + (m3 + m4)    o1 = d + (2 m3 - m4 / 2)    o2 = s + (4 m3 + m4 / 4)    o3 = (d + (8 m3 - m4 / 8)) + m5
+// A channel's plane of a stage is [q][x][4] (v0..v3, one 16-byte write and read) followed by [q][x][2] (v4, v5, 8 bytes):
+// neighbouring lanes read neighbouring 16- / 8-byte words.  The weight slice is [t * 3 + kx][cin][cout] as in global memory.
+// Staging job = one (channel, row quad, x) of a chunk: six loads, one BatchNorm pair, two LDS writes.  Masks, repeated jobs,
+// the neutral BatchNorm pair and the padded last chunk are handled as for the F(2,3) tiles (see WinoStage).
+template <class C>
+struct Wino4Stage {
+    static constexpr int N = C::WINO4 ? C::X_ITERS : 1;
+    static constexpr int NW = C::WINO4 ? C::W_ITERS : 1;
+    unsigned off[N][6];  // BYTE offset of row 4q - 1 + r at the job's x from the chunk's first channel in this image (0: masked row)
+    unsigned msk[N][3];  // all ones: the column and row 4q - 1 (0), rows 4q .. 4q + 3 (1), row 4q + 4 (2) lie inside the image; 0: padding
+    int lds4[N], lds2[N];  // stage offsets of the job's v0 and v4
+    int bn[N];             // the job's channel within the chunk
+    unsigned woff[NW];     // BYTE offset of the lane's float4 i of the weight slice from the chunk's first channel row ...
+    int wlds[NW];          // ... and its float4 index in the staged slice (a lane without a float4 i repeats its float4 i - 1)
+    float xw[N][6];
+    float bn_s[N], bn_t[N];
+    f32x4 wv[NW];
+    float floor;  // ReLU of the pre-activation: 0; no pre-activation: -inf
+    int abase;    // operand reads: the lane's weight of tap 0, channel 0 of stage 0 ...
+    int bbase4[2][C::CK / 2], bbase2[2][C::CK / 2];  // ... and its pixel's v0 / v4 in stage s, channel pair cp
+};
+
+template <class C, int T>
+__device__ __forceinline__ void issue_item_wino4(const char* in_cb, const char* w_cb, Wino4Stage<C>& ws) {
+    if constexpr (T < C::X_ITERS) {
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+            wino_opaque(ws.off[T][r]);
+            ws.xw[T][r] = *reinterpret_cast<const float*>(in_cb + ws.off[T][r]);
+        }
+    } else {
+        constexpr int I = T - C::X_ITERS;
+        wino_opaque(ws.woff[I]);
+        ws.wv[I] = *reinterpret_cast<const f32x4*>(w_cb + ws.woff[I]);
+    }
+}
+
+template <class C, int T>
+__device__ __forceinline__ void bn_item_wino4(const float* sbn, int cb, Wino4Stage<C>& ws) {
+    if constexpr (T < C::X_ITERS) {
+        const float2 st = *reinterpret_cast<const float2*>(sbn + 2 * (cb + ws.bn[T]));
+        ws.bn_s[T] = st.x;
+        ws.bn_t[T] = st.y;
+    }
+}
+
+// BatchNorm + ReLU, zero padding AFTER the activation, the input transform, a 16-byte and an 8-byte LDS write into stage NEXT
+template <class C, int T, int NEXT>
+__device__ __forceinline__ void write_item_wino4(float* smem, const Wino4Stage<C>& ws) {
+    if constexpr (T < C::X_ITERS) {
+        float d[6];
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+            const float v = fmaxf(fmaf(ws.xw[T][r], ws.bn_s[T], ws.bn_t[T]), ws.floor);
+            d[r] = __uint_as_float(__float_as_uint(v) & ws.msk[T][r == 0 ? 0 : r == 5 ? 2 : 1]);
+        }
+        const float v0 = fmaf(-1.5f, d[3], fmaf(-2.f, d[2], fmaf(1.5f, d[1], d[0]))) + d[4];
+        const float v1 = fmaf(-0.5f, d[3], fmaf(-2.5f, d[2], -d[1])) + d[4];
+        const float v2 = fmaf(-2.5f, d[3], fmaf(0.5f, d[2], d[1])) + d[4];
+        const float v3 = fmaf(0.5f, d[3], fmaf(-0.5f, d[1], -d[2])) + d[4];
+        const float v4 = fmaf(-2.f, d[3], fmaf(2.f, d[1], -d[2])) + d[4];
+        const float v5 = fmaf(-1.5f, d[4], fmaf(-2.f, d[3], fmaf(1.5f, d[2], d[1]))) + d[5];
+        *reinterpret_cast<f32x4*>(smem + NEXT * C::STAGE + ws.lds4[T]) = f32x4{v0, v1, v2, v3};
+        *reinterpret_cast<float2*>(smem + NEXT * C::STAGE + ws.lds2[T]) = make_float2(v4, v5);
+    } else {
+        constexpr int I = T - C::X_ITERS;
+        reinterpret_cast<f32x4*>(smem + NEXT * C::STAGE + C::XT_PAD)[ws.wlds[I]] = ws.wv[I];
+    }
+}
+
+// The MFMAs of one K-chunk out of LDS stage CUR, as compute_chunk_wino: k-steps (kx, channel pair) in a fixed order, per step
+// the six GEMMs t = 0..5 of the wave's row quad; with STAGE_NEXT the next chunk is staged in the MFMAs' shadow.
+template <class C, int CUR, bool STAGE_NEXT>
+__device__ __forceinline__ void compute_chunk_wino4(float* smem, const float* sbn, const char* in_cb, const char* w_cb, int cb_next,
+                                                    Wino4Stage<C>& ws, f32x16 (&acc)[6]) {
+    constexpr int T_TOT = C::X_ITERS + C::W_ITERS;
+    constexpr int ISSUE_SPAN = C::KSTEPS / 2 > 0 ? C::KSTEPS / 2 : 1;
+    constexpr int WRITE_SPAN = ISSUE_SPAN;
+    constexpr int WRITE_START = C::KSTEPS - WRITE_SPAN;
+    const float* const st = smem + CUR * C::STAGE;
+    float av[2][6];
+    f32x4 bv4[2];  // v0..v3 of the lane's pixel column: one 16-byte read
+    float2 bv2[2];  // v4, v5: one 8-byte read
+#pragma unroll
+    for (int t = 0; t < 6; ++t) av[0][t] = st[ws.abase + t * 3 * C::CK * C::COUT_T];
+    bv4[0] = *reinterpret_cast<const f32x4*>(smem + ws.bbase4[CUR][0]);
+    bv2[0] = *reinterpret_cast<const float2*>(smem + ws.bbase2[CUR][0]);
+    static_for<0, C::KSTEPS>([&](auto ksc) {
+        constexpr int ks = decltype(ksc)::value;
+        constexpr int nx = ks + 1;
+        // ONE wait per k-step (see compute_chunk_wino)
+        __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (nx < C::KSTEPS) {
+            constexpr int kx = nx / (C::CK / 2), cp = nx % (C::CK / 2);
+#pragma unroll
+            for (int t = 0; t < 6; ++t) av[nx & 1][t] = st[ws.abase + ((t * 3 + kx) * C::CK + 2 * cp) * C::COUT_T];
+            bv4[nx & 1] = *reinterpret_cast<const f32x4*>(smem + ws.bbase4[CUR][cp] + kx * 4);
+            bv2[nx & 1] = *reinterpret_cast<const float2*>(smem + ws.bbase2[CUR][cp] + kx * 2);
+        }
+        auto bval = [&](auto tc) {
+            constexpr int t = decltype(tc)::value;
+            if constexpr (t < 4) return bv4[ks & 1][t];
+            else if constexpr (t == 4) return bv2[ks & 1].x;
+            else return bv2[ks & 1].y;
+        };
+        constexpr int LEAD = 2;
+        static_for<0, 6>([&](auto tc) {
+            constexpr int t = decltype(tc)::value;
+            if constexpr (t < LEAD) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[ks & 1][t], bval(tc), acc[t], 0, 0, 0);
+        });
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (STAGE_NEXT) {
+            // ONE wait for the global loads a k-step writes to LDS: what may stay in flight is what was requested after the
+            // last item written here (a job is six loads, a weight float4 one)
+            if constexpr (ks >= WRITE_START) {
+                constexpr int t_last = ((ks - WRITE_START + 1) * T_TOT + WRITE_SPAN - 1) / WRITE_SPAN - 1;
+                static_assert(WRITE_START + (t_last * WRITE_SPAN) / T_TOT == ks && (t_last + 1 == T_TOT || WRITE_START + ((t_last + 1) * WRITE_SPAN) / T_TOT > ks));
+                constexpr int later = (t_last + 1 < C::X_ITERS ? 6 * (C::X_ITERS - t_last - 1) + C::W_ITERS : T_TOT - t_last - 1);
+                static_assert(later < 16);
+                __builtin_amdgcn_s_waitcnt(0x0F70 | later);  // vmcnt(later)
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            static_for<0, T_TOT>([&](auto tc) {
+                constexpr int t = decltype(tc)::value;
+                if constexpr ((t * ISSUE_SPAN) / T_TOT == ks) {
+                    issue_item_wino4<C, t>(in_cb, w_cb, ws);
+                    bn_item_wino4<C, t>(sbn, cb_next, ws);
+                }
+                if constexpr (WRITE_START + (t * WRITE_SPAN) / T_TOT == ks) write_item_wino4<C, t, CUR ^ 1>(smem, ws);
+            });
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        __builtin_amdgcn_s_setprio(1);
+        static_for<0, 6>([&](auto tc) {
+            constexpr int t = decltype(tc)::value;
+            if constexpr (t >= LEAD) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[ks & 1][t], bval(tc), acc[t], 0, 0, 0);
+        });
+        __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_sched_barrier(0);
+    });
+}
+
+template <class C>
+__device__ __forceinline__ void wino4_forget_bases(Wino4Stage<C>& ws) {
+    wino_opaque(ws.abase);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int cp = 0; cp < C::CK / 2; ++cp) {
+            wino_opaque(ws.bbase4[s][cp]);
+            wino_opaque(ws.bbase2[s][cp]);
+        }
+#pragma unroll
+    for (int i = 0; i < C::X_ITERS; ++i) {
+        wino_opaque(ws.lds4[i]);
+        wino_opaque(ws.lds2[i]);
+    }
+}
+
+// the channel of job i of lane tid within its chunk (a lane without a job repeats the job WJOBS earlier)
+template <class C>
+__device__ __forceinline__ int wino4_job_channel(int tid, int i) {
+    const int e = tid + i * 256;
+    return (e < C::WJOBS ? e : e - C::WJOBS) / ((C::TRI / 4) * C::PW);
+}
+
+// The channels of a padded last chunk beyond cin: their jobs become padding (mask 0, load offset 0)
+template <class C>
+__device__ __forceinline__ void wino4_mask_tail(const ConvArgs& a, int cb, int tid, Wino4Stage<C>& ws) {
+#pragma unroll
+    for (int i = 0; i < C::X_ITERS; ++i) {
+        const bool okc = cb + wino4_job_channel<C>(tid, i) < a.cin;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) ws.msk[i][q] = okc ? ws.msk[i][q] : 0u;
+#pragma unroll
+        for (int r = 0; r < 6; ++r) ws.off[i][r] = okc ? ws.off[i][r] : 0u;
+    }
+}
+
+// The whole K loop of an F(4,3) tile and the output transform into the direct tile's accumulator layout (acc[0][n]: n = output
+// row of the wave's quad).  The chunk schedule is wino_main's: unrolled by two, one barrier per chunk, the last chunk (the
+// only one that can hold channels beyond cin) staged after wino4_mask_tail().
+template <class C>
+__device__ __forceinline__ void wino4_main(const ConvArgs& a, float* smem, const int tid, const int y0, const int x0, const int b0,
+                                           const int co0, const unsigned HWin, const int woff, f32x16 (&acc)[C::MT][C::NT], long long* t_loop) {
+    static_assert(!C::WINO4 || 256 * C::X_ITERS - C::WJOBS <= C::WJOBS, "a lane without a job repeats an earlier job");
+    static_assert(!C::WINO4 || (C::TRI % 4 == 0 && C::NT == 4 && C::MT == 1), "one row quad per wave; rows 4q .. 4q + 3 of a tile share one mask");
+    static_assert(!C::WINO4 || (C::WT / 4 > 256 * (C::W_ITERS - 1) && C::WT / 4 >= 256), "a lane without a float4 repeats its previous one");
+    const int lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
+    Wino4Stage<C> ws;
+    constexpr int JPC = (C::TRI / 4) * C::PW;  // jobs per channel
+    constexpr int Q4 = JPC * 4;                // floats of a channel's [q][x][4] part
+#pragma unroll
+    for (int i = 0; i < C::X_ITERS; ++i) {
+        const int e0 = tid + i * 256;
+        const int e = e0 < C::WJOBS ? e0 : e0 - C::WJOBS;
+        const int c = e / JPC;
+        const int rem = e - c * JPC;
+        const int q = rem / C::PW;
+        const int xx = rem - q * C::PW;
+        const int y = y0 + 4 * q - 1, x = x0 + xx - 1;
+        const bool okx = x >= 0 && x < a.W && b0 < a.B;
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {  // (rows 4q .. 4q + 3 are rows of the tile: the image's height is a multiple of the tile's)
+            const bool ok = okx && y + r >= 0 && y + r < a.H;
+            if (r == 0 || r == 1 || r == 5) ws.msk[i][r == 0 ? 0 : r == 5 ? 2 : 1] = ok ? 0xFFFFFFFFu : 0u;
+            ws.off[i][r] = ok ? (unsigned(c) * HWin + unsigned((y + r) * a.W + x)) * 4u : 0u;
+        }
+        ws.lds4[i] = c * C::PLANE + rem * 4;
+        ws.lds2[i] = c * C::PLANE + Q4 + rem * 2;
+        ws.bn[i] = c;
+    }
+#pragma unroll
+    for (int i = 0; i < C::W_ITERS; ++i) {  // float4 index f -> (tap, c, cout4), as the direct tiles' slice
+        const int f0 = tid + i * 256;
+        const int f = f0 < C::WT / 4 ? f0 : f0 - 256;
+        const int row = f / (C::COUT_T / 4);
+        const int c4 = f - row * (C::COUT_T / 4);
+        const int tap = row / C::CK;
+        const int c = row - tap * C::CK;
+        ws.woff[i] = unsigned((tap * a.cin_pad + c) * a.cout_pad + co0 + c4 * 4) * 4u;
+        ws.wlds[i] = f;
+    }
+    ws.floor = __int_as_float(__builtin_amdgcn_readfirstlane(a.pre_scale != nullptr ? 0 : int(0xFF800000u)));  // (a scalar)
+    ws.abase = woff;
+    wino_opaque(ws.abase);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int cp = 0; cp < C::CK / 2; ++cp) {
+            ws.bbase4[s][cp] = s * C::STAGE + (2 * cp + half) * C::PLANE + (wave * C::PW + l31) * 4;
+            ws.bbase2[s][cp] = s * C::STAGE + (2 * cp + half) * C::PLANE + Q4 + (wave * C::PW + l31) * 2;
+            wino_opaque(ws.bbase4[s][cp]);
+            wino_opaque(ws.bbase2[s][cp]);
+        }
+    float* const sbn = smem + 2 * C::STAGE;
+    // wave-uniform bases of chunk 0
+    const char* const in0 = reinterpret_cast<const char*>(a.in + size_t((b0 < a.B ? b0 : 0) * a.in_ctot + a.in_coff) * HWin);
+    const char* const w0 = reinterpret_cast<const char*>(a.w);
+    constexpr int T_TOT = C::X_ITERS + C::W_ITERS;
+    const int last = a.cin_pad - C::CK;  // first channel of the last chunk
+    const bool odd = (a.cin_pad / C::CK) & 1;
+    // prologue as wino_main's: the LAST chunk is multiplied out of stage 1, so chunk 0 goes to stage 1 where the count is odd
+    if (last == 0) wino4_mask_tail<C>(a, 0, tid, ws);
+    static_for<0, T_TOT>([&](auto tc) { issue_item_wino4<C, decltype(tc)::value>(in0, w0, ws); });
+    for (int i = tid; i < a.cin_pad; i += 256) {
+        sbn[2 * i] = a.pre_scale != nullptr ? a.pre_scale[i] : 1.f;
+        sbn[2 * i + 1] = a.pre_scale != nullptr ? a.pre_shift[i] : -0.f;
+    }
+    __syncthreads();
+    static_for<0, T_TOT>([&](auto tc) { bn_item_wino4<C, decltype(tc)::value>(sbn, 0, ws); });
+    if (odd) {
+        static_for<0, T_TOT>([&](auto tc) { write_item_wino4<C, decltype(tc)::value, 1>(smem, ws); });
+    } else {
+        static_for<0, T_TOT>([&](auto tc) { write_item_wino4<C, decltype(tc)::value, 0>(smem, ws); });
+    }
+    __syncthreads();
+#if defined(MVLM_CONV_TIMING)
+    *t_loop = clock64();
+#endif
+    f32x16 wacc[6];
+#pragma unroll
+    for (int t = 0; t < 6; ++t) wacc[t] = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (last > 0) {
+        int cb = 0;  // the chunk to multiply next
+        const size_t in_step = size_t(C::CK) * HWin * 4, w_cstep = size_t(C::CK) * a.cout_pad * 4;
+        const char* in_nx = in0 + in_step;
+        const char* w_nx = w0 + w_cstep;
+        if (odd) {  // (three chunks or more: chunk 1 is not the last)
+            compute_chunk_wino4<C, 1, true>(smem, sbn, in_nx, w_nx, C::CK, ws, wacc);
+            __syncthreads();  // next stage complete; everybody is done reading this one
+            cb = C::CK, in_nx += in_step, w_nx += w_cstep;
+        }
+        wino4_forget_bases<C>(ws);
+        for (; cb + C::CK < last; cb += 2 * C::CK) {
+            compute_chunk_wino4<C, 0, true>(smem, sbn, in_nx, w_nx, cb + C::CK, ws, wacc);
+            __syncthreads();
+            in_nx += in_step, w_nx += w_cstep;
+            compute_chunk_wino4<C, 1, true>(smem, sbn, in_nx, w_nx, cb + 2 * C::CK, ws, wacc);
+            __syncthreads();
+            in_nx += in_step, w_nx += w_cstep;
+        }
+        wino4_forget_bases<C>(ws);
+        wino4_mask_tail<C>(a, last, tid, ws);
+        compute_chunk_wino4<C, 0, true>(smem, sbn, in_nx, w_nx, last, ws, wacc);
+        __syncthreads();
+    }
+    compute_chunk_wino4<C, 1, false>(smem, sbn, nullptr, nullptr, 0, ws, wacc);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const float m0 = wacc[0][r], m1 = wacc[1][r], m2 = wacc[2][r], m3 = wacc[3][r], m4 = wacc[4][r], m5 = wacc[5][r];
+        const float s = m1 + m2, d = m1 - m2;
+        acc[0][0][r] = (m0 + s) + (m3 + m4);
+        acc[0][1][r] = d + fmaf(-0.5f, m4, 2.f * m3);
+        acc[0][2][r] = s + fmaf(0.25f, m4, 4.f * m3);
+        acc[0][3][r] = (d + fmaf(-0.125f, m4, 8.f * m3)) + m5;
+    }
+    (void)t_loop;
+}
+
 // Software-pipelined main loop, one workgroup (4 waves, one per SIMD) per CU-resident tile:
 //   while the MFMAs of K-chunk c run out of LDS stage c&1, the global loads of chunk c+1 are
 //   in flight into registers; after the MFMAs they get their BatchNorm+ReLU and are written to
@@ -825,7 +1145,13 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a_in, const int tiles_
             }
         }
     }
-    if constexpr (C::WINO) {
+    if constexpr (C::WINO4) {
+#if defined(MVLM_CONV_TIMING)
+        wino4_main<C>(a, smem, tid, y0, x0, b0, co0, HWin, woff, acc, &t_loop);
+#else
+        wino4_main<C>(a, smem, tid, y0, x0, b0, co0, HWin, woff, acc, nullptr);
+#endif
+    } else if constexpr (C::WINO) {
 #if defined(MVLM_CONV_TIMING)
         wino_main<C>(a, smem, tid, y0, x0, b0, co0, HWin, woff, acc, &t_loop);
 #else
@@ -1627,6 +1953,8 @@ int check_variant(mvlm_ctx* ctx, ConvArgs& a, ConvGrid& g) {
                  "conv: a second input tensor (upsample + skip on the load) is served by the 128-channel 8x32 tile only");
     MVLM_REQUIRE(ctx, !C::WINO || (!a.up_in && !a.in2 && !a.amax_val && a.up_out != 2 && a.n_par == 1 && a.kparts <= 1),
                  "conv: the Winograd tiles serve plain, pooling and scattering 3x3 layers (no upsampled / second input, no fused argmax, no K parts)");
+    MVLM_REQUIRE(ctx, !C::WINO4 || (!a.up_in && !a.in2 && !a.amax_val && a.up_out != 2 && a.n_par == 1 && a.kparts <= 1),
+                 "conv: the F(4,3) Winograd tile serves plain, pooling and scattering 3x3 layers (no upsampled / second input, no fused argmax, no K parts)");
     MVLM_REQUIRE(ctx, a.W % C::TW == 0 && a.H % C::TRI == 0, "conv: spatial size not a multiple of the tile");
     MVLM_REQUIRE(ctx, !C::SPLITK || a.cin_pad % 32 == 0, "conv: split-K tiles need 32-channel chunks");
     MVLM_REQUIRE(ctx, !(C::SPLITK && C::NT > 1) || (a.kparts <= 1 && !a.amax_val), "conv: the two-column split-K tiles have no K-parts / argmax form");
@@ -1634,6 +1962,7 @@ int check_variant(mvlm_ctx* ctx, ConvArgs& a, ConvGrid& g) {
     MVLM_REQUIRE(ctx, a.cin_pad % C::CK == 0, "conv: cin_pad must be a multiple of the K-chunk");
     MVLM_REQUIRE(ctx, !a.pre_scale || a.cin_pad <= C::BN_MAXC, "conv: pre-activation BatchNorm supports up to 256 input channels");
     MVLM_REQUIRE(ctx, !C::WINO || a.cin_pad <= C::BN_MAXC, "conv: the Winograd tiles keep a BatchNorm pair of every input channel in LDS, with or without pre-activation (up to 256)");
+    MVLM_REQUIRE(ctx, !C::WINO4 || a.cin_pad <= C::BN_MAXC, "conv: the F(4,3) Winograd tile keeps a BatchNorm pair of every input channel in LDS, with or without pre-activation (up to 256)");
     if (C::TAIL4) MVLM_REQUIRE(ctx, a.up_out != 1 && (a.out || (a.amax_val && C::HAS_AMAX)), "conv: the 84-channel tile writes a plain (or parity) output tensor or argmax partials");
     if (C::TAIL16)
         MVLM_REQUIRE(ctx, !a.res1 && !a.res2 && !a.out_raw && !a.post_scale && a.up_out != 1 && !a.pool_out,
@@ -1674,7 +2003,8 @@ int check_variant(mvlm_ctx* ctx, ConvArgs& a, ConvGrid& g) {
 // applies to the current device's copy of the function; the ctx mutex held by every entry point guards the mask)
 template <class C>
 int set_variant_attributes(mvlm_ctx* ctx, int variant_id) {
-    if ((ctx->conv_attr_mask >> variant_id) & 1ull) return 0;
+    // (the F(4,3) tile is not a base id: a flag of its own, not a bit of the mask the base ids and the fast kernels share)
+    if (C::WINO4 ? ctx->conv_wino4_attr_set : bool((ctx->conv_attr_mask >> variant_id) & 1ull)) return 0;
     MVLM_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_mfma_kernel<C, false>),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, int(C::LDS_BYTES)));
     if constexpr (C::HAS_AMAX)
@@ -1686,7 +2016,10 @@ int set_variant_attributes(mvlm_ctx* ctx, int variant_id) {
     if constexpr (C::HAS_IN2)
         MVLM_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_mfma_kernel<C, false, true>),
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, int(C::LDS_BYTES)));
-    ctx->conv_attr_mask |= 1ull << variant_id;
+    if constexpr (C::WINO4)
+        ctx->conv_wino4_attr_set = true;
+    else
+        ctx->conv_attr_mask |= 1ull << variant_id;
     return 0;
 }
 

@@ -61,6 +61,7 @@
 #include "conv_tuned_net.h"
 #include "conv_pair_tuned.h"
 #include "conv_tuned_wino.h"
+#include "conv_tuned_wino4.h"
 
 // one launcher per variant, defined in conv_inst_g*.hip
 #define X(id, name, ...)                                         \
@@ -68,6 +69,9 @@
     int mvlm_conv_pair_launch_##id(mvlm_ctx* ctx, const ConvArgs& a0, const ConvArgs& a1);
 MVLM_CONV_VARIANTS(X)
 #undef X
+// The F(4,3) Winograd tile is not a base variant (conv_variants.h): its own code MVLM_CONV_VARIANT_WINO4 and this launcher, defined
+// in conv_inst_q0.hip.  A weak reference: a build without that translation unit has no such tile, and every question about it says no.
+int mvlm_conv_launch_wino4(mvlm_ctx* ctx, const ConvArgs& a) __attribute__((weak));
 
 namespace {
 
@@ -195,6 +199,18 @@ int wino_candidate(const ConvArgs& a) {
     return -1;
 }
 
+// Does the F(4,3) tile exist in this build and divide this layer?  (cin_pad <= BN_MAXC as for the F(2,3) tiles.)
+using Wino4Cfg = MVLM_CONV_WINO4_CFG;
+bool wino4_fits(int ksize, int cin_pad, int cout_pad, int H, int W) {
+    return mvlm_conv_launch_wino4 != nullptr && ksize == Wino4Cfg::KS && W % Wino4Cfg::TW == 0 && H % Wino4Cfg::TRI == 0 &&
+           cout_pad % Wino4Cfg::COUT_T == 0 && cin_pad % Wino4Cfg::CK == 0 && cin_pad <= Wino4Cfg::BN_MAXC;
+}
+// its code where it can serve this launch at all (shape and features, the launch's own transformed weights), or -1
+int wino4_candidate(const ConvArgs& a) {
+    if (!a.w_wino4 || a.up_in || a.in2 || a.amax_val || a.up_out == 2 || a.n_par != 1 || a.H != a.W) return -1;
+    return wino4_fits(a.ksize, a.cin_pad, a.cout_pad, a.H, a.W) ? MVLM_CONV_VARIANT_WINO4 : -1;
+}
+
 }  // namespace
 
 ConvKey mvlm_conv_key(const ConvArgs& a) {
@@ -204,6 +220,12 @@ ConvKey mvlm_conv_key(const ConvArgs& a) {
 bool mvlm_conv_variant_is_wino(int v) {
     const ConvVariantInfo* t = conv_variant(v);
     return t && t->WINO;
+}
+
+bool mvlm_conv_variant_is_wino4(int v) { return v == MVLM_CONV_VARIANT_WINO4; }
+
+bool mvlm_conv_wino4_serves_slot(int ksize, int cin_pad, int cout_pad) {
+    return wino4_fits(ksize, cin_pad, cout_pad, Wino4Cfg::TRI, Wino4Cfg::TW);  // (a slot has no size yet: asked at the tile's own)
 }
 
 bool mvlm_conv_wino_serves_slot(int ksize, int cin_pad, int cout_pad) {
@@ -217,13 +239,26 @@ bool mvlm_conv_wino_serves_slot(int ksize, int cin_pad, int cout_pad) {
 // Winograd routing of the exact path, a pure function of (shape, kind, batch) and the context's settings: a tuning override
 // that names a Winograd variant first; then mode 0 never, 2 wherever a variant can serve, 1 the measured table
 // (conv_tuned_wino.h: the Winograd launch beat what runs otherwise from `min_batch` views per device batch on).
+// The F(4,3) tile comes first, for a launch that carries its weights (ConvArgs::w_wino4) and while the Winograd mode is not 0:
+// F(4,3) mode 2 wherever the tile can serve, mode 1 its own measured table (conv_tuned_wino4.h) - consulted in Winograd mode 1
+// only, so that Winograd mode 2 stays "every layer on the F(2,3) tile" unless F(4,3) mode 2 asks otherwise.
 int mvlm_conv_wino_variant(const mvlm_ctx* ctx, const ConvArgs& a) {
     const int cand = wino_candidate(a);
-    if (cand < 0) return -1;
+    const int cand4 = wino4_candidate(a);
+    if (cand < 0 && cand4 < 0) return -1;
     const ConvKey k = mvlm_conv_key(a);
-    if (const ConvOverride* o = find_override(ctx, k)) return mvlm_conv_variant_is_wino(o->variant) ? o->variant : -1;
+    if (const ConvOverride* o = find_override(ctx, k))
+        return ((cand >= 0 && mvlm_conv_variant_is_wino(o->variant)) || (cand4 >= 0 && mvlm_conv_variant_is_wino4(o->variant))) ? o->variant : -1;
     const int mode = ctx ? ctx->conv_winograd : 1;
     if (mode == 0) return -1;
+    const int mode4 = ctx ? ctx->conv_winograd4 : 1;
+    if (cand4 >= 0 && mode4 == 2) return cand4;
+    if (cand4 >= 0 && mode4 == 1 && mode == 1)
+        for (int i = 0; i < MVLM_CONV_TUNED_WINO4_N; ++i) {
+            const ConvTunedWino4& e = MVLM_CONV_TUNED_WINO4[i];
+            if (e.cin_pad == k.cin_pad && e.cout_pad == k.cout_pad && e.size == k.size && e.kind == k.kind && k.batch >= e.min_batch) return e.variant;
+        }
+    if (cand < 0) return -1;
     if (mode == 2) return cand;
     for (int i = 0; i < MVLM_CONV_TUNED_WINO_N; ++i) {
         const ConvTunedWino& e = MVLM_CONV_TUNED_WINO[i];
@@ -255,6 +290,7 @@ int mvlm_conv_kparts_workspace(mvlm_ctx* ctx, float** ws, unsigned** cnt) {
 }
 
 const char* mvlm_conv_variant_name_impl(int v) {
+    if (v == MVLM_CONV_VARIANT_WINO4) return MVLM_CONV_WINO4_NAME;
     if (v == MVLM_CONV_VARIANT_FAST) return "conv3x3_bf16x3_t8x32";
     if (v == MVLM_CONV_VARIANT_FAST16) return "conv3x3_f16x2_t8x32";
     if (v >= 256) {
@@ -299,6 +335,7 @@ bool mvlm_conv_can_pool(const mvlm_ctx* ctx, const ConvArgs& a_in) {
 }
 
 bool mvlm_conv_variant_can_pool(int v) {
+    if (v == MVLM_CONV_VARIANT_WINO4) return Wino4Cfg::CAN_POOL_ANY;
     const ConvVariantInfo* t = conv_variant(v & 255);
     return t && t->CAN_POOL_ANY;
 }
@@ -387,6 +424,18 @@ int mvlm_launch_conv(mvlm_ctx* ctx, const ConvArgs& a, int* variant_out) {
     // conv_force_variant (mvlm_conv_bench only): >= 0 that variant, -2 the rules without the tuned table
     const int v = ctx->conv_force_variant >= 0 ? ctx->conv_force_variant
                   : ctx->conv_force_variant == -2 ? pick_variant(ctx, a, true) : route_variant(ctx, a);
+    if (v == MVLM_CONV_VARIANT_WINO4) {  // its own code: none of the base ids' arithmetic (id & 255, K parts) applies
+        MVLM_REQUIRE(ctx, mvlm_conv_launch_wino4 != nullptr, "conv: the F(4,3) Winograd tile is not part of this build");
+        MVLM_REQUIRE(ctx, a.w_wino4, "conv: the F(4,3) Winograd tile needs the layer's transformed weights (mvlm_pack_winograd4_weights)");
+        MVLM_REQUIRE(ctx, !a.in2, "conv: the F(4,3) Winograd tile has no second-input form");
+        MVLM_REQUIRE(ctx, !a.pool_out || px / 4 * a.pool_ctot < lim, "conv: pooled output exceeds 32-bit element offsets");
+        MVLM_REQUIRE(ctx, a.out || a.pool_out, "conv: no output requested");
+        if (variant_out) *variant_out = v;
+        ConvArgs b = a;
+        b.kparts = 1;
+        b.w = a.w_wino4;
+        return mvlm_conv_launch_wino4(ctx, b);  // (check_variant<> refuses what the tile cannot serve: shape, features)
+    }
     MVLM_REQUIRE(ctx, v >= 0, "conv: no kernel variant for this shape");
     const bool wino = mvlm_conv_variant_is_wino(v);
     MVLM_REQUIRE(ctx, !wino || a.w_wino, "conv: a Winograd tile needs the layer's transformed weights (mvlm_pack_winograd_weights)");
@@ -410,6 +459,7 @@ int mvlm_launch_conv(mvlm_ctx* ctx, const ConvArgs& a, int* variant_out) {
 // this shape and kind?  (kind 2: a tile that cannot pool in its epilogue is followed by the pool kernel; the 80- / 84-row tiles
 // serve conv6 / conv10 only)
 extern "C" int mvlm_conv_variant_serves(int variant, int ksize, int cin_pad, int cout_pad, int size, int kind) {
+    if (variant == MVLM_CONV_VARIANT_WINO4) return kind >= 0 && kind <= 2 && wino4_fits(ksize, cin_pad, cout_pad, size, size);
     if (variant < 0 || variant >= 1024 || ksize != 3 || kind < 0 || kind > 2) return 0;
     const ConvVariantInfo* t = conv_variant(variant & 255);
     if (!t || !tile_fits(*t, ksize, cin_pad, cout_pad, size, size)) return 0;
@@ -461,5 +511,27 @@ void mvlm_winograd_transform(const float* w9, int cin_pad, int cout_pad, float* 
 extern "C" int mvlm_pack_winograd_weights(const float* w9_host, int cin_pad, int cout_pad, float* w12_host) {
     if (!w9_host || !w12_host || cin_pad <= 0 || cout_pad <= 0) return 1;
     mvlm_winograd_transform(w9_host, cin_pad, cout_pad, w12_host);
+    return 0;
+}
+
+// The F(4,3) form on the points 0, 1, -1, 2, -1/2, inf: u0 = g0, u1 = -(g0 + g1 + g2) / 3, u2 = (g0 - g1 + g2) / 3,
+// u3 = (g0 + 2 g1 + 4 g2) / 15, u4 = (-16 g0 + 8 g1 - 4 g2) / 15, u5 = g2, likewise in float64 and rounded once; slice t * 3 + kx.
+void mvlm_winograd4_transform(const float* w9, int cin_pad, int cout_pad, float* w18) {
+    const size_t n = size_t(cin_pad) * cout_pad;
+    for (int kx = 0; kx < 3; ++kx)
+        for (size_t i = 0; i < n; ++i) {
+            const double g0 = w9[size_t(kx) * n + i], g1 = w9[size_t(3 + kx) * n + i], g2 = w9[size_t(6 + kx) * n + i];
+            w18[size_t(kx) * n + i] = float(g0);
+            w18[size_t(3 + kx) * n + i] = float(0.0 - (g0 + g1 + g2) / 3.0);  // (0 - x: a padded channel stays +0)
+            w18[size_t(6 + kx) * n + i] = float((g0 - g1 + g2) / 3.0);
+            w18[size_t(9 + kx) * n + i] = float((g0 + 2.0 * g1 + 4.0 * g2) / 15.0);
+            w18[size_t(12 + kx) * n + i] = float((-16.0 * g0 + 8.0 * g1 - 4.0 * g2) / 15.0);
+            w18[size_t(15 + kx) * n + i] = float(g2);
+        }
+}
+
+extern "C" int mvlm_pack_winograd4_weights(const float* w9_host, int cin_pad, int cout_pad, float* w18_host) {
+    if (!w9_host || !w18_host || cin_pad <= 0 || cout_pad <= 0) return 1;
+    mvlm_winograd4_transform(w9_host, cin_pad, cout_pad, w18_host);
     return 0;
 }

@@ -30,6 +30,12 @@ CASES = [  # name, cin, cout, size, k, batch, pre-BN, residual, bias+post-BN  (M
     ("winograd     256->128 @128 (w64)", 256, 128, 128, 3, 64, True, True, False, 40),
     ("winograd     128-> 64 @128 (w64)", 128, 64, 128, 3, 64, True, True, False, 40),
     ("winograd      64-> 64 @ 64 (w64)", 64, 64, 64, 3, 64, True, True, False, 40),
+    # the F(4,3) Winograd tile (variant code 2048, conv3x3q_c32_t16x32), forced
+    ("winograd4    256->128 @128 (q32)", 256, 128, 128, 3, 64, True, True, False, 2048),
+    ("winograd4    128-> 64 @128 (q32)", 128, 64, 128, 3, 64, True, True, False, 2048),
+    ("winograd4     64-> 64 @ 64 (q32)", 64, 64, 64, 3, 64, True, True, False, 2048),
+    ("winograd4     64-> 32 @256 (q32)", 64, 32, 256, 3, 64, True, True, False, 2048),
+    ("direct        64-> 32 @256 (c32)", 64, 32, 256, 3, 64, True, True, False, 3),
 ]
 
 

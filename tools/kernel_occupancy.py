@@ -4,7 +4,7 @@
     tools/kernel_occupancy.py            print the table
     tools/kernel_occupancy.py --write    rewrite tests/golden/kernel_occupancy.json (and kernel_occupancy_msaa.json,
                                          kernel_occupancy_vcolor.json, kernel_occupancy_wino.json,
-                                         kernel_occupancy_report.json) from the build
+                                         kernel_occupancy_wino4.json, kernel_occupancy_report.json) from the build
 
 A convolution tile's rate depends on how many workgroups a CU holds, i.e. on which side of 168 / 128 / 102 ... registers the
 compiler lands - and every epilogue kind compiled into a tile moves that number (round 4: two new kinds took the 80-row tile
@@ -14,7 +14,8 @@ committed table: fewer waves per SIMD or more spilled registers than recorded fa
 rasteriser's kernels are built into an object directory of their own (build/msaa/) with a table of their own,
 tests/golden/kernel_occupancy_msaa.json, held to the same rule by tests/test_msaa_occupancy.py; so are the tile kernels that
 shade with per-vertex colours (build/vcolor/, kernel_occupancy_vcolor.json, tests/test_vcolor_occupancy.py) and the Winograd convolution
-tiles (build/wino/, tests/golden/kernel_occupancy_wino.json, tests/test_winograd_occupancy.py) and the two kernels of the opt-in
+tiles (build/wino/, tests/golden/kernel_occupancy_wino.json, tests/test_winograd_occupancy.py), the F(4,3) Winograd tile
+(build/wino4/, tests/golden/kernel_occupancy_wino4.json, tests/test_winograd4_occupancy.py) and the two kernels of the opt-in
 landmark report (build/report/, tests/golden/kernel_occupancy_report.json, tests/test_report_occupancy.py)."""
 import json
 import re
@@ -29,6 +30,7 @@ TABLE = REPO / "tests" / "golden" / "kernel_occupancy.json"
 MSAA_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_msaa.json"
 VCOLOR_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_vcolor.json"
 WINO_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_wino.json"
+WINO4_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_wino4.json"
 REPORT_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_report.json"
 BUILD = REPO / "mvlm_amd" / "csrc" / "build"
 
@@ -73,7 +75,7 @@ def build_table(objdir: Path = BUILD) -> dict:
 
 if __name__ == "__main__":
     for table_path, objdir in ((TABLE, BUILD), (MSAA_TABLE, BUILD / "msaa"), (VCOLOR_TABLE, BUILD / "vcolor"),
-                                (WINO_TABLE, BUILD / "wino"), (REPORT_TABLE, BUILD / "report")):
+                                (WINO_TABLE, BUILD / "wino"), (WINO4_TABLE, BUILD / "wino4"), (REPORT_TABLE, BUILD / "report")):
         t = build_table(objdir)
         if "--write" in sys.argv:
             table_path.write_text(json.dumps({k: {"waves_per_simd": v["waves_per_simd"], "spilled": v["spilled"]} for k, v in t.items()}, indent=1) + "\n")
