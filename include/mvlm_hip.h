@@ -166,6 +166,34 @@ int mvlm_render_get_profile(mvlm_ctx* ctx, int32_t* n_views, int32_t* n_verts, i
  * (tile lists overflowed) of the renders since the last check */
 int mvlm_render_check(mvlm_ctx* ctx);
 
+/* ---- landmark view (replaces utils/viewer.py's offscreen window: VTKViewer(..., save=True), main.py:66-67) ---- */
+/* The mesh with a shaded sphere at every landmark, in a window of `size` x `size` pixels (a multiple of 16, 64..2048;
+ * n_views <= 128 and n_views * size * size <= 8 * 2048 * 2048 per call: 8 views at 2048, 32 at 1024, 128 up to 512) - a rasteriser object of its own beside mvlm_render, whose kernels,
+ * scratch and key planes it does not touch ("Landmark view"; build-defined, the viewer's arithmetic lives in VTK).
+ *   rot_host f64[n_views,9]     M = Ry*Rx*Rz per view, as mvlm_render takes them
+ *   frame_host f32[n_views,3]   cx, cy, half: the view-space point at the window's centre and the model units from the centre to
+ *                               the border (0, 0, 150 = the window the network sees)
+ *   landmarks_host f64[n_lm,3]  in the mesh's coordinates (NULL allowed when n_lm == 0); radius: the spheres', in model units
+ *   lm_rgb_host u8[n_lm,3]      a colour per landmark, NULL = blue (viewer.py:71)
+ *   out_dev u8[n_views,size,size,4]  RGBA, alpha 255, top row first
+ *   lm_pixels_dev i32[n_views,n_lm] or NULL: the pixels each landmark's sphere won in each view (0 = hidden there)
+ * The mesh is drawn by mvlm_render's one-sample contract with the window generalised, under the context's shading and
+ * sub-pixel-bits settings: at size 256 with the frame (0, 0, 150) and no landmarks the RGB bytes are 255 x mvlm_render's RGB
+ * planes.  It draws ONE sample per pixel: mvlm_set_render_multisamples does not apply to it.  The spheres are analytic under the
+ * orthographic camera, shaded by a head light (colour x height / radius), depth-tested against the mesh (they win ties; among
+ * spheres the nearer wins, the higher index on equal depth).
+ * A size or view count outside the range, a non-finite frame or half <= 0, a negative or non-finite radius, a non-finite landmark return an
+ * error and launch nothing.  Only enqueues work on the launch stream; a tile-list overflow is reported by mvlm_render_check. */
+int mvlm_render_landmark_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot_host, int n_views, int size,
+                              const float* frame_host /* [n_views,3]: cx, cy, half */,
+                              const double* landmarks_host /* [n_lm,3], may be NULL when n_lm == 0 */, int n_lm,
+                              float radius, const uint8_t* lm_rgb_host /* [n_lm,3] or NULL = blue */,
+                              uint8_t* out_dev /* [n_views,size,size,4] */, int32_t* lm_pixels_dev /* [n_views,n_lm] or NULL */);
+/* With mvlm_render_set_profiling on, the last landmark view's stages in milliseconds (HIP events), f32[7]: the copies and fills in
+ * front of the kernels (the key plane, 8 bytes per pixel, is filled in every call), transform, classify, scan, bin fill, landmark
+ * projection, tile.  Waits for the stream. */
+int mvlm_landmark_view_stage_ms(mvlm_ctx* ctx, float* ms7);
+
 /* ---- landmark network (replaces paulsenpredictor.py:89-110, :167-217) ------------ */
 /* blob/desc: output of mvlm_amd.weights.pack_for_device (BN folded, weights as
  * [tap][cin_pad][cout_pad]); copied to the device. */

@@ -4,8 +4,9 @@ Same behaviour as the reference's ``main.py`` (:9-67): collect ``*.obj`` files, 
 available pipeline over them and write ``<stem>_<pipeline>.txt`` (comma-separated [NL,3]
 landmarks, ``np.savetxt(..., delimiter=",")``, main.py:62; with ``--report`` also ``<stem>_<pipeline>_report.csv``, the
 per-landmark quality report of mvlm_amd/utils/report.py).  Only the pipelines whose 2-D
-predictor this build ships are looped ("bu3dfe", "dtu3d"); the viewer flags of the reference
-(``--visualize-iter`` / ``--visualize-img``) need VTK and are not available.
+predictor this build ships are looped ("bu3dfe", "dtu3d").  ``--visualize-img`` (main.py:66-67) writes
+``visualization/<stem>_<pipeline>.png`` under the working directory: the scan with a sphere at every landmark, drawn on the GPU
+(mvlm_amd/utils/viewer.py); the interactive viewer flag of the reference (``--visualize-iter``) needs VTK and is not available.
 """
 from __future__ import annotations
 
@@ -52,6 +53,11 @@ def build_parser() -> argparse.ArgumentParser:
                         help="write <stem>_<pipeline>_report.csv beside every landmark file: one row per landmark with the surviving "
                              "views, inliers, RANSAC branch, ray spread, snap distance, triangle, barycentric weights and uv "
                              "(lengths in the space the network sees; x,y,z in file coordinates; INTEGRATION.md)")
+    parser.add_argument("--visualize-img", action="store_true",
+                        help="write visualization/<stem>_<pipeline>.png under the working directory for every scan: the mesh with a "
+                             "sphere at every landmark (with --report the spheres are coloured by the RANSAC branch: blue inlier fit, "
+                             "orange fallback to all lines, red fewer than three lines)")
+    parser.add_argument("--visualize-size", type=int, default=1024, help="side of that picture in pixels (a multiple of 16, 64..2048)")
     return parser
 
 
@@ -92,6 +98,9 @@ def main(argv=None) -> int:
         extra["render_multisamples"] = args.multisamples
     if args.report:
         extra["landmark_report"] = True
+    if args.visualize_img:
+        extra["visualize_img"] = True
+        extra["visualize_size"] = args.visualize_size
     if args.config is not None:
         from . import config as mvlm_config
 
@@ -108,6 +117,7 @@ def main(argv=None) -> int:
         if args.seed is not None:
             np.random.seed(args.seed)
         dm = make()
+        dm.visualize_name = pname
         # ingest of the next scans overlaps the GPU work
         for file, landmarks in dm.predict_files(obj_files, batch_scans=args.batch_scans):
             print(f"Current file: {file}")

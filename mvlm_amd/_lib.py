@@ -52,6 +52,9 @@ SIGNATURES = {
     "mvlm_jpeg_decode": (C.c_int, [C.c_void_p, c_uint8_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int)]),
     "mvlm_render": (C.c_int, [C.c_void_p, C.c_void_p, c_double_p, C.c_int, C.c_void_p]),
     "mvlm_render_check": (C.c_int, [C.c_void_p]),
+    "mvlm_render_landmark_view": (C.c_int, [C.c_void_p, C.c_void_p, c_double_p, C.c_int, C.c_int, c_float_p, c_double_p, C.c_int,
+                                            C.c_float, c_uint8_p, C.c_void_p, C.c_void_p]),
+    "mvlm_landmark_view_stage_ms": (C.c_int, [C.c_void_p, c_float_p]),
     "mvlm_render_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),
     "mvlm_render_get_profile": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p, c_int32_p, c_float_p, C.c_int]),
     "mvlm_render_rotations_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),

@@ -5,7 +5,10 @@
 
 #include <memory>
 
+#include <cmath>
+
 #include "common.h"
+#include "raster_view_math.h"
 
 void* mvlm_ctx::get_scratch(const char* name, size_t bytes) {
     auto& e = scratch[name];
@@ -78,6 +81,8 @@ extern "C" void mvlm_ctx_destroy(mvlm_ctx* ctx) {
     for (auto e : ctx->cnn.event_pool)
         if (e) hipEventDestroy(e);
     for (auto e : ctx->render_events)
+        if (e) hipEventDestroy(e);
+    for (auto e : ctx->view_events)
         if (e) hipEventDestroy(e);
     for (auto e : ctx->cnn.sync_events)
         if (e) hipEventDestroy(e);
@@ -876,4 +881,51 @@ extern "C" int mvlm_conv_pair_bench(mvlm_ctx* ctx, int batch, int cin, int cout,
     if (e1) hipEventDestroy(e1);
     ctx->conv_force_variant = saved;
     return rc;
+}
+
+// ---- landmark view (raster_view.hip; DESIGN.md 5.1, "Landmark view") ---------------------------------------------------
+// Checks the arguments - a bad one returns an error and launches nothing - and hands the launch set to raster_view.hip.
+extern "C" int mvlm_render_landmark_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot_host, int n_views, int size,
+                                         const float* frame_host, const double* landmarks_host, int n_lm, float radius,
+                                         const uint8_t* lm_rgb_host, uint8_t* out_dev, int32_t* lm_pixels_dev) {
+    MVLM_ENTER(ctx);
+    MVLM_REQUIRE(ctx, mesh && rot_host && frame_host && out_dev && n_views > 0, "landmark view: bad arguments");
+    MVLM_REQUIRE(ctx, mesh->n_verts > 0 && mesh->n_tris > 0, "landmark view: empty mesh");
+    MVLM_REQUIRE(ctx, size >= RV_MIN_SIZE && size <= RV_MAX_SIZE && size % RM_TILE == 0,
+                 "landmark view: size must be a multiple of 16 in 64..2048 (" + std::to_string(size) + " given)");
+    MVLM_REQUIRE(ctx, n_views <= RV_MAX_VIEWS, "landmark view: at most 128 views per call (" + std::to_string(n_views) + " given)");
+    MVLM_REQUIRE(ctx, (long long)n_views * size * size <= RV_MAX_PIXELS,
+                 "landmark view: n_views * size * size exceeds 8 * 2048 * 2048 pixels per call");
+    MVLM_REQUIRE(ctx, n_lm >= 0 && (n_lm == 0 || landmarks_host), "landmark view: landmarks missing");
+    MVLM_REQUIRE(ctx, std::isfinite(radius) && radius >= 0.0f, "landmark view: the radius must be finite and >= 0");
+    for (int k = 0; k < n_views * 9; ++k) MVLM_REQUIRE(ctx, std::isfinite(rot_host[k]), "landmark view: non-finite rotation");
+    std::vector<float> frames(size_t(n_views) * 4);
+    for (int v = 0; v < n_views; ++v) {
+        const float cx = frame_host[3 * v], cy = frame_host[3 * v + 1], half = frame_host[3 * v + 2];
+        MVLM_REQUIRE(ctx, std::isfinite(cx) && std::isfinite(cy) && std::isfinite(half) && half > 0.0f,
+                     "landmark view: a frame needs finite cx, cy and half > 0");
+        const float k = rv_scale(size, half);
+        MVLM_REQUIRE(ctx, std::isfinite(k) && k > 0.0f, "landmark view: half is too small or too large for this size");
+        frames[4 * v] = cx;
+        frames[4 * v + 1] = cy;
+        frames[4 * v + 2] = half;
+        frames[4 * v + 3] = k;
+    }
+    for (int k = 0; k < n_lm * 3; ++k) MVLM_REQUIRE(ctx, std::isfinite(landmarks_host[k]), "landmark view: non-finite landmark");
+    if (mvlm_mesh_wait_ready(ctx, mesh, ctx->stream)) return 1;  // the upload runs on a stream of its own
+    return mvlm_launch_landmark_view(ctx, mesh, rot_host, n_views, size, frames.data(), landmarks_host, n_lm, radius, lm_rgb_host,
+                                     out_dev, lm_pixels_dev);
+}
+
+// Milliseconds of the last landmark view's stages (copies and fills - the key plane's among them -, transform, classify, scan,
+// bin fill, landmark projection, tile) while
+// mvlm_render_set_profiling is on; waits for the stream.
+extern "C" int mvlm_landmark_view_stage_ms(mvlm_ctx* ctx, float* ms7) {
+    MVLM_ENTER(ctx);
+    MVLM_REQUIRE(ctx, ms7, "landmark_view_stage_ms: null pointer");
+    MVLM_REQUIRE(ctx, ctx->view_events_valid && ctx->view_events.size() >= 8,
+                 "landmark_view_stage_ms: no landmark view was drawn with render profiling on");
+    MVLM_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < 7; ++k) MVLM_CHECK_HIP(ctx, hipEventElapsedTime(&ms7[k], ctx->view_events[k], ctx->view_events[k + 1]));
+    return 0;
 }

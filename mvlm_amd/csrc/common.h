@@ -289,6 +289,10 @@ struct mvlm_ctx {
     std::vector<RenderProfileRec> render_prof;
     std::vector<hipEvent_t> render_events;
     size_t render_event_cursor = 0;
+    // landmark view (raster_view.hip): the eight events around its seven stages (copies and fills first) while render_profiling is on, and whether the
+    // last view recorded them (mvlm_landmark_view_stage_ms)
+    std::vector<hipEvent_t> view_events;
+    bool view_events_valid = false;
     // device buffers of freed meshes, reused by the next upload: a folder of scans would otherwise pay
     // four hipMalloc + four (device-synchronising) hipFree per scan
     struct PoolEntry {
@@ -403,6 +407,11 @@ int mvlm_launch_conv_fast(mvlm_ctx* ctx, const ConvArgs& a, const unsigned short
 constexpr int MVLM_CONV_VARIANT_WINO4 = 2048;
 constexpr int MVLM_CONV_VARIANT_FAST = 62;    // id reported for launches of the bf16x3 kernel
 constexpr int MVLM_CONV_VARIANT_FAST16 = 61;  // ... of the f16x2 kernel
+
+// raster_view.hip: the launch set of mvlm_render_landmark_view (api.hip checks the arguments and holds the context)
+int mvlm_launch_landmark_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot_host, int n_views, int size,
+                              const float* frames_host, const double* landmarks_host, int n_lm, float radius,
+                              const uint8_t* lm_rgb_host, uint8_t* out_dev, int32_t* lm_pixels_dev);
 
 // surface.hip: passes 0 and 1 of the surface snap (bound, de-indexed triangles, per-chunk winners in the context's scratch)
 // for an entry point that holds the context; its final kernel follows (mvlm_project_to_surface, mvlm_surface_attach)

@@ -1,0 +1,406 @@
+// The landmark view (mvlm_render_landmark_view): the reference's offscreen viewer (utils/viewer.py with save=True - the mesh
+// and a sphere at every landmark in one window) as a rasteriser object of its own beside the network's 256 x 256 one.  The
+// window has a side S of 64..2048 pixels and a frame per view; the mesh is drawn by the one-sample contract of raster_math.h
+// with that window (raster_view_math.h), the spheres analytically, depth-tested against the mesh ("Landmark
+// view").  One sample per pixel: the context's multisample setting does not apply here.
+//
+// Structure as raster.hip, with runtime tile counts ((S / 16)^2, up to 16 384 per view):
+//   1. transform   one thread per (view, vertex)
+//   2. classify    one thread per (view, triangle): boxes of <= 128 pixel centres (VIEW_SMALL_PIXELS) resolved with the 64-bit atomicMin of the
+//                  (depth, id) key, larger ones counted into 16 x 16 tiles and appended to the view's big list, one atomic per wave
+//   3. scan        one workgroup per view over its tile counters
+//   4. bin fill    big triangles' ids into the per-tile lists
+//   5. project     one thread per (view, landmark): window position, depth, radius in pixels, colour, pixel box - 32 bytes
+//   6. tile        one workgroup per (view, tile), a thread per pixel: resolves and shades the mesh as tile_body does, then
+//                  compacts the spheres whose box touches the tile into an LDS list (ballots, VIEW_SPHERE_CAP candidates a
+//                  round, any number of rounds), every pixel walks the list; the winners' pixel counts are summed per tile in
+//                  LDS and added to the global counts with one atomic per (tile, landmark) that is non-zero.
+// Only the 64-bit edge functions are used (the 24-bit ones of raster_tile.h give the same integers).  The key plane
+// ("view.keys", 32 MB per view at S = 2048) is filled inside every call.
+#include "raster_common.h"
+#include "raster_view_math.h"
+
+namespace {
+
+static_assert(sizeof(rv_sphere) == 32 && alignof(rv_sphere) == 16, "the tile kernel moves a sphere as two 16-byte words");
+// A triangle whose pixel-centre box holds at most this many pixels is resolved by classify's atomics, not binned.  Larger than
+// raster.hip's 16: the bench mesh's triangles span 5 x 5 pixel centres in a 1024^2 window and 10 x 10 at 2048^2, and with all of
+// them binned every pixel of a tile walked ~55 triangles through the 64-bit edge functions - 353 of the view's 450 us at 1024^2
+// (profiles/landmark_view_time.txt).  The key makes the image independent of which path a triangle takes.
+constexpr int VIEW_SMALL_PIXELS = 128;
+constexpr int VIEW_SPHERE_CAP = 256;   // spheres in a tile's LDS list at a time: one candidate per thread and round
+constexpr int VIEW_COUNT_SPAN = 1024;  // landmarks whose per-tile pixel counts are held in LDS at a time
+
+struct view_frame {  // per view: the window's centre in view space, model units from centre to border, pixels per model unit
+    float cx, cy, half, k;
+};
+
+__global__ void view_transform_kernel(const float* __restrict__ verts, int n_verts, const double* __restrict__ rot,
+                                      const view_frame* __restrict__ frames, int n_views, int sub_bits,
+                                      vert12* __restrict__ tv) {
+    int view, chunk;
+    if (!view_chunk((n_verts + 255) / 256, n_views, &view, &chunk)) return;
+    const int v = chunk * 256 + int(threadIdx.x);
+    if (v >= n_verts) return;
+    double m[9];
+    for (int k = 0; k < 9; ++k) m[k] = rot[view * 9 + k];
+    const view_frame f = frames[view];
+    const rm_vert o = rv_transform(m, verts[3 * v], verts[3 * v + 1], verts[3 * v + 2], sub_bits, f.cx, f.cy, f.half, f.k);
+    vert12 w;
+    w.X = o.X;
+    w.Y = o.Y;
+    w.z = o.z;
+    tv[size_t(view) * n_verts + v] = w;
+}
+
+__device__ inline rm_tri view_load_tri(const vert12* tvv, const int32_t* tris, int t, int size) {
+    return rv_setup(load_vert(tvv, tris[3 * t]), load_vert(tvv, tris[3 * t + 1]), load_vert(tvv, tris[3 * t + 2]), size);
+}
+
+// cull / resolve small boxes with atomics / count big ones into tiles; true for a big triangle (classify_one of raster.hip)
+__device__ inline bool view_classify_one(int view, int t, const rm_vert& va, const rm_vert& vb, const rm_vert& vc, int size,
+                                         unsigned long long* __restrict__ keys, int* __restrict__ counts) {
+    const rm_tri tr = rv_setup(va, vb, vc, size);
+    if (!tr.valid) return false;
+    const int w = tr.ix1 - tr.ix0 + 1, h = tr.iy1 - tr.iy0 + 1;
+    if (w * h <= VIEW_SMALL_PIXELS) {
+        unsigned long long* kv = keys + size_t(view) * size * size;
+        for (int j = tr.iy0; j <= tr.iy1; ++j)
+            for (int ii = tr.ix0; ii <= tr.ix1; ++ii) {
+                float b0, b1, b2;
+                if (!rm_cover(&tr, ii, j, &b0, &b1, &b2)) continue;
+                const float z = rm_interp(b0, b1, b2, tr.z0, tr.z1, tr.z2);
+                if (!(z >= 0.0f && z <= 1.0f)) continue;  // near / far clip
+                atomicMin(&kv[size_t(j) * size + ii], (unsigned long long)rm_key(z, uint32_t(t)));
+            }
+        return false;
+    }
+    const int tiles_x = size / RM_TILE;
+    const int tx0 = tr.ix0 / RM_TILE, tx1 = tr.ix1 / RM_TILE, ty0 = tr.iy0 / RM_TILE, ty1 = tr.iy1 / RM_TILE;
+    for (int ty = ty0; ty <= ty1; ++ty)
+        for (int tx = tx0; tx <= tx1; ++tx) atomicAdd(&counts[size_t(view) * tiles_x * tiles_x + ty * tiles_x + tx], 1);
+    return true;
+}
+
+__global__ __launch_bounds__(256) void view_classify_kernel(const vert12* __restrict__ tv, const int32_t* __restrict__ tris,
+                                                            int n_verts, int n_tris, int n_views, int size,
+                                                            unsigned long long* __restrict__ keys, int* __restrict__ counts,
+                                                            int* __restrict__ n_big, int* __restrict__ big_list) {
+    int view, chunk;
+    if (!view_chunk((n_tris + 255) / 256, n_views, &view, &chunk)) return;
+    const vert12* const tvv = tv + size_t(view) * n_verts;
+    const int t = chunk * 256 + int(threadIdx.x);
+    const int tt = t < n_tris ? t : 0;
+    const rm_vert va = load_vert(tvv, tris[3 * tt]), vb = load_vert(tvv, tris[3 * tt + 1]), vc = load_vert(tvv, tris[3 * tt + 2]);
+    const int lane = int(threadIdx.x) & 63;
+    const bool big = t < n_tris && view_classify_one(view, t, va, vb, vc, size, keys, counts);
+    const unsigned long long m = __ballot(big);
+    if (m) {  // (wave-uniform) one atomic per wave appends its big triangles
+        const int leader = __ffsll(static_cast<long long>(m)) - 1;
+        int base = 0;
+        if (lane == leader) base = atomicAdd(&n_big[view], __popcll(m));
+        base = __shfl(base, leader);
+        if (big) big_list[size_t(view) * n_tris + base + __popcll(m & ((1ull << lane) - 1ull))] = t;
+    }
+}
+
+// exclusive prefix sum over a view's tile counters (up to 16 384): a thread sums its run of `per` counters, the 256 run sums
+// are scanned in LDS, the thread writes its run's offsets.  The sums are 64-bit - 16 384 tiles times the triangles of a folded
+// or badly scaled mesh that all span the window pass 2^31 - and an offset is stored saturated at `cap`: a list beyond the
+// capacity is empty (the tile kernel's min(count, cap - offset)), never in front of the buffer.
+__global__ __launch_bounds__(256) void view_scan_kernel(const int* __restrict__ counts, int* __restrict__ offsets, int tiles,
+                                                        int cap, int* __restrict__ overflow) {
+    __shared__ long long s[256];
+    const int view = blockIdx.x, t = threadIdx.x;
+    const int per = (tiles + 255) / 256, lo = min(t * per, tiles), hi = min(lo + per, tiles);
+    const int* const c = counts + size_t(view) * tiles;
+    long long sum = 0;
+    for (int q = lo; q < hi; ++q) sum += c[q];
+    s[t] = sum;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {
+        const long long v = t >= d ? s[t - d] : 0;
+        __syncthreads();
+        s[t] += v;
+        __syncthreads();
+    }
+    long long run = s[t] - sum;
+    for (int q = lo; q < hi; ++q) {
+        offsets[size_t(view) * tiles + q] = int(run < cap ? run : cap);
+        run += c[q];
+    }
+    if (t == 255 && s[t] > cap) *overflow = 1;
+}
+
+__global__ void view_bin_fill_kernel(const vert12* __restrict__ tv, const int32_t* __restrict__ tris, int n_verts, int n_tris,
+                                     int n_views, int size, const int* __restrict__ n_big, const int* __restrict__ big_list,
+                                     const int* __restrict__ offsets, int* __restrict__ cursors, int* __restrict__ bins, int cap,
+                                     int* __restrict__ overflow) {
+    int view, wg;
+    if (!view_chunk(FILL_WGS, n_views, &view, &wg)) return;
+    const int n = n_big[view];
+    const int tiles_x = size / RM_TILE;
+    for (int k = wg * 256 + int(threadIdx.x); k < n; k += FILL_WGS * 256) {
+        const int t = big_list[size_t(view) * n_tris + k];
+        const rm_tri tr = view_load_tri(tv + size_t(view) * n_verts, tris, t, size);
+        const int tx0 = tr.ix0 / RM_TILE, tx1 = tr.ix1 / RM_TILE, ty0 = tr.iy0 / RM_TILE, ty1 = tr.iy1 / RM_TILE;
+        for (int ty = ty0; ty <= ty1; ++ty)
+            for (int tx = tx0; tx <= tx1; ++tx) {
+                const size_t tile = size_t(view) * tiles_x * tiles_x + ty * tiles_x + tx;
+                const int pos = offsets[tile] + atomicAdd(&cursors[tile], 1);
+                if (pos >= 0 && pos < cap)
+                    bins[size_t(view) * cap + pos] = t;
+                else
+                    *overflow = 1;
+            }
+    }
+}
+
+__global__ void view_project_kernel(const double* __restrict__ landmarks, const uint8_t* __restrict__ lm_rgb, int n_lm,
+                                    const double* __restrict__ rot, const view_frame* __restrict__ frames, int n_views, int size,
+                                    float radius, rv_sphere* __restrict__ spheres) {
+    const int q = blockIdx.x * 256 + int(threadIdx.x);
+    if (q >= n_views * n_lm) return;
+    const int view = q / n_lm, l = q % n_lm;
+    double m[9], p[3];
+    for (int k = 0; k < 9; ++k) m[k] = rot[view * 9 + k];
+    for (int k = 0; k < 3; ++k) p[k] = landmarks[3 * l + k];
+    const view_frame f = frames[view];
+    const uint32_t rgb = lm_rgb ? uint32_t(lm_rgb[3 * l]) | (uint32_t(lm_rgb[3 * l + 1]) << 8) | (uint32_t(lm_rgb[3 * l + 2]) << 16)
+                                : 0xFF0000u;  // blue (viewer.py:71)
+    spheres[q] = rv_project_landmark(m, p, f.cx, f.cy, f.half, f.k, radius, rgb, size);
+}
+
+__global__ __launch_bounds__(256) void view_tile_kernel(
+    const vert12* __restrict__ tv, const int32_t* __restrict__ tris, const float* __restrict__ uvs, const uint8_t* __restrict__ tex,
+    int tex_w, int tex_h, const uchar4* __restrict__ colors, int n_verts, const int* __restrict__ counts,
+    const int* __restrict__ offsets, const int* __restrict__ bins, int cap, const unsigned long long* __restrict__ keys,
+    const view_frame* __restrict__ frames, int shading, int n_views, int size, const rv_sphere* __restrict__ spheres, int n_lm,
+    int* __restrict__ lm_pixels, const int* __restrict__ overflow, int* __restrict__ overflow_host, uint32_t* __restrict__ out) {
+    __shared__ rm_tri s_tri[256];
+    __shared__ int s_id[256];
+    __shared__ rv_sphere s_sph[VIEW_SPHERE_CAP];
+    __shared__ int s_sph_id[VIEW_SPHERE_CAP];
+    __shared__ int s_wave[4];
+    __shared__ int s_cnt[VIEW_COUNT_SPAN];
+    const int tiles_x = size / RM_TILE, tiles = tiles_x * tiles_x;
+    int view, tile;
+    if (!view_chunk(tiles, n_views, &view, &tile)) return;
+    const size_t vt = size_t(view) * tiles + tile;
+    const int tid = threadIdx.x;
+    const int tx0 = (tile % tiles_x) * RM_TILE, ty0 = (tile / tiles_x) * RM_TILE;
+    const int i = tx0 + (tid & (RM_TILE - 1));
+    const int j = ty0 + (tid >> 4);
+    const vert12* const tvv = tv + size_t(view) * n_verts;
+    const int n = min(counts[vt], cap - offsets[vt]);
+    const int* const list = bins + size_t(view) * cap + offsets[vt];
+    const view_frame frame = frames[view];
+
+    uint64_t best = keys[(size_t(view) * size + j) * size + i];  // what the small triangles left
+    if (blockIdx.x == 0 && tid == 0) {  // the overflow flag of the kernels before this one, to the host's pinned word
+        __atomic_store_n(overflow_host, *overflow, __ATOMIC_RELAXED);
+        __threadfence_system();
+    }
+
+    // ---- the tile's big triangles, set up into LDS a chunk at a time ----
+    for (int base = 0; base < n; base += 256) {
+        const int m = min(256, n - base);
+        __syncthreads();
+        if (tid < m) {
+            const int t = list[base + tid];
+            s_id[tid] = t;
+            s_tri[tid] = view_load_tri(tvv, tris, t, size);
+        }
+        __syncthreads();
+        for (int k = 0; k < m; ++k) {
+            const rm_tri* t = &s_tri[k];
+            if (i < t->ix0 || i > t->ix1 || j < t->iy0 || j > t->iy1) continue;
+            float b0, b1, b2;
+            if (!rm_cover(t, i, j, &b0, &b1, &b2)) continue;
+            const float z = rm_interp(b0, b1, b2, t->z0, t->z1, t->z2);
+            if (!(z >= 0.0f && z <= 1.0f)) continue;  // near / far clip
+            const uint64_t key = rm_key(z, uint32_t(s_id[k]));
+            best = key < best ? key : best;
+        }
+    }
+
+    // ---- shade the mesh's winner: the byte mvlm_render divides by 255 ----
+    uint32_t rgb = 0xFFFFFFu;  // white background
+    float zbest = INFINITY;    // depth the spheres are tested against: +inf where no triangle covers the pixel
+    if (best != RM_KEY_EMPTY) {
+        const int t = int(rm_key_tri(best));
+        int a = tris[3 * t], b = tris[3 * t + 1], c = tris[3 * t + 2];
+        const rm_tri tr = rv_setup(load_vert(tvv, a), load_vert(tvv, b), load_vert(tvv, c), size);
+        float b0 = 0.f, b1 = 0.f, b2 = 0.f;
+        rm_cover(&tr, i, j, &b0, &b1, &b2);
+        if (tr.swapped) {
+            const int s = b;
+            b = c;
+            c = s;
+        }
+        if (shading == 1) {
+            const uint32_t g = uint32_t(rv_geometry_u8(&tr, rv_geometry_kz(size, frame.half)));
+            rgb = g | (g << 8) | (g << 16);
+        } else if (colors) {
+            const uchar4 c0 = colors[a], c1 = colors[b], c2 = colors[c];
+            const int r = rm_color_u8(rm_interp(0.f, b1, b2, float(c0.x) / 255.0f, float(c1.x) / 255.0f, float(c2.x) / 255.0f));
+            const int g = rm_color_u8(rm_interp(0.f, b1, b2, float(c0.y) / 255.0f, float(c1.y) / 255.0f, float(c2.y) / 255.0f));
+            const int bl = rm_color_u8(rm_interp(0.f, b1, b2, float(c0.z) / 255.0f, float(c1.z) / 255.0f, float(c2.z) / 255.0f));
+            rgb = uint32_t(r) | (uint32_t(g) << 8) | (uint32_t(bl) << 16);
+        } else if (tex && uvs) {
+            const float u = rm_interp(b0, b1, b2, uvs[2 * a], uvs[2 * b], uvs[2 * c]);
+            const float v = rm_interp(b0, b1, b2, uvs[2 * a + 1], uvs[2 * b + 1], uvs[2 * c + 1]);
+            // one (unaligned) 4-byte load per texel: the buffer carries 4 spare bytes behind the last one (api.hip)
+            uint32_t texel;
+            __builtin_memcpy(&texel, tex + size_t(rm_texel(u, v, tex_w, tex_h)) * 3, 4);
+            rgb = texel & 0xFFFFFFu;
+        }
+        zbest = rm_key_z(best);
+    }
+
+    // ---- spheres: drawn after the mesh (they win ties), in landmark order (the later one wins an equal depth) ----
+    int win = -1;
+    for (int base = 0; base < n_lm; base += VIEW_SPHERE_CAP) {
+        const int cand = base + tid;
+        bool touch = false;
+        uint4 w0 = make_uint4(0, 0, 0, 0), w1 = w0;  // the record as two 16-byte words: X Y z R | rgb, x box, y box, pad
+        if (cand < n_lm) {
+            const uint4* const src = reinterpret_cast<const uint4*>(spheres + size_t(view) * n_lm + cand);
+            w0 = src[0];
+            w1 = src[1];
+            const int ix0 = short(w1.y & 0xFFFFu), ix1 = short(w1.y >> 16), iy0 = short(w1.z & 0xFFFFu), iy1 = short(w1.z >> 16);
+            touch = ix0 <= tx0 + RM_TILE - 1 && ix1 >= tx0 && iy0 <= ty0 + RM_TILE - 1 && iy1 >= ty0;
+        }
+        const unsigned long long m = __ballot(touch);
+        const int wave = tid >> 6, lane = tid & 63;
+        __syncthreads();  // (the previous round's walk is over)
+        if (lane == 0) s_wave[wave] = __popcll(m);
+        __syncthreads();
+        int off = 0, total = 0;
+        for (int w = 0; w < 4; ++w) {
+            off += w < wave ? s_wave[w] : 0;
+            total += s_wave[w];
+        }
+        if (touch) {
+            const int pos = off + __popcll(m & ((1ull << lane) - 1ull));
+            uint4* const dst = reinterpret_cast<uint4*>(&s_sph[pos]);
+            dst[0] = w0;
+            dst[1] = w1;
+            s_sph_id[pos] = cand;
+        }
+        __syncthreads();
+        for (int q = 0; q < total; ++q) {
+            float zs, shade;
+            if (!rv_sphere_fragment(&s_sph[q], i, j, frame.k, &zs, &shade)) continue;
+            if (!(zs <= zbest)) continue;
+            zbest = zs;
+            win = s_sph_id[q];
+            rgb = rv_sphere_colour(s_sph[q].rgb, shade);
+        }
+    }
+
+    // RGBA, alpha 255, top row first: one aligned 4-byte store per pixel
+    out[(size_t(view) * size + (size - 1 - j)) * size + i] = rgb | 0xFF000000u;
+
+    // ---- pixels each landmark's sphere won in this tile ----
+    if (lm_pixels && n_lm > 0 && __syncthreads_or(win >= 0)) {
+        for (int base = 0; base < n_lm; base += VIEW_COUNT_SPAN) {
+            for (int q = tid; q < VIEW_COUNT_SPAN; q += 256) s_cnt[q] = 0;
+            __syncthreads();
+            if (win >= base && win < base + VIEW_COUNT_SPAN) atomicAdd(&s_cnt[win - base], 1);
+            __syncthreads();
+            for (int q = tid; q < VIEW_COUNT_SPAN && base + q < n_lm; q += 256)
+                if (s_cnt[q]) atomicAdd(&lm_pixels[size_t(view) * n_lm + base + q], s_cnt[q]);
+            __syncthreads();
+        }
+    }
+}
+
+}  // namespace
+
+// The launch set of one landmark view, for an entry point that holds the context and has checked its arguments (api.hip:
+// mvlm_render_landmark_view).  frames_host f32[n_views,4]: cx, cy, half, k = rv_scale(size, half).
+int mvlm_launch_landmark_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot_host, int n_views, int size,
+                              const float* frames_host, const double* landmarks_host, int n_lm, float radius,
+                              const uint8_t* lm_rgb_host, uint8_t* out_dev, int32_t* lm_pixels_dev) {
+    const int V = mesh->n_verts, T = mesh->n_tris;
+    const int tiles_x = size / RM_TILE, tiles = tiles_x * tiles_x;
+    const int cap = 4 * T + 8 * tiles;  // tile-list entries per view; larger lists raise an error (mvlm_render_check)
+    const size_t n_ctr = size_t(n_views) * tiles;
+    const size_t ctr_ints = 2 * n_ctr + n_views + 4;  // counts | cursors | n_big | overflow: one memset clears them
+    const size_t key_bytes = size_t(n_views) * size * size * sizeof(unsigned long long);
+    auto* tv = static_cast<vert12*>(ctx->get_scratch("view.tv", size_t(n_views) * V * sizeof(vert12)));
+    auto* rot = static_cast<double*>(ctx->get_scratch("view.rot", size_t(n_views) * 9 * sizeof(double)));
+    auto* frames = static_cast<view_frame*>(ctx->get_scratch("view.frames", size_t(n_views) * sizeof(view_frame)));
+    auto* ctr = static_cast<int*>(ctx->get_scratch("view.ctr", ctr_ints * sizeof(int)));
+    auto* offsets = static_cast<int*>(ctx->get_scratch("view.off", n_ctr * sizeof(int)));
+    auto* bins = static_cast<int*>(ctx->get_scratch("view.bins", size_t(n_views) * cap * sizeof(int)));
+    auto* big_list = static_cast<int*>(ctx->get_scratch("view.big", size_t(n_views) * T * sizeof(int)));
+    auto* keys = static_cast<unsigned long long*>(ctx->get_scratch("view.keys", key_bytes));
+    MVLM_REQUIRE(ctx, tv && rot && frames && ctr && offsets && bins && big_list && keys, "landmark view: scratch allocation failed");
+    double* lm = nullptr;
+    uint8_t* lm_rgb = nullptr;
+    rv_sphere* spheres = nullptr;
+    if (n_lm > 0) {
+        lm = static_cast<double*>(ctx->get_scratch("view.lm", size_t(n_lm) * 3 * sizeof(double)));
+        spheres = static_cast<rv_sphere*>(ctx->get_scratch("view.spheres", size_t(n_views) * n_lm * sizeof(rv_sphere)));
+        MVLM_REQUIRE(ctx, lm && spheres, "landmark view: scratch allocation failed");
+        if (lm_rgb_host) {
+            lm_rgb = static_cast<uint8_t*>(ctx->get_scratch("view.lm_rgb", size_t(n_lm) * 3));
+            MVLM_REQUIRE(ctx, lm_rgb, "landmark view: scratch allocation failed");
+        }
+    }
+    int* counts = ctr;
+    int* cursors = ctr + n_ctr;
+    int* n_big = ctr + 2 * n_ctr;
+    int* overflow = n_big + n_views;
+    hipStream_t st = ctx->stream;
+    // mvlm_render_set_profiling: events between the stages, the first in front of the copies and fills (mvlm_landmark_view_stage_ms)
+    hipEvent_t* ev = nullptr;
+    if (ctx->render_profiling) {
+        if (ctx->view_events.size() < 8) ctx->view_events.resize(8, nullptr);
+        for (hipEvent_t& e : ctx->view_events)
+            if (!e) MVLM_CHECK_HIP(ctx, hipEventCreate(&e));
+        ev = ctx->view_events.data();
+    }
+    ctx->view_events_valid = false;
+    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[0], st));
+    MVLM_CHECK_HIP(ctx, hipMemcpyAsync(rot, rot_host, size_t(n_views) * 9 * sizeof(double), hipMemcpyHostToDevice, st));
+    MVLM_CHECK_HIP(ctx, hipMemcpyAsync(frames, frames_host, size_t(n_views) * sizeof(view_frame), hipMemcpyHostToDevice, st));
+    if (n_lm > 0) {
+        MVLM_CHECK_HIP(ctx, hipMemcpyAsync(lm, landmarks_host, size_t(n_lm) * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+        if (lm_rgb) MVLM_CHECK_HIP(ctx, hipMemcpyAsync(lm_rgb, lm_rgb_host, size_t(n_lm) * 3, hipMemcpyHostToDevice, st));
+        if (lm_pixels_dev) MVLM_CHECK_HIP(ctx, hipMemsetAsync(lm_pixels_dev, 0, size_t(n_views) * n_lm * sizeof(int32_t), st));
+    }
+    MVLM_CHECK_HIP(ctx, hipMemsetAsync(ctr, 0, ctr_ints * sizeof(int), st));
+    MVLM_CHECK_HIP(ctx, hipMemsetAsync(keys, 0xFF, key_bytes, st));  // RM_KEY_EMPTY everywhere, in every call
+    if (!ctx->render_overflow_host) {
+        MVLM_CHECK_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->render_overflow_host), sizeof(int)));
+        *ctx->render_overflow_host = 0;
+    }
+    const uint8_t* const vcol = ctx->render_shading == 0 && mesh->colors && !(mesh->tex && mesh->uvs) ? mesh->colors : nullptr;
+    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[1], st));
+    hipLaunchKernelGGL(view_transform_kernel, dim3(view_chunk_grid((V + 255) / 256, n_views)), dim3(256), 0, st, mesh->verts, V, rot,
+                       frames, n_views, ctx->render_subpixel_bits, tv);
+    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[2], st));
+    hipLaunchKernelGGL(view_classify_kernel, dim3(view_chunk_grid((T + 255) / 256, n_views)), dim3(256), 0, st, tv, mesh->tris, V, T,
+                       n_views, size, keys, counts, n_big, big_list);
+    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[3], st));
+    hipLaunchKernelGGL(view_scan_kernel, dim3(n_views), dim3(256), 0, st, counts, offsets, tiles, cap, overflow);
+    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[4], st));
+    hipLaunchKernelGGL(view_bin_fill_kernel, dim3(view_chunk_grid(FILL_WGS, n_views)), dim3(256), 0, st, tv, mesh->tris, V, T, n_views,
+                       size, n_big, big_list, offsets, cursors, bins, cap, overflow);
+    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[5], st));
+    if (n_lm > 0)
+        hipLaunchKernelGGL(view_project_kernel, dim3((n_views * n_lm + 255) / 256), dim3(256), 0, st, lm, lm_rgb, n_lm, rot, frames,
+                           n_views, size, radius, spheres);
+    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[6], st));
+    hipLaunchKernelGGL(view_tile_kernel, dim3(view_chunk_grid(tiles, n_views)), dim3(256), 0, st, tv, mesh->tris, mesh->uvs, mesh->tex,
+                       mesh->tex_w, mesh->tex_h, reinterpret_cast<const uchar4*>(vcol), V, counts, offsets, bins, cap, keys, frames,
+                       ctx->render_shading, n_views, size, spheres, n_lm, lm_pixels_dev, overflow, ctx->render_overflow_host,
+                       reinterpret_cast<uint32_t*>(out_dev));
+    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[7], st));
+    MVLM_CHECK_HIP(ctx, hipGetLastError());
+    ctx->view_events_valid = ev != nullptr;
+    return 0;
+}

@@ -90,7 +90,8 @@ class Pipeline(abc.ABC):
     def __init__(self, render_image_stack: bool = False, offscreen: bool = True, n_views: int = 8,
                  render_image_folder: Path | None = None, visualize_rays: bool = False,
                  screenshot_folder: Path | None = None, device: int = 0, shard_views: bool = False,
-                 verbose: bool = True, render_multisamples: int = 0, landmark_report: bool = False):
+                 verbose: bool = True, render_multisamples: int = 0, landmark_report: bool = False,
+                 visualize_img: bool = False, visualize_size: int = 1024, visualize_name: str | None = None):
         self.render_image_stack = render_image_stack
         self.render_image_folder = render_image_folder
         self.n_views = n_views
@@ -108,6 +109,18 @@ class Pipeline(abc.ABC):
         # coordinates.  Off (the default): nothing of it is launched, allocated or copied.
         self.landmark_report = bool(landmark_report)
         self.last_report = None
+        # visualize_img: after every successful prediction the RESIDENT device mesh is drawn with a sphere at every landmark
+        # (the reference's --visualize-img, main.py:66-67; HipRenderer3D.render_landmark_view) into
+        # visualization/<stem>_<visualize_name>.png under the working directory, visualize_size pixels a side.  With
+        # landmark_report the spheres carry the report's branch colours (utils/report.py: BRANCH_COLOURS).  Off (the
+        # default): nothing of it is launched or allocated.
+        self.visualize_img = bool(visualize_img)
+        self.visualize_size = int(visualize_size)
+        if self.visualize_img and (self.visualize_size < 64 or self.visualize_size > 2048 or self.visualize_size % 16):
+            raise ValueError(f"visualize_size must be a multiple of 16 in 64..2048, not {visualize_size}")
+        name = type(self).__name__.lower()
+        self.visualize_name = visualize_name if visualize_name is not None else name[:-len("pipeline")] if name.endswith("pipeline") else name
+        self.last_view_path = None
         self._rays = None  # (mesh, starts, ends) of the current call when visualize_rays is set
         self._buffers: dict = {}
         self._lock = threading.RLock()  # see _serialised
@@ -147,10 +160,10 @@ class Pipeline(abc.ABC):
     def _texture_needed(self) -> bool:
         """Does anything downstream read a texture-shaded plane of the views?  The reference always decodes the JPEG
         (utils3d.py:26-36) and renders RGB + depth; a depth or geometry(+depth) model then never looks at the colours.
-        Kept: whenever the views are written out (render_image_stack) or go to a predictor whose planes are unknown."""
+        Kept: whenever the views are written out (render_image_stack), the scan is drawn (visualize_img) or the views go to a predictor whose planes are unknown."""
         sel = getattr(self.predictor_2d, "chan_sel", None)
-        if self.render_image_stack or sel is None or not isinstance(self.renderer_3d, HipRenderer3D):
-            return True
+        if self.render_image_stack or self.visualize_img or sel is None or not isinstance(self.renderer_3d, HipRenderer3D):
+            return True  # (visualize_img draws the scan itself: with its texture)
         if self.renderer_3d.shading == "geometry":
             return False  # planes 0..2 carry the build-defined geometry shading
         return any(int(c) < 3 for c in sel)
@@ -215,6 +228,7 @@ class Pipeline(abc.ABC):
                          view_indices: list[int] | None = None, clip_rays_to_mesh: bool = True):
         if self.predictor_2d is None:
             raise ValueError("Predictor2D is not initialized.")
+        self._check_visualize()
         file_name = Path(file_name)
         if not file_name.exists():
             print(f"File {file_name} does not exist")
@@ -441,7 +455,38 @@ class Pipeline(abc.ABC):
                 return p2.repeat_without_fp16(lambda: self.predict_mesh_device(mesh, transform_stack))
         self._say("Landmarks [Error]: ", f"{error:08.6f}", " mm")
         self.last_error = error
+        if self.visualize_img and (not sharded or rank == 0):  # (sharded: every rank holds the result, one draws)
+            self._draw_landmark_view(mesh, landmarks, self.last_report if layout is not None else None)  # (THIS pass's report)
         return landmarks, error
+
+    def _check_visualize(self):
+        """``visualize_img`` needs the renderer that holds the mesh on the device: said before the prediction, not after it."""
+        if self.visualize_img and not isinstance(self.renderer_3d, HipRenderer3D):
+            raise ValueError("visualize_img needs a HipRenderer3D in the renderer slot (it draws the mesh resident on the device), "
+                             f"not {type(self.renderer_3d).__name__}")
+
+    def _draw_landmark_view(self, mesh, landmarks, report=None):
+        """``visualize_img``: the mesh as it lies on the device - no second ingest, no second upload - with the landmarks in the
+        space it was uploaded in (with a pre-align block: before the inverse mapping, so the points sit on the drawn surface),
+        front view, ``frame="fit"``; written as ``LandmarkViewer`` names it.  ``report``: the LandmarkReport of THIS prediction
+        (its branches colour the spheres) or None (blue).  A landmark that is not finite (a consensus without lines can leave one)
+        is left out of the picture: the flag does not fail a prediction that succeeded."""
+        from ..utils.viewer import view_path, write_view_png
+
+        if landmarks is None:
+            return None
+        self._check_visualize()
+        with self._timer.stage("visualize"):
+            landmarks = np.asarray(landmarks, dtype=np.float64).reshape(-1, 3)
+            colours = report.branch_colours() if report is not None else None
+            finite = np.isfinite(landmarks).all(axis=1)
+            if not finite.all():
+                landmarks = landmarks[finite]
+                colours = None if colours is None else colours[finite]
+            image = self.renderer_3d.render_landmark_view(mesh, landmarks, size=self.visualize_size, colors=colours)[0]
+            self.last_view_path = write_view_png(image, view_path(getattr(mesh, "path", None) or "mesh.obj", self.visualize_name))
+        self._say(f"[Pipeline] landmark view written to {self.last_view_path}")
+        return self.last_view_path
 
     def _groupable(self, n_scans: int) -> bool:
         """Can ``n_scans`` scans share one network pass (predict_meshes_device)?"""
@@ -454,6 +499,8 @@ class Pipeline(abc.ABC):
             return False
         if self.landmark_report:
             return False  # one report per scan, made by the scan's own pass
+        if self.visualize_img:
+            return False  # one picture per scan, drawn by the scan's own pass while its mesh is resident
         n = int(self.renderer_3d.n_views)
         return e3.expected_counts(p2.get_lm_count(), n) is not None and n_scans * n <= (p2.device_batch or 128)
 
@@ -566,6 +613,7 @@ class Pipeline(abc.ABC):
         files = [Path(f) for f in files]
         if self.predictor_2d is None:
             raise ValueError("Predictor2D is not initialized.")
+        self._check_visualize()
         if not self._fusable() or prefetch <= 0:
             for f in files:
                 yield f, self.predict_one_file(f)
@@ -718,6 +766,7 @@ class Pipeline(abc.ABC):
         self._say("Landmarks [Error]: ", f"{error:08.6f}", " mm")
         self.last_error = error
         self._dump_pre_aligned(pd, file_name)
+        drawn = landmarks  # (the picture: in the space the mesh was rendered in)
         # a mesh handle that went through the config's pre-align block carries its matrix: results go back to
         # the file's coordinates (the rays kept for visualisation stay in the aligned space, with the mesh handle)
         landmarks = self._to_original(pd, landmarks)
@@ -725,6 +774,8 @@ class Pipeline(abc.ABC):
             kept = np.asarray(valid)
             self.last_report = LandmarkReport(arrays, landmarks=landmarks,
                                               view_indices=np.nonzero(kept)[0] if kept.dtype == bool else kept)
+        if self.visualize_img:  # behind the report: the spheres carry THIS scan's branches
+            self._draw_landmark_view(pd, drawn, self.last_report if arrays is not None else None)
         return landmarks
 
     def visualize_image_stack(self, image_stack: np.ndarray, file_name: Path, first_index: int = 0):

@@ -272,6 +272,91 @@ class HipRenderer3D:
                                                 C.c_void_p(out.data_ptr())))
         return out
 
+    # ---- landmark view (utils/viewer.py's offscreen window) ----------------------------------
+    def landmark_view_arguments(self, mesh: Mesh, landmarks, poses=None, frame="fit", radius=None):
+        """The host half of ``render_landmark_view``: (poses [n,3], frames f32 [n,3], landmarks f64 [NL,3], radius), computed from
+        the arrays the ``Mesh`` object holds.
+
+        ``frame="fit"`` is the orthographic reading of viewer.py:74-78 (``ResetCamera`` then ``Zoom(1.4)``): the window's centre is
+        the view-space centre of the 3-D bounding box of the mesh's vertices and the landmarks, ``half`` that box's half diagonal
+        divided by 1.4.  ``frame="network"`` is (0, 0, 150), the window the network saw; a tuple ``(cx, cy, half)`` (or one row per
+        pose) is taken as given.  ``radius=None`` is 0.008 x the diagonal of the landmarks' bounding box (viewer.py:119-128); with
+        ONE landmark that diagonal is 0 and the radius falls back to 0.008 x the mesh's diagonal; with none nothing is drawn."""
+        poses = np.zeros((1, 3)) if poses is None else np.asarray(poses, dtype=np.float64).reshape(-1, 3)
+        n = poses.shape[0]
+        lm = np.zeros((0, 3)) if landmarks is None else np.ascontiguousarray(landmarks, dtype=np.float64).reshape(-1, 3)
+        verts = np.asarray(mesh.verts, dtype=np.float64).reshape(-1, 3)
+        v_lo, v_hi = verts.min(axis=0), verts.max(axis=0)
+        if isinstance(frame, str):
+            if frame == "network":
+                frames = np.tile(np.array([0.0, 0.0, self.side_length], np.float32), (n, 1))
+            elif frame == "fit":
+                lo = np.minimum(v_lo, lm.min(axis=0)) if len(lm) else v_lo
+                hi = np.maximum(v_hi, lm.max(axis=0)) if len(lm) else v_hi
+                centre = view_rotations(poses).reshape(n, 3, 3) @ ((lo + hi) / 2)
+                half = float(np.linalg.norm(hi - lo)) / 2 / 1.4
+                frames = np.column_stack([centre[:, 0], centre[:, 1], np.full(n, half)]).astype(np.float32)
+            else:
+                raise ValueError('frame must be "fit", "network" or (cx, cy, half)')
+        else:
+            f = np.asarray(frame, dtype=np.float32)
+            frames = np.tile(f, (n, 1)) if f.shape == (3,) else f.reshape(n, 3)
+        if radius is None:
+            if len(lm) == 0:
+                radius = 0.0
+            else:
+                diag = float(np.linalg.norm(lm.max(axis=0) - lm.min(axis=0)))
+                radius = 0.008 * (diag if diag > 0.0 else float(np.linalg.norm(v_hi - v_lo)))
+        return poses, np.ascontiguousarray(frames, dtype=np.float32), lm, float(radius)
+
+    def render_landmark_view_device(self, mesh: Mesh, landmarks, poses=None, size: int = 1024, frame="fit", radius=None,
+                                    colors=None, return_pixels: bool = False):
+        """``render_landmark_view`` with the results left on the device: uint8 [n,S,S,4] RGBA (and int32 [n,NL] with
+        ``return_pixels``).  Only enqueues work; ``check()`` reports a deferred failure."""
+        import torch
+
+        poses, frames, lm, radius = self.landmark_view_arguments(mesh, landmarks, poses, frame, radius)
+        n, nl = poses.shape[0], lm.shape[0]
+        rgb = None
+        if colors is not None:
+            rgb = np.ascontiguousarray(colors, dtype=np.uint8)
+            if rgb.shape != (nl, 3):
+                raise ValueError(f"colors must be uint8 [{nl},3], not {rgb.shape}")
+        size = int(size)
+        if size < 64 or size > 2048 or size % 16:
+            raise ValueError(f"size must be a multiple of 16 in 64..2048, not {size}")
+        dev = torch.device("cuda", self.ctx.device)
+        out = torch.empty((n, size, size, 4), dtype=torch.uint8, device=dev)
+        pixels = torch.empty((n, nl), dtype=torch.int32, device=dev) if return_pixels else None
+        rot = np.ascontiguousarray(view_rotations(poses), dtype=np.float64)
+        handle = upload_mesh(self.ctx, mesh)
+        self.ctx.bind_current_stream(torch, dev)
+        mode = (1 if self.shading == "geometry" else 0, self.subpixel_bits, self.multisamples)
+        if getattr(self.ctx, "_render_mode", None) != mode:  # (the view reads the shading and the sub-pixel bits)
+            self.ctx.check(self.ctx.lib.mvlm_set_render_shading(self.ctx.handle, mode[0]))
+            self.ctx.check(self.ctx.lib.mvlm_set_render_subpixel_bits(self.ctx.handle, mode[1]))
+            self.ctx.check(self.ctx.lib.mvlm_set_render_multisamples(self.ctx.handle, mode[2]))
+            self.ctx._render_mode = mode
+        self.ctx.check(self.ctx.lib.mvlm_render_landmark_view(
+            self.ctx.handle, handle, _lib.as_ptr(rot, C.c_double), n, size, _lib.as_ptr(frames, C.c_float),
+            _lib.as_ptr(lm, C.c_double) if nl else None, nl, C.c_float(radius), None if rgb is None or nl == 0 else _lib.as_ptr(rgb, C.c_uint8),
+            C.c_void_p(out.data_ptr()), C.c_void_p(pixels.data_ptr()) if pixels is not None and nl else None), ValueError)
+        return (out, pixels) if return_pixels else out
+
+    def render_landmark_view(self, mesh: Mesh, landmarks, poses=None, size: int = 1024, frame="fit", radius=None, colors=None,
+                             return_pixels: bool = False):
+        """The mesh with a shaded sphere at every landmark, as the reference's offscreen viewer draws it (utils/viewer.py with
+        ``save=True``): uint8 [n,S,S,3], and with ``return_pixels`` also int32 [n,NL], the pixels each landmark's sphere won in
+        each view (0: hidden there).  ``poses`` [n,3] degrees (rx, ry, rz), default one front view (viewer.py:45-55);
+        ``landmarks`` [NL,3] in the mesh's coordinates; ``colors`` uint8 [NL,3], default blue; ``frame`` / ``radius``: see
+        ``landmark_view_arguments``.  One sample per pixel, whatever ``multisamples`` is ("Landmark view")."""
+        res = self.render_landmark_view_device(mesh, landmarks, poses, size, frame, radius, colors, return_pixels)
+        out, pixels = res if return_pixels else (res, None)
+        image = out.cpu().numpy()[..., :3].copy()
+        counts = pixels.cpu().numpy() if pixels is not None else None
+        self.check()
+        return (image, counts) if return_pixels else image
+
     def rotations_device(self):
         """The last render's rotation table where the rasteriser keeps it on the device (f64[N,9]; valid until this context's
         next render): an object with ``data_ptr()`` that ``HipEstimator3D.lines_device(rot_dev=...)`` takes - the rays of the

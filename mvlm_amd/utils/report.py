@@ -69,6 +69,11 @@ def texel(u, v, tex_w: int, tex_h: int):
     return np.where(bad, -1, tx), np.where(bad, -1, tex_h - 1 - ty)
 
 
+# The landmark view (Pipeline(visualize_img=True)) colours a landmark's sphere by the branch of its report: refitted on its
+# inliers (1) blue, fallback to all lines (2) orange, fewer than three lines (0) red.
+BRANCH_COLOURS = {1: (0, 0, 255), 2: (255, 165, 0), 0: (255, 0, 0)}
+
+
 class LandmarkReport:
     """See the module docstring for the coordinate spaces.  NL landmarks, N views (those that remained after a
     detector's ``valid`` mask: ``view_indices`` names them in the pose table).
@@ -87,6 +92,11 @@ class LandmarkReport:
     """
 
     VIEW_KEPT, VIEW_DRAWN, VIEW_INLIER, VIEW_USED = VIEW_KEPT, VIEW_DRAWN, VIEW_INLIER, VIEW_USED
+
+    def branch_colours(self) -> np.ndarray:
+        """uint8 [NL,3]: ``BRANCH_COLOURS`` of every landmark's branch (the sphere colours of the landmark view)."""
+        table = np.array([BRANCH_COLOURS[b] for b in (0, 1, 2)], np.uint8)
+        return table[np.clip(np.asarray(self.branch, np.int64), 0, 2)]
 
     def __init__(self, arrays: dict, landmarks=None, view_indices=None):
         a = arrays

@@ -4,7 +4,8 @@
     tools/kernel_occupancy.py            print the table
     tools/kernel_occupancy.py --write    rewrite tests/golden/kernel_occupancy.json (and kernel_occupancy_msaa.json,
                                          kernel_occupancy_vcolor.json, kernel_occupancy_wino.json,
-                                         kernel_occupancy_wino4.json, kernel_occupancy_report.json) from the build
+                                         kernel_occupancy_wino4.json, kernel_occupancy_report.json,
+                                         kernel_occupancy_view.json) from the build
 
 A convolution tile's rate depends on how many workgroups a CU holds, i.e. on which side of 168 / 128 / 102 ... registers the
 compiler lands - and every epilogue kind compiled into a tile moves that number (round 4: two new kinds took the 80-row tile
@@ -16,7 +17,9 @@ tests/golden/kernel_occupancy_msaa.json, held to the same rule by tests/test_msa
 shade with per-vertex colours (build/vcolor/, kernel_occupancy_vcolor.json, tests/test_vcolor_occupancy.py) and the Winograd convolution
 tiles (build/wino/, tests/golden/kernel_occupancy_wino.json, tests/test_winograd_occupancy.py), the F(4,3) Winograd tile
 (build/wino4/, tests/golden/kernel_occupancy_wino4.json, tests/test_winograd4_occupancy.py) and the two kernels of the opt-in
-landmark report (build/report/, tests/golden/kernel_occupancy_report.json, tests/test_report_occupancy.py)."""
+landmark report (build/report/, tests/golden/kernel_occupancy_report.json, tests/test_report_occupancy.py) and the six kernels
+of the landmark view (build/view/, tests/golden/kernel_occupancy_view.json, tests/test_view_occupancy.py), whose table also
+records the bytes of scratch memory per work-item (0)."""
 import json
 import re
 import subprocess
@@ -32,6 +35,7 @@ VCOLOR_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_vcolor.json"
 WINO_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_wino.json"
 WINO4_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_wino4.json"
 REPORT_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_report.json"
+VIEW_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_view.json"
 BUILD = REPO / "mvlm_amd" / "csrc" / "build"
 
 
@@ -58,9 +62,11 @@ def object_kernels(obj: Path) -> dict:
                 nm = re.search(r"\.name:\s+(\S+)", blk)
                 vg = re.search(r"\.vgpr_count:\s+(\d+)", blk)
                 sp = re.search(r"\.vgpr_spill_count:\s+(\d+)", blk)
+                sc = re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk)
                 if nm and vg and sp:
                     out[nm.group(1)] = {"vgprs": int(vg.group(1)), "spilled": int(sp.group(1)),
-                                                       "waves_per_simd": waves_per_simd(int(vg.group(1)))}
+                                                       "waves_per_simd": waves_per_simd(int(vg.group(1))),
+                                                       "scratch": int(sc.group(1)) if sc else 0}
             n += 1
             i = j + 4
     return out
@@ -75,10 +81,12 @@ def build_table(objdir: Path = BUILD) -> dict:
 
 if __name__ == "__main__":
     for table_path, objdir in ((TABLE, BUILD), (MSAA_TABLE, BUILD / "msaa"), (VCOLOR_TABLE, BUILD / "vcolor"),
-                                (WINO_TABLE, BUILD / "wino"), (WINO4_TABLE, BUILD / "wino4"), (REPORT_TABLE, BUILD / "report")):
+                                (WINO_TABLE, BUILD / "wino"), (WINO4_TABLE, BUILD / "wino4"), (REPORT_TABLE, BUILD / "report"),
+                                (VIEW_TABLE, BUILD / "view")):
         t = build_table(objdir)
         if "--write" in sys.argv:
-            table_path.write_text(json.dumps({k: {"waves_per_simd": v["waves_per_simd"], "spilled": v["spilled"]} for k, v in t.items()}, indent=1) + "\n")
+            fields = ("waves_per_simd", "spilled", "scratch") if table_path == VIEW_TABLE else ("waves_per_simd", "spilled")
+            table_path.write_text(json.dumps({k: {f: v[f] for f in fields} for k, v in t.items()}, indent=1) + "\n")
             print(f"{len(t)} kernels -> {table_path}")
         else:
             for k, v in t.items():
