@@ -194,6 +194,31 @@ int mvlm_render_landmark_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double
  * projection, tile.  Waits for the stream. */
 int mvlm_landmark_view_stage_ms(mvlm_ctx* ctx, float* ms7);
 
+/* ---- ray view (replaces visualization/ray_visualizer.py's RayVisualizer for the offscreen case) ---- */
+/* mvlm_render_landmark_view's picture with n_rays rays between the mesh and the spheres: each an opaque, head-lit capsule, the
+ * points within ray_radius model units of the segment start -> end ("Ray view").  Every argument shared with
+ * mvlm_render_landmark_view means the same and is checked the same.
+ *   starts_dev, ends_dev f64[n_rays,3]  ON THE DEVICE, in the mesh's coordinates (mvlm_estimate_lines' starts / ends, clipped or
+ *                               not); NULL allowed when n_rays == 0; at most 65 536 rays and n_views * n_rays <= 1 048 576
+ *                               per call (a 64-byte record per view and ray in the context's grow-only scratch: at most 64 MB).  A ray with a non-finite
+ *                               coordinate is skipped: it covers no pixel and raises no error
+ *   ray_rgb_host u8[n_rays,3]   a colour per ray, NULL = (26, 230, 26), the reference's (0.1, 0.9, 0.1)
+ *   ray_pixels_dev i32[n_views,n_rays] or NULL: the pixels each ray won in each view
+ * Order: the mesh, then the rays (a ray wins an equal depth against the mesh; among rays the nearer wins, the higher index on
+ * equal depth), then the spheres (a sphere wins an equal depth against a ray).  A ray seen end-on, or projected shorter than
+ * 1 / 256 of its radius in pixels, is the sphere of its nearer end, bit for bit.  With n_rays == 0 the output is
+ * mvlm_render_landmark_view's, byte for byte.  A negative or non-finite ray_radius, n_rays outside 0..65536, n_views * n_rays beyond 1 048 576, NULL starts or ends
+ * with n_rays > 0 set an error that starts with "ray view:" and launch nothing.  Only enqueues work; a tile-list overflow is
+ * reported by mvlm_render_check. */
+int mvlm_render_ray_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot_host, int n_views, int size,
+                         const float* frame_host, const double* landmarks_host, int n_lm, float radius, const uint8_t* lm_rgb_host,
+                         const double* starts_dev, const double* ends_dev, int n_rays /* f64[n_rays,3], device */,
+                         float ray_radius, const uint8_t* ray_rgb_host /* [n_rays,3] or NULL = (26,230,26) */,
+                         uint8_t* out_dev, int32_t* lm_pixels_dev, int32_t* ray_pixels_dev /* [n_views,n_rays] or NULL */);
+/* With mvlm_render_set_profiling on, the last ray view's stages in milliseconds, f32[8]: mvlm_landmark_view_stage_ms's first six
+ * (copies and fills, transform, classify, scan, bin fill, landmark projection), the ray projection, the tile kernel. */
+int mvlm_ray_view_stage_ms(mvlm_ctx* ctx, float* ms8);
+
 /* ---- landmark network (replaces paulsenpredictor.py:89-110, :167-217) ------------ */
 /* blob/desc: output of mvlm_amd.weights.pack_for_device (BN folded, weights as
  * [tap][cin_pad][cout_pad]); copied to the device. */

@@ -57,7 +57,13 @@ def build_parser() -> argparse.ArgumentParser:
                         help="write visualization/<stem>_<pipeline>.png under the working directory for every scan: the mesh with a "
                              "sphere at every landmark (with --report the spheres are coloured by the RANSAC branch: blue inlier fit, "
                              "orange fallback to all lines, red fewer than three lines)")
-    parser.add_argument("--visualize-size", type=int, default=1024, help="side of that picture in pixels (a multiple of 16, 64..2048)")
+    parser.add_argument("--visualize-size", type=int, default=1024,
+                        help="side of that picture, and of --visualize-rays' pictures, in pixels (a multiple of 16, 64..2048)")
+    parser.add_argument("--visualize-rays", action="store_true",
+                        help="write visualization/ray_screenshots/<stem>_<pipeline>_rays_<i>.png under the working directory for every "
+                             "scan: the mesh, every view's ray for every landmark clipped to its first hit with the surface, and the "
+                             "landmarks, from the front and from 60 degrees left and right (with --report the rays are green where the "
+                             "consensus used them, orange where it kept but did not use them, grey where the score filter dropped them)")
     return parser
 
 
@@ -100,6 +106,9 @@ def main(argv=None) -> int:
         extra["landmark_report"] = True
     if args.visualize_img:
         extra["visualize_img"] = True
+        extra["visualize_size"] = args.visualize_size
+    if args.visualize_rays:
+        extra["visualize_rays_img"] = True
         extra["visualize_size"] = args.visualize_size
     if args.config is not None:
         from . import config as mvlm_config

@@ -883,38 +883,70 @@ extern "C" int mvlm_conv_pair_bench(mvlm_ctx* ctx, int batch, int cin, int cout,
     return rc;
 }
 
-// ---- landmark view (raster_view.hip; DESIGN.md 5.1, "Landmark view") ---------------------------------------------------
-// Checks the arguments - a bad one returns an error and launches nothing - and hands the launch set to raster_view.hip.
-extern "C" int mvlm_render_landmark_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot_host, int n_views, int size,
-                                         const float* frame_host, const double* landmarks_host, int n_lm, float radius,
-                                         const uint8_t* lm_rgb_host, uint8_t* out_dev, int32_t* lm_pixels_dev) {
-    MVLM_ENTER(ctx);
-    MVLM_REQUIRE(ctx, mesh && rot_host && frame_host && out_dev && n_views > 0, "landmark view: bad arguments");
-    MVLM_REQUIRE(ctx, mesh->n_verts > 0 && mesh->n_tris > 0, "landmark view: empty mesh");
+// ---- landmark view (raster_view.hip; DESIGN.md 5.1, "Landmark view") and ray view (raster_rays.hip; "Ray view") -----------
+// The checks of the arguments the two entry points share, under the entry's own name; fills the frames with k.
+static int view_check_arguments(mvlm_ctx* ctx, const std::string& what, const mvlm_mesh* mesh, const double* rot_host, int n_views,
+                                int size, const float* frame_host, const double* landmarks_host, int n_lm, float radius,
+                                const uint8_t* out_dev, std::vector<float>& frames) {
+    MVLM_REQUIRE(ctx, mesh && rot_host && frame_host && out_dev && n_views > 0, what + ": bad arguments");
+    MVLM_REQUIRE(ctx, mesh->n_verts > 0 && mesh->n_tris > 0, what + ": empty mesh");
     MVLM_REQUIRE(ctx, size >= RV_MIN_SIZE && size <= RV_MAX_SIZE && size % RM_TILE == 0,
-                 "landmark view: size must be a multiple of 16 in 64..2048 (" + std::to_string(size) + " given)");
-    MVLM_REQUIRE(ctx, n_views <= RV_MAX_VIEWS, "landmark view: at most 128 views per call (" + std::to_string(n_views) + " given)");
+                 what + ": size must be a multiple of 16 in 64..2048 (" + std::to_string(size) + " given)");
+    MVLM_REQUIRE(ctx, n_views <= RV_MAX_VIEWS, what + ": at most 128 views per call (" + std::to_string(n_views) + " given)");
     MVLM_REQUIRE(ctx, (long long)n_views * size * size <= RV_MAX_PIXELS,
-                 "landmark view: n_views * size * size exceeds 8 * 2048 * 2048 pixels per call");
-    MVLM_REQUIRE(ctx, n_lm >= 0 && (n_lm == 0 || landmarks_host), "landmark view: landmarks missing");
-    MVLM_REQUIRE(ctx, std::isfinite(radius) && radius >= 0.0f, "landmark view: the radius must be finite and >= 0");
-    for (int k = 0; k < n_views * 9; ++k) MVLM_REQUIRE(ctx, std::isfinite(rot_host[k]), "landmark view: non-finite rotation");
-    std::vector<float> frames(size_t(n_views) * 4);
+                 what + ": n_views * size * size exceeds 8 * 2048 * 2048 pixels per call");
+    MVLM_REQUIRE(ctx, n_lm >= 0 && (n_lm == 0 || landmarks_host), what + ": landmarks missing");
+    MVLM_REQUIRE(ctx, std::isfinite(radius) && radius >= 0.0f, what + ": the radius must be finite and >= 0");
+    for (int k = 0; k < n_views * 9; ++k) MVLM_REQUIRE(ctx, std::isfinite(rot_host[k]), what + ": non-finite rotation");
+    frames.assign(size_t(n_views) * 4, 0.0f);
     for (int v = 0; v < n_views; ++v) {
         const float cx = frame_host[3 * v], cy = frame_host[3 * v + 1], half = frame_host[3 * v + 2];
         MVLM_REQUIRE(ctx, std::isfinite(cx) && std::isfinite(cy) && std::isfinite(half) && half > 0.0f,
-                     "landmark view: a frame needs finite cx, cy and half > 0");
+                     what + ": a frame needs finite cx, cy and half > 0");
         const float k = rv_scale(size, half);
-        MVLM_REQUIRE(ctx, std::isfinite(k) && k > 0.0f, "landmark view: half is too small or too large for this size");
+        MVLM_REQUIRE(ctx, std::isfinite(k) && k > 0.0f, what + ": half is too small or too large for this size");
         frames[4 * v] = cx;
         frames[4 * v + 1] = cy;
         frames[4 * v + 2] = half;
         frames[4 * v + 3] = k;
     }
-    for (int k = 0; k < n_lm * 3; ++k) MVLM_REQUIRE(ctx, std::isfinite(landmarks_host[k]), "landmark view: non-finite landmark");
+    for (int k = 0; k < n_lm * 3; ++k) MVLM_REQUIRE(ctx, std::isfinite(landmarks_host[k]), what + ": non-finite landmark");
+    return 0;
+}
+
+// Checks the arguments - a bad one returns an error and launches nothing - and hands the launch set to raster_view.hip.
+extern "C" int mvlm_render_landmark_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot_host, int n_views, int size,
+                                         const float* frame_host, const double* landmarks_host, int n_lm, float radius,
+                                         const uint8_t* lm_rgb_host, uint8_t* out_dev, int32_t* lm_pixels_dev) {
+    MVLM_ENTER(ctx);
+    std::vector<float> frames;
+    if (view_check_arguments(ctx, "landmark view", mesh, rot_host, n_views, size, frame_host, landmarks_host, n_lm, radius, out_dev,
+                             frames))
+        return 1;
     if (mvlm_mesh_wait_ready(ctx, mesh, ctx->stream)) return 1;  // the upload runs on a stream of its own
     return mvlm_launch_landmark_view(ctx, mesh, rot_host, n_views, size, frames.data(), landmarks_host, n_lm, radius, lm_rgb_host,
                                      out_dev, lm_pixels_dev);
+}
+
+// The same with the rays: the shared arguments are checked the same, the rays' own under "ray view:"; hands over to raster_rays.hip.
+extern "C" int mvlm_render_ray_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot_host, int n_views, int size,
+                                    const float* frame_host, const double* landmarks_host, int n_lm, float radius,
+                                    const uint8_t* lm_rgb_host, const double* starts_dev, const double* ends_dev, int n_rays,
+                                    float ray_radius, const uint8_t* ray_rgb_host, uint8_t* out_dev, int32_t* lm_pixels_dev,
+                                    int32_t* ray_pixels_dev) {
+    MVLM_ENTER(ctx);
+    std::vector<float> frames;
+    if (view_check_arguments(ctx, "ray view", mesh, rot_host, n_views, size, frame_host, landmarks_host, n_lm, radius, out_dev, frames))
+        return 1;
+    MVLM_REQUIRE(ctx, n_rays >= 0 && n_rays <= RV_MAX_RAYS,
+                 "ray view: 0..65536 rays per call (" + std::to_string(n_rays) + " given)");
+    MVLM_REQUIRE(ctx, (long long)n_views * n_rays <= RV_MAX_RAY_RECORDS,
+                 "ray view: n_views * n_rays exceeds 1048576 records per call (" + std::to_string((long long)n_views * n_rays) + " asked)");
+    MVLM_REQUIRE(ctx, n_rays == 0 || (starts_dev && ends_dev), "ray view: ray starts or ends missing");
+    MVLM_REQUIRE(ctx, std::isfinite(ray_radius) && ray_radius >= 0.0f, "ray view: the ray radius must be finite and >= 0");
+    if (mvlm_mesh_wait_ready(ctx, mesh, ctx->stream)) return 1;
+    return mvlm_launch_ray_view(ctx, mesh, rot_host, n_views, size, frames.data(), landmarks_host, n_lm, radius, lm_rgb_host, starts_dev,
+                                ends_dev, n_rays, ray_radius, ray_rgb_host, out_dev, lm_pixels_dev, ray_pixels_dev);
 }
 
 // Milliseconds of the last landmark view's stages (copies and fills - the key plane's among them -, transform, classify, scan,
@@ -927,5 +959,16 @@ extern "C" int mvlm_landmark_view_stage_ms(mvlm_ctx* ctx, float* ms7) {
                  "landmark_view_stage_ms: no landmark view was drawn with render profiling on");
     MVLM_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int k = 0; k < 7; ++k) MVLM_CHECK_HIP(ctx, hipEventElapsedTime(&ms7[k], ctx->view_events[k], ctx->view_events[k + 1]));
+    return 0;
+}
+
+// Likewise the last ray view's eight stages: the landmark view's first six, the ray projection, the tile kernel.
+extern "C" int mvlm_ray_view_stage_ms(mvlm_ctx* ctx, float* ms8) {
+    MVLM_ENTER(ctx);
+    MVLM_REQUIRE(ctx, ms8, "ray_view_stage_ms: null pointer");
+    MVLM_REQUIRE(ctx, ctx->ray_events_valid && ctx->view_events.size() >= 9,
+                 "ray_view_stage_ms: no ray view was drawn with render profiling on");
+    MVLM_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < 8; ++k) MVLM_CHECK_HIP(ctx, hipEventElapsedTime(&ms8[k], ctx->view_events[k], ctx->view_events[k + 1]));
     return 0;
 }

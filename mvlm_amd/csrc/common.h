@@ -293,6 +293,7 @@ struct mvlm_ctx {
     // last view recorded them (mvlm_landmark_view_stage_ms)
     std::vector<hipEvent_t> view_events;
     bool view_events_valid = false;
+    bool ray_events_valid = false;  // likewise the last ray view (raster_rays.hip: nine events, mvlm_ray_view_stage_ms)
     // device buffers of freed meshes, reused by the next upload: a folder of scans would otherwise pay
     // four hipMalloc + four (device-synchronising) hipFree per scan
     struct PoolEntry {
@@ -412,6 +413,12 @@ constexpr int MVLM_CONV_VARIANT_FAST16 = 61;  // ... of the f16x2 kernel
 int mvlm_launch_landmark_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot_host, int n_views, int size,
                               const float* frames_host, const double* landmarks_host, int n_lm, float radius,
                               const uint8_t* lm_rgb_host, uint8_t* out_dev, int32_t* lm_pixels_dev);
+
+// raster_rays.hip: the launch set of mvlm_render_ray_view (likewise)
+int mvlm_launch_ray_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot_host, int n_views, int size,
+                         const float* frames_host, const double* landmarks_host, int n_lm, float radius, const uint8_t* lm_rgb_host,
+                         const double* starts_dev, const double* ends_dev, int n_rays, float ray_radius, const uint8_t* ray_rgb_host,
+                         uint8_t* out_dev, int32_t* lm_pixels_dev, int32_t* ray_pixels_dev);
 
 // surface.hip: passes 0 and 1 of the surface snap (bound, de-indexed triangles, per-chunk winners in the context's scratch)
 // for an entry point that holds the context; its final kernel follows (mvlm_project_to_surface, mvlm_surface_attach)

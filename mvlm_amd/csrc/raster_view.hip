@@ -17,23 +17,17 @@
 //                  LDS and added to the global counts with one atomic per (tile, landmark) that is non-zero.
 // Only the 64-bit edge functions are used (the 24-bit ones of raster_tile.h give the same integers).  The key plane
 // ("view.keys", 32 MB per view at S = 2048) is filled inside every call.
-#include "raster_common.h"
-#include "raster_view_math.h"
+// The tile stage's device code and the launch of the stages in front of it are shared with the ray view (raster_rays.hip):
+// raster_view_tile.h.
+#include "raster_view_tile.h"
 
 namespace {
 
-static_assert(sizeof(rv_sphere) == 32 && alignof(rv_sphere) == 16, "the tile kernel moves a sphere as two 16-byte words");
 // A triangle whose pixel-centre box holds at most this many pixels is resolved by classify's atomics, not binned.  Larger than
 // raster.hip's 16: the bench mesh's triangles span 5 x 5 pixel centres in a 1024^2 window and 10 x 10 at 2048^2, and with all of
 // them binned every pixel of a tile walked ~55 triangles through the 64-bit edge functions - 353 of the view's 450 us at 1024^2
 // (profiles/landmark_view_time.txt).  The key makes the image independent of which path a triangle takes.
 constexpr int VIEW_SMALL_PIXELS = 128;
-constexpr int VIEW_SPHERE_CAP = 256;   // spheres in a tile's LDS list at a time: one candidate per thread and round
-constexpr int VIEW_COUNT_SPAN = 1024;  // landmarks whose per-tile pixel counts are held in LDS at a time
-
-struct view_frame {  // per view: the window's centre in view space, model units from centre to border, pixels per model unit
-    float cx, cy, half, k;
-};
 
 __global__ void view_transform_kernel(const float* __restrict__ verts, int n_verts, const double* __restrict__ rot,
                                       const view_frame* __restrict__ frames, int n_views, int sub_bits,
@@ -53,9 +47,6 @@ __global__ void view_transform_kernel(const float* __restrict__ verts, int n_ver
     tv[size_t(view) * n_verts + v] = w;
 }
 
-__device__ inline rm_tri view_load_tri(const vert12* tvv, const int32_t* tris, int t, int size) {
-    return rv_setup(load_vert(tvv, tris[3 * t]), load_vert(tvv, tris[3 * t + 1]), load_vert(tvv, tris[3 * t + 2]), size);
-}
 
 // cull / resolve small boxes with atomics / count big ones into tiles; true for a big triangle (classify_one of raster.hip)
 __device__ inline bool view_classify_one(int view, int t, const rm_vert& va, const rm_vert& vb, const rm_vert& vc, int size,
@@ -202,127 +193,26 @@ __global__ __launch_bounds__(256) void view_tile_kernel(
         __threadfence_system();
     }
 
-    // ---- the tile's big triangles, set up into LDS a chunk at a time ----
-    for (int base = 0; base < n; base += 256) {
-        const int m = min(256, n - base);
-        __syncthreads();
-        if (tid < m) {
-            const int t = list[base + tid];
-            s_id[tid] = t;
-            s_tri[tid] = view_load_tri(tvv, tris, t, size);
-        }
-        __syncthreads();
-        for (int k = 0; k < m; ++k) {
-            const rm_tri* t = &s_tri[k];
-            if (i < t->ix0 || i > t->ix1 || j < t->iy0 || j > t->iy1) continue;
-            float b0, b1, b2;
-            if (!rm_cover(t, i, j, &b0, &b1, &b2)) continue;
-            const float z = rm_interp(b0, b1, b2, t->z0, t->z1, t->z2);
-            if (!(z >= 0.0f && z <= 1.0f)) continue;  // near / far clip
-            const uint64_t key = rm_key(z, uint32_t(s_id[k]));
-            best = key < best ? key : best;
-        }
-    }
-
-    // ---- shade the mesh's winner: the byte mvlm_render divides by 255 ----
-    uint32_t rgb = 0xFFFFFFu;  // white background
-    float zbest = INFINITY;    // depth the spheres are tested against: +inf where no triangle covers the pixel
-    if (best != RM_KEY_EMPTY) {
-        const int t = int(rm_key_tri(best));
-        int a = tris[3 * t], b = tris[3 * t + 1], c = tris[3 * t + 2];
-        const rm_tri tr = rv_setup(load_vert(tvv, a), load_vert(tvv, b), load_vert(tvv, c), size);
-        float b0 = 0.f, b1 = 0.f, b2 = 0.f;
-        rm_cover(&tr, i, j, &b0, &b1, &b2);
-        if (tr.swapped) {
-            const int s = b;
-            b = c;
-            c = s;
-        }
-        if (shading == 1) {
-            const uint32_t g = uint32_t(rv_geometry_u8(&tr, rv_geometry_kz(size, frame.half)));
-            rgb = g | (g << 8) | (g << 16);
-        } else if (colors) {
-            const uchar4 c0 = colors[a], c1 = colors[b], c2 = colors[c];
-            const int r = rm_color_u8(rm_interp(0.f, b1, b2, float(c0.x) / 255.0f, float(c1.x) / 255.0f, float(c2.x) / 255.0f));
-            const int g = rm_color_u8(rm_interp(0.f, b1, b2, float(c0.y) / 255.0f, float(c1.y) / 255.0f, float(c2.y) / 255.0f));
-            const int bl = rm_color_u8(rm_interp(0.f, b1, b2, float(c0.z) / 255.0f, float(c1.z) / 255.0f, float(c2.z) / 255.0f));
-            rgb = uint32_t(r) | (uint32_t(g) << 8) | (uint32_t(bl) << 16);
-        } else if (tex && uvs) {
-            const float u = rm_interp(b0, b1, b2, uvs[2 * a], uvs[2 * b], uvs[2 * c]);
-            const float v = rm_interp(b0, b1, b2, uvs[2 * a + 1], uvs[2 * b + 1], uvs[2 * c + 1]);
-            // one (unaligned) 4-byte load per texel: the buffer carries 4 spare bytes behind the last one (api.hip)
-            uint32_t texel;
-            __builtin_memcpy(&texel, tex + size_t(rm_texel(u, v, tex_w, tex_h)) * 3, 4);
-            rgb = texel & 0xFFFFFFu;
-        }
-        zbest = rm_key_z(best);
-    }
-
-    // ---- spheres: drawn after the mesh (they win ties), in landmark order (the later one wins an equal depth) ----
-    int win = -1;
-    for (int base = 0; base < n_lm; base += VIEW_SPHERE_CAP) {
-        const int cand = base + tid;
-        bool touch = false;
-        uint4 w0 = make_uint4(0, 0, 0, 0), w1 = w0;  // the record as two 16-byte words: X Y z R | rgb, x box, y box, pad
-        if (cand < n_lm) {
-            const uint4* const src = reinterpret_cast<const uint4*>(spheres + size_t(view) * n_lm + cand);
-            w0 = src[0];
-            w1 = src[1];
-            const int ix0 = short(w1.y & 0xFFFFu), ix1 = short(w1.y >> 16), iy0 = short(w1.z & 0xFFFFu), iy1 = short(w1.z >> 16);
-            touch = ix0 <= tx0 + RM_TILE - 1 && ix1 >= tx0 && iy0 <= ty0 + RM_TILE - 1 && iy1 >= ty0;
-        }
-        const unsigned long long m = __ballot(touch);
-        const int wave = tid >> 6, lane = tid & 63;
-        __syncthreads();  // (the previous round's walk is over)
-        if (lane == 0) s_wave[wave] = __popcll(m);
-        __syncthreads();
-        int off = 0, total = 0;
-        for (int w = 0; w < 4; ++w) {
-            off += w < wave ? s_wave[w] : 0;
-            total += s_wave[w];
-        }
-        if (touch) {
-            const int pos = off + __popcll(m & ((1ull << lane) - 1ull));
-            uint4* const dst = reinterpret_cast<uint4*>(&s_sph[pos]);
-            dst[0] = w0;
-            dst[1] = w1;
-            s_sph_id[pos] = cand;
-        }
-        __syncthreads();
-        for (int q = 0; q < total; ++q) {
-            float zs, shade;
-            if (!rv_sphere_fragment(&s_sph[q], i, j, frame.k, &zs, &shade)) continue;
-            if (!(zs <= zbest)) continue;
-            zbest = zs;
-            win = s_sph_id[q];
-            rgb = rv_sphere_colour(s_sph[q].rgb, shade);
-        }
-    }
+    best = view_tile_resolve(best, tvv, tris, list, n, size, i, j, tid, s_tri, s_id);
+    float zbest;
+    uint32_t rgb = view_tile_shade(best, tvv, tris, uvs, tex, tex_w, tex_h, colors, shading, frame, size, i, j, &zbest);
+    const int win = view_tile_spheres(spheres, view, n_lm, tx0, ty0, i, j, tid, frame, s_sph, s_sph_id, s_wave, &zbest,
+                                      &rgb);
 
     // RGBA, alpha 255, top row first: one aligned 4-byte store per pixel
     out[(size_t(view) * size + (size - 1 - j)) * size + i] = rgb | 0xFF000000u;
 
-    // ---- pixels each landmark's sphere won in this tile ----
-    if (lm_pixels && n_lm > 0 && __syncthreads_or(win >= 0)) {
-        for (int base = 0; base < n_lm; base += VIEW_COUNT_SPAN) {
-            for (int q = tid; q < VIEW_COUNT_SPAN; q += 256) s_cnt[q] = 0;
-            __syncthreads();
-            if (win >= base && win < base + VIEW_COUNT_SPAN) atomicAdd(&s_cnt[win - base], 1);
-            __syncthreads();
-            for (int q = tid; q < VIEW_COUNT_SPAN && base + q < n_lm; q += 256)
-                if (s_cnt[q]) atomicAdd(&lm_pixels[size_t(view) * n_lm + base + q], s_cnt[q]);
-            __syncthreads();
-        }
-    }
+    view_tile_count(lm_pixels, view, n_lm, win, tid, s_cnt);
 }
 
 }  // namespace
 
-// The launch set of one landmark view, for an entry point that holds the context and has checked its arguments (api.hip:
-// mvlm_render_landmark_view).  frames_host f32[n_views,4]: cx, cy, half, k = rv_scale(size, half).
-int mvlm_launch_landmark_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot_host, int n_views, int size,
-                              const float* frames_host, const double* landmarks_host, int n_lm, float radius,
-                              const uint8_t* lm_rgb_host, uint8_t* out_dev, int32_t* lm_pixels_dev) {
+// Scratch, copies, fills and the kernels in front of a tile stage: the mesh stages and the landmark projection, for the landmark
+// view's launch set below and the ray view's (raster_rays.hip).  frames_host f32[n_views,4]: cx, cy, half, k = rv_scale(size, half).
+int mvlm_view_launch_stages(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot_host, int n_views, int size,
+                            const float* frames_host, const double* landmarks_host, int n_lm, float radius,
+                            const uint8_t* lm_rgb_host, int32_t* lm_pixels_dev, const char* what, mvlm_view_stages* out) {
+    const std::string no_scratch = std::string(what) + ": scratch allocation failed";
     const int V = mesh->n_verts, T = mesh->n_tris;
     const int tiles_x = size / RM_TILE, tiles = tiles_x * tiles_x;
     const int cap = 4 * T + 8 * tiles;  // tile-list entries per view; larger lists raise an error (mvlm_render_check)
@@ -337,17 +227,17 @@ int mvlm_launch_landmark_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double
     auto* bins = static_cast<int*>(ctx->get_scratch("view.bins", size_t(n_views) * cap * sizeof(int)));
     auto* big_list = static_cast<int*>(ctx->get_scratch("view.big", size_t(n_views) * T * sizeof(int)));
     auto* keys = static_cast<unsigned long long*>(ctx->get_scratch("view.keys", key_bytes));
-    MVLM_REQUIRE(ctx, tv && rot && frames && ctr && offsets && bins && big_list && keys, "landmark view: scratch allocation failed");
+    MVLM_REQUIRE(ctx, tv && rot && frames && ctr && offsets && bins && big_list && keys, no_scratch);
     double* lm = nullptr;
     uint8_t* lm_rgb = nullptr;
     rv_sphere* spheres = nullptr;
     if (n_lm > 0) {
         lm = static_cast<double*>(ctx->get_scratch("view.lm", size_t(n_lm) * 3 * sizeof(double)));
         spheres = static_cast<rv_sphere*>(ctx->get_scratch("view.spheres", size_t(n_views) * n_lm * sizeof(rv_sphere)));
-        MVLM_REQUIRE(ctx, lm && spheres, "landmark view: scratch allocation failed");
+        MVLM_REQUIRE(ctx, lm && spheres, no_scratch);
         if (lm_rgb_host) {
             lm_rgb = static_cast<uint8_t*>(ctx->get_scratch("view.lm_rgb", size_t(n_lm) * 3));
-            MVLM_REQUIRE(ctx, lm_rgb, "landmark view: scratch allocation failed");
+            MVLM_REQUIRE(ctx, lm_rgb, no_scratch);
         }
     }
     int* counts = ctr;
@@ -355,15 +245,17 @@ int mvlm_launch_landmark_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double
     int* n_big = ctr + 2 * n_ctr;
     int* overflow = n_big + n_views;
     hipStream_t st = ctx->stream;
-    // mvlm_render_set_profiling: events between the stages, the first in front of the copies and fills (mvlm_landmark_view_stage_ms)
+    // mvlm_render_set_profiling: events between the stages, the first in front of the copies and fills (mvlm_landmark_view_stage_ms,
+    // mvlm_ray_view_stage_ms)
     hipEvent_t* ev = nullptr;
     if (ctx->render_profiling) {
-        if (ctx->view_events.size() < 8) ctx->view_events.resize(8, nullptr);
+        if (ctx->view_events.size() < 9) ctx->view_events.resize(9, nullptr);
         for (hipEvent_t& e : ctx->view_events)
             if (!e) MVLM_CHECK_HIP(ctx, hipEventCreate(&e));
         ev = ctx->view_events.data();
     }
     ctx->view_events_valid = false;
+    ctx->ray_events_valid = false;
     if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[0], st));
     MVLM_CHECK_HIP(ctx, hipMemcpyAsync(rot, rot_host, size_t(n_views) * 9 * sizeof(double), hipMemcpyHostToDevice, st));
     MVLM_CHECK_HIP(ctx, hipMemcpyAsync(frames, frames_host, size_t(n_views) * sizeof(view_frame), hipMemcpyHostToDevice, st));
@@ -378,7 +270,6 @@ int mvlm_launch_landmark_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double
         MVLM_CHECK_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->render_overflow_host), sizeof(int)));
         *ctx->render_overflow_host = 0;
     }
-    const uint8_t* const vcol = ctx->render_shading == 0 && mesh->colors && !(mesh->tex && mesh->uvs) ? mesh->colors : nullptr;
     if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[1], st));
     hipLaunchKernelGGL(view_transform_kernel, dim3(view_chunk_grid((V + 255) / 256, n_views)), dim3(256), 0, st, mesh->verts, V, rot,
                        frames, n_views, ctx->render_subpixel_bits, tv);
@@ -395,12 +286,37 @@ int mvlm_launch_landmark_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double
         hipLaunchKernelGGL(view_project_kernel, dim3((n_views * n_lm + 255) / 256), dim3(256), 0, st, lm, lm_rgb, n_lm, rot, frames,
                            n_views, size, radius, spheres);
     if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[6], st));
-    hipLaunchKernelGGL(view_tile_kernel, dim3(view_chunk_grid(tiles, n_views)), dim3(256), 0, st, tv, mesh->tris, mesh->uvs, mesh->tex,
-                       mesh->tex_w, mesh->tex_h, reinterpret_cast<const uchar4*>(vcol), V, counts, offsets, bins, cap, keys, frames,
-                       ctx->render_shading, n_views, size, spheres, n_lm, lm_pixels_dev, overflow, ctx->render_overflow_host,
-                       reinterpret_cast<uint32_t*>(out_dev));
-    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[7], st));
+    out->tv = tv;
+    out->frames = frames;
+    out->rot = rot;
+    out->counts = counts;
+    out->offsets = offsets;
+    out->bins = bins;
+    out->cap = cap;
+    out->keys = keys;
+    out->overflow = overflow;
+    out->spheres = spheres;
+    out->vcol = ctx->render_shading == 0 && mesh->colors && !(mesh->tex && mesh->uvs) ? mesh->colors : nullptr;
+    out->ev = ev;
+    return 0;
+}
+
+// The launch set of one landmark view, for an entry point that holds the context and has checked its arguments (api.hip:
+// mvlm_render_landmark_view).  frames_host f32[n_views,4]: cx, cy, half, k = rv_scale(size, half).
+int mvlm_launch_landmark_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot_host, int n_views, int size,
+                              const float* frames_host, const double* landmarks_host, int n_lm, float radius,
+                              const uint8_t* lm_rgb_host, uint8_t* out_dev, int32_t* lm_pixels_dev) {
+    mvlm_view_stages s;
+    if (mvlm_view_launch_stages(ctx, mesh, rot_host, n_views, size, frames_host, landmarks_host, n_lm, radius, lm_rgb_host,
+                                lm_pixels_dev, "landmark view", &s))
+        return 1;
+    const int tiles_x = size / RM_TILE, tiles = tiles_x * tiles_x;
+    hipLaunchKernelGGL(view_tile_kernel, dim3(view_chunk_grid(tiles, n_views)), dim3(256), 0, ctx->stream, s.tv, mesh->tris, mesh->uvs,
+                       mesh->tex, mesh->tex_w, mesh->tex_h, reinterpret_cast<const uchar4*>(s.vcol), mesh->n_verts, s.counts,
+                       s.offsets, s.bins, s.cap, s.keys, s.frames, ctx->render_shading, n_views, size, s.spheres, n_lm,
+                       lm_pixels_dev, s.overflow, ctx->render_overflow_host, reinterpret_cast<uint32_t*>(out_dev));
+    if (s.ev) MVLM_CHECK_HIP(ctx, hipEventRecord(s.ev[7], ctx->stream));
     MVLM_CHECK_HIP(ctx, hipGetLastError());
-    ctx->view_events_valid = ev != nullptr;
+    ctx->view_events_valid = s.ev != nullptr;
     return 0;
 }

@@ -141,4 +141,145 @@ RM_FN uint32_t rv_sphere_colour(uint32_t rgb, float shade) {
     return r | (g << 8) | (b << 16);
 }
 
+/* ---- rays (raster_rays.hip): capsules under the same camera --------------------------------------------------------------- */
+/* A ray is the set of points within ray_radius of the segment a -> b.  Its record, 64 bytes: both ends projected as
+ * rv_project_landmark projects a landmark (window pixels, NOT snapped, z-buffer depth), R = ray_radius * k, the colour, a pixel
+ * box that holds every pixel the capsule can cover, and three per-ray terms of the side's arithmetic, in double:
+ *   ux = (double)Xb - Xa, uy = (double)Yb - Ya, P2 = ux ux + uy uy            (projected length squared, pixels)
+ *   uw = ((double)zb - za) * (1500.0 * (double)k), L2 = P2 + uw uw            (depth extent and 3-D length squared, pixels)
+ *   cosi = sqrt(P2 / L2)                                                      (cosine of the inclination to the window plane)
+ *   g = uw / sqrt(L2 * P2)
+ * A ray whose projected length is at most R / 256 - P2 > (R R) 2^-16 fails, also for a zero-length or end-on ray, P2 = 0 -
+ * is drawn from its caps alone (cosi = g = 0): the side could show only in a crescent at most R / 256 pixel wide beside the
+ * nearer cap's disc, and below that length its quadratic's leading coefficient P2 is lost against the other terms.
+ * A ray with a non-finite end (as given or projected) gets the empty box ix0 > ix1 and covers nothing. */
+typedef struct __attribute__((aligned(16))) {
+    float Xa, Ya, za, R;
+    float Xb, Yb, zb;
+    uint32_t rgb;
+    int16_t ix0, ix1, iy0, iy1;
+    double cosi, g, P2;
+} rv_ray;
+
+#define RV_MAX_RAYS 65536 /* of one call: 478 landmarks x 128 views */
+#define RV_MAX_RAY_RECORDS (1ll << 20) /* n_views * n_rays of one call: 64 MB of records ("rays.rec", grow-only scratch); 3 x 61 184 uses 11.7 MB */
+#define RV_RAY_RGB 0x1AE61Au /* the reference's (0.1, 0.9, 0.1) (ray_visualizer.py) as bytes (26, 230, 26): r | g << 8 | b << 16 */
+
+RM_FN int rv_finite(double x) { return x - x == 0.0; }
+
+RM_FN rv_ray rv_project_ray(const double* m, const double* a, const double* b, float cx, float cy, float half, float k,
+                            float ray_radius, uint32_t rgb, int size) {
+    const rv_sphere sa = rv_project_landmark(m, a, cx, cy, half, k, ray_radius, rgb, size);
+    const rv_sphere sb = rv_project_landmark(m, b, cx, cy, half, k, ray_radius, rgb, size);
+    rv_ray r;
+    r.Xa = sa.X; r.Ya = sa.Y; r.za = sa.z; r.R = sa.R;
+    r.Xb = sb.X; r.Yb = sb.Y; r.zb = sb.z;
+    r.rgb = rgb;
+    r.ix0 = sa.ix0 < sb.ix0 ? sa.ix0 : sb.ix0;
+    r.ix1 = sa.ix1 > sb.ix1 ? sa.ix1 : sb.ix1;
+    r.iy0 = sa.iy0 < sb.iy0 ? sa.iy0 : sb.iy0;
+    r.iy1 = sa.iy1 > sb.iy1 ? sa.iy1 : sb.iy1;
+    r.cosi = 0.0; r.g = 0.0; r.P2 = 0.0;
+    int finite = rv_finite(sa.X) && rv_finite(sa.Y) && rv_finite(sa.z) && rv_finite(sb.X) && rv_finite(sb.Y) && rv_finite(sb.z) &&
+                 rv_finite(sa.R);
+    for (int c = 0; c < 3; ++c) finite = finite && rv_finite(a[c]) && rv_finite(b[c]);
+    if (!finite) {
+        r.Xa = r.Ya = r.za = r.Xb = r.Yb = r.zb = r.R = 0.0f;
+        r.ix0 = r.iy0 = 1;
+        r.ix1 = r.iy1 = 0;
+        return r;
+    }
+    const double ux = (double)r.Xb - (double)r.Xa, uy = (double)r.Yb - (double)r.Ya;
+    const double P2 = ux * ux + uy * uy;
+    const double uw = ((double)r.zb - (double)r.za) * (1500.0 * (double)k);
+    const double L2 = P2 + uw * uw;
+    const double Rd = (double)r.R;
+    if (P2 > (Rd * Rd) * (1.0 / 65536.0)) {
+        r.P2 = P2;
+        r.cosi = sqrt(P2 / L2);
+        r.g = uw / sqrt(L2 * P2);
+    }
+    return r;
+}
+
+/* The ray's fragment at pixel (i, j): the capsule's point nearest the camera on the line of sight through the pixel centre
+ * (px, py) = ((float)i + 0.5f, (float)j + 0.5f) - one of up to three candidates, then ONE clip test on its depth.
+ *   cap A, cap B (float, rv_sphere_fragment's arithmetic before its clip): dx = px - X, dy = py - Y, d2 = dx dx + dy dy,
+ *     candidate iff d2 < R R; hgt = sqrtf(R R - d2), z = z_end - (hgt / k) / 1500, shade = hgt / R
+ *   side (double, only when cosi > 0): qx = (double)px - Xa, qy = (double)py - Ya, e = qx ux + qy uy, cr = qx uy - qy ux,
+ *     h2 = R R - (cr cr) / P2, candidate iff h2 > 0 and 0 <= t <= 1 with hgt = sqrt(h2), t = e / P2 - g hgt (the axis
+ *     parameter of the surface point); up = hgt cosi is the camera-ward part of the radius vector there;
+ *     z = (float)((za + t (zb - za)) - (up / k) / 1500)  - the axis point's z-buffer value minus a height over k and 1500,
+ *     as the sphere forms it, never a depth in pixels -;  shade = (float)(up / R)
+ * The side's candidate, where there is one, IS the fragment: the capsule is convex, a surface point with 0 <= t <= 1 is where the
+ * line of sight enters it, and the caps' points there lie behind or on it - by less than a float of z can tell at k = 50, so
+ * they are not compared.  Otherwise the nearer cap, B only when strictly nearer than A.  No fragment without a candidate - the
+ * union of the three is the 2-D capsule of radius R - or when the chosen z leaves [0, 1]. */
+RM_FN int rv_ray_fragment(const rv_ray* r, int i, int j, float k, float* zr, float* shade) {
+    const float px = (float)i + 0.5f, py = (float)j + 0.5f;
+    const float rr = r->R * r->R;
+    int found = 0;
+    float z = 0.0f, s = 0.0f;
+    {
+        const float dx = px - r->Xa, dy = py - r->Ya;
+        const float d2 = dx * dx + dy * dy;
+        if (d2 < rr) {
+            const float hgt = sqrtf(rr - d2);
+            z = r->za - (hgt / k) / 1500.0f;
+            s = hgt / r->R;
+            found = 1;
+        }
+    }
+    {
+        const float dx = px - r->Xb, dy = py - r->Yb;
+        const float d2 = dx * dx + dy * dy;
+        if (d2 < rr) {
+            const float hgt = sqrtf(rr - d2);
+            const float zb = r->zb - (hgt / k) / 1500.0f;
+            if (!found || zb < z) {
+                z = zb;
+                s = hgt / r->R;
+                found = 1;
+            }
+        }
+    }
+    if (r->cosi > 0.0) {
+        const double ux = (double)r->Xb - (double)r->Xa, uy = (double)r->Yb - (double)r->Ya;
+        const double qx = (double)px - (double)r->Xa, qy = (double)py - (double)r->Ya;
+        const double e = qx * ux + qy * uy, cr = qx * uy - qy * ux;
+        const double Rd = (double)r->R;
+        const double h2 = Rd * Rd - (cr * cr) / r->P2;
+        if (h2 > 0.0) {
+            const double hgt = sqrt(h2);
+            const double t = e / r->P2 - r->g * hgt;
+            if (t >= 0.0 && t <= 1.0) {
+                const double up = hgt * r->cosi;
+                z = (float)(((double)r->za + t * ((double)r->zb - (double)r->za)) - (up / (double)k) / 1500.0);
+                s = (float)(up / Rd);
+                found = 1;
+            }
+        }
+    }
+    if (!found || !(z >= 0.0f && z <= 1.0f)) return 0;
+    *zr = z;
+    *shade = s;
+    return 1;
+}
+
+/* Conservative: 0 only where no pixel of the 16 x 16 tile at (tx0, ty0) can have a fragment of the ray.  The box first; then the
+ * float distance from the centre of the tile's pixel centres to the projected segment against R + the half diagonal of those
+ * centres (7.5 sqrt 2 < 10.75) + a margin for the roundings of this very distance: 1 pixel and 2^-18 of the coordinates'
+ * magnitudes (the foot point's parameter carries a relative error of a few 2^-24 of them).  A NaN anywhere says "touches". */
+RM_FN int rv_ray_touches_tile(const rv_ray* r, int tx0, int ty0) {
+    if (!(r->ix0 <= tx0 + 15 && r->ix1 >= tx0 && r->iy0 <= ty0 + 15 && r->iy1 >= ty0)) return 0;
+    const float ux = r->Xb - r->Xa, uy = r->Yb - r->Ya;
+    const float qx = ((float)tx0 + 8.0f) - r->Xa, qy = ((float)ty0 + 8.0f) - r->Ya;
+    const float p2 = ux * ux + uy * uy;
+    float t = p2 > 0.0f ? (qx * ux + qy * uy) / p2 : 0.0f;
+    t = t > 0.0f ? (t < 1.0f ? t : 1.0f) : 0.0f;
+    const float dx = qx - t * ux, dy = qy - t * uy;
+    const float thr = (r->R + 11.75f) + (((fabsf(r->Xa) + fabsf(r->Ya)) + (fabsf(r->Xb) + fabsf(r->Yb))) * (1.0f / 262144.0f));
+    return !(dx * dx + dy * dy > thr * thr);
+}
+
 #endif

@@ -91,7 +91,8 @@ class Pipeline(abc.ABC):
                  render_image_folder: Path | None = None, visualize_rays: bool = False,
                  screenshot_folder: Path | None = None, device: int = 0, shard_views: bool = False,
                  verbose: bool = True, render_multisamples: int = 0, landmark_report: bool = False,
-                 visualize_img: bool = False, visualize_size: int = 1024, visualize_name: str | None = None):
+                 visualize_img: bool = False, visualize_size: int = 1024, visualize_name: str | None = None,
+                 visualize_rays_img: bool = False, visualize_rays_poses=((0, 0, 0), (0, 60, 0), (0, -60, 0))):
         self.render_image_stack = render_image_stack
         self.render_image_folder = render_image_folder
         self.n_views = n_views
@@ -116,7 +117,21 @@ class Pipeline(abc.ABC):
         # default): nothing of it is launched or allocated.
         self.visualize_img = bool(visualize_img)
         self.visualize_size = int(visualize_size)
-        if self.visualize_img and (self.visualize_size < 64 or self.visualize_size > 2048 or self.visualize_size % 16):
+        # visualize_rays_img: after every successful prediction the resident mesh is drawn with every selected view ray (the device
+        # tensors the consensus just used, clipped on the device when clip_rays_to_mesh is set) and the landmarks, one picture
+        # per pose of visualize_rays_poses in ONE call (the reference's visualize_rays=True, visualization/ray_visualizer.py;
+        # HipRenderer3D.render_ray_view), into <screenshot_folder or visualization/ray_screenshots>/
+        # <stem>_<visualize_name>_rays_<i>.png.  With landmark_report the rays carry LandmarkReport.ray_colours().  A flag of
+        # its own: visualize_rays keeps writing its .npz and nothing else.
+        self.visualize_rays_img = bool(visualize_rays_img)
+        self.visualize_rays_poses = np.asarray(visualize_rays_poses, dtype=np.float64).reshape(-1, 3)
+        self.last_ray_view_paths: list = []
+        # (mesh, starts, ends, landmarks in the uploaded space, report) of the current call, kept only between a prediction made by
+        # predict_one_file / predict_files (_keep_ray_view) and the _after_prediction that draws it: predict_mesh_device called on
+        # its own has no file name, draws nothing and leaves nothing behind
+        self._ray_view = None
+        self._keep_ray_view = False
+        if (self.visualize_img or self.visualize_rays_img) and (self.visualize_size < 64 or self.visualize_size > 2048 or self.visualize_size % 16):
             raise ValueError(f"visualize_size must be a multiple of 16 in 64..2048, not {visualize_size}")
         name = type(self).__name__.lower()
         self.visualize_name = visualize_name if visualize_name is not None else name[:-len("pipeline")] if name.endswith("pipeline") else name
@@ -248,6 +263,7 @@ class Pipeline(abc.ABC):
             load_seconds = time.perf_counter() - t0
         with self._lock:
             self._rays = None
+            self._ray_view, self._keep_ray_view = None, self.visualize_rays_img
             with self._timer.stage("total"):
                 if mesh is not None:
                     landmarks = self._predict_fused(file_name, mesh=mesh)
@@ -268,6 +284,54 @@ class Pipeline(abc.ABC):
             except Exception as e:  # noqa: BLE001 - general_pipeline.py:129-130: a failed visualisation never fails the call
                 print(f"[Pipeline] Ray visualization failed: {e}")
         self._rays = None
+        if self.visualize_rays_img and self._ray_view is not None and landmarks is not None:
+            try:
+                self.draw_ray_view(file_name, landmark_indices, view_indices, clip_rays_to_mesh)
+            except Exception as e:  # noqa: BLE001 - as the ray dump: a failed picture never fails the call
+                print(f"[Pipeline] Ray view failed: {e}")
+        self._ray_view, self._keep_ray_view = None, False
+
+    def draw_ray_view(self, file_name: Path, landmark_indices=None, view_indices=None, clip_to_mesh: bool = True):
+        """``visualize_rays_img``: the pictures the reference's ``RayVisualizer`` shows (ray_visualizer.py:150-338), drawn by
+        ``HipRenderer3D.render_ray_view_device`` - the mesh as it lies on the device, the rays of the selected landmarks and
+        views (subset exactly as ``dump_rays`` subsets them) from the tensors the consensus used, clipped on the device, the
+        landmarks in the uploaded space; all poses in one call.  Returns the paths (also ``last_ray_view_paths``)."""
+        import torch
+
+        from ..utils.viewer import write_view_png
+
+        self._check_visualize()
+        mesh, starts, ends, landmarks, report = self._ray_view
+        with self._timer.stage("visualize_rays"):
+            dev = torch.device("cuda", self.renderer_3d.ctx.device)
+            starts = starts if hasattr(starts, "data_ptr") else torch.from_numpy(np.ascontiguousarray(starts, dtype=np.float64)).to(dev)
+            ends = ends if hasattr(ends, "data_ptr") else torch.from_numpy(np.ascontiguousarray(ends, dtype=np.float64)).to(dev)
+            nl, nv = int(starts.shape[0]), int(starts.shape[1])
+            lm_idx = list(range(nl)) if landmark_indices is None else [int(i) % nl for i in landmark_indices]
+            v_idx = list(range(nv)) if view_indices is None else [int(i) % nv for i in view_indices]
+            li = torch.as_tensor(lm_idx, dtype=torch.long, device=dev)
+            vi = torch.as_tensor(v_idx, dtype=torch.long, device=dev)
+            fs = starts.index_select(0, li).index_select(1, vi).contiguous()
+            fe = ends.index_select(0, li).index_select(1, vi).contiguous()
+            if clip_to_mesh and fs.numel():
+                fe, _ = self.estimator_3d.clip_rays_device(mesh, fs, fe)
+            landmarks = np.asarray(landmarks, dtype=np.float64).reshape(-1, 3)
+            colours = report.branch_colours() if report is not None else None
+            ray_colours = None
+            if report is not None:
+                ray_colours = report.ray_colours(np.asarray(report.view_indices)[v_idx])[lm_idx].reshape(-1, 3)
+            finite = np.isfinite(landmarks).all(axis=1)
+            if not finite.all():
+                landmarks = landmarks[finite]
+                colours = None if colours is None else colours[finite]
+            images = self.renderer_3d.render_ray_view(mesh, landmarks, fs, fe, poses=self.visualize_rays_poses, size=self.visualize_size,
+                                                      colors=colours, ray_colors=ray_colours)
+            folder = Path(self.screenshot_folder) if self.screenshot_folder else Path.cwd() / "visualization" / "ray_screenshots"
+            stem = Path(file_name).stem
+            self.last_ray_view_paths = [write_view_png(image, folder / f"{stem}_{self.visualize_name}_rays_{i}.png")
+                                        for i, image in enumerate(images)]
+        self._say(f"[Pipeline] ray view written to {[str(q) for q in self.last_ray_view_paths]}")
+        return self.last_ray_view_paths
 
     def dump_rays(self, file_name: Path, landmarks, landmark_indices=None, view_indices=None, clip_to_mesh: bool = True):
         """What the reference hands to its VTK ``RayVisualizer`` (general_pipeline.py:111-128), written
@@ -457,10 +521,16 @@ class Pipeline(abc.ABC):
         self.last_error = error
         if self.visualize_img and (not sharded or rank == 0):  # (sharded: every rank holds the result, one draws)
             self._draw_landmark_view(mesh, landmarks, self.last_report if layout is not None else None)  # (THIS pass's report)
+        if self._keep_ray_view and (not sharded or rank == 0):  # drawn by _after_prediction, which knows the file and the selection
+            self._ray_view = (mesh, starts, ends, landmarks, self.last_report if layout is not None else None)
         return landmarks, error
 
     def _check_visualize(self):
-        """``visualize_img`` needs the renderer that holds the mesh on the device: said before the prediction, not after it."""
+        """``visualize_img`` and ``visualize_rays_img`` need the renderer that holds the mesh on the device: said before the
+        prediction, not after it."""
+        if self.visualize_rays_img and not isinstance(self.renderer_3d, HipRenderer3D):
+            raise ValueError("visualize_rays_img needs a HipRenderer3D in the renderer slot (it draws the mesh resident on the "
+                             f"device), not {type(self.renderer_3d).__name__}")
         if self.visualize_img and not isinstance(self.renderer_3d, HipRenderer3D):
             raise ValueError("visualize_img needs a HipRenderer3D in the renderer slot (it draws the mesh resident on the device), "
                              f"not {type(self.renderer_3d).__name__}")
@@ -499,7 +569,7 @@ class Pipeline(abc.ABC):
             return False
         if self.landmark_report:
             return False  # one report per scan, made by the scan's own pass
-        if self.visualize_img:
+        if self.visualize_img or self.visualize_rays_img:
             return False  # one picture per scan, drawn by the scan's own pass while its mesh is resident
         n = int(self.renderer_3d.n_views)
         return e3.expected_counts(p2.get_lm_count(), n) is not None and n_scans * n <= (p2.device_batch or 128)
@@ -680,6 +750,7 @@ class Pipeline(abc.ABC):
                     continue
                 with self._lock:
                     self._rays = None
+                    self._ray_view, self._keep_ray_view = None, self.visualize_rays_img
                     with self._timer.stage("total"):
                         landmarks = self._predict_fused(f, mesh=mesh)
                     self._after_prediction(f, landmarks)
@@ -776,6 +847,8 @@ class Pipeline(abc.ABC):
                                               view_indices=np.nonzero(kept)[0] if kept.dtype == bool else kept)
         if self.visualize_img:  # behind the report: the spheres carry THIS scan's branches
             self._draw_landmark_view(pd, drawn, self.last_report if arrays is not None else None)
+        if self._keep_ray_view:
+            self._ray_view = (pd, np.asarray(lines_s), np.asarray(lines_e), drawn, self.last_report if arrays is not None else None)
         return landmarks
 
     def visualize_image_stack(self, image_stack: np.ndarray, file_name: Path, first_index: int = 0):

@@ -357,6 +357,102 @@ class HipRenderer3D:
         self.check()
         return (image, counts) if return_pixels else image
 
+    # ---- ray view (visualization/ray_visualizer.py's offscreen window) -------------------------
+    @staticmethod
+    def _ray_array(x, what):
+        """starts / ends as given: a device tensor stays on the device (float64, contiguous, [n,3]); anything else becomes a numpy
+        float64 [n,3]."""
+        if hasattr(x, "data_ptr"):
+            import torch
+
+            if x.shape[-1] != 3:
+                raise ValueError(f"{what} must have shape [..., 3], not {tuple(x.shape)}")
+            return x.to(torch.float64).reshape(-1, 3).contiguous()
+        a = np.asarray(x, dtype=np.float64)
+        if a.ndim == 0 or a.shape[-1] != 3:
+            raise ValueError(f"{what} must have shape [..., 3], not {a.shape}")
+        return np.ascontiguousarray(a.reshape(-1, 3))
+
+    @classmethod
+    def ray_view_arguments(cls, starts, ends, ray_radius=0.5, ray_colors=None):
+        """The host checks of ``render_ray_view`` that need no device: (starts [n,3], ends [n,3], ray_radius, ray_colors u8 [n,3] or
+        None).  ``starts`` / ``ends`` [..., 3], numpy or device tensors, are flattened to [n,3] float64."""
+        a, b = cls._ray_array(starts, "starts"), cls._ray_array(ends, "ends")
+        if tuple(a.shape) != tuple(b.shape):
+            raise ValueError(f"starts and ends must hold the same rays, not {tuple(a.shape)} and {tuple(b.shape)}")
+        n = int(a.shape[0])
+        if n > 65536:
+            raise ValueError(f"at most 65536 rays per call, not {n}")
+        ray_radius = float(ray_radius)
+        if not np.isfinite(ray_radius) or ray_radius < 0.0:
+            raise ValueError(f"ray_radius must be finite and >= 0, not {ray_radius}")
+        rgb = None
+        if ray_colors is not None:
+            rgb = np.ascontiguousarray(ray_colors, dtype=np.uint8)
+            if rgb.shape != (n, 3):
+                raise ValueError(f"ray_colors must be uint8 [{n},3], not {rgb.shape}")
+        return a, b, ray_radius, rgb
+
+    def render_ray_view_device(self, mesh: Mesh, landmarks, starts, ends, poses=None, size: int = 1024, frame="fit", radius=None,
+                               ray_radius: float = 0.5, colors=None, ray_colors=None, return_pixels: bool = False):
+        """``render_ray_view`` with the results left on the device: uint8 [n,S,S,4] RGBA (and int32 [n,NL], int32 [n,NR] with
+        ``return_pixels``).  Device tensors of rays are read where they are.  Only enqueues work."""
+        import torch
+
+        a, b, ray_radius, rrgb = self.ray_view_arguments(starts, ends, ray_radius, ray_colors)
+        poses, frames, lm, radius = self.landmark_view_arguments(mesh, landmarks, poses, frame, radius)
+        n, nl, nr = poses.shape[0], lm.shape[0], int(a.shape[0])
+        rgb = None
+        if colors is not None:
+            rgb = np.ascontiguousarray(colors, dtype=np.uint8)
+            if rgb.shape != (nl, 3):
+                raise ValueError(f"colors must be uint8 [{nl},3], not {rgb.shape}")
+        size = int(size)
+        if size < 64 or size > 2048 or size % 16:
+            raise ValueError(f"size must be a multiple of 16 in 64..2048, not {size}")
+        dev = torch.device("cuda", self.ctx.device)
+        a_dev = a.to(dev) if hasattr(a, "data_ptr") else torch.from_numpy(a).to(dev)
+        b_dev = b.to(dev) if hasattr(b, "data_ptr") else torch.from_numpy(b).to(dev)
+        out = torch.empty((n, size, size, 4), dtype=torch.uint8, device=dev)
+        pixels = torch.empty((n, nl), dtype=torch.int32, device=dev) if return_pixels else None
+        ray_pixels = torch.empty((n, nr), dtype=torch.int32, device=dev) if return_pixels else None
+        rot = np.ascontiguousarray(view_rotations(poses), dtype=np.float64)
+        handle = upload_mesh(self.ctx, mesh)
+        self.ctx.bind_current_stream(torch, dev)
+        mode = (1 if self.shading == "geometry" else 0, self.subpixel_bits, self.multisamples)
+        if getattr(self.ctx, "_render_mode", None) != mode:  # (the view reads the shading and the sub-pixel bits)
+            self.ctx.check(self.ctx.lib.mvlm_set_render_shading(self.ctx.handle, mode[0]))
+            self.ctx.check(self.ctx.lib.mvlm_set_render_subpixel_bits(self.ctx.handle, mode[1]))
+            self.ctx.check(self.ctx.lib.mvlm_set_render_multisamples(self.ctx.handle, mode[2]))
+            self.ctx._render_mode = mode
+        self.ctx.check(self.ctx.lib.mvlm_render_ray_view(
+            self.ctx.handle, handle, _lib.as_ptr(rot, C.c_double), n, size, _lib.as_ptr(frames, C.c_float),
+            _lib.as_ptr(lm, C.c_double) if nl else None, nl, C.c_float(radius), None if rgb is None or nl == 0 else _lib.as_ptr(rgb, C.c_uint8),
+            C.c_void_p(a_dev.data_ptr()) if nr else None, C.c_void_p(b_dev.data_ptr()) if nr else None, nr, C.c_float(ray_radius),
+            None if rrgb is None or nr == 0 else _lib.as_ptr(rrgb, C.c_uint8), C.c_void_p(out.data_ptr()),
+            C.c_void_p(pixels.data_ptr()) if pixels is not None and nl else None,
+            C.c_void_p(ray_pixels.data_ptr()) if ray_pixels is not None and nr else None), ValueError)
+        self._ray_view_keepalive = (a_dev, b_dev)  # (read by the enqueued kernels)
+        return (out, pixels, ray_pixels) if return_pixels else out
+
+    def render_ray_view(self, mesh: Mesh, landmarks, starts, ends, poses=None, size: int = 1024, frame="fit", radius=None,
+                        ray_radius: float = 0.5, colors=None, ray_colors=None, return_pixels: bool = False):
+        """The landmark view with every ray ``starts[r] -> ends[r]`` drawn between the mesh and the spheres, as the reference's
+        ``RayVisualizer`` shows them (visualization/ray_visualizer.py): an opaque, head-lit tube of ``ray_radius`` model units,
+        green unless ``ray_colors`` (uint8 [NR,3]) says otherwise, depth-tested against the mesh and the spheres.  uint8 [n,S,S,3];
+        with ``return_pixels`` also int32 [n,NL] and int32 [n,NR], the pixels each sphere and each ray won in each view.
+        ``starts`` / ``ends`` [..., 3]: numpy arrays or device tensors (``HipEstimator3D.lines_device``'s, clipped or not), in
+        the mesh's coordinates; a ray with a non-finite coordinate is left out.  ``frame="fit"`` fits the mesh and the landmarks,
+        not the rays, which reach 500 units out.  The other arguments: ``render_landmark_view`` ("Ray view")."""
+        res = self.render_ray_view_device(mesh, landmarks, starts, ends, poses, size, frame, radius, ray_radius, colors, ray_colors,
+                                          return_pixels)
+        out, pixels, ray_pixels = res if return_pixels else (res, None, None)
+        image = out.cpu().numpy()[..., :3].copy()
+        counts = pixels.cpu().numpy() if pixels is not None else None
+        ray_counts = ray_pixels.cpu().numpy() if ray_pixels is not None else None
+        self.check()
+        return (image, counts, ray_counts) if return_pixels else image
+
     def rotations_device(self):
         """The last render's rotation table where the rasteriser keeps it on the device (f64[N,9]; valid until this context's
         next render): an object with ``data_ptr()`` that ``HipEstimator3D.lines_device(rot_dev=...)`` takes - the rays of the

@@ -22,6 +22,8 @@ __all__ = ["LandmarkReport", "ReportLayout", "CSV_HEADER", "texel"]
 
 N_STATS = 9  # MVLM_REPORT_STATS: rms, max_dist, sigma2, cov xx yy zz xy xz yz
 VIEW_KEPT, VIEW_DRAWN, VIEW_INLIER, VIEW_USED = 1, 2, 4, 8  # MVLM_VIEW_* (include/mvlm_hip.h)
+# the ray view's colours by what the consensus did with a view's ray (LandmarkReport.ray_colours)
+RAY_USED, RAY_KEPT, RAY_FILTERED = (26, 230, 26), (255, 165, 0), (160, 160, 160)
 CSV_HEADER = "index,x,y,z,n_kept,n_inliers,n_used,branch,error,rms,sigma,snap_dist,tri,b0,b1,b2,u,v"
 
 
@@ -97,6 +99,25 @@ class LandmarkReport:
         """uint8 [NL,3]: ``BRANCH_COLOURS`` of every landmark's branch (the sphere colours of the landmark view)."""
         table = np.array([BRANCH_COLOURS[b] for b in (0, 1, 2)], np.uint8)
         return table[np.clip(np.asarray(self.branch, np.int64), 0, 2)]
+
+    def ray_colours(self, views=None) -> np.ndarray:
+        """uint8 [NL,len(views),3]: a colour per view ray (the ray view, Pipeline(visualize_rays_img=True)) - ``RAY_USED`` green
+        for a line of the final fit (``VIEW_USED``), ``RAY_KEPT`` orange for one that survived the score filter but was not
+        used, ``RAY_FILTERED`` grey for one filtered out.  ``views``: view numbers as ``view_indices`` lists them (default:
+        all of them, in that order); a view the report does not hold raises."""
+        cols = np.arange(self.view_flags.shape[1])
+        if views is not None:
+            where = {int(v): j for j, v in enumerate(np.asarray(self.view_indices))}
+            missing = [int(v) for v in np.asarray(views).ravel() if int(v) not in where]
+            if missing:
+                raise ValueError(f"views {missing} are not among the report's view_indices")
+            cols = np.array([where[int(v)] for v in np.asarray(views).ravel()], dtype=np.int64)
+        flags = np.asarray(self.view_flags)[:, cols]
+        out = np.empty(flags.shape + (3,), np.uint8)
+        out[...] = RAY_FILTERED
+        out[(flags & VIEW_KEPT) != 0] = RAY_KEPT
+        out[(flags & VIEW_USED) != 0] = RAY_USED
+        return out
 
     def __init__(self, arrays: dict, landmarks=None, view_indices=None):
         a = arrays

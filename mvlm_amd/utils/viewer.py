@@ -7,11 +7,12 @@ window (``save=False``, ``--visualize-iter``) is out of scope.
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from pathlib import Path
 
 import numpy as np
 
-__all__ = ["LandmarkViewer", "view_path", "write_view_png"]
+__all__ = ["LandmarkViewer", "RayVisualizer", "RayVisualizerConfig", "view_path", "write_view_png"]
 
 
 def view_path(filename, pname: str | None = None) -> Path:
@@ -46,3 +47,65 @@ class LandmarkViewer:
         mesh = load_mesh(self.filename)
         self.image = renderer.render_landmark_view(mesh, landmarks, size=self.size)[0]
         self.out_path = write_view_png(self.image, view_path(self.filename, pname))
+
+
+def colour_byte(c: float) -> int:
+    """A colour component in 0..1 as the byte the views carry: round(255 c), clamped."""
+    return int(min(255, max(0, int(float(c) * 255.0 + 0.5))))
+
+
+@dataclass
+class RayVisualizerConfig:
+    """What the offscreen ray view honours of the reference's ``RayVisualizerConfig`` (ray_visualizer.py) - ``ray_color``,
+    ``landmark_color``, ``landmark_radius`` - and three fields of its own: the pictures' side in pixels, the rays' radius in
+    model units (the reference draws lines 8 pixels wide, whatever the zoom) and the poses (degrees rx, ry, rz), one picture each.
+    Rays are opaque here; the reference's 0.9 opacity and its bounding-box outline are left out."""
+    ray_color: tuple = (0.1, 0.9, 0.1)
+    landmark_color: tuple = (0.1, 0.1, 0.9)
+    landmark_radius: float = 1.5
+    size: int = 1024
+    ray_radius: float = 0.5
+    poses: tuple = ((0, 0, 0), (0, 60, 0), (0, -60, 0))
+
+
+class RayVisualizer:
+    """The reference's ``RayVisualizer`` for the offscreen case: ``show`` selects and clips the rays as the reference does, draws
+    them with the mesh and the landmarks (HipRenderer3D.render_ray_view) and writes one PNG per pose.  No window is opened."""
+
+    def __init__(self, config: RayVisualizerConfig | None = None, device: int = 0):
+        self.config = config or RayVisualizerConfig()
+        self.device = device
+        self.images = None
+
+    def show(self, mesh, line_starts, line_ends, landmarks=None, screenshot_dir=None, landmark_indices=None, view_indices=None,
+             obj_path=None, clip_to_mesh: bool = True):
+        """``mesh``: a ``Mesh``; ``line_starts`` / ``line_ends`` [NL,N,3]; ``landmarks`` [NL,3] or None.  ``landmark_indices`` /
+        ``view_indices`` pick rows and columns of the rays (default all).  The PNGs go to ``screenshot_dir`` (default
+        ``visualization/ray_screenshots`` under the working directory) as ``<stem>_rays_<i>.png``, ``stem`` from ``obj_path``
+        or the mesh's own path.  Returns their paths."""
+        from .estimator3d import HipEstimator3D
+        from .mesh_io import Mesh
+        from .render3d import HipRenderer3D
+
+        if not isinstance(mesh, Mesh):
+            raise TypeError("RayVisualizer.show expects a Mesh (mvlm_amd.utils.load_mesh)")
+        cfg = self.config
+        starts, ends = np.asarray(line_starts, dtype=np.float64), np.asarray(line_ends, dtype=np.float64)
+        if starts.ndim != 3 or starts.shape[-1] != 3 or starts.shape != ends.shape:
+            raise ValueError(f"line_starts and line_ends must both be [NL,N,3], not {starts.shape} and {ends.shape}")
+        lm_idx = list(range(starts.shape[0])) if landmark_indices is None else [int(i) % starts.shape[0] for i in landmark_indices]
+        v_idx = list(range(starts.shape[1])) if view_indices is None else [int(i) % starts.shape[1] for i in view_indices]
+        fs = np.ascontiguousarray(starts[np.ix_(lm_idx, v_idx)])
+        fe = np.ascontiguousarray(ends[np.ix_(lm_idx, v_idx)])
+        if clip_to_mesh and fs.size:
+            fe, _ = HipEstimator3D(device=self.device).clip_rays_to_mesh(mesh, fs, fe)
+        renderer = HipRenderer3D(n_views=1, device=self.device, verbose=False)
+        nl = 0 if landmarks is None else len(np.asarray(landmarks).reshape(-1, 3))
+        nr = fs.reshape(-1, 3).shape[0]
+        self.images = renderer.render_ray_view(
+            mesh, landmarks, fs, fe, poses=cfg.poses, size=cfg.size, radius=cfg.landmark_radius, ray_radius=cfg.ray_radius,
+            colors=np.tile(np.array([colour_byte(c) for c in cfg.landmark_color], np.uint8), (nl, 1)) if nl else None,
+            ray_colors=np.tile(np.array([colour_byte(c) for c in cfg.ray_color], np.uint8), (nr, 1)) if nr else None)
+        folder = Path(screenshot_dir) if screenshot_dir else Path("visualization") / "ray_screenshots"
+        stem = Path(obj_path or getattr(mesh, "path", None) or "mesh.obj").stem
+        return [write_view_png(image, folder / f"{stem}_rays_{i}.png") for i, image in enumerate(self.images)]
