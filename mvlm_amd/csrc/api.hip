@@ -57,8 +57,8 @@ extern "C" void mvlm_ctx_destroy(mvlm_ctx* ctx) {
     if (ctx->cnn.blob) hipFree(ctx->cnn.blob);
     if (ctx->cnn.fast_blob) hipFree(ctx->cnn.fast_blob);
     if (ctx->cnn.fast16_blob) hipFree(ctx->cnn.fast16_blob);
-    if (ctx->cnn.wino_blob) hipFree(ctx->cnn.wino_blob);
-    if (ctx->cnn.wino4_blob) hipFree(ctx->cnn.wino4_blob);
+    for (auto& ww : ctx->cnn.wino)
+        if (ww.blob) hipFree(ww.blob);
     if (ctx->cnn.fast16_flag) hipFree(ctx->cnn.fast16_flag);
     if (ctx->switch_event) hipEventDestroy(ctx->switch_event);
     for (int i = 0; i < 2; ++i) {
@@ -86,8 +86,7 @@ extern "C" void mvlm_ctx_destroy(mvlm_ctx* ctx) {
         if (e) hipEventDestroy(e);
     for (auto e : ctx->cnn.sync_events)
         if (e) hipEventDestroy(e);
-    for (auto& g : ctx->cnn.graphs)
-        if (g.exec) hipGraphExecDestroy(g.exec);
+    ctx->cnn.drop_graphs();
     if (ctx->cnn.side_stream) hipStreamDestroy(ctx->cnn.side_stream);
     if (ctx->cnn.capture_stream) hipStreamDestroy(ctx->cnn.capture_stream);
     delete ctx;
@@ -610,16 +609,14 @@ extern "C" int mvlm_conv2d(mvlm_ctx* ctx, const float* x_dev, int batch, int cin
         for (int i = 0; i < n; ++i) blob[off + i] = src[i];
         return long(off);
     };
-    // the Winograd form beside it where such a tile could be chosen or forced
-    long ww_off = -1;
-    if (mvlm_conv_wino_serves_slot(ksize, cin_pad, cout_pad)) {
-        ww_off = long(push(size_t(12) * cin_pad * cout_pad));
-        mvlm_winograd_transform(blob.data() + w_off, cin_pad, cout_pad, blob.data() + ww_off);
-    }
-    long ww4_off = -1;
-    if (mvlm_conv_wino4_serves_slot(ksize, cin_pad, cout_pad)) {
-        ww4_off = long(push(size_t(18) * cin_pad * cout_pad));
-        mvlm_winograd4_transform(blob.data() + w_off, cin_pad, cout_pad, blob.data() + ww4_off);
+    // the Winograd forms beside it where such a tile could be chosen or forced
+    long ww_off[MVLM_WINO_FORMS_N];
+    for (int f = 0; f < MVLM_WINO_FORMS_N; ++f) {
+        const WinoForm& form = mvlm_wino_form(f);
+        ww_off[f] = -1;
+        if (!form.serves_slot(ksize, cin_pad, cout_pad)) continue;
+        ww_off[f] = long(push(size_t(form.slices) * cin_pad * cout_pad));
+        form.transform(blob.data() + w_off, cin_pad, cout_pad, blob.data() + ww_off[f]);
     }
     const long b_off = vec(bias_host, cout, cout_pad);
     const long ps_off = vec(pre_scale_host, cin, cin_pad), pt_off = vec(pre_shift_host, cin, cin_pad);
@@ -637,8 +634,7 @@ extern "C" int mvlm_conv2d(mvlm_ctx* ctx, const float* x_dev, int batch, int cin
     a.H = h;
     a.W = w;
     a.w = d + w_off;
-    a.w_wino = ww_off < 0 ? nullptr : d + ww_off;
-    a.w_wino4 = ww4_off < 0 ? nullptr : d + ww4_off;
+    for (int f = 0; f < MVLM_WINO_FORMS_N; ++f) a.*mvlm_wino_form(f).weights = ww_off[f] < 0 ? nullptr : d + ww_off[f];
     a.cout = cout;
     a.cout_pad = cout_pad;
     a.ksize = ksize;
@@ -690,8 +686,8 @@ extern "C" int mvlm_conv_bench(mvlm_ctx* ctx, int batch, int cin, int cout, int 
     a.B = batch;
     a.H = a.W = size;
     a.w = w;
-    if (mvlm_conv_wino_serves_slot(ksize, cin_pad, cout_pad)) a.w_wino = w;  // zero data: the transformed weights are zeros too
-    if (mvlm_conv_wino4_serves_slot(ksize, cin_pad, cout_pad)) a.w_wino4 = w;
+    for (int f = 0; f < MVLM_WINO_FORMS_N; ++f)  // (zero data: the transformed weights are zeros too)
+        if (mvlm_wino_form(f).serves_slot(ksize, cin_pad, cout_pad)) a.*mvlm_wino_form(f).weights = w;
     a.cout = cout;
     a.cout_pad = cout_pad;
     a.ksize = ksize;

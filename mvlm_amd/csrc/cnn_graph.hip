@@ -171,8 +171,10 @@ struct Exec {
         a.cin_pad = r[4];
         a.cout_pad = r[5];
         a.w = blob(r[6]);
-        a.w_wino = (size_t(slot) < st.wino_off.size() && st.wino_off[size_t(slot)] >= 0) ? st.wino_blob + st.wino_off[size_t(slot)] : nullptr;
-        a.w_wino4 = (size_t(slot) < st.wino4_off.size() && st.wino4_off[size_t(slot)] >= 0) ? st.wino4_blob + st.wino4_off[size_t(slot)] : nullptr;
+        for (int f = 0; f < MVLM_WINO_FORMS_N; ++f) {
+            const CnnState::WinoWeights& ww = st.wino[f];
+            a.*mvlm_wino_form(f).weights = (size_t(slot) < ww.off.size() && ww.off[size_t(slot)] >= 0) ? ww.blob + ww.off[size_t(slot)] : nullptr;
+        }
         a.bias = blob(r[7]);
         a.pre_scale = blob(r[8]);
         a.pre_shift = blob(r[9]);
@@ -204,7 +206,8 @@ struct Exec {
     // the multiply-adds the launch's MFMAs execute: an F(2,3) Winograd tile spends 6 per output and input channel, the F(4,3) tile 4.5,
     // where a direct 3x3 spends 9
     static double conv_flops(const ConvArgs& a, int variant = -1) {
-        const double taps = mvlm_conv_variant_is_wino(variant) ? 6.0 : mvlm_conv_variant_is_wino4(variant) ? 4.5 : double(a.ksize * a.ksize);
+        const double taps = mvlm_conv_variant_is_wino(variant) ? mvlm_wino_form(MVLM_WINO_F23).macs
+                            : mvlm_conv_variant_is_wino4(variant) ? mvlm_wino_form(MVLM_WINO_F43).macs : double(a.ksize * a.ksize);
         return 2.0 * a.cin * a.cout * taps * double(a.H) * a.W * a.B * a.n_par;
     }
 
@@ -874,21 +877,14 @@ extern "C" int mvlm_cnn_load(mvlm_ctx* ctx, const float* blob_host, size_t n_flo
         (void)hipFree(st.fast16_blob);
         st.fast16_blob = nullptr;
     }
-    st.wino_off.clear();
-    st.wino_bytes = 0;
-    if (st.wino_blob) {
-        (void)hipFree(st.wino_blob);
-        st.wino_blob = nullptr;
+    for (CnnState::WinoWeights& ww : st.wino) {
+        ww.off.clear();
+        if (ww.blob) {
+            (void)hipFree(ww.blob);
+            ww.blob = nullptr;
+        }
     }
-    st.wino4_off.clear();
-    st.wino4_bytes = 0;
-    if (st.wino4_blob) {
-        (void)hipFree(st.wino4_blob);
-        st.wino4_blob = nullptr;
-    }
-    for (auto& g : st.graphs)
-        if (g.exec) hipGraphExecDestroy(g.exec);  // captured launches point into the old weight blob
-    st.graphs.clear();
+    st.drop_graphs();  // captured launches point into the old weight blob
     st.desc.assign(desc_host, desc_host + size_t(n_slots) * MVLM_CONV_DESC_INTS);
     // validate every offset before anything is launched with it
     for (int s = 0; s < n_slots; ++s) {
@@ -910,40 +906,24 @@ extern "C" int mvlm_cnn_load(mvlm_ctx* ctx, const float* blob_host, size_t n_flo
                  "cnn_load: conv11 output channels != n_landmarks");
     MVLM_CHECK_HIP(ctx, hipMalloc(&st.blob, n_floats * sizeof(float)));
     MVLM_CHECK_HIP(ctx, hipMemcpy(st.blob, blob_host, n_floats * sizeof(float), hipMemcpyHostToDevice));
-    // The weights are fixed for the life of the model: the Winograd form of every 3x3 slot a Winograd tile can serve is
-    // made here, once (4/3 of those slots' weight bytes in a buffer of its own).
-    {
-        std::vector<float> wino;
-        st.wino_off.assign(size_t(n_slots), -1);
+    // The weights are fixed for the life of the model: each Winograd form of every 3x3 slot a tile of that form can serve is
+    // made here, once, in a buffer of its own (4/3 of those slots' weight bytes for F(2,3), twice for F(4,3)).
+    for (int f = 0; f < MVLM_WINO_FORMS_N; ++f) {
+        const WinoForm& form = mvlm_wino_form(f);
+        CnnState::WinoWeights& ww = st.wino[f];
+        std::vector<float> host;
+        ww.off.assign(size_t(n_slots), -1);
         for (int s = 0; s < n_slots; ++s) {
             const int32_t* r = &st.desc[size_t(s) * MVLM_CONV_DESC_INTS];
-            if (!r[0] || !mvlm_conv_wino_serves_slot(r[3], r[4], r[5])) continue;
-            const size_t off = wino.size();
-            wino.resize(off + size_t(12) * r[4] * r[5]);
-            mvlm_winograd_transform(blob_host + r[6], r[4], r[5], wino.data() + off);
-            st.wino_off[size_t(s)] = (long long)off;
+            if (!r[0] || !form.serves_slot(r[3], r[4], r[5])) continue;
+            const size_t off = host.size();
+            host.resize(off + size_t(form.slices) * r[4] * r[5]);
+            form.transform(blob_host + r[6], r[4], r[5], host.data() + off);
+            ww.off[size_t(s)] = (long long)off;
         }
-        if (!wino.empty()) {
-            MVLM_CHECK_HIP(ctx, hipMalloc(&st.wino_blob, wino.size() * sizeof(float)));
-            MVLM_CHECK_HIP(ctx, hipMemcpy(st.wino_blob, wino.data(), wino.size() * sizeof(float), hipMemcpyHostToDevice));
-            st.wino_bytes = wino.size() * sizeof(float);
-        }
-    }
-    {  // likewise the F(4,3) form of the slots its tile can serve (twice those slots' weight bytes)
-        std::vector<float> wino4;
-        st.wino4_off.assign(size_t(n_slots), -1);
-        for (int s = 0; s < n_slots; ++s) {
-            const int32_t* r = &st.desc[size_t(s) * MVLM_CONV_DESC_INTS];
-            if (!r[0] || !mvlm_conv_wino4_serves_slot(r[3], r[4], r[5])) continue;
-            const size_t off = wino4.size();
-            wino4.resize(off + size_t(18) * r[4] * r[5]);
-            mvlm_winograd4_transform(blob_host + r[6], r[4], r[5], wino4.data() + off);
-            st.wino4_off[size_t(s)] = (long long)off;
-        }
-        if (!wino4.empty()) {
-            MVLM_CHECK_HIP(ctx, hipMalloc(&st.wino4_blob, wino4.size() * sizeof(float)));
-            MVLM_CHECK_HIP(ctx, hipMemcpy(st.wino4_blob, wino4.data(), wino4.size() * sizeof(float), hipMemcpyHostToDevice));
-            st.wino4_bytes = wino4.size() * sizeof(float);
+        if (!host.empty()) {
+            MVLM_CHECK_HIP(ctx, hipMalloc(&ww.blob, host.size() * sizeof(float)));
+            MVLM_CHECK_HIP(ctx, hipMemcpy(ww.blob, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
         }
     }
     st.n_landmarks = n_landmarks;
@@ -980,11 +960,7 @@ extern "C" int mvlm_cnn_set_execution(mvlm_ctx* ctx, int graph_mode, int concurr
     MVLM_REQUIRE(ctx, (graph_mode == 0 || graph_mode == 1) && (concurrency == 0 || concurrency == 1),
                  "cnn_set_execution: flags must be 0 or 1");
     CnnState& st = ctx->cnn;
-    if (concurrency != st.concurrency) {  // captured graphs encode the launch order
-        for (auto& g : st.graphs)
-            if (g.exec) hipGraphExecDestroy(g.exec);
-        st.graphs.clear();
-    }
+    if (concurrency != st.concurrency) st.drop_graphs();  // captured graphs encode the launch order
     st.graph_mode = graph_mode;
     st.concurrency = concurrency;
     return 0;
@@ -1001,11 +977,7 @@ extern "C" int mvlm_cnn_set_selection(mvlm_ctx* ctx, int method) {
         MVLM_REQUIRE(ctx, r[0] != 0 && (r[5] == 96 || r[5] == 80 || r[5] == 84) && r[3] == 2,
                      "cnn_set_selection: the fused moment selection needs conv11's parity slots in the packed weights");
     }
-    if (method != st.selection) {  // captured graphs encode the launches
-        for (auto& g : st.graphs)
-            if (g.exec) hipGraphExecDestroy(g.exec);
-        st.graphs.clear();
-    }
+    if (method != st.selection) st.drop_graphs();  // captured graphs encode the launches
     st.selection = method;
     return 0;
 }
@@ -1014,37 +986,26 @@ extern "C" int mvlm_cnn_set_pairing(mvlm_ctx* ctx, int mode) {
     MVLM_ENTER(ctx);
     MVLM_REQUIRE(ctx, mode >= 0 && mode <= 2, "cnn_set_pairing: 0 never, 1 the measured table (default), 2 wherever one kernel variant serves both");
     CnnState& st = ctx->cnn;
-    if (mode != st.pairing) {  // captured graphs encode the launches
-        for (auto& g : st.graphs)
-            if (g.exec) hipGraphExecDestroy(g.exec);
-        st.graphs.clear();
-    }
+    if (mode != st.pairing) st.drop_graphs();  // captured graphs encode the launches
     st.pairing = mode;
     return 0;
 }
 
-extern "C" int mvlm_cnn_set_winograd(mvlm_ctx* ctx, int mode) {
+// a Winograd mode of the context (captured graphs encode the launches)
+static int set_winograd_mode(mvlm_ctx* ctx, int mvlm_ctx::*which, int mode, const char* usage) {
     MVLM_ENTER(ctx);
-    MVLM_REQUIRE(ctx, mode >= 0 && mode <= 2, "cnn_set_winograd: 0 never, 1 the measured table (default), 2 every layer a Winograd variant can serve");
-    if (mode != ctx->conv_winograd) {  // captured graphs encode the launches
-        for (auto& g : ctx->cnn.graphs)
-            if (g.exec) hipGraphExecDestroy(g.exec);
-        ctx->cnn.graphs.clear();
-    }
-    ctx->conv_winograd = mode;
+    MVLM_REQUIRE(ctx, mode >= 0 && mode <= 2, usage);
+    if (mode != ctx->*which) ctx->cnn.drop_graphs();
+    ctx->*which = mode;
     return 0;
 }
 
+extern "C" int mvlm_cnn_set_winograd(mvlm_ctx* ctx, int mode) {
+    return set_winograd_mode(ctx, &mvlm_ctx::conv_winograd, mode, "cnn_set_winograd: 0 never, 1 the measured table (default), 2 every layer a Winograd variant can serve");
+}
+
 extern "C" int mvlm_cnn_set_winograd4(mvlm_ctx* ctx, int mode) {
-    MVLM_ENTER(ctx);
-    MVLM_REQUIRE(ctx, mode >= 0 && mode <= 2, "cnn_set_winograd4: 0 never, 1 the measured table (default), 2 every layer the F(4,3) Winograd tile can serve");
-    if (mode != ctx->conv_winograd4) {  // captured graphs encode the launches
-        for (auto& g : ctx->cnn.graphs)
-            if (g.exec) hipGraphExecDestroy(g.exec);
-        ctx->cnn.graphs.clear();
-    }
-    ctx->conv_winograd4 = mode;
-    return 0;
+    return set_winograd_mode(ctx, &mvlm_ctx::conv_winograd4, mode, "cnn_set_winograd4: 0 never, 1 the measured table (default), 2 every layer the F(4,3) Winograd tile can serve");
 }
 
 extern "C" int mvlm_cnn_execution_stats(mvlm_ctx* ctx, int64_t* eager_runs, int64_t* graph_captures,
@@ -1072,9 +1033,7 @@ extern "C" int mvlm_cnn_load_fast(mvlm_ctx* ctx, const uint16_t* blob_host, size
         const size_t need = size_t(mvlm_fast_cin_pad(r[1]) / 16) * 9 * 2 * 3 * size_t(mvlm_fast_cout_pad(r[2])) * 8;
         MVLM_REQUIRE(ctx, slot_offsets[s] % 8 == 0 && size_t(slot_offsets[s]) + need <= n_u16, "cnn_load_fast: offset out of range");
     }
-    for (auto& g : st.graphs)
-        if (g.exec) hipGraphExecDestroy(g.exec);
-    st.graphs.clear();
+    st.drop_graphs();
     if (st.fast == 1) st.fast = 0;
     if (st.fast_blob) {
         MVLM_CHECK_HIP(ctx, hipFree(st.fast_blob));
@@ -1102,9 +1061,7 @@ extern "C" int mvlm_cnn_load_fast16(mvlm_ctx* ctx, const uint16_t* blob_host, si
         MVLM_REQUIRE(ctx, slot_offsets[s] % 8 == 0 && size_t(slot_offsets[s]) + need <= n_u16, "cnn_load_fast16: offset out of range");
         MVLM_REQUIRE(ctx, slot_unscale[s] > 0.f && slot_unscale[s] < 3.0e38f, "cnn_load_fast16: bad inverse scale");
     }
-    for (auto& g : st.graphs)
-        if (g.exec) hipGraphExecDestroy(g.exec);
-    st.graphs.clear();
+    st.drop_graphs();
     if (st.fast == 2) st.fast = 0;
     if (st.fast16_blob) {
         MVLM_CHECK_HIP(ctx, hipFree(st.fast16_blob));
@@ -1141,11 +1098,7 @@ extern "C" int mvlm_cnn_set_precision(mvlm_ctx* ctx, int fast) {
     MVLM_REQUIRE(ctx, fast >= 0 && fast <= 2, "cnn_set_precision: 0 (exact fp32), 1 (bf16x3 split) or 2 (f16x2 split on the eligible layers)");
     MVLM_REQUIRE(ctx, fast != 1 || st.fast_blob, "cnn_set_precision: mvlm_cnn_load_fast has not been called");
     MVLM_REQUIRE(ctx, fast != 2 || st.fast16_blob, "cnn_set_precision: mvlm_cnn_load_fast16 has not been called");
-    if (fast != st.fast) {  // captured graphs encode the kernels
-        for (auto& g : st.graphs)
-            if (g.exec) hipGraphExecDestroy(g.exec);
-        st.graphs.clear();
-    }
+    if (fast != st.fast) st.drop_graphs();  // captured graphs encode the kernels
     st.fast = fast;
     return 0;
 }

@@ -169,6 +169,19 @@ struct CnnGraphEntry {
     hipGraphExec_t exec = nullptr;
 };
 
+// The two Winograd forms of a 3x3 layer's weights, described once (conv_mfma.hip: mvlm_wino_form): what loading, packing, the
+// executor and the dispatcher need to know about a form.  A variant's row names its form (ConvVariantInfo::form).
+enum { MVLM_WINO_F23 = 0, MVLM_WINO_F43 = 1, MVLM_WINO_FORMS_N = 2 };
+struct WinoForm {
+    int slices;                                                                  // the weights are [slices][cin_pad][cout_pad]: 4 or 6 per kx
+    void (*transform)(const float* w9, int cin_pad, int cout_pad, float* out);   // host: packed [9][cin_pad][cout_pad] -> that
+    bool (*serves_slot)(int ksize, int cin_pad, int cout_pad);                   // a tile of this form exists for these channels
+    const float* ConvArgs::*weights;                                             // the launch's member that carries them
+    double macs;                                                                 // multiply-adds per output and input channel (direct: 9)
+    const char* pack_fn;                                                         // the C entry point that makes them, for messages
+};
+const WinoForm& mvlm_wino_form(int form);
+
 struct CnnState {
     bool loaded = false;
     int n_landmarks = 0, in_channels = 0;
@@ -196,16 +209,20 @@ struct CnnState {
     std::vector<long long> fast16_off;
     std::vector<float> fast16_unscale;
     unsigned* fast16_flag = nullptr;         // device word: an f16x2 launch of the current pass met |x| >= 65504
-    // F(2,3) Winograd form of the 3x3 slots a Winograd tile can serve (exact path): transformed weights, float offset per slot (-1: none)
-    float* wino_blob = nullptr;
-    std::vector<long long> wino_off;
-    size_t wino_bytes = 0;
-    // likewise the F(4,3) form ([18][cin_pad][cout_pad]) of the slots the F(4,3) tile can serve
-    float* wino4_blob = nullptr;
-    std::vector<long long> wino4_off;
-    size_t wino4_bytes = 0;
+    // per Winograd form, the transformed weights of the 3x3 slots a tile of that form can serve (exact path) and the float offset
+    // per slot (-1: none)
+    struct WinoWeights {
+        float* blob = nullptr;
+        std::vector<long long> off;
+    } wino[MVLM_WINO_FORMS_N];
     std::vector<CnnGraphEntry> graphs;
     long graph_replays = 0, graph_captures = 0, eager_runs = 0, graph_failures = 0;
+    // forget the captured passes: they encode the kernels, their order and pointers into the weight blobs
+    void drop_graphs() {
+        for (CnnGraphEntry& g : graphs)
+            if (g.exec) hipGraphExecDestroy(g.exec);
+        graphs.clear();
+    }
 };
 
 struct mvlm_mesh {
@@ -271,8 +288,10 @@ struct mvlm_ctx {
     // table (conv_tuned_wino4.h) has an entry and Winograd mode is 1, 2 every layer the tile can serve (tests); MVLM_WINOGRAD4 (default 1)
     int conv_winograd4 = [] { const char* e = getenv("MVLM_WINOGRAD4"); return (e && e[0] >= '0' && e[0] <= '2' && !e[1]) ? e[0] - '0' : 1; }();
     std::vector<ConvOverride> conv_overrides;  // tools/tune_in_network.py: kernel variant per (shape, kind), before any table
-    unsigned long long conv_attr_mask = 0;  // conv variants whose launch attributes are set on this ctx's device
-    bool conv_wino4_attr_set = false;       // likewise the F(4,3) Winograd tile (MVLM_CONV_VARIANT_WINO4: not a base id, no bit of the mask)
+    // Conv kernels whose launch attributes are set on this ctx's device.  The 64 bits: a base variant's bit is its id (all below
+    // MVLM_CONV_FAST_ATTR_BIT0, none MVLM_CONV_WINO4_ATTR_BIT: conv_mfma.hip asserts it), the F(4,3) tile has bit 41, the fast
+    // kernels (conv_fast.hip) the bits from 54 on.
+    unsigned long long conv_attr_mask = 0;
     // a depth-key plane's buffer and capacity when it was last left all-EMPTY ({nullptr, 0}: not known clean); keyed on both,
     // so a buffer that get_scratch replaced by one of the same size is filled again
     struct KeyPlaneState {
@@ -404,8 +423,10 @@ inline bool mvlm_fast_channels_ok(int cin, int cout) {
 }
 bool mvlm_conv_fast_ok(const ConvArgs& a, int splits);  // splits: 3 = bf16x3 ("fast"), 2 = f16x2 ("fast16")
 int mvlm_launch_conv_fast(mvlm_ctx* ctx, const ConvArgs& a, const unsigned short* wq_dev, int splits = 3, float unscale = 1.f);
-// the F(4,3) Winograd tile (conv3x3q_c32_t16x32): a code beyond the base ids and their K-part forms (0..1023) and below the pair flag
+// the F(4,3) Winograd tile (conv3x3q_c32_t16x32): a code beyond the base ids and their K-part forms (0..1023) and below the pair
+// flag - a row of the variant table like the others (conv_mfma.hip: decode_variant reads the code), and a bit of conv_attr_mask
 constexpr int MVLM_CONV_VARIANT_WINO4 = 2048;
+constexpr int MVLM_CONV_WINO4_ATTR_BIT = 41, MVLM_CONV_FAST_ATTR_BIT0 = 54;
 constexpr int MVLM_CONV_VARIANT_FAST = 62;    // id reported for launches of the bf16x3 kernel
 constexpr int MVLM_CONV_VARIANT_FAST16 = 61;  // ... of the f16x2 kernel
 

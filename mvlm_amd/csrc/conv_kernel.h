@@ -2001,10 +2001,10 @@ int check_variant(mvlm_ctx* ctx, ConvArgs& a, ConvGrid& g) {
 
 // dynamic-LDS limit of this variant's kernels: set once per context, i.e. per device (hipFuncSetAttribute
 // applies to the current device's copy of the function; the ctx mutex held by every entry point guards the mask)
+// attr_bit: the variant's bit of mvlm_ctx::conv_attr_mask (a base id, MVLM_CONV_WINO4_ATTR_BIT)
 template <class C>
-int set_variant_attributes(mvlm_ctx* ctx, int variant_id) {
-    // (the F(4,3) tile is not a base id: a flag of its own, not a bit of the mask the base ids and the fast kernels share)
-    if (C::WINO4 ? ctx->conv_wino4_attr_set : bool((ctx->conv_attr_mask >> variant_id) & 1ull)) return 0;
+int set_variant_attributes(mvlm_ctx* ctx, int attr_bit) {
+    if ((ctx->conv_attr_mask >> attr_bit) & 1ull) return 0;
     MVLM_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_mfma_kernel<C, false>),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, int(C::LDS_BYTES)));
     if constexpr (C::HAS_AMAX)
@@ -2016,15 +2016,12 @@ int set_variant_attributes(mvlm_ctx* ctx, int variant_id) {
     if constexpr (C::HAS_IN2)
         MVLM_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_mfma_kernel<C, false, true>),
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, int(C::LDS_BYTES)));
-    if constexpr (C::WINO4)
-        ctx->conv_wino4_attr_set = true;
-    else
-        ctx->conv_attr_mask |= 1ull << variant_id;
+    ctx->conv_attr_mask |= 1ull << attr_bit;
     return 0;
 }
 
 template <class C>
-int launch_variant(mvlm_ctx* ctx, const ConvArgs& a_in, int variant_id) {
+int launch_variant(mvlm_ctx* ctx, const ConvArgs& a_in, int attr_bit) {
     ConvArgs a = a_in;
 #if defined(MVLM_CONV_TIMING)  // diagnostic build: the tool passes its counter buffer through the environment
     if (const char* e = getenv("MVLM_CONV_TIMING_BUF")) a.timing = reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 0));
@@ -2035,7 +2032,7 @@ int launch_variant(mvlm_ctx* ctx, const ConvArgs& a_in, int variant_id) {
         MVLM_REQUIRE(ctx, g.tiles <= MVLM_KPARTS_MAX_TILES && g.nblk <= MVLM_KPARTS_MAX_PARTS, "conv: too many tiles for the K-part workspace");
         if (mvlm_conv_kparts_workspace(ctx, &a.kws, &a.kcnt)) return 1;
     }
-    if (set_variant_attributes<C>(ctx, variant_id)) return 1;
+    if (set_variant_attributes<C>(ctx, attr_bit)) return 1;
     if (a.amax_val) {
         if constexpr (C::HAS_AMAX) {
             hipLaunchKernelGGL((conv_mfma_kernel<C, true>), dim3((unsigned)g.nblk), dim3(256), C::LDS_BYTES, ctx->cur_stream(),
@@ -2060,7 +2057,7 @@ int launch_variant(mvlm_ctx* ctx, const ConvArgs& a_in, int variant_id) {
 
 // two independent convolutions on this variant's tiles in one grid (conv_pair_kernel); kparts of each problem in its ConvArgs
 template <class C>
-int launch_variant_pair(mvlm_ctx* ctx, const ConvArgs& a0, const ConvArgs& a1, int variant_id) {
+int launch_variant_pair(mvlm_ctx* ctx, const ConvArgs& a0, const ConvArgs& a1, int attr_bit) {
     if constexpr (!C::PAIRABLE) {
         return ctx->fail("conv: this kernel variant has no two-problem form");
     } else {
@@ -2095,7 +2092,7 @@ int launch_variant_pair(mvlm_ctx* ctx, const ConvArgs& a0, const ConvArgs& a1, i
         p.nblk0_pad = (p.nblk[0] + 7) / 8 * 8;
         const long total = long(p.nblk0_pad) + p.nblk[1];
         MVLM_REQUIRE(ctx, total < (1l << 31), "conv: bad grid");
-        if (set_variant_attributes<C>(ctx, variant_id)) return 1;
+        if (set_variant_attributes<C>(ctx, attr_bit)) return 1;
         hipLaunchKernelGGL((conv_pair_kernel<C>), dim3((unsigned)total), dim3(256), C::LDS_BYTES, ctx->cur_stream(), p);
         MVLM_CHECK_HIP(ctx, hipGetLastError());
         return 0;

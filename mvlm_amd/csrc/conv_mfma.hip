@@ -35,16 +35,21 @@
 //   where the direct form spends 6 - same instruction, fp32 in and out.  mvlm_conv_wino_variant() routes a launch there where
 //   the measured table conv_tuned_wino.h says it is faster (mvlm_cnn_set_winograd / MVLM_WINOGRAD: 0 never, 1 table, 2 always).
 //   A profile record of such a launch counts the FLOPs its MFMAs execute (12 Cin Cout H W B, not 18).
+//   The F(4,3) form along y (Cfg::WINO4, conv3x3q_c32_t16x32) likewise: six GEMMs per four output rows, 9 Cin Cout H W B.  What the
+//   two forms differ in on the host (slices, transform, which ConvArgs member carries the weights) is mvlm_wino_form() below.
 //
-// How a launch finds its kernel.  Every variant of conv_variants.h has one row in VARIANTS below (tile geometry, features,
-// launchers); tile_fits() is the one statement of "this tile divides this layer".  A launch is looked up by its ConvKey
-// (ksize, cin_pad, cout_pad, size, kind, batch), in this order:
+// How a launch finds its kernel.  Every variant of conv_variants.h, the F(4,3) tile included, has one row in VARIANTS below
+// (tile geometry, features, Winograd form, launchers); tile_fits() is the one statement of "this tile divides this layer", and
+// decode_variant() the one reading of a variant code (the F(4,3) tile's own code 2048; base id + 256 log2(K parts) below 1024).
+// A launch is looked up by its ConvKey (ksize, cin_pad, cout_pad, size, kind, batch), in this order:
 //   1. a tuning override of the context for the key's shape and kind (mvlm_conv_set_override),
-//   2. the Winograd routing (mode 0 never, 2 wherever a Winograd tile can serve, 1 the measured table conv_tuned_wino.h),
+//   2. the Winograd routing (mvlm_conv_wino_variant: the F(4,3) tile before the F(2,3) tiles, each by its mode - 0 never, 2 wherever
+//      it can serve, 1 its measured table conv_tuned_wino4.h / conv_tuned_wino.h),
 //   3. the in-network table conv_tuned_net.h, 4. the single-layer table conv_tuned.h - both by the entry of the smallest
 //      tuned batch >= the launch's, 5. the rules (pick_variant_rules).
 // Launches with a fused argmax, an upsampled input or a parity output and the 2x2 layers go straight to the rules: one
-// kernel can serve them.  Every decision is pinned by tests/golden/conv_routing.txt (tests/test_conv_routing_cpu.py).
+// kernel can serve them.  Every decision is pinned by tests/golden/conv_routing.txt and, for launches that carry the F(4,3)
+// weights, tests/golden/conv_routing_wino4.txt (tests/test_conv_routing_cpu.py).
 #include <algorithm>
 #include <array>
 #include <cstdlib>
@@ -69,46 +74,74 @@
     int mvlm_conv_pair_launch_##id(mvlm_ctx* ctx, const ConvArgs& a0, const ConvArgs& a1);
 MVLM_CONV_VARIANTS(X)
 #undef X
-// The F(4,3) Winograd tile is not a base variant (conv_variants.h): its own code MVLM_CONV_VARIANT_WINO4 and this launcher, defined
-// in conv_inst_q0.hip.  A weak reference: a build without that translation unit has no such tile, and every question about it says no.
-int mvlm_conv_launch_wino4(mvlm_ctx* ctx, const ConvArgs& a) __attribute__((weak));
+int mvlm_conv_launch_wino4(mvlm_ctx* ctx, const ConvArgs& a);  // the F(4,3) tile's, defined in conv_inst_q0.hip
+
+// ---- the two Winograd forms (common.h: WinoForm) ----------------------------------------------------------------------------
+const WinoForm& mvlm_wino_form(int form) {
+    static const WinoForm forms[MVLM_WINO_FORMS_N] = {
+        {12, mvlm_winograd_transform, mvlm_conv_wino_serves_slot, &ConvArgs::w_wino, 6.0, "mvlm_pack_winograd_weights"},
+        {18, mvlm_winograd4_transform, mvlm_conv_wino4_serves_slot, &ConvArgs::w_wino4, 4.5, "mvlm_pack_winograd4_weights"},
+    };
+    return forms[form];
+}
 
 namespace {
 
 // ---- the variant table ------------------------------------------------------------------------------------------------------
 struct ConvVariantInfo {
-    int id;
+    int id;  // a base id, or the F(4,3) tile's own code
     const char* name;
     int KS, TW, TRI, NIMG, COUT_T, CK, PIX_T, NT, BN_MAXC;
-    bool SPLITK, WINO, TAIL16, PAIRABLE, CAN_POOL_ANY, HAS_IN2;
+    int form;  // MVLM_WINO_F23 / MVLM_WINO_F43 (mvlm_wino_form), -1: a direct tile
+    bool SPLITK, TAIL16, PAIRABLE, CAN_POOL_ANY, HAS_IN2;
     int (*launch)(mvlm_ctx*, const ConvArgs&);
-    int (*launch_pair)(mvlm_ctx*, const ConvArgs&, const ConvArgs&);
+    int (*launch_pair)(mvlm_ctx*, const ConvArgs&, const ConvArgs&);  // (null: the F(4,3) tile, which no pair code names)
 };
 constexpr int MAX_VARIANT_ID = 64;  // base ids live in the low byte of a variant code; the table is indexed by them
 
+// A base id is also the variant's bit of mvlm_ctx::conv_attr_mask (common.h: the partition of its 64 bits).
 template <int ID, class V>
 constexpr ConvVariantInfo variant_info(const char* name, int (*launch)(mvlm_ctx*, const ConvArgs&),
                                        int (*launch_pair)(mvlm_ctx*, const ConvArgs&, const ConvArgs&)) {
-    static_assert(ID >= 0 && ID < MAX_VARIANT_ID, "conv variant ids are below 64");
+    static_assert(ID == MVLM_CONV_VARIANT_WINO4 || (ID >= 0 && ID < MVLM_CONV_FAST_ATTR_BIT0 && ID != MVLM_CONV_WINO4_ATTR_BIT),
+                  "base ids are below the fast kernels' attribute bits and leave the F(4,3) tile's free");
+    static_assert((ID == MVLM_CONV_VARIANT_WINO4) == V::WINO4, "the F(4,3) tile has the code of its own, and nothing else has");
     return {ID, name, V::KS, V::TW, V::TRI, V::NIMG, V::COUT_T, V::CK, V::PIX_T, V::NT, V::BN_MAXC,
-            V::SPLITK, V::WINO, V::TAIL16, V::PAIRABLE, V::CAN_POOL_ANY, V::HAS_IN2, launch, launch_pair};
+            V::WINO ? MVLM_WINO_F23 : V::WINO4 ? MVLM_WINO_F43 : -1, V::SPLITK, V::TAIL16, V::PAIRABLE, V::CAN_POOL_ANY, V::HAS_IN2, launch, launch_pair};
 }
 
 constexpr ConvVariantInfo VARIANTS[] = {
 #define X(id, name, ...) variant_info<id, __VA_ARGS__>(name, mvlm_conv_launch_##id, mvlm_conv_pair_launch_##id),
     MVLM_CONV_VARIANTS(X)
 #undef X
+    variant_info<MVLM_CONV_VARIANT_WINO4, MVLM_CONV_WINO4_CFG>(MVLM_CONV_WINO4_NAME, mvlm_conv_launch_wino4, nullptr),  // (the last row)
 };
 
-// the variant of this base id, or null
+// the row of this base id or of the F(4,3) tile's code, or null
 const ConvVariantInfo* conv_variant(int id) {
     static const std::array<const ConvVariantInfo*, MAX_VARIANT_ID> by_id = [] {
         std::array<const ConvVariantInfo*, MAX_VARIANT_ID> t{};
-        for (const ConvVariantInfo& v : VARIANTS) t[size_t(v.id)] = &v;
+        for (const ConvVariantInfo& v : VARIANTS)
+            if (v.id < MAX_VARIANT_ID) t[size_t(v.id)] = &v;
         return t;
     }();
+    if (id == MVLM_CONV_VARIANT_WINO4) return &VARIANTS[sizeof VARIANTS / sizeof VARIANTS[0] - 1];
     return id >= 0 && id < MAX_VARIANT_ID ? by_id[size_t(id)] : nullptr;
 }
+
+// What the variant code of a single launch names: 2048 the F(4,3) tile's row on one K part; a code below 1024 the row of its low
+// byte (null: no such base id) on 1 << (code >> 8) K parts; any other code nothing (kparts 0).
+struct VariantCode {
+    const ConvVariantInfo* row;
+    int kparts;
+};
+VariantCode decode_variant(int v) {
+    if (v == MVLM_CONV_VARIANT_WINO4) return {conv_variant(v), 1};
+    if (v >= 0 && v < 1024) return {conv_variant(v & 255), 1 << (v >> 8)};
+    return {nullptr, 0};
+}
+// the row behind any code, a pair's and a garbled one included: they carry a base id in the low byte
+const ConvVariantInfo* variant_row(int v) { return conv_variant(v == MVLM_CONV_VARIANT_WINO4 ? v : v & 255); }
 
 // Does the tile divide this layer?  Every "can this variant serve ..." question is this plus the caller's own conditions.
 // (check_variant<C> in conv_kernel.h states the same once more at the launch, as the last line of defence.)
@@ -190,25 +223,30 @@ int pick_variant(const mvlm_ctx* ctx, const ConvArgs& a, bool rules_only = false
     return by_rule;
 }
 
-// The Winograd variant that can serve this launch at all (shape and features), or -1.
-int wino_candidate(const ConvArgs& a) {
+// The variant of this Winograd form that can serve this launch at all (shape and features), or -1.
+int wino_candidate(const ConvArgs& a, int form) {
     if (a.ksize != 3 || a.up_in || a.in2 || a.amax_val || a.up_out == 2 || a.n_par != 1 || a.H != a.W) return -1;
     // (cin_pad <= BN_MAXC: the pre-BN parameters must fit the LDS; asked whether or not this layer has a pre-BN)
     for (const ConvVariantInfo& t : VARIANTS)
-        if (t.WINO && tile_fits(t, a.ksize, a.cin_pad, a.cout_pad, a.H, a.W) && a.cin_pad <= t.BN_MAXC) return t.id;
+        if (t.form == form && tile_fits(t, a.ksize, a.cin_pad, a.cout_pad, a.H, a.W) && a.cin_pad <= t.BN_MAXC) return t.id;
     return -1;
 }
 
-// Does the F(4,3) tile exist in this build and divide this layer?  (cin_pad <= BN_MAXC as for the F(2,3) tiles.)
-using Wino4Cfg = MVLM_CONV_WINO4_CFG;
-bool wino4_fits(int ksize, int cin_pad, int cout_pad, int H, int W) {
-    return mvlm_conv_launch_wino4 != nullptr && ksize == Wino4Cfg::KS && W % Wino4Cfg::TW == 0 && H % Wino4Cfg::TRI == 0 &&
-           cout_pad % Wino4Cfg::COUT_T == 0 && cin_pad % Wino4Cfg::CK == 0 && cin_pad <= Wino4Cfg::BN_MAXC;
+// A slot has channels but no size yet: can a tile of this form serve it at the tile's own size?
+bool form_serves_slot(int form, int ksize, int cin_pad, int cout_pad, bool bn_bound) {
+    for (const ConvVariantInfo& t : VARIANTS)
+        if (t.form == form && tile_fits(t, ksize, cin_pad, cout_pad, t.TRI, t.TW) && (!bn_bound || cin_pad <= t.BN_MAXC)) return true;
+    return false;
 }
-// its code where it can serve this launch at all (shape and features, the launch's own transformed weights), or -1
-int wino4_candidate(const ConvArgs& a) {
-    if (!a.w_wino4 || a.up_in || a.in2 || a.amax_val || a.up_out == 2 || a.n_par != 1 || a.H != a.W) return -1;
-    return wino4_fits(a.ksize, a.cin_pad, a.cout_pad, a.H, a.W) ? MVLM_CONV_VARIANT_WINO4 : -1;
+
+// the variant a measured Winograd table ({cin_pad, cout_pad, size, kind, min_batch, variant}) sends this key to, or -1
+template <class E>
+int wino_table_variant(const E* table, int n, const ConvKey& k) {
+    for (int i = 0; i < n; ++i) {
+        const E& e = table[i];
+        if (e.cin_pad == k.cin_pad && e.cout_pad == k.cout_pad && e.size == k.size && e.kind == k.kind && k.batch >= e.min_batch) return e.variant;
+    }
+    return -1;
 }
 
 }  // namespace
@@ -219,22 +257,18 @@ ConvKey mvlm_conv_key(const ConvArgs& a) {
 
 bool mvlm_conv_variant_is_wino(int v) {
     const ConvVariantInfo* t = conv_variant(v);
-    return t && t->WINO;
+    return t && t->form == MVLM_WINO_F23;
 }
 
-bool mvlm_conv_variant_is_wino4(int v) { return v == MVLM_CONV_VARIANT_WINO4; }
-
-bool mvlm_conv_wino4_serves_slot(int ksize, int cin_pad, int cout_pad) {
-    return wino4_fits(ksize, cin_pad, cout_pad, Wino4Cfg::TRI, Wino4Cfg::TW);  // (a slot has no size yet: asked at the tile's own)
+bool mvlm_conv_variant_is_wino4(int v) {
+    const ConvVariantInfo* t = conv_variant(v);
+    return t && t->form == MVLM_WINO_F43;
 }
 
-bool mvlm_conv_wino_serves_slot(int ksize, int cin_pad, int cout_pad) {
-    // a slot has channels but no size yet: asked at the tile's own size.  No cin_pad <= BN_MAXC here (historical: a wider
-    // slot gets transformed weights that no launch is routed to).
-    for (const ConvVariantInfo& t : VARIANTS)
-        if (t.WINO && tile_fits(t, ksize, cin_pad, cout_pad, t.TRI, t.TW)) return true;
-    return false;
-}
+bool mvlm_conv_wino4_serves_slot(int ksize, int cin_pad, int cout_pad) { return form_serves_slot(MVLM_WINO_F43, ksize, cin_pad, cout_pad, true); }
+
+// No cin_pad <= BN_MAXC here (historical: a wider slot gets transformed weights that no launch is routed to).
+bool mvlm_conv_wino_serves_slot(int ksize, int cin_pad, int cout_pad) { return form_serves_slot(MVLM_WINO_F23, ksize, cin_pad, cout_pad, false); }
 
 // Winograd routing of the exact path, a pure function of (shape, kind, batch) and the context's settings: a tuning override
 // that names a Winograd variant first; then mode 0 never, 2 wherever a variant can serve, 1 the measured table
@@ -243,8 +277,8 @@ bool mvlm_conv_wino_serves_slot(int ksize, int cin_pad, int cout_pad) {
 // F(4,3) mode 2 wherever the tile can serve, mode 1 its own measured table (conv_tuned_wino4.h) - consulted in Winograd mode 1
 // only, so that Winograd mode 2 stays "every layer on the F(2,3) tile" unless F(4,3) mode 2 asks otherwise.
 int mvlm_conv_wino_variant(const mvlm_ctx* ctx, const ConvArgs& a) {
-    const int cand = wino_candidate(a);
-    const int cand4 = wino4_candidate(a);
+    const int cand = wino_candidate(a, MVLM_WINO_F23);
+    const int cand4 = a.w_wino4 ? wino_candidate(a, MVLM_WINO_F43) : -1;
     if (cand < 0 && cand4 < 0) return -1;
     const ConvKey k = mvlm_conv_key(a);
     if (const ConvOverride* o = find_override(ctx, k))
@@ -253,18 +287,12 @@ int mvlm_conv_wino_variant(const mvlm_ctx* ctx, const ConvArgs& a) {
     if (mode == 0) return -1;
     const int mode4 = ctx ? ctx->conv_winograd4 : 1;
     if (cand4 >= 0 && mode4 == 2) return cand4;
-    if (cand4 >= 0 && mode4 == 1 && mode == 1)
-        for (int i = 0; i < MVLM_CONV_TUNED_WINO4_N; ++i) {
-            const ConvTunedWino4& e = MVLM_CONV_TUNED_WINO4[i];
-            if (e.cin_pad == k.cin_pad && e.cout_pad == k.cout_pad && e.size == k.size && e.kind == k.kind && k.batch >= e.min_batch) return e.variant;
-        }
-    if (cand < 0) return -1;
-    if (mode == 2) return cand;
-    for (int i = 0; i < MVLM_CONV_TUNED_WINO_N; ++i) {
-        const ConvTunedWino& e = MVLM_CONV_TUNED_WINO[i];
-        if (e.cin_pad == k.cin_pad && e.cout_pad == k.cout_pad && e.size == k.size && e.kind == k.kind && k.batch >= e.min_batch) return e.variant;
+    if (cand4 >= 0 && mode4 == 1 && mode == 1) {
+        const int v = wino_table_variant(MVLM_CONV_TUNED_WINO4, MVLM_CONV_TUNED_WINO4_N, k);
+        if (v >= 0) return v;
     }
-    return -1;
+    if (cand < 0) return -1;
+    return mode == 2 ? cand : wino_table_variant(MVLM_CONV_TUNED_WINO, MVLM_CONV_TUNED_WINO_N, k);
 }
 
 // the variant a launch runs on: the Winograd routing first, the direct tiles' tables and rules otherwise
@@ -290,7 +318,7 @@ int mvlm_conv_kparts_workspace(mvlm_ctx* ctx, float** ws, unsigned** cnt) {
 }
 
 const char* mvlm_conv_variant_name_impl(int v) {
-    if (v == MVLM_CONV_VARIANT_WINO4) return MVLM_CONV_WINO4_NAME;
+    if (const ConvVariantInfo* t = conv_variant(v)) return t->name;
     if (v == MVLM_CONV_VARIANT_FAST) return "conv3x3_bf16x3_t8x32";
     if (v == MVLM_CONV_VARIANT_FAST16) return "conv3x3_f16x2_t8x32";
     if (v >= 256) {
@@ -312,8 +340,7 @@ const char* mvlm_conv_variant_name_impl(int v) {
         }
         return it->second.c_str();
     }
-    const ConvVariantInfo* t = conv_variant(v);
-    return t ? t->name : "?";
+    return "?";
 }
 
 // Would the dispatcher run this layer on the tile that can add a second, half-resolution input tensor on its load
@@ -335,8 +362,7 @@ bool mvlm_conv_can_pool(const mvlm_ctx* ctx, const ConvArgs& a_in) {
 }
 
 bool mvlm_conv_variant_can_pool(int v) {
-    if (v == MVLM_CONV_VARIANT_WINO4) return Wino4Cfg::CAN_POOL_ANY;
-    const ConvVariantInfo* t = conv_variant(v & 255);
+    const ConvVariantInfo* t = variant_row(v);
     return t && t->CAN_POOL_ANY;
 }
 
@@ -424,33 +450,22 @@ int mvlm_launch_conv(mvlm_ctx* ctx, const ConvArgs& a, int* variant_out) {
     // conv_force_variant (mvlm_conv_bench only): >= 0 that variant, -2 the rules without the tuned table
     const int v = ctx->conv_force_variant >= 0 ? ctx->conv_force_variant
                   : ctx->conv_force_variant == -2 ? pick_variant(ctx, a, true) : route_variant(ctx, a);
-    if (v == MVLM_CONV_VARIANT_WINO4) {  // its own code: none of the base ids' arithmetic (id & 255, K parts) applies
-        MVLM_REQUIRE(ctx, mvlm_conv_launch_wino4 != nullptr, "conv: the F(4,3) Winograd tile is not part of this build");
-        MVLM_REQUIRE(ctx, a.w_wino4, "conv: the F(4,3) Winograd tile needs the layer's transformed weights (mvlm_pack_winograd4_weights)");
-        MVLM_REQUIRE(ctx, !a.in2, "conv: the F(4,3) Winograd tile has no second-input form");
-        MVLM_REQUIRE(ctx, !a.pool_out || px / 4 * a.pool_ctot < lim, "conv: pooled output exceeds 32-bit element offsets");
-        MVLM_REQUIRE(ctx, a.out || a.pool_out, "conv: no output requested");
-        if (variant_out) *variant_out = v;
-        ConvArgs b = a;
-        b.kparts = 1;
-        b.w = a.w_wino4;
-        return mvlm_conv_launch_wino4(ctx, b);  // (check_variant<> refuses what the tile cannot serve: shape, features)
-    }
     MVLM_REQUIRE(ctx, v >= 0, "conv: no kernel variant for this shape");
-    const bool wino = mvlm_conv_variant_is_wino(v);
-    MVLM_REQUIRE(ctx, !wino || a.w_wino, "conv: a Winograd tile needs the layer's transformed weights (mvlm_pack_winograd_weights)");
+    const VariantCode d = decode_variant(v);
+    const WinoForm* form = d.row && d.row->form >= 0 ? &mvlm_wino_form(d.row->form) : nullptr;  // the row says which weights the launch gets
+    MVLM_REQUIRE(ctx, !form || a.*form->weights, std::string("conv: a Winograd tile needs the layer's transformed weights (") + form->pack_fn + ")");
     MVLM_REQUIRE(ctx, !a.in2 || v == 0, "conv: a second input tensor needs the 128-channel 8x32 tile (ask mvlm_conv_in2_ok first)");
     MVLM_REQUIRE(ctx, !a.in2 || px / 4 * a.in2_ctot < lim, "conv: second input exceeds 32-bit element offsets");
     MVLM_REQUIRE(ctx, !a.pool_out || mvlm_conv_variant_can_pool(v), "conv: this shape's kernel variant cannot emit the pooled tensor");
     MVLM_REQUIRE(ctx, !a.pool_out || px / 4 * a.pool_ctot < lim, "conv: pooled output exceeds 32-bit element offsets");
+    MVLM_REQUIRE(ctx, !form || !a.amax_val || a.out || a.pool_out, "conv: a Winograd tile has no fused argmax, and no other output is requested");
     MVLM_REQUIRE(ctx, a.out || a.pool_out || a.amax_val, "conv: no output requested");
     if (variant_out) *variant_out = v;
-    MVLM_REQUIRE(ctx, v < 1024, "conv: unknown kernel variant");
+    MVLM_REQUIRE(ctx, d.kparts > 0, "conv: unknown kernel variant");
     ConvArgs b = a;
-    b.kparts = 1 << (v >> 8);
-    if (wino) b.w = a.w_wino;
-    const ConvVariantInfo* t = conv_variant(v & 255);
-    return t ? t->launch(ctx, b) : ctx->fail("conv: unreachable variant");
+    b.kparts = d.kparts;
+    if (form) b.w = a.*form->weights;
+    return d.row ? d.row->launch(ctx, b) : ctx->fail("conv: unreachable variant");  // (check_variant<> refuses what the tile cannot serve)
 }
 
 
@@ -459,13 +474,12 @@ int mvlm_launch_conv(mvlm_ctx* ctx, const ConvArgs& a, int* variant_out) {
 // this shape and kind?  (kind 2: a tile that cannot pool in its epilogue is followed by the pool kernel; the 80- / 84-row tiles
 // serve conv6 / conv10 only)
 extern "C" int mvlm_conv_variant_serves(int variant, int ksize, int cin_pad, int cout_pad, int size, int kind) {
-    if (variant == MVLM_CONV_VARIANT_WINO4) return kind >= 0 && kind <= 2 && wino4_fits(ksize, cin_pad, cout_pad, size, size);
-    if (variant < 0 || variant >= 1024 || ksize != 3 || kind < 0 || kind > 2) return 0;
-    const ConvVariantInfo* t = conv_variant(variant & 255);
-    if (!t || !tile_fits(*t, ksize, cin_pad, cout_pad, size, size)) return 0;
-    const int parts = 1 << (variant >> 8);
+    const VariantCode d = decode_variant(variant);
+    const ConvVariantInfo* t = d.row;
+    if (!t || ksize != 3 || kind < 0 || kind > 2 || !tile_fits(*t, ksize, cin_pad, cout_pad, size, size)) return 0;
+    const int parts = d.kparts;
     const bool residual_block_tile = !t->TAIL16 && t->COUT_T != 96;                // (the 80-, 84- and 96-row tiles serve the last layers only)
-    const bool bn_fits = !t->WINO || cin_pad <= t->BN_MAXC;                         // (as wino_candidate; the direct tiles check it at the launch)
+    const bool bn_fits = t->form < 0 || cin_pad <= t->BN_MAXC;                      // (as wino_candidate; the direct tiles check it at the launch)
     const bool parts_ok = parts == 1 || (t->SPLITK && t->PIX_T == 32 && cin_pad % (parts * t->CK) == 0);
     return residual_block_tile && bn_fits && parts_ok;
 }
@@ -487,9 +501,7 @@ extern "C" int mvlm_conv_set_override(mvlm_ctx* ctx, int ksize, int cin_pad, int
             ov.push_back({k.ksize, k.cin_pad, k.cout_pad, k.size, k.kind, variant});
         }
     }
-    for (auto& g : ctx->cnn.graphs)
-        if (g.exec) hipGraphExecDestroy(g.exec);
-    ctx->cnn.graphs.clear();
+    ctx->cnn.drop_graphs();
     return 0;
 }
 

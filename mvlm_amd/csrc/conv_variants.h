@@ -70,10 +70,10 @@
     X(40, "conv3x3w_c64_t8x32", Cfg<64, 32, 8, 1, 32, 4>)
 // F(4,3) Winograd along y (KS parameter 34 = "3x3 as F(4,3)", conv_kernel.h: Cfg::WINO4): 6 MFMAs per four output rows and
 // (kx, cin) on the tile geometry of conv3x3_c32_t16x32, host-transformed weights [18][cin_pad][cout_pad].  Instantiated in
-// conv_inst_q0.hip, built into build/wino4/ (occupancy table tests/golden/kernel_occupancy_wino4.json).  It is NOT one of the
-// base variants below: the table of base ids (what every id in 0..1023 is called and serves) is pinned by
-// tests/golden/conv_routing.txt and stays as it is; the tile has a code of its own beyond that range
-// (common.h: MVLM_CONV_VARIANT_WINO4) and one launcher, mvlm_conv_launch_wino4.
+// conv_inst_q0.hip, built into build/wino4/ (occupancy table tests/golden/kernel_occupancy_wino4.json).  It has no base id: what
+// every id in 0..1023 is called and serves is pinned by tests/golden/conv_routing.txt, so the tile has a code of its own beyond
+// that range (common.h: MVLM_CONV_VARIANT_WINO4), one launcher, mvlm_conv_launch_wino4, and no pair form.  In the dispatcher it is
+// a row of the variant table like every variant below (conv_mfma.hip: VARIANTS, decode_variant).
 #define MVLM_CONV_WINO4_NAME "conv3x3q_c32_t16x32"
 #define MVLM_CONV_WINO4_CFG Cfg<32, 32, 16, 1, 34, 4>
 #define MVLM_CONV_VARIANTS(X) \

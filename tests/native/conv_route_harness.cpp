@@ -6,7 +6,13 @@
 // The output (tests/golden/conv_routing.txt) is run-length encoded over the batch axis (BATCHES) and grouped: one line
 //   <what> {<case> <case> ...} | <batches> <result>, <batches> <result>, ...
 // for all cases of <what> (context states, input channels, launch features ...) that decide alike at every batch.
+// Run with the argument "wino4", the same program gives every launch the F(4,3) tile's weights as well (ConvArgs::w_wino4) and
+// adds what only that tile decides: the Winograd mode x F(4,3) mode axis over the shapes of both Winograd tables, the launch
+// features with and without w_wino4, code 2048 as override and as forced variant, and the per-variant queries for the codes
+// 1024..4200 (tests/golden/conv_routing_wino4.txt).  There a refused launch prints a bare E: which launches are refused, which
+// succeed and where they land is pinned, not the wording.
 #include <cstdio>
+#include <cstring>
 #include <functional>
 #include <map>
 #include <set>
@@ -20,6 +26,7 @@
 #include "../../mvlm_amd/csrc/conv_tuned_net.h"
 #include "../../mvlm_amd/csrc/conv_pair_tuned.h"
 #include "../../mvlm_amd/csrc/conv_tuned_wino.h"
+#include "../../mvlm_amd/csrc/conv_tuned_wino4.h"
 
 // ---- stubs ------------------------------------------------------------------------------------------------------------------
 hipError_t hipSetDevice(int) { return hipSuccess; }
@@ -48,11 +55,16 @@ struct Reached {
     }
 MVLM_CONV_VARIANTS(X)
 #undef X
+int mvlm_conv_launch_wino4(mvlm_ctx*, const ConvArgs& a) {
+    g_reached = {MVLM_CONV_VARIANT_WINO4, a.kparts, 0, a.w};
+    return 0;
+}
 
 namespace {
 
-float g_dummy, g_dummy_wino;
+float g_dummy, g_dummy_wino, g_dummy_wino4;
 int g_dummy_int;
+bool g_wino4 = false;  // the second pass: every launch carries w_wino4
 
 std::vector<int> batches() {
     std::vector<int> b;
@@ -136,6 +148,7 @@ ConvArgs make_args(const Shape& s, int kind, int batch) {
     a.B = batch;
     a.in = a.w = &g_dummy;
     a.w_wino = &g_dummy_wino;
+    if (g_wino4) a.w_wino4 = &g_dummy_wino4;
     a.out = &g_dummy;
     if (kind == 1) {
         a.up_out = 1;
@@ -151,8 +164,9 @@ ConvArgs make_args(const Shape& s, int kind, int batch) {
 
 // One launch as a token: "<variant_out>" when mvlm_launch_conv succeeded, "E<n>" (+ "@<variant_out>" if it was set) when not,
 // then a letter per query that says yes: p mvlm_conv_can_pool, i mvlm_conv_in2_ok, w mvlm_conv_wino_variant >= 0 (+ its id
-// where that is not variant_out), s the stub received w_wino as its weights.  A successful launch must reach stub
-// variant_out & 255 with kparts 1 << (variant_out >> 8); otherwise "!<stub>/<kparts>" follows.
+// where that is not variant_out), s the stub received w_wino as its weights, q it received w_wino4.  A successful launch must
+// reach stub variant_out & 255 with kparts 1 << (variant_out >> 8), code 2048 the F(4,3) stub with kparts 1; otherwise
+// "!<stub>/<kparts>" follows.  The second pass prints a refusal as "E[@<variant_out>]", without the message's number.
 // pool_as_asked: give the launch a pooled output exactly where mvlm_conv_can_pool allows one, as the network does
 std::string single(mvlm_ctx& ctx, ConvArgs a, bool pool_as_asked = true) {
     const int pool = mvlm_conv_can_pool(&ctx, a), in2 = mvlm_conv_in2_ok(&ctx, a), wino = mvlm_conv_wino_variant(&ctx, a);
@@ -161,12 +175,14 @@ std::string single(mvlm_ctx& ctx, ConvArgs a, bool pool_as_asked = true) {
     ctx.err.clear();
     int v = -9;
     const int rc = mvlm_launch_conv(&ctx, a, &v);
-    std::string t = rc ? error_token(ctx.err) + (v != -9 ? "@" + std::to_string(v) : "") : std::to_string(v);
+    std::string t = rc ? (g_wino4 ? "E" : error_token(ctx.err)) + (v != -9 ? "@" + std::to_string(v) : "") : std::to_string(v);
     if (pool) t += "p";
     if (in2) t += "i";
     if (wino >= 0) t += wino == v ? "w" : "w" + std::to_string(wino);
     if (g_reached.w == &g_dummy_wino) t += "s";
-    if (rc ? g_reached.id != -1 : (g_reached.id != (v & 255) || g_reached.kparts0 != 1 << (v >> 8)))
+    if (g_reached.w == &g_dummy_wino4) t += "q";
+    const bool is4 = v == MVLM_CONV_VARIANT_WINO4;
+    if (rc ? g_reached.id != -1 : (g_reached.id != (is4 ? v : v & 255) || g_reached.kparts0 != (is4 ? 1 : 1 << (v >> 8))))
         t += "!" + std::to_string(g_reached.id) + "/" + std::to_string(g_reached.kparts0);
     return t;
 }
@@ -192,10 +208,11 @@ std::string pair(mvlm_ctx& ctx, ConvArgs a0, ConvArgs a1, int mode) {
 
 struct State {
     const char* name;
-    int winograd, force;
+    int winograd, force, winograd4 = 1;
 };
 void set_state(mvlm_ctx& ctx, const State& st) {
     ctx.conv_winograd = st.winograd;
+    ctx.conv_winograd4 = st.winograd4;
     ctx.conv_force_variant = st.force;
 }
 const State DEFAULT_STATE = {"w1", 1, -1};
@@ -210,7 +227,7 @@ void singles(mvlm_ctx& ctx, Grouped& g, const std::vector<Shape>& shapes, const 
 }
 
 // launch features beyond the kind, for the fixed list
-const char* const FEATURES[] = {"plain", "kind1", "amax", "up_in", "up_out2", "up_out2x4", "in2", "pool_out", "no_w_wino"};
+const char* const FEATURES[] = {"plain", "kind1", "amax", "up_in", "up_out2", "up_out2x4", "in2", "pool_out", "no_w_wino", "no_w_wino4"};
 ConvArgs feature_args(const Shape& s, int feature, int batch) {
     ConvArgs a = make_args(s, feature == 1 ? 1 : 0, batch);
     switch (feature) {
@@ -236,13 +253,16 @@ ConvArgs feature_args(const Shape& s, int feature, int batch) {
         a.pool_ctot = a.cout_pad;
         break;
     case 8: a.w_wino = nullptr; break;
+    case 9: a.w_wino4 = nullptr; break;
     }
     return a;
 }
 
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
+    g_wino4 = argc > 1 && !std::strcmp(argv[1], "wino4");
+    const int n_features = g_wino4 ? 10 : 9;  // (no_w_wino4 says something in the second pass only)
     mvlm_ctx ctx;
     set_state(ctx, DEFAULT_STATE);
     Grouped g;
@@ -268,8 +288,10 @@ int main() {
         const ConvTunedWino& e = MVLM_CONV_TUNED_WINO[i];
         table_set.insert({3, e.cin_pad, e.cout_pad, e.size});
     }
-    const std::vector<Shape> table_shapes(table_set.begin(), table_set.end());
-
+    std::set<Shape> wino_set;  // the shapes of the two Winograd tables (all of them among the tables' shapes already)
+    for (int i = 0; i < MVLM_CONV_TUNED_WINO_N; ++i) wino_set.insert({3, MVLM_CONV_TUNED_WINO[i].cin_pad, MVLM_CONV_TUNED_WINO[i].cout_pad, MVLM_CONV_TUNED_WINO[i].size});
+    for (int i = 0; i < MVLM_CONV_TUNED_WINO4_N; ++i) wino_set.insert({3, MVLM_CONV_TUNED_WINO4[i].cin_pad, MVLM_CONV_TUNED_WINO4[i].cout_pad, MVLM_CONV_TUNED_WINO4[i].size});
+    const std::vector<Shape> table_shapes(table_set.begin(), table_set.end()), wino_shapes(wino_set.begin(), wino_set.end());
 
     std::printf("# single launches.  Result of a launch: <variant_out> or E<n>[@<variant_out>], then p = can_pool, i = in2_ok, w[<id>] = routed to a\n"
                 "# Winograd variant, s = the weights were swapped for w_wino.  Context states: w<m> Winograd mode m; rules conv_force_variant -2;\n"
@@ -278,8 +300,20 @@ int main() {
     for (const State& st : {State{"w0", 0, -1}, DEFAULT_STATE, State{"w2", 2, -1}, State{"rules", 1, -2}}) singles(ctx, g, table_shapes, st);
     g.print();
 
+    if (g_wino4) {
+        std::printf("# -- second pass: every launch carries w_wino4; q = the weights were swapped for it; a refusal is E[@<variant_out>].\n"
+                    "# Shapes of the two Winograd tables, Winograd mode x F(4,3) mode: <shape> <kind> {w<mode>q<mode4>}\n");
+        for (int m = 0; m < 3; ++m)
+            for (int m4 = 0; m4 < 3; ++m4) {
+                const std::string name = "w" + std::to_string(m) + "q" + std::to_string(m4);
+                singles(ctx, g, wino_shapes, State{name.c_str(), m, -1, m4});
+            }
+        g.print();
+    }
+
     const int couts[] = {32, 64, 80, 84, 96, 128}, sizes[] = {4, 8, 16, 32, 64, 128, 256}, cins[] = {4, 16, 32, 64, 128, 256, 320};
-    const State fixed_states[] = {State{"w0", 0, -1}, DEFAULT_STATE, State{"w2", 2, -1}, State{"rules", 1, -2}};
+    std::vector<State> fixed_states = {State{"w0", 0, -1}, DEFAULT_STATE, State{"w2", 2, -1}, State{"rules", 1, -2}};
+    if (g_wino4) fixed_states.insert(fixed_states.end(), {State{"w1q2", 1, -1, 2}, State{"w2q2", 2, -1, 2}, State{"w1q0", 1, -1, 0}});
     std::printf("# -- fixed list, plain 3x3 layers: k3 *><cout_pad> @<size> {<state>:<cin_pad>}\n");
     for (const State& st : fixed_states) {
         set_state(ctx, st);
@@ -297,11 +331,11 @@ int main() {
         for (int ks : {1, 2, 3})
             for (int co : couts)
                 for (int s : {16, 32, 128})
-                    for (int f = ks == 3 ? 1 : 0; f < 9; ++f) {
+                    for (int f = ks == 3 ? 1 : 0; f < n_features; ++f) {
                         // (the plain 3x3 layers are above; 1x1 and 2x2 do not look at the Winograd mode)
-                        if (ks != 3 && st.winograd == 2) continue;
+                        if (ks != 3 && (st.winograd == 2 || st.winograd4 != 1)) continue;
                         if (ks == 1 && f != 0 && f != 1 && f != 7) continue;
-                        if (ks == 2 && (f == 1 || f == 3 || f == 7 || f == 8)) continue;
+                        if (ks == 2 && (f == 1 || f == 3 || f == 7 || f == 8 || f == 9)) continue;
                         const Shape sh{ks, 128, co, s};
                         g.add(shape_label(sh), std::string(st.name) + ":" + FEATURES[f], runs([&](int b) { return single(ctx, feature_args(sh, f, b), false); }));
                     }
@@ -314,7 +348,23 @@ int main() {
     for (const Shape& s : table_shapes)
         if (std::get<1>(s) == 128 && std::get<2>(s) == 64 && std::get<3>(s) >= 64) ov_shapes.push_back(s);
     singles(ctx, g, ov_shapes, {"force10", 1, 10});
-    for (int variant : {9, 40, -1, 0, 265}) {
+    if (g_wino4) {
+        singles(ctx, g, ov_shapes, {"force2048", 1, MVLM_CONV_VARIANT_WINO4});
+        // the forced F(4,3) tile with each feature: a shape it divides, one too small for it, one with more channels than its LDS table
+        ctx.conv_force_variant = MVLM_CONV_VARIANT_WINO4;
+        for (const Shape& sh : {Shape{3, 128, 64, 64}, Shape{3, 128, 64, 8}, Shape{3, 320, 64, 64}})
+            for (int f = 0; f < n_features; ++f)
+                g.add(shape_label(sh), std::string("force2048:") + FEATURES[f], runs([&](int b) { return single(ctx, feature_args(sh, f, b), false); }));
+        ctx.conv_force_variant = -1;
+    }
+    std::vector<int> ov_variants = {9, 40, -1, 0, 265};
+    if (g_wino4) {
+        ov_variants.push_back(MVLM_CONV_VARIANT_WINO4);
+        ctx.err.clear();
+        const int rc = mvlm_conv_set_override(&ctx, 3, 128, 64, 8, 0, MVLM_CONV_VARIANT_WINO4);  // (8x8: the tile does not divide it)
+        std::printf("set_override %d at size 8 -> %d%s, %d entries\n", MVLM_CONV_VARIANT_WINO4, rc, rc ? (" " + error_token(ctx.err)).c_str() : "", int(ctx.conv_overrides.size()));
+    }
+    for (int variant : ov_variants) {
         ctx.err.clear();
         const int rc = mvlm_conv_set_override(&ctx, 3, 128, 64, 64, 0, variant);
         std::printf("set_override %d -> %d%s, %d entries\n", variant, rc, rc ? (" " + error_token(ctx.err)).c_str() : "", int(ctx.conv_overrides.size()));
@@ -405,8 +455,9 @@ int main() {
         g.print();
     }
 
-    std::printf("# mvlm_conv_variant_serves: k<ksize> *><cout_pad> @<size> {<cin_pad>:<kinds of -1..3 with this answer>} | the ids of -1..1023 that serve\n");
-    {
+    // the ids of first..last that serve every shape of the list, per kind
+    auto serves = [&](int first, int last) {
+        std::printf("# mvlm_conv_variant_serves: k<ksize> *><cout_pad> @<size> {<cin_pad>:<kinds of -1..3 with this answer>} | the ids of %d..%d that serve\n", first, last);
         std::vector<Shape> shapes = table_shapes;
         for (int co : couts)
             for (int s : sizes)
@@ -415,7 +466,7 @@ int main() {
             Grouped kinds;  // the kinds of this shape with equal answers
             for (int kind = -1; kind <= 3; ++kind) {
                 std::string ids;
-                for (int v = -1; v < 1024; ++v)
+                for (int v = first; v <= last; ++v)
                     if (mvlm_conv_variant_serves(v, std::get<0>(s), std::get<1>(s), std::get<2>(s), std::get<3>(s), kind)) ids += " " + std::to_string(v);
                 kinds.add(ids, std::to_string(kind), "");
             }
@@ -428,7 +479,9 @@ int main() {
             }
         }
         g.print();
-    }
+    };
+    serves(-1, 1023);
+    if (g_wino4) serves(1024, 4200);
 
     std::printf("# variant ids -1..255: <first>-<last> | name is_wino can_pool\n");
     {
@@ -459,6 +512,22 @@ int main() {
         for (int v : {260, 527, 808, 1063, P | 0, P | 10, P | 15 | (1 << 8) | (2 << 10), P | 13 | (3 << 10), P | 40, P | 63, 2 * P | 10})
             std::printf("id %d | %s\n", v, describe(v).c_str());
     }
+    if (g_wino4) {
+        std::printf("# variant codes 1024..4200: <first>-<last> | name is_wino is_wino4 can_pool\n");
+        auto describe = [](int v) {
+            return std::string(mvlm_conv_variant_name_impl(v)) + " " + std::to_string(int(mvlm_conv_variant_is_wino(v))) + " " +
+                   std::to_string(int(mvlm_conv_variant_is_wino4(v))) + " " + std::to_string(int(mvlm_conv_variant_can_pool(v)));
+        };
+        std::string cur = describe(1024);
+        int first = 1024;
+        for (int v = 1025; v <= 4201; ++v) {
+            const std::string d = v <= 4200 ? describe(v) : std::string();
+            if (d == cur) continue;
+            std::printf("code %d-%d | %s\n", first, v - 1, cur.c_str());
+            cur = d;
+            first = v;
+        }
+    }
 
     std::printf("# mvlm_conv_wino_serves_slot: k<ksize> {cin_pad} | the cout_pad it serves\n");
     for (int ks : {1, 2, 3})
@@ -469,6 +538,17 @@ int main() {
             g.add("slot k" + std::to_string(ks), std::to_string(ci), cos.empty() ? "none" : cos.substr(1));
         }
     g.print();
+    if (g_wino4) {
+        std::printf("# mvlm_conv_wino4_serves_slot: k<ksize> {cin_pad} | the cout_pad it serves\n");
+        for (int ks : {1, 2, 3})
+            for (int ci : {3, 4, 6, 16, 32, 64, 76, 84, 128, 256, 320}) {
+                std::string cos;
+                for (int co : {32, 64, 80, 84, 96, 128, 192, 256})
+                    if (mvlm_conv_wino4_serves_slot(ks, ci, co)) cos += " " + std::to_string(co);
+                g.add("slot4 k" + std::to_string(ks), std::to_string(ci), cos.empty() ? "none" : cos.substr(1));
+            }
+        g.print();
+    }
 
     std::printf("# error messages\n");
     for (size_t i = 0; i < g_errors.size(); ++i) std::printf("E%d: %s\n", int(i) + 1, g_errors[i].c_str());

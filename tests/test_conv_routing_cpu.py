@@ -6,8 +6,14 @@ decisions for the shapes of the four tuned tables, a fixed list that reaches eve
 (Winograd modes, forced variants, tuning overrides), the pair routing and the per-variant queries, run-length encoded over the
 batch axis, the cases that decide alike on one line.  The output must equal tests/golden/conv_routing.txt byte for byte.
 
-The golden is a function of the committed tuned tables and of the variant list: a retune or a new variant regenerates it
-(run the harness built as below and keep its output) - a change of the dispatcher's code alone must not move it."""
+Run with the argument "wino4", the harness gives every launch the F(4,3) Winograd tile's weights (ConvArgs::w_wino4) as well and
+adds what only that tile decides: the Winograd mode x F(4,3) mode axis over the shapes of both Winograd tables, the launch
+features with and without those weights, code 2048 as tuning override and as forced variant, and the per-variant queries for
+the codes 1024..4200.  That output must equal tests/golden/conv_routing_wino4.txt byte for byte.  It prints a refused launch
+without its message, so it pins which launches are refused, which succeed and on which kernel they land, not the wording.
+
+The goldens are a function of the committed tuned tables and of the variant list: a retune or a new variant regenerates them
+(run the harness built as below and keep its output) - a change of the dispatcher's code alone must not move them."""
 import shutil
 import subprocess
 from pathlib import Path
@@ -20,8 +26,12 @@ HIPCC = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if Path("/opt/rocm/bin/h
 HOST = ["--offload-host-only", "-std=c++17", "-O1", "-Wall", "-Wno-unused-value"]
 
 
-@pytest.mark.skipif(HIPCC is None, reason="needs hipcc")
-def test_dispatcher_decisions_equal_the_golden(tmp_path):
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    """The harness binary, built once for both tests."""
+    if HIPCC is None:
+        pytest.skip("needs hipcc")
+    tmp_path = tmp_path_factory.mktemp("conv_route")
     objs = []
     for src in ("mvlm_amd/csrc/conv_mfma.hip", "tests/native/conv_route_harness.cpp"):
         obj = tmp_path / (Path(src).stem + ".o")
@@ -31,13 +41,25 @@ def test_dispatcher_decisions_equal_the_golden(tmp_path):
     exe = tmp_path / "conv_route_harness"
     r = subprocess.run([HIPCC, "--offload-host-only", "-no-hip-rt", *objs, "-o", str(exe)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
-    r = subprocess.run([str(exe)], capture_output=True)
+    return exe
+
+
+def _equals_golden(exe, args, golden):
+    r = subprocess.run([str(exe), *args], capture_output=True)
     assert r.returncode == 0, r.stderr[-3000:]
-    want = (REPO / "tests/golden/conv_routing.txt").read_bytes()
+    want = (REPO / "tests/golden" / golden).read_bytes()
     if r.stdout != want:
         got_lines, want_lines = r.stdout.decode().splitlines(), want.decode().splitlines()
         first = next((i for i, (g, w) in enumerate(zip(got_lines, want_lines)) if g != w), min(len(got_lines), len(want_lines)))
         differing = sum(g != w for g, w in zip(got_lines, want_lines)) + abs(len(got_lines) - len(want_lines))
-        pytest.fail(f"{differing} lines differ from the golden, the first at line {first + 1}:\n"
+        pytest.fail(f"{differing} lines differ from {golden}, the first at line {first + 1}:\n"
                     f"  golden: {want_lines[first] if first < len(want_lines) else '<end>'}\n"
                     f"  now:    {got_lines[first] if first < len(got_lines) else '<end>'}")
+
+
+def test_dispatcher_decisions_equal_the_golden(harness):
+    _equals_golden(harness, [], "conv_routing.txt")
+
+
+def test_dispatcher_decisions_with_f43_weights_equal_the_golden(harness):
+    _equals_golden(harness, ["wino4"], "conv_routing_wino4.txt")

@@ -7,6 +7,7 @@
 
 `dump` writes DIR/conv_identity.json, name -> shape, dtype, sha256 of
   - every layer of tests/test_gpu_winograd.py::LAYER_CASES with variant 40 forced (same seeds, same tensors),
+  - every layer of tests/test_gpu_winograd4.py::LAYER_CASES with the F(4,3) tile's code 2048 forced, likewise,
   - tests/test_gpu_parity.py::CONV_CASES through mvlm_conv2d,
   - tests/test_gpu_round4.py::PAIR_CASES through mvlm_conv2d_pair (both problems' outputs and raw copies),
   - the cases of test_two_column_split_k_tiles_match_torch with their variant forced,
@@ -74,11 +75,12 @@ def _layers(ctx, table) -> None:
     import test_gpu_parity as TP
     import test_gpu_round4 as T4
     import test_gpu_winograd as TW
+    import test_gpu_winograd4 as TW4
     import torch
 
     tag = lambda opts: "-".join(sorted(opts)) or "plain"
-    for variant in TW.WINO_IDS:
-        for cin, cout, size, batch, opts in TW.LAYER_CASES:
+    for variant, cases in [(v, TW.LAYER_CASES) for v in TW.WINO_IDS] + [(TW4.WINO4, TW4.LAYER_CASES)]:
+        for cin, cout, size, batch, opts in cases:
             t = _tensors(np.random.RandomState(cin * 7 + cout + size), cin, cout, size, 3, batch, opts)
             table[f"layer_v{variant}_{cin}_{cout}_{size}_b{batch}_{tag(opts)}"] = _entry(_conv2d(ctx, *t, variant=variant))
     for cin, cout, size, k, batch, opts in TP.CONV_CASES:
