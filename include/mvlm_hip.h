@@ -219,6 +219,31 @@ int mvlm_render_ray_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot
  * (copies and fills, transform, classify, scan, bin fill, landmark projection), the ray projection, the tile kernel. */
 int mvlm_ray_view_stage_ms(mvlm_ctx* ctx, float* ms8);
 
+/* ---- PNG on the device (the views' files without the picture crossing to the host) ---- */
+/* Bytes that hold any file mvlm_png_encode writes for a picture of height x width (each 1..4096): the filtered stream
+ * height * (1 + 3 * width), 10 bytes per 32 768-byte segment of it (5 of a stored block's header, 5 of the flush), and 63 of
+ * signature, IHDR, IDAT framing, zlib header, Adler-32 and IEND.  No GPU and no context.  0, or 1 for a size out of range, 2 for
+ * a NULL pointer. */
+int mvlm_png_bound(int height, int width, size_t* bytes);
+/* rgba_dev u8[n_images,height,width,4] on the device, the layout mvlm_render_landmark_view and mvlm_render_ray_view write (alpha
+ * is dropped) -> n_images complete PNG files (8-bit RGB: colour type 2, no interlace, one IDAT) in host memory, file i at
+ * png_host + i * stride_bytes with png_bytes_out[i] bytes.  The files are complete when the call returns (it waits for the
+ * launch stream); only the compressed bytes are copied from the device.
+ *   filter_mode   -1: every row takes the filter type (0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth) with the smallest sum of
+ *                 b < 128 ? b : 256 - b over its filtered bytes, the lowest type on a tie; 0..4: that type for every row
+ * The filtered stream is cut into segments of 32 768 bytes, each compressed on its own by one workgroup: literals and matches
+ * of distance 1 (runs), one DEFLATE block per segment - stored, fixed or dynamic Huffman, whichever makes the segment smallest -
+ * and an empty stored block behind every compressed segment but the last.  The bytes are a function of the pixels only
+ * (DESIGN.md 4.5 states every rule; tests/png_model.py states them a second time).
+ * height and width 1..4096, n_images 1..128, n_images * height * width <= 8 * 2048 * 2048 as the view calls allow; a value out of
+ * range, a filter_mode outside -1..4, stride_bytes below mvlm_png_bound's, a NULL pointer return an error that starts with
+ * "png:" and launch nothing. */
+int mvlm_png_encode(mvlm_ctx* ctx, const uint8_t* rgba_dev, int n_images, int height, int width, int filter_mode,
+                    uint8_t* png_host, size_t stride_bytes, size_t* png_bytes_out /* [n_images] */);
+/* With mvlm_render_set_profiling on, the last mvlm_png_encode's stages in milliseconds (HIP events), f32[4]: filter, deflate,
+ * gather (offsets and copy on the device), copy to host (with the host's wait for the sizes in front of it). */
+int mvlm_png_stage_ms(mvlm_ctx* ctx, float* ms4);
+
 /* ---- landmark network (replaces paulsenpredictor.py:89-110, :167-217) ------------ */
 /* blob/desc: output of mvlm_amd.weights.pack_for_device (BN folded, weights as
  * [tap][cin_pad][cout_pad]); copied to the device. */

@@ -64,6 +64,10 @@ def build_parser() -> argparse.ArgumentParser:
                              "scan: the mesh, every view's ray for every landmark clipped to its first hit with the surface, and the "
                              "landmarks, from the front and from 60 degrees left and right (with --report the rays are green where the "
                              "consensus used them, orange where it kept but did not use them, grey where the score filter dropped them)")
+    parser.add_argument("--png-encoder", choices=("host", "device"), default="host",
+                        help="who makes the PNG files of --visualize-img and --visualize-rays: 'host' copies the picture to the host "
+                             "and encodes it with Pillow; 'device' filters and compresses it on the GPU and copies only the file's "
+                             "bytes (the same pixels, other bytes)")
     return parser
 
 
@@ -110,6 +114,8 @@ def main(argv=None) -> int:
     if args.visualize_rays:
         extra["visualize_rays_img"] = True
         extra["visualize_size"] = args.visualize_size
+    if args.png_encoder != "host":
+        extra["view_png_encoder"] = args.png_encoder
     if args.config is not None:
         from . import config as mvlm_config
 

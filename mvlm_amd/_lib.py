@@ -59,6 +59,10 @@ SIGNATURES = {
                                        C.c_float, c_uint8_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, c_uint8_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "mvlm_ray_view_stage_ms": (C.c_int, [C.c_void_p, c_float_p]),
+    "mvlm_png_bound": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "mvlm_png_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                  C.POINTER(C.c_size_t)]),
+    "mvlm_png_stage_ms": (C.c_int, [C.c_void_p, c_float_p]),
     "mvlm_render_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),
     "mvlm_render_get_profile": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p, c_int32_p, c_float_p, C.c_int]),
     "mvlm_render_rotations_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),

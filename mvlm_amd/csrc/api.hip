@@ -84,6 +84,8 @@ extern "C" void mvlm_ctx_destroy(mvlm_ctx* ctx) {
         if (e) hipEventDestroy(e);
     for (auto e : ctx->view_events)
         if (e) hipEventDestroy(e);
+    for (auto e : ctx->png_events)
+        if (e) hipEventDestroy(e);
     for (auto e : ctx->cnn.sync_events)
         if (e) hipEventDestroy(e);
     ctx->cnn.drop_graphs();

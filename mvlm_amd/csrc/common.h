@@ -313,6 +313,9 @@ struct mvlm_ctx {
     std::vector<hipEvent_t> view_events;
     bool view_events_valid = false;
     bool ray_events_valid = false;  // likewise the last ray view (raster_rays.hip: nine events, mvlm_ray_view_stage_ms)
+    // PNG encoder (png_encode.hip): the five events around its four stages while render_profiling is on (mvlm_png_stage_ms)
+    std::vector<hipEvent_t> png_events;
+    bool png_events_valid = false;
     // device buffers of freed meshes, reused by the next upload: a folder of scans would otherwise pay
     // four hipMalloc + four (device-synchronising) hipFree per scan
     struct PoolEntry {

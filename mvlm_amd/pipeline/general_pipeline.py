@@ -92,7 +92,8 @@ class Pipeline(abc.ABC):
                  screenshot_folder: Path | None = None, device: int = 0, shard_views: bool = False,
                  verbose: bool = True, render_multisamples: int = 0, landmark_report: bool = False,
                  visualize_img: bool = False, visualize_size: int = 1024, visualize_name: str | None = None,
-                 visualize_rays_img: bool = False, visualize_rays_poses=((0, 0, 0), (0, 60, 0), (0, -60, 0))):
+                 visualize_rays_img: bool = False, visualize_rays_poses=((0, 0, 0), (0, 60, 0), (0, -60, 0)),
+                 view_png_encoder: str = "host"):
         self.render_image_stack = render_image_stack
         self.render_image_folder = render_image_folder
         self.n_views = n_views
@@ -126,6 +127,13 @@ class Pipeline(abc.ABC):
         self.visualize_rays_img = bool(visualize_rays_img)
         self.visualize_rays_poses = np.asarray(visualize_rays_poses, dtype=np.float64).reshape(-1, 3)
         self.last_ray_view_paths: list = []
+        # view_png_encoder: who makes the PNG files of visualize_img and visualize_rays_img.  "host" (the default): the picture
+        # is copied to the host and Pillow encodes it.  "device": the picture stays where render_*_view_device left it and
+        # HipRenderer3D.encode_png filters and compresses it there (mvlm_png_encode; the ray view's pictures in one call) - the
+        # same pixels in a file of other bytes, and only the compressed bytes cross to the host.
+        from ..utils.viewer import check_png_encoder
+
+        self.view_png_encoder = check_png_encoder(view_png_encoder)
         # (mesh, starts, ends, landmarks in the uploaded space, report) of the current call, kept only between a prediction made by
         # predict_one_file / predict_files (_keep_ray_view) and the _after_prediction that draws it: predict_mesh_device called on
         # its own has no file name, draws nothing and leaves nothing behind
@@ -324,12 +332,18 @@ class Pipeline(abc.ABC):
             if not finite.all():
                 landmarks = landmarks[finite]
                 colours = None if colours is None else colours[finite]
-            images = self.renderer_3d.render_ray_view(mesh, landmarks, fs, fe, poses=self.visualize_rays_poses, size=self.visualize_size,
-                                                      colors=colours, ray_colors=ray_colours)
+            device = self.view_png_encoder == "device"
+            draw = self.renderer_3d.render_ray_view_device if device else self.renderer_3d.render_ray_view
+            images = draw(mesh, landmarks, fs, fe, poses=self.visualize_rays_poses, size=self.visualize_size, colors=colours,
+                          ray_colors=ray_colours)
             folder = Path(self.screenshot_folder) if self.screenshot_folder else Path.cwd() / "visualization" / "ray_screenshots"
             stem = Path(file_name).stem
-            self.last_ray_view_paths = [write_view_png(image, folder / f"{stem}_{self.visualize_name}_rays_{i}.png")
-                                        for i, image in enumerate(images)]
+            paths = [folder / f"{stem}_{self.visualize_name}_rays_{i}.png" for i in range(len(images))]
+            if device:  # the pictures stay on the device: one encode call for all poses
+                self.last_ray_view_paths = write_view_png(images, paths, encoder="device", renderer=self.renderer_3d)
+                self.renderer_3d.check()
+            else:
+                self.last_ray_view_paths = [write_view_png(image, q) for image, q in zip(images, paths)]
         self._say(f"[Pipeline] ray view written to {[str(q) for q in self.last_ray_view_paths]}")
         return self.last_ray_view_paths
 
@@ -553,8 +567,14 @@ class Pipeline(abc.ABC):
             if not finite.all():
                 landmarks = landmarks[finite]
                 colours = None if colours is None else colours[finite]
-            image = self.renderer_3d.render_landmark_view(mesh, landmarks, size=self.visualize_size, colors=colours)[0]
-            self.last_view_path = write_view_png(image, view_path(getattr(mesh, "path", None) or "mesh.obj", self.visualize_name))
+            out_path = view_path(getattr(mesh, "path", None) or "mesh.obj", self.visualize_name)
+            if self.view_png_encoder == "device":  # the picture stays on the device
+                image = self.renderer_3d.render_landmark_view_device(mesh, landmarks, size=self.visualize_size, colors=colours)[0]
+                self.last_view_path = write_view_png(image, out_path, encoder="device", renderer=self.renderer_3d)
+                self.renderer_3d.check()
+            else:
+                image = self.renderer_3d.render_landmark_view(mesh, landmarks, size=self.visualize_size, colors=colours)[0]
+                self.last_view_path = write_view_png(image, out_path)
         self._say(f"[Pipeline] landmark view written to {self.last_view_path}")
         return self.last_view_path
 

@@ -453,6 +453,48 @@ class HipRenderer3D:
         self.check()
         return (image, counts, ray_counts) if return_pixels else image
 
+    # ---- PNG on the device -------------------------------------------------------------------
+    @staticmethod
+    def png_bound(height: int, width: int) -> int:
+        """Bytes that hold any file ``encode_png`` writes for a picture of this size (mvlm_png_bound; no GPU)."""
+        n = C.c_size_t()
+        if _lib.load().mvlm_png_bound(int(height), int(width), C.byref(n)) != 0:
+            raise ValueError(f"png: height and width must be 1..4096, not {height} x {width}")
+        return int(n.value)
+
+    def encode_png(self, rgba, filter_mode: int = -1) -> list:
+        """The pictures of a uint8 device tensor [H,W,4] or [n,H,W,4] (RGBA as ``render_landmark_view_device`` and
+        ``render_ray_view_device`` leave them; alpha is dropped) as complete 8-bit RGB PNG files, one ``bytes`` per picture,
+        filtered and compressed on the device: only the compressed bytes cross to the host (mvlm_png_encode).
+        ``filter_mode`` -1 picks a filter type per row, 0..4 forces one."""
+        import torch
+
+        if not hasattr(rgba, "data_ptr") or not rgba.is_cuda or rgba.dtype != torch.uint8:
+            raise ValueError("png: encode_png takes a uint8 tensor on the device")
+        if rgba.device.index != self.ctx.device:
+            raise ValueError(f"png: the tensor lives on {rgba.device}, the renderer on cuda:{self.ctx.device}")
+        if rgba.dim() == 3:
+            rgba = rgba[None]
+        if rgba.dim() != 4 or rgba.shape[-1] != 4:
+            raise ValueError(f"png: the pictures must be [H,W,4] or [n,H,W,4], not {tuple(rgba.shape)}")
+        rgba = rgba.contiguous()
+        n, h, w = int(rgba.shape[0]), int(rgba.shape[1]), int(rgba.shape[2])
+        if n < 1 or not (1 <= h <= 4096 and 1 <= w <= 4096):
+            raise ValueError(f"png: n >= 1 pictures of 1..4096 pixels a side, not {tuple(rgba.shape)}")
+        stride = self.png_bound(h, w)
+        host = np.empty((n, stride), dtype=np.uint8)
+        sizes = (C.c_size_t * n)()
+        self.ctx.bind_current_stream(torch, rgba.device)
+        self.ctx.check(self.ctx.lib.mvlm_png_encode(self.ctx.handle, C.c_void_p(rgba.data_ptr()), n, h, w, int(filter_mode),
+                                                    C.c_void_p(host.ctypes.data), C.c_size_t(stride), sizes), ValueError)
+        return [host[i, :int(sizes[i])].tobytes() for i in range(n)]
+
+    def png_stage_ms(self) -> np.ndarray:
+        """Milliseconds of the last ``encode_png``'s stages under render profiling: filter, deflate, gather, copy to host."""
+        ms = np.zeros(4, dtype=np.float32)
+        self.ctx.check(self.ctx.lib.mvlm_png_stage_ms(self.ctx.handle, _lib.as_ptr(ms, C.c_float)))
+        return ms
+
     def rotations_device(self):
         """The last render's rotation table where the rasteriser keeps it on the device (f64[N,9]; valid until this context's
         next render): an object with ``data_ptr()`` that ``HipEstimator3D.lines_device(rot_dev=...)`` takes - the rays of the

@@ -21,8 +21,38 @@ def view_path(filename, pname: str | None = None) -> Path:
     return Path("visualization") / f"{Path(filename).stem}{suffix}.png"
 
 
-def write_view_png(image: np.ndarray, out_path: Path) -> Path:
-    """uint8 [S,S,3] -> PNG through Pillow (as Pipeline.visualize_image_stack); makes the folder (viewer.py:93)."""
+PNG_ENCODERS = ("host", "device")
+
+
+def check_png_encoder(encoder: str) -> str:
+    if encoder not in PNG_ENCODERS:
+        raise ValueError(f"the PNG encoder must be 'host' or 'device', not {encoder!r}")
+    return encoder
+
+
+def write_view_png(image, out_path, encoder: str = "host", renderer=None):
+    """uint8 [S,S,3] -> PNG through Pillow (as Pipeline.visualize_image_stack); makes the folder (viewer.py:93).
+
+    ``encoder="device"``: ``image`` is the uint8 device tensor [S,S,4] a ``render_*_view_device`` call left (or [n,S,S,4] with
+    ``out_path`` a sequence of n paths; the list of paths is returned): filtered and compressed on the device
+    (``HipRenderer3D.encode_png``, all pictures in one call), so the pixels never cross to the host.  ``renderer``: the
+    ``HipRenderer3D`` to encode with (default: one on the tensor's device)."""
+    if check_png_encoder(encoder) == "device":
+        if not hasattr(image, "data_ptr"):
+            raise ValueError("write_view_png(encoder='device') takes the device tensor of a render_*_view_device call")
+        if renderer is None:
+            from .render3d import HipRenderer3D
+
+            renderer = HipRenderer3D(n_views=1, device=image.device.index or 0, verbose=False)
+        single = image.dim() == 3
+        paths = [Path(out_path)] if single else [Path(q) for q in out_path]
+        files = renderer.encode_png(image)
+        if len(files) != len(paths):
+            raise ValueError(f"{len(files)} pictures but {len(paths)} paths")
+        for q, data in zip(paths, files):
+            q.parent.mkdir(parents=True, exist_ok=True)
+            q.write_bytes(data)
+        return paths[0] if single else paths
     from PIL import Image
 
     out_path = Path(out_path)
@@ -33,7 +63,7 @@ def write_view_png(image: np.ndarray, out_path: Path) -> Path:
 
 class LandmarkViewer:
     def __init__(self, filename, landmarks: np.ndarray | None = None, pname: str | None = None, save: bool = True,
-                 size: int = 1024, device: int = 0) -> None:
+                 size: int = 1024, device: int = 0, encoder: str = "host") -> None:
         if not save:
             raise NotImplementedError("LandmarkViewer draws offscreen only (save=True): the interactive window of the "
                                       "reference's VTKViewer (--visualize-iter) is out of scope")
@@ -45,8 +75,14 @@ class LandmarkViewer:
         self.size = int(size)
         renderer = HipRenderer3D(n_views=1, device=device, verbose=False)
         mesh = load_mesh(self.filename)
-        self.image = renderer.render_landmark_view(mesh, landmarks, size=self.size)[0]
-        self.out_path = write_view_png(self.image, view_path(self.filename, pname))
+        if check_png_encoder(encoder) == "device":  # the picture stays on the device; ``image`` is read back on demand only
+            self.image_device = renderer.render_landmark_view_device(mesh, landmarks, size=self.size)[0]
+            self.out_path = write_view_png(self.image_device, view_path(self.filename, pname), encoder="device", renderer=renderer)
+            renderer.check()
+            self.image = None
+        else:
+            self.image = renderer.render_landmark_view(mesh, landmarks, size=self.size)[0]
+            self.out_path = write_view_png(self.image, view_path(self.filename, pname))
 
 
 def colour_byte(c: float) -> int:
@@ -58,7 +94,8 @@ def colour_byte(c: float) -> int:
 class RayVisualizerConfig:
     """What the offscreen ray view honours of the reference's ``RayVisualizerConfig`` (ray_visualizer.py) - ``ray_color``,
     ``landmark_color``, ``landmark_radius`` - and three fields of its own: the pictures' side in pixels, the rays' radius in
-    model units (the reference draws lines 8 pixels wide, whatever the zoom) and the poses (degrees rx, ry, rz), one picture each.
+    model units (the reference draws lines 8 pixels wide, whatever the zoom) and the poses (degrees rx, ry, rz), one picture each;
+    ``encoder``: "host" (Pillow) or "device" (the PNG files are made on the device, all pictures in one call).
     Rays are opaque here; the reference's 0.9 opacity and its bounding-box outline are left out."""
     ray_color: tuple = (0.1, 0.9, 0.1)
     landmark_color: tuple = (0.1, 0.1, 0.9)
@@ -66,6 +103,7 @@ class RayVisualizerConfig:
     size: int = 1024
     ray_radius: float = 0.5
     poses: tuple = ((0, 0, 0), (0, 60, 0), (0, -60, 0))
+    encoder: str = "host"
 
 
 class RayVisualizer:
@@ -102,10 +140,17 @@ class RayVisualizer:
         renderer = HipRenderer3D(n_views=1, device=self.device, verbose=False)
         nl = 0 if landmarks is None else len(np.asarray(landmarks).reshape(-1, 3))
         nr = fs.reshape(-1, 3).shape[0]
-        self.images = renderer.render_ray_view(
+        device = check_png_encoder(cfg.encoder) == "device"
+        draw = renderer.render_ray_view_device if device else renderer.render_ray_view
+        self.images = draw(
             mesh, landmarks, fs, fe, poses=cfg.poses, size=cfg.size, radius=cfg.landmark_radius, ray_radius=cfg.ray_radius,
             colors=np.tile(np.array([colour_byte(c) for c in cfg.landmark_color], np.uint8), (nl, 1)) if nl else None,
             ray_colors=np.tile(np.array([colour_byte(c) for c in cfg.ray_color], np.uint8), (nr, 1)) if nr else None)
         folder = Path(screenshot_dir) if screenshot_dir else Path("visualization") / "ray_screenshots"
         stem = Path(obj_path or getattr(mesh, "path", None) or "mesh.obj").stem
+        if device:  # (``images`` stays the device tensor [n,S,S,4]; one encode call for all poses)
+            paths = write_view_png(self.images, [folder / f"{stem}_rays_{i}.png" for i in range(len(self.images))], encoder="device",
+                                   renderer=renderer)
+            renderer.check()
+            return paths
         return [write_view_png(image, folder / f"{stem}_rays_{i}.png") for i, image in enumerate(self.images)]

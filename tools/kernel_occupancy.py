@@ -5,7 +5,8 @@
     tools/kernel_occupancy.py --write    rewrite tests/golden/kernel_occupancy.json (and kernel_occupancy_msaa.json,
                                          kernel_occupancy_vcolor.json, kernel_occupancy_wino.json,
                                          kernel_occupancy_wino4.json, kernel_occupancy_report.json,
-                                         kernel_occupancy_view.json, kernel_occupancy_rays.json) from the build
+                                         kernel_occupancy_view.json, kernel_occupancy_rays.json,
+                                         kernel_occupancy_png.json) from the build
 
 A convolution tile's rate depends on how many workgroups a CU holds, i.e. on which side of 168 / 128 / 102 ... registers the
 compiler lands - and every epilogue kind compiled into a tile moves that number (round 4: two new kinds took the 80-row tile
@@ -20,7 +21,8 @@ tiles (build/wino/, tests/golden/kernel_occupancy_wino.json, tests/test_winograd
 landmark report (build/report/, tests/golden/kernel_occupancy_report.json, tests/test_report_occupancy.py) and the six kernels
 of the landmark view (build/view/, tests/golden/kernel_occupancy_view.json, tests/test_view_occupancy.py), whose table also
 records the bytes of scratch memory per work-item (0); likewise the two kernels of the ray view (build/rays/,
-tests/golden/kernel_occupancy_rays.json, tests/test_rays_occupancy.py)."""
+tests/golden/kernel_occupancy_rays.json, tests/test_rays_occupancy.py) and the four kernels of the PNG encoder (build/png/,
+tests/golden/kernel_occupancy_png.json, tests/test_png_occupancy.py)."""
 import json
 import re
 import subprocess
@@ -38,6 +40,7 @@ WINO4_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_wino4.json"
 REPORT_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_report.json"
 VIEW_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_view.json"
 RAYS_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_rays.json"
+PNG_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_png.json"
 BUILD = REPO / "mvlm_amd" / "csrc" / "build"
 
 
@@ -84,10 +87,10 @@ def build_table(objdir: Path = BUILD) -> dict:
 if __name__ == "__main__":
     for table_path, objdir in ((TABLE, BUILD), (MSAA_TABLE, BUILD / "msaa"), (VCOLOR_TABLE, BUILD / "vcolor"),
                                 (WINO_TABLE, BUILD / "wino"), (WINO4_TABLE, BUILD / "wino4"), (REPORT_TABLE, BUILD / "report"),
-                                (VIEW_TABLE, BUILD / "view"), (RAYS_TABLE, BUILD / "rays")):
+                                (VIEW_TABLE, BUILD / "view"), (RAYS_TABLE, BUILD / "rays"), (PNG_TABLE, BUILD / "png")):
         t = build_table(objdir)
         if "--write" in sys.argv:
-            fields = ("waves_per_simd", "spilled", "scratch") if table_path in (VIEW_TABLE, RAYS_TABLE) else ("waves_per_simd", "spilled")
+            fields = ("waves_per_simd", "spilled", "scratch") if table_path in (VIEW_TABLE, RAYS_TABLE, PNG_TABLE) else ("waves_per_simd", "spilled")
             table_path.write_text(json.dumps({k: {f: v[f] for f in fields} for k, v in t.items()}, indent=1) + "\n")
             print(f"{len(t)} kernels -> {table_path}")
         else:
