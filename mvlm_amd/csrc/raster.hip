@@ -30,6 +30,7 @@
 
 namespace {
 
+// (transform_kernel and scan_kernel have a twin each in raster_view.hip; why the two pairs are not merged: raster_bins.h)
 __global__ void transform_kernel(const float* __restrict__ verts, int n_verts, const double* __restrict__ rot,
                                  int n_views, int sub_bits, vert12* __restrict__ tv) {
     int view, chunk;
@@ -73,6 +74,8 @@ __device__ inline bool classify_one(int view, int t, const rm_vert& va, const rm
         if (small) {
             tri24 tr;
             if (!setup24(va, vb, vc, &tr)) return false;
+            // (resolve_small_box<tri24, cover24<tri24>, int> written out: through the helper the row prologue of this loop, which
+            // every triangle of a dense scan takes, came out in another instruction order)
             for (int j = iy0; j <= iy1; ++j)
                 for (int ii = ix0; ii <= ix1; ++ii) {
                     float b0, b1, b2;
@@ -84,14 +87,7 @@ __device__ inline bool classify_one(int view, int t, const rm_vert& va, const rm
         } else {  // a long sliver that crosses the window's edge: few pixel centres inside, vertices far apart
             const rm_tri tr = rm_setup(va, vb, vc);
             if (!tr.valid) return false;
-            for (int j = tr.iy0; j <= tr.iy1; ++j)
-                for (int ii = tr.ix0; ii <= tr.ix1; ++ii) {
-                    float b0, b1, b2;
-                    if (!rm_cover(&tr, ii, j, &b0, &b1, &b2)) continue;
-                    const float z = rm_interp(b0, b1, b2, tr.z0, tr.z1, tr.z2);
-                    if (!(z >= 0.0f && z <= 1.0f)) continue;
-                    atomicMin(&kv[j * RM_SIZE + ii], (unsigned long long)rm_key(z, uint32_t(t)));
-                }
+            resolve_small_box<rm_tri, rm_cover, int>(kv, RM_SIZE, tr.ix0, tr.ix1, tr.iy0, tr.iy1, tr, t);
         }
         return false;
     }
@@ -101,18 +97,14 @@ __device__ inline bool classify_one(int view, int t, const rm_vert& va, const rm
     } else if (int64_t(vb.X - va.X) * (vc.Y - va.Y) == int64_t(vb.Y - va.Y) * (vc.X - va.X)) {
         return false;
     }
-    const int tx0 = ix0 / RM_TILE, tx1 = ix1 / RM_TILE, ty0 = iy0 / RM_TILE, ty1 = iy1 / RM_TILE;
-    for (int ty = ty0; ty <= ty1; ++ty)
-        for (int tx = tx0; tx <= tx1; ++tx) atomicAdd(&counts[view * TILES + ty * RM_TILES + tx], 1);
+    count_tile_range<int>(counts, view, RM_TILES, ix0, ix1, iy0, iy1);
     return true;
 }
 
 // A thread takes TPT triangles and has all their loads (indices, then three vertices each) in flight together.  Measured
 // (tools/raster_bench.py, 96 views of the bench mesh): TPT 1 / 2 / 4 = 164 / 161 / 163 us per render - the pass does not
 // wait for latency (without its key atomics it still takes 43 of its 59 us: 9.5 M threads x four 12-byte gathers through
-// the L1s), so TPT stays 1.  The ids of a wave's big triangles are appended to the view's list with ONE atomicAdd per
-// wave: a coarse mesh - every triangle big - made 3 000 returning atomics on one counter per view, 54 us for 3 042
-// triangles (now 6).
+// the L1s), so TPT stays 1.  (The big triangles' ids go to the view's list with one atomic per wave: raster_bins.h, append_big.)
 constexpr int CLASSIFY_TPT = 1;
 template <int TPT>
 __global__ __launch_bounds__(256) void classify_kernel(const vert12* __restrict__ tv, const int32_t* __restrict__ tris, int n_verts,
@@ -138,18 +130,10 @@ __global__ __launch_bounds__(256) void classify_kernel(const vert12* __restrict_
         vb[k] = load_vert(tvv, ib[k]);
         vc[k] = load_vert(tvv, ic[k]);
     }
-    const int lane = int(threadIdx.x) & 63;
 #pragma unroll
     for (int k = 0; k < TPT; ++k) {
         const bool big = t[k] < n_tris && classify_one(view, t[k], va[k], vb[k], vc[k], keys, counts);
-        const unsigned long long m = __ballot(big);
-        if (m) {  // (wave-uniform)
-            const int leader = __ffsll(static_cast<long long>(m)) - 1;
-            int base = 0;
-            if (lane == leader) base = atomicAdd(&n_big[view], __popcll(m));
-            base = __shfl(base, leader);
-            if (big) big_list[size_t(view) * n_tris + base + __popcll(m & ((1ull << lane) - 1ull))] = t[k];
-        }
+        append_big(big, t[k], view, n_tris, n_big, big_list);
     }
 }
 
@@ -167,16 +151,7 @@ __global__ void bin_fill_kernel(const vert12* __restrict__ tv, const int32_t* __
     for (int k = wg * 256 + int(threadIdx.x); k < n; k += FILL_WGS * 256) {
         const int t = big_list[size_t(view) * n_tris + k];
         const rm_tri tr = load_tri(tv + size_t(view) * n_verts, tris, t);
-        const int tx0 = tr.ix0 / RM_TILE, tx1 = tr.ix1 / RM_TILE, ty0 = tr.iy0 / RM_TILE, ty1 = tr.iy1 / RM_TILE;
-        for (int ty = ty0; ty <= ty1; ++ty)
-            for (int tx = tx0; tx <= tx1; ++tx) {
-                const int tile = view * TILES + ty * RM_TILES + tx;
-                const int pos = offsets[tile] + atomicAdd(&cursors[tile], 1);
-                if (pos < cap)
-                    bins[size_t(view) * cap + pos] = t;
-                else
-                    *overflow = 1;
-            }
+        scatter_tile_range<int>(view, RM_TILES, offsets, cursors, bins, cap, overflow, tr.ix0, tr.ix1, tr.iy0, tr.iy1, t);
     }
 }
 
@@ -216,16 +191,10 @@ extern "C" int mvlm_render(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* r
     MVLM_REQUIRE(ctx, mesh->n_verts > 0 && mesh->n_tris > 0, "render: empty mesh");
     if (mvlm_mesh_wait_ready(ctx, mesh, ctx->stream)) return 1;  // the upload runs on a stream of its own
     const int V = mesh->n_verts, T = mesh->n_tris;
-    const int cap = 4 * T + 16384;  // tile-list entries per view; larger lists raise an error
     auto* tv = static_cast<vert12*>(ctx->get_scratch("raster.tv", size_t(n_views) * V * sizeof(vert12)));
     auto* rot = static_cast<double*>(ctx->get_scratch("raster.rot", size_t(n_views) * 9 * sizeof(double)));
-    // counts | cursors | n_big | overflow in one block so a single memset clears them
-    const size_t n_ctr = size_t(n_views) * TILES;
-    const size_t ctr_ints = 2 * n_ctr + n_views + 4;
-    auto* ctr = static_cast<int*>(ctx->get_scratch("raster.ctr", ctr_ints * sizeof(int)));
-    auto* offsets = static_cast<int*>(ctx->get_scratch("raster.off", n_ctr * sizeof(int)));
-    auto* bins = static_cast<int*>(ctx->get_scratch("raster.bins", size_t(n_views) * cap * sizeof(int)));
-    auto* big_list = static_cast<int*>(ctx->get_scratch("raster.big", size_t(n_views) * T * sizeof(int)));
+    raster_bins b;  // (tile-list entries per view: 4 T + 16 384)
+    const bool have_bins = raster_bins_scratch(ctx, "raster", n_views, TILES, T, 4 * T + 16384, &b);
     // one key per pixel, or S per pixel in a plane of its own when multisampling (allocated only then)
     const int S = ctx->render_multisamples;
     // per-vertex colours shade the RGB planes of the unlit render of a mesh without a usable texture
@@ -233,14 +202,9 @@ extern "C" int mvlm_render(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* r
     const char* const key_name = S ? "raster.keys4" : "raster.keys";
     const size_t key_bytes = size_t(n_views) * RM_SIZE * RM_SIZE * size_t(S ? S : 1) * sizeof(unsigned long long);
     auto* keys = static_cast<unsigned long long*>(ctx->get_scratch(key_name, key_bytes));
-    MVLM_REQUIRE(ctx, tv && rot && ctr && offsets && bins && big_list && keys, "render: scratch allocation failed");
-    int* counts = ctr;
-    int* cursors = ctr + n_ctr;
-    int* n_big = ctr + 2 * n_ctr;
-    int* overflow = n_big + n_views;
-    MVLM_CHECK_HIP(ctx, hipMemcpyAsync(rot, rot_host, size_t(n_views) * 9 * sizeof(double), hipMemcpyHostToDevice,
-                                       ctx->stream));
-    MVLM_CHECK_HIP(ctx, hipMemsetAsync(ctr, 0, ctr_ints * sizeof(int), ctx->stream));
+    MVLM_REQUIRE(ctx, tv && rot && have_bins && keys, "render: scratch allocation failed");
+    MVLM_CHECK_HIP(ctx, hipMemcpyAsync(rot, rot_host, size_t(n_views) * 9 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    MVLM_CHECK_HIP(ctx, hipMemsetAsync(b.counts, 0, b.ctr_ints * sizeof(int), ctx->stream));
     // The key plane is EMPTY between renders (tile_kernel clears what it reads); it is filled here only when the buffer is new
     // or a render did not run to its end.  `clean` = the buffer and capacity it was last known clean at: a buffer that
     // get_scratch replaced (after a failed allocation, say) is filled even when its size is the old one.
@@ -249,10 +213,8 @@ extern "C" int mvlm_render(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* r
     if (clean.ptr != keys || clean.cap != keys_cap)
         MVLM_CHECK_HIP(ctx, hipMemsetAsync(keys, 0xFF, keys_cap, ctx->stream));  // RM_KEY_EMPTY everywhere
     clean = mvlm_ctx::KeyPlaneState{};  // (until this call has enqueued its tile kernel)
-    if (!ctx->render_overflow_host) {
-        MVLM_CHECK_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->render_overflow_host), sizeof(int)));
-        *ctx->render_overflow_host = 0;  // (a render that fails before its tile kernel leaves no garbage for render_check)
-    }
+    int* const overflow_host = render_overflow_word(ctx);
+    MVLM_REQUIRE(ctx, overflow_host, "render: pinned allocation failed");
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (ctx->render_profiling) {  // HIP events on the launch stream around the five kernels of this call
         if (ctx->render_event_cursor + 2 > ctx->render_events.size()) ctx->render_events.resize(ctx->render_event_cursor + 2, nullptr);
@@ -269,23 +231,21 @@ extern "C" int mvlm_render(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* r
                        mesh->verts, V, rot, n_views, ctx->render_subpixel_bits, tv);
     if (S == 0) {
         hipLaunchKernelGGL(classify_kernel<CLASSIFY_TPT>, dim3(view_chunk_grid((T + 256 * CLASSIFY_TPT - 1) / (256 * CLASSIFY_TPT), n_views)), dim3(256), 0,
-                           ctx->stream, tv, mesh->tris, V, T, n_views, keys, counts, n_big, big_list);
-        hipLaunchKernelGGL(scan_kernel, dim3(n_views), dim3(TILES), 0, ctx->stream, counts, offsets, cap, overflow);
+                           ctx->stream, tv, mesh->tris, V, T, n_views, keys, b.counts, b.n_big, b.big_list);
+        hipLaunchKernelGGL(scan_kernel, dim3(n_views), dim3(TILES), 0, ctx->stream, b.counts, b.offsets, b.cap, b.overflow);
         hipLaunchKernelGGL(bin_fill_kernel, dim3(view_chunk_grid(FILL_WGS, n_views)), dim3(256), 0, ctx->stream, tv,
-                           mesh->tris, V, T, n_views, n_big, big_list, offsets, cursors, bins, cap, overflow);
+                           mesh->tris, V, T, n_views, b.n_big, b.big_list, b.offsets, b.cursors, b.bins, b.cap, b.overflow);
         if (vcol)
-            raster_vc_tile(ctx->stream, 0, tv, mesh->tris, vcol, V, n_views, counts, offsets, bins, cap, keys, ctx->render_shading,
-                           overflow, ctx->render_overflow_host, out_dev);
+            raster_vc_tile(ctx->stream, 0, tv, mesh->tris, vcol, V, n_views, b, keys, ctx->render_shading, overflow_host, out_dev);
         else
             hipLaunchKernelGGL(tile_kernel, dim3(view_chunk_grid(TILES, n_views)), dim3(256), 0, ctx->stream, tv, mesh->tris,
-                               mesh->uvs, mesh->tex, mesh->tex_w, mesh->tex_h, V, counts, offsets, bins, cap, keys,
-                               ctx->render_shading, n_views, overflow, ctx->render_overflow_host, out_dev);
+                               mesh->uvs, mesh->tex, mesh->tex_w, mesh->tex_h, V, b.counts, b.offsets, b.bins, b.cap, keys,
+                               ctx->render_shading, n_views, b.overflow, overflow_host, out_dev);
     } else {  // S == 4 (mvlm_set_render_multisamples admits nothing else): the kernels of raster_ms.hip
-        raster_ms_classify(ctx->stream, S, tv, mesh->tris, V, T, n_views, keys, counts, n_big, big_list);
-        hipLaunchKernelGGL(scan_kernel, dim3(n_views), dim3(TILES), 0, ctx->stream, counts, offsets, cap, overflow);
-        raster_ms_bin_and_tile(ctx->stream, S, tv, mesh->tris, mesh->uvs, mesh->tex, mesh->tex_w, mesh->tex_h, V, T, n_views,
-                               n_big, big_list, counts, offsets, cursors, bins, cap, keys, ctx->render_shading, overflow,
-                               ctx->render_overflow_host, out_dev, vcol);
+        raster_ms_classify(ctx->stream, S, tv, mesh->tris, V, T, n_views, keys, b);
+        hipLaunchKernelGGL(scan_kernel, dim3(n_views), dim3(TILES), 0, ctx->stream, b.counts, b.offsets, b.cap, b.overflow);
+        raster_ms_bin_and_tile(ctx->stream, S, tv, mesh->tris, mesh->uvs, mesh->tex, mesh->tex_w, mesh->tex_h, V, T, n_views, b,
+                               keys, ctx->render_shading, overflow_host, out_dev, vcol);
     }
     MVLM_CHECK_HIP(ctx, hipGetLastError());
     clean = mvlm_ctx::KeyPlaneState{keys, keys_cap};
@@ -293,8 +253,7 @@ extern "C" int mvlm_render(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* r
         MVLM_CHECK_HIP(ctx, hipEventRecord(e1, ctx->stream));
         ctx->render_prof.push_back({n_views, V, T, e0, e1});
     }
-    // (the overflow flag has travelled to pinned host memory inside the tile kernel; mvlm_render_check examines it after the
-    // caller's own synchronisation point)
+    // (the tile kernel carries the overflow flag to pinned host memory; mvlm_render_check reads it after the caller's synchronisation)
     return 0;
 }
 

@@ -1,6 +1,6 @@
 // Pieces of the multi-view rasteriser shared by its one-sample kernels (raster.hip), its multisampled ones (raster_ms.hip)
 // and the per-vertex-colour tile kernels (raster_vc.hip) - the latter two objects of their own: tools/kernel_occupancy.py
-// keeps a table of each one's kernels beside the main one.  The tile stage's bodies: raster_tile.h.
+// keeps a table of each one's kernels beside the main one.  The tile stage's bodies: raster_tile.h; the binning front end: raster_bins.h.
 #ifndef MVLM_RASTER_COMMON_H
 #define MVLM_RASTER_COMMON_H
 
@@ -47,25 +47,43 @@ __device__ inline bool small_extent(const rm_vert& a, const rm_vert& b, const rm
     return maxx - minx < RM_SMALL_EXTENT && maxy - miny < RM_SMALL_EXTENT;
 }
 
+// A per-vertex colour attribute at the pixel: the three vertices' colours (one aligned 4-byte load each, u8[V,4] on the
+// device) through rm_interp per channel, then rm_color_u8; r | g << 8 | b << 16.  b and c are the indices AFTER the winding
+// swap, b1 and b2 the weights of those vertices.
+__device__ inline uint32_t vertex_colour(const uchar4* __restrict__ colors, int a, int b, int c, float b1, float b2) {
+    const uchar4 c0 = colors[a], c1 = colors[b], c2 = colors[c];
+    const int r = rm_color_u8(rm_interp(0.f, b1, b2, float(c0.x) / 255.0f, float(c1.x) / 255.0f, float(c2.x) / 255.0f));
+    const int g = rm_color_u8(rm_interp(0.f, b1, b2, float(c0.y) / 255.0f, float(c1.y) / 255.0f, float(c2.y) / 255.0f));
+    const int bl = rm_color_u8(rm_interp(0.f, b1, b2, float(c0.z) / 255.0f, float(c1.z) / 255.0f, float(c2.z) / 255.0f));
+    return uint32_t(r) | (uint32_t(g) << 8) | (uint32_t(bl) << 16);
+}
+
+// The nearest texel of (u, v), r | g << 8 | b << 16, with one (unaligned) 4-byte load: the buffer carries 4 spare bytes behind
+// the last texel (api.hip).
+__device__ inline uint32_t fetch_texel(const uint8_t* __restrict__ tex, float u, float v, int tex_w, int tex_h) {
+    uint32_t rgb;
+    __builtin_memcpy(&rgb, tex + size_t(rm_texel(u, v, tex_w, tex_h)) * 3, 4);
+    return rgb & 0xFFFFFFu;
+}
+
 constexpr int SMALL_PIXELS = 16;  // triangles covering at most this many pixel centres skip the bins
 constexpr int FILL_WGS = 32;      // bin-fill workgroups per view (raster.hip, bin_fill_kernel)
 
 }  // namespace
 
+#include "raster_bins.h"  // the binning front end, shared by every launch set
+
 // The multisampled kernels of one mvlm_render at `samples` samples per pixel (raster_ms.hip); raster.hip launches the
 // transform before and the scan between them.  `tv` is the transformed-vertex scratch (vert12[n_views][n_verts]).
 // `colors` (u8[V,4] on the device, or null): the tile stage is raster_vc_tile's, shading with the per-vertex colours.
 void raster_ms_classify(hipStream_t stream, int samples, const void* tv, const int32_t* tris, int n_verts, int n_tris,
-                        int n_views, unsigned long long* keys, int* counts, int* n_big, int* big_list);
+                        int n_views, unsigned long long* keys, const raster_bins& b);
 void raster_ms_bin_and_tile(hipStream_t stream, int samples, const void* tv, const int32_t* tris, const float* uvs,
-                            const uint8_t* tex, int tex_w, int tex_h, int n_verts, int n_tris, int n_views, const int* n_big,
-                            const int* big_list, const int* counts, const int* offsets, int* cursors, int* bins, int cap,
-                            unsigned long long* keys, int shading, int* overflow, int* overflow_host, float* out,
-                            const uint8_t* colors);
+                            const uint8_t* tex, int tex_w, int tex_h, int n_verts, int n_tris, int n_views, const raster_bins& b,
+                            unsigned long long* keys, int shading, int* overflow_host, float* out, const uint8_t* colors);
 // The tile stage with per-vertex colours (raster_vc.hip), at `samples` = 0 (one sample, in place of raster.hip's tile_kernel)
 // or 4 (in place of tile_ms_kernel, behind raster_ms.hip's bin fill).
 void raster_vc_tile(hipStream_t stream, int samples, const void* tv, const int32_t* tris, const uint8_t* colors, int n_verts,
-                    int n_views, const int* counts, const int* offsets, const int* bins, int cap, unsigned long long* keys,
-                    int shading, const int* overflow, int* overflow_host, float* out);
+                    int n_views, const raster_bins& b, unsigned long long* keys, int shading, int* overflow_host, float* out);
 
 #endif

@@ -17,7 +17,7 @@ __device__ inline bool classify_ms_one(int view, int t, const rm_vert& va, const
     if ((ix1 - ix0 + 1) * (iy1 - iy0 + 1) <= SMALL_PIXELS) {
         const rm_tri tr = ms_setup<S>(va, vb, vc);
         if (!tr.valid) return false;
-        unsigned long long* kv = keys + size_t(view) * RM_SIZE * RM_SIZE * S;
+        unsigned long long* kv = keys + size_t(view) * RM_SIZE * RM_SIZE * S;  // (S keys per pixel: not resolve_small_box's form)
         for (int j = iy0; j <= iy1; ++j)
             for (int ii = ix0; ii <= ix1; ++ii) {
                 float z[S];
@@ -33,8 +33,7 @@ __device__ inline bool classify_ms_one(int view, int t, const rm_vert& va, const
     } else if (int64_t(vb.X - va.X) * (vc.Y - va.Y) == int64_t(vb.Y - va.Y) * (vc.X - va.X)) {
         return false;
     }
-    for (int ty = iy0 / RM_TILE; ty <= iy1 / RM_TILE; ++ty)
-        for (int tx = ix0 / RM_TILE; tx <= ix1 / RM_TILE; ++tx) atomicAdd(&counts[view * TILES + ty * RM_TILES + tx], 1);
+    count_tile_range<int>(counts, view, RM_TILES, ix0, ix1, iy0, iy1);
     return true;
 }
 
@@ -49,16 +48,8 @@ __global__ __launch_bounds__(256) void classify_ms_kernel(const vert12* __restri
     const int t = chunk * 256 + int(threadIdx.x);
     const int tt = t < n_tris ? t : 0;
     const rm_vert va = load_vert(tvv, tris[3 * tt]), vb = load_vert(tvv, tris[3 * tt + 1]), vc = load_vert(tvv, tris[3 * tt + 2]);
-    const int lane = int(threadIdx.x) & 63;
     const bool big = t < n_tris && classify_ms_one<S>(view, t, va, vb, vc, keys, counts);
-    const unsigned long long m = __ballot(big);
-    if (m) {  // (wave-uniform)
-        const int leader = __ffsll(static_cast<long long>(m)) - 1;
-        int base = 0;
-        if (lane == leader) base = atomicAdd(&n_big[view], __popcll(m));
-        base = __shfl(base, leader);
-        if (big) big_list[size_t(view) * n_tris + base + __popcll(m & ((1ull << lane) - 1ull))] = t;
-    }
+    append_big(big, t, view, n_tris, n_big, big_list);
 }
 
 // bin_fill_kernel with the tiles of the sample box
@@ -77,15 +68,7 @@ __global__ void bin_fill_ms_kernel(const vert12* __restrict__ tv, const int32_t*
         int32_t ix0, ix1, iy0, iy1;
         ms_box<S>(min(a.X, min(b.X, c.X)), max(a.X, max(b.X, c.X)), min(a.Y, min(b.Y, c.Y)), max(a.Y, max(b.Y, c.Y)), &ix0, &ix1,
                   &iy0, &iy1);
-        for (int ty = iy0 / RM_TILE; ty <= iy1 / RM_TILE; ++ty)
-            for (int tx = ix0 / RM_TILE; tx <= ix1 / RM_TILE; ++tx) {
-                const int tile = view * TILES + ty * RM_TILES + tx;
-                const int pos = offsets[tile] + atomicAdd(&cursors[tile], 1);
-                if (pos < cap)
-                    bins[size_t(view) * cap + pos] = t;
-                else
-                    *overflow = 1;
-            }
+        scatter_tile_range<int>(view, RM_TILES, offsets, cursors, bins, cap, overflow, ix0, ix1, iy0, iy1, t);
     }
 }
 
@@ -105,25 +88,22 @@ __global__ __launch_bounds__(256) void tile_ms_kernel(const vert12* __restrict__
 }  // namespace
 
 void raster_ms_classify(hipStream_t stream, int samples, const void* tv, const int32_t* tris, int n_verts, int n_tris,
-                        int n_views, unsigned long long* keys, int* counts, int* n_big, int* big_list) {
+                        int n_views, unsigned long long* keys, const raster_bins& b) {
     (void)samples;  // 4: the one sample count mvlm_set_render_multisamples admits
     hipLaunchKernelGGL(classify_ms_kernel<4>, dim3(view_chunk_grid((n_tris + 255) / 256, n_views)), dim3(256), 0, stream,
-                       static_cast<const vert12*>(tv), tris, n_verts, n_tris, n_views, keys, counts, n_big, big_list);
+                       static_cast<const vert12*>(tv), tris, n_verts, n_tris, n_views, keys, b.counts, b.n_big, b.big_list);
 }
 
 void raster_ms_bin_and_tile(hipStream_t stream, int samples, const void* tv, const int32_t* tris, const float* uvs,
-                            const uint8_t* tex, int tex_w, int tex_h, int n_verts, int n_tris, int n_views, const int* n_big,
-                            const int* big_list, const int* counts, const int* offsets, int* cursors, int* bins, int cap,
-                            unsigned long long* keys, int shading, int* overflow, int* overflow_host, float* out,
-                            const uint8_t* colors) {
+                            const uint8_t* tex, int tex_w, int tex_h, int n_verts, int n_tris, int n_views, const raster_bins& b,
+                            unsigned long long* keys, int shading, int* overflow_host, float* out, const uint8_t* colors) {
     (void)samples;
     const vert12* const v = static_cast<const vert12*>(tv);
     hipLaunchKernelGGL(bin_fill_ms_kernel<4>, dim3(view_chunk_grid(FILL_WGS, n_views)), dim3(256), 0, stream, v, tris, n_verts,
-                       n_tris, n_views, n_big, big_list, offsets, cursors, bins, cap, overflow);
+                       n_tris, n_views, b.n_big, b.big_list, b.offsets, b.cursors, b.bins, b.cap, b.overflow);
     if (colors)  // per-vertex colours: the tile stage of raster_vc.hip
-        raster_vc_tile(stream, 4, tv, tris, colors, n_verts, n_views, counts, offsets, bins, cap, keys, shading, overflow, overflow_host,
-                       out);
+        raster_vc_tile(stream, 4, tv, tris, colors, n_verts, n_views, b, keys, shading, overflow_host, out);
     else
         hipLaunchKernelGGL(tile_ms_kernel<4>, dim3(view_chunk_grid(TILES, n_views)), dim3(256), 0, stream, v, tris, uvs, tex, tex_w,
-                           tex_h, n_verts, counts, offsets, bins, cap, keys, shading, n_views, overflow, overflow_host, out);
+                           tex_h, n_verts, b.counts, b.offsets, b.bins, b.cap, keys, shading, n_views, b.overflow, overflow_host, out);
 }

@@ -53,24 +53,15 @@ __global__ __launch_bounds__(256) void rays_tile_kernel(
     __shared__ int s_cnt[VIEW_COUNT_SPAN];
     __shared__ rv_ray s_ray[RAYS_CAP];
     __shared__ int s_ray_id[RAYS_CAP];
-    const int tiles_x = size / RM_TILE, tiles = tiles_x * tiles_x;
+    const int tiles_x = size / RM_TILE;
     int view, tile;
-    if (!view_chunk(tiles, n_views, &view, &tile)) return;
-    const size_t vt = size_t(view) * tiles + tile;
+    if (!view_chunk(tiles_x * tiles_x, n_views, &view, &tile)) return;
     const int tid = threadIdx.x;
-    const int tx0 = (tile % tiles_x) * RM_TILE, ty0 = (tile / tiles_x) * RM_TILE;
-    const int i = tx0 + (tid & (RM_TILE - 1));
-    const int j = ty0 + (tid >> 4);
-    const vert12* const tvv = tv + size_t(view) * n_verts;
-    const int n = min(counts[vt], cap - offsets[vt]);
-    const int* const list = bins + size_t(view) * cap + offsets[vt];
+    const auto [tx0, ty0, i, j, tvv, n, list] = tile_prologue<size_t>(view, tile, tiles_x, tv, n_verts, counts, offsets, bins, cap);
     const view_frame frame = frames[view];
 
     uint64_t best = keys[(size_t(view) * size + j) * size + i];  // what the small triangles left
-    if (blockIdx.x == 0 && tid == 0) {  // the overflow flag of the kernels before this one, to the host's pinned word
-        __atomic_store_n(overflow_host, *overflow, __ATOMIC_RELAXED);
-        __threadfence_system();
-    }
+    publish_overflow(overflow, overflow_host);
     best = view_tile_resolve(best, tvv, tris, list, n, size, i, j, tid, s_tri, s_id);
     float zbest;
     uint32_t rgb = view_tile_shade(best, tvv, tris, uvs, tex, tex_w, tex_h, colors, shading, frame, size, i, j, &zbest);
@@ -99,7 +90,7 @@ __global__ __launch_bounds__(256) void rays_tile_kernel(
         const unsigned long long m = __ballot(touch);
         if (lane == 0) s_wave[wave] = __popcll(m);
         __syncthreads();
-        int off = 0, total = 0;
+        int off = 0, total = 0;  // (as in view_tile_spheres; why this is not a shared helper: raster_bins.h)
         for (int w = 0; w < 4; ++w) {
             off += w < wave ? s_wave[w] : 0;
             total += s_wave[w];
@@ -179,9 +170,9 @@ int mvlm_launch_ray_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot
     if (s.ev) MVLM_CHECK_HIP(ctx, hipEventRecord(s.ev[7], st));
     const int tiles_x = size / RM_TILE, tiles = tiles_x * tiles_x;
     hipLaunchKernelGGL(rays_tile_kernel, dim3(view_chunk_grid(tiles, n_views)), dim3(256), 0, st, s.tv, mesh->tris, mesh->uvs, mesh->tex,
-                       mesh->tex_w, mesh->tex_h, reinterpret_cast<const uchar4*>(s.vcol), mesh->n_verts, s.counts, s.offsets, s.bins,
-                       s.cap, s.keys, s.frames, ctx->render_shading, n_views, size, s.spheres, n_lm, lm_pixels_dev, rays, n_rays,
-                       n_rays > 0 ? ray_pixels_dev : nullptr, s.overflow, ctx->render_overflow_host,
+                       mesh->tex_w, mesh->tex_h, reinterpret_cast<const uchar4*>(s.vcol), mesh->n_verts, s.bins.counts, s.bins.offsets, s.bins.bins,
+                       s.bins.cap, s.keys, s.frames, ctx->render_shading, n_views, size, s.spheres, n_lm, lm_pixels_dev, rays, n_rays,
+                       n_rays > 0 ? ray_pixels_dev : nullptr, s.bins.overflow, ctx->render_overflow_host,
                        reinterpret_cast<uint32_t*>(out_dev));
     if (s.ev) MVLM_CHECK_HIP(ctx, hipEventRecord(s.ev[8], st));
     MVLM_CHECK_HIP(ctx, hipGetLastError());

@@ -2,7 +2,7 @@
 // without per-vertex colours.  raster.hip (tile_kernel) and raster_ms.hip (tile_ms_kernel<4>) wrap the VCOL = false forms in
 // kernels whose signatures the occupancy tables know; raster_vc.hip wraps the VCOL = true forms, which shade the RGB planes
 // with the mesh's per-vertex colours instead of a texel ("Per-vertex colours").  Also here: what the bodies
-// share with the classify kernels of their files - the 24-bit edge functions and the sample pattern.
+// share with the classify kernels of their files - the 24-bit edge functions and the sample pattern.  (Their prologue: raster_bins.h.)
 #ifndef MVLM_RASTER_TILE_H
 #define MVLM_RASTER_TILE_H
 
@@ -75,17 +75,6 @@ __device__ inline int cover24(const T* t, int i, int j, float* b0, float* b1, fl
     return 1;
 }
 
-// A per-vertex colour attribute at the pixel: the three vertices' colours (one aligned 4-byte load each, u8[V,4] on the
-// device) through rm_interp per channel, then rm_color_u8; r | g << 8 | b << 16.  b and c are the indices AFTER the winding
-// swap, b1 and b2 the weights of those vertices.
-__device__ inline uint32_t vertex_colour(const uchar4* __restrict__ colors, int a, int b, int c, float b1, float b2) {
-    const uchar4 c0 = colors[a], c1 = colors[b], c2 = colors[c];
-    const int r = rm_color_u8(rm_interp(0.f, b1, b2, float(c0.x) / 255.0f, float(c1.x) / 255.0f, float(c2.x) / 255.0f));
-    const int g = rm_color_u8(rm_interp(0.f, b1, b2, float(c0.y) / 255.0f, float(c1.y) / 255.0f, float(c2.y) / 255.0f));
-    const int bl = rm_color_u8(rm_interp(0.f, b1, b2, float(c0.z) / 255.0f, float(c1.z) / 255.0f, float(c2.z) / 255.0f));
-    return uint32_t(r) | (uint32_t(g) << 8) | (uint32_t(bl) << 16);
-}
-
 // One workgroup per (view, 16x16-pixel tile), one thread per pixel.  More pixels per thread with the loads of a stage
 // (key, triangle, vertices and texture coordinates, texel) in flight together were built and measured (2 and 4 pixels:
 // 161 / 163 us per render against 164): the kernel does not wait for latency, it moves its bytes at the rate the memory
@@ -103,24 +92,15 @@ __device__ __forceinline__ void tile_body(const vert12* __restrict__ tv, const i
     __shared__ int s_id[256];
     int view, tile;
     if (!view_chunk(TILES, n_views, &view, &tile)) return;
-    const int vt = view * TILES + tile;
     const int tid = threadIdx.x;
-    const int i = (tile % RM_TILES) * RM_TILE + (tid & (RM_TILE - 1));
-    const int j = (tile / RM_TILES) * RM_TILE + (tid >> 4);
-    const vert12* const tvv = tv + size_t(view) * n_verts;
-    const int n = min(counts[vt], cap - offsets[vt]);
-    const int* const list = bins + size_t(view) * cap + offsets[vt];
+    const auto [x0, y0, i, j, tvv, n, list] = tile_prologue<int>(view, tile, RM_TILES, tv, n_verts, counts, offsets, bins, cap);
 
     unsigned long long* const key_slot = keys + (size_t(view) * RM_SIZE + j) * RM_SIZE + i;
     uint64_t best = *key_slot;  // what the small triangles left
     // The key plane is handed back EMPTY: this kernel reads every slot of the rendered views exactly once, so it also clears
     // what classify dirtied - instead of a 67 MB fill in front of every render (14 us + a launch gap at 128 views)
     if (best != RM_KEY_EMPTY) *key_slot = RM_KEY_EMPTY;
-    // and the first workgroup carries the overflow flag of the kernels before it to the host's pinned word (no copy node)
-    if (blockIdx.x == 0 && tid == 0) {
-        __atomic_store_n(overflow_host, *overflow, __ATOMIC_RELAXED);
-        __threadfence_system();
-    }
+    publish_overflow(overflow, overflow_host);
 
     // ---- phase B: every pixel walks the tile's big triangles, set up into LDS a chunk at a time ----
     for (int base = 0; base < n; base += 256) {
@@ -184,9 +164,7 @@ __device__ __forceinline__ void tile_body(const vert12* __restrict__ tv, const i
         } else if (shading != 1 && tex && uvs) {
             const float u = rm_interp(b0, b1, b2, uvs[2 * a], uvs[2 * b], uvs[2 * c]);
             const float v = rm_interp(b0, b1, b2, uvs[2 * a + 1], uvs[2 * b + 1], uvs[2 * c + 1]);
-            // one (unaligned) 4-byte load per texel: the buffer carries 4 spare bytes behind the last one (api.hip)
-            uint32_t rgb;
-            __builtin_memcpy(&rgb, tex + size_t(rm_texel(u, v, tex_w, tex_h)) * 3, 4);
+            const uint32_t rgb = fetch_texel(tex, u, v, tex_w, tex_h);
             r = float(rgb & 255u);
             g = float((rgb >> 8) & 255u);
             bl = float((rgb >> 16) & 255u);
@@ -350,9 +328,7 @@ __device__ inline uint32_t ms_shade(const vert12* __restrict__ tvv, const int32_
     } else {
         const float u = rm_interp(0.f, b1, b2, uvs[2 * a], uvs[2 * b], uvs[2 * c]);
         const float v = rm_interp(0.f, b1, b2, uvs[2 * a + 1], uvs[2 * b + 1], uvs[2 * c + 1]);
-        uint32_t rgb;  // (the buffer carries 4 spare bytes behind the last texel, api.hip)
-        __builtin_memcpy(&rgb, tex + size_t(rm_texel(u, v, tex_w, tex_h)) * 3, 4);
-        return rgb & 0xFFFFFFu;
+        return fetch_texel(tex, u, v, tex_w, tex_h);
     }
 }
 
@@ -382,23 +358,15 @@ __device__ __forceinline__ void tile_ms_body(const vert12* __restrict__ tv, cons
     __shared__ int s_id[256];
     int view, tile;
     if (!view_chunk(TILES, n_views, &view, &tile)) return;
-    const int vt = view * TILES + tile;
     const int tid = threadIdx.x;
-    const int i = (tile % RM_TILES) * RM_TILE + (tid & (RM_TILE - 1));
-    const int j = (tile / RM_TILES) * RM_TILE + (tid >> 4);
-    const vert12* const tvv = tv + size_t(view) * n_verts;
-    const int n = min(counts[vt], cap - offsets[vt]);
-    const int* const list = bins + size_t(view) * cap + offsets[vt];
+    const auto [x0, y0, i, j, tvv, n, list] = tile_prologue<int>(view, tile, RM_TILES, tv, n_verts, counts, offsets, bins, cap);
 
     ulonglong2* const key_slot = reinterpret_cast<ulonglong2*>(keys + ((size_t(view) * RM_SIZE + j) * RM_SIZE + i) * S);
     const ulonglong2 k01 = key_slot[0], k23 = key_slot[1];
     uint64_t best[S] = {k01.x, k01.y, k23.x, k23.y};  // what the small triangles left
     if ((k01.x & k01.y) != RM_KEY_EMPTY) key_slot[0] = make_ulonglong2(RM_KEY_EMPTY, RM_KEY_EMPTY);
     if ((k23.x & k23.y) != RM_KEY_EMPTY) key_slot[1] = make_ulonglong2(RM_KEY_EMPTY, RM_KEY_EMPTY);
-    if (blockIdx.x == 0 && tid == 0) {
-        __atomic_store_n(overflow_host, *overflow, __ATOMIC_RELAXED);
-        __threadfence_system();
-    }
+    publish_overflow(overflow, overflow_host);
 
     for (int base = 0; base < n; base += 256) {
         const int m = min(256, n - base);

@@ -33,14 +33,13 @@ __global__ __launch_bounds__(256) void tile_vc_ms_kernel(const vert12* __restric
 }  // namespace
 
 void raster_vc_tile(hipStream_t stream, int samples, const void* tv, const int32_t* tris, const uint8_t* colors, int n_verts,
-                    int n_views, const int* counts, const int* offsets, const int* bins, int cap, unsigned long long* keys,
-                    int shading, const int* overflow, int* overflow_host, float* out) {
+                    int n_views, const raster_bins& b, unsigned long long* keys, int shading, int* overflow_host, float* out) {
     const vert12* const v = static_cast<const vert12*>(tv);
     const uchar4* const col = reinterpret_cast<const uchar4*>(colors);
     if (samples == 0)
-        hipLaunchKernelGGL(tile_vc_kernel, dim3(view_chunk_grid(TILES, n_views)), dim3(256), 0, stream, v, tris, col, n_verts, counts,
-                           offsets, bins, cap, keys, shading, n_views, overflow, overflow_host, out);
+        hipLaunchKernelGGL(tile_vc_kernel, dim3(view_chunk_grid(TILES, n_views)), dim3(256), 0, stream, v, tris, col, n_verts, b.counts,
+                           b.offsets, b.bins, b.cap, keys, shading, n_views, b.overflow, overflow_host, out);
     else  // 4: the one sample count mvlm_set_render_multisamples admits
         hipLaunchKernelGGL(tile_vc_ms_kernel<4>, dim3(view_chunk_grid(TILES, n_views)), dim3(256), 0, stream, v, tris, col, n_verts,
-                           counts, offsets, bins, cap, keys, shading, n_views, overflow, overflow_host, out);
+                           b.counts, b.offsets, b.bins, b.cap, keys, shading, n_views, b.overflow, overflow_host, out);
 }

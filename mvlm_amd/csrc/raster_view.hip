@@ -29,6 +29,7 @@ namespace {
 // (profiles/landmark_view_time.txt).  The key makes the image independent of which path a triangle takes.
 constexpr int VIEW_SMALL_PIXELS = 128;
 
+// (view_transform_kernel and view_scan_kernel beside raster.hip's transform_kernel and scan_kernel: raster_bins.h says why)
 __global__ void view_transform_kernel(const float* __restrict__ verts, int n_verts, const double* __restrict__ rot,
                                       const view_frame* __restrict__ frames, int n_views, int sub_bits,
                                       vert12* __restrict__ tv) {
@@ -56,20 +57,11 @@ __device__ inline bool view_classify_one(int view, int t, const rm_vert& va, con
     const int w = tr.ix1 - tr.ix0 + 1, h = tr.iy1 - tr.iy0 + 1;
     if (w * h <= VIEW_SMALL_PIXELS) {
         unsigned long long* kv = keys + size_t(view) * size * size;
-        for (int j = tr.iy0; j <= tr.iy1; ++j)
-            for (int ii = tr.ix0; ii <= tr.ix1; ++ii) {
-                float b0, b1, b2;
-                if (!rm_cover(&tr, ii, j, &b0, &b1, &b2)) continue;
-                const float z = rm_interp(b0, b1, b2, tr.z0, tr.z1, tr.z2);
-                if (!(z >= 0.0f && z <= 1.0f)) continue;  // near / far clip
-                atomicMin(&kv[size_t(j) * size + ii], (unsigned long long)rm_key(z, uint32_t(t)));
-            }
+        resolve_small_box<rm_tri, rm_cover, size_t>(kv, size, tr.ix0, tr.ix1, tr.iy0, tr.iy1, tr, t);
         return false;
     }
     const int tiles_x = size / RM_TILE;
-    const int tx0 = tr.ix0 / RM_TILE, tx1 = tr.ix1 / RM_TILE, ty0 = tr.iy0 / RM_TILE, ty1 = tr.iy1 / RM_TILE;
-    for (int ty = ty0; ty <= ty1; ++ty)
-        for (int tx = tx0; tx <= tx1; ++tx) atomicAdd(&counts[size_t(view) * tiles_x * tiles_x + ty * tiles_x + tx], 1);
+    count_tile_range<size_t>(counts, view, tiles_x, tr.ix0, tr.ix1, tr.iy0, tr.iy1);
     return true;
 }
 
@@ -83,16 +75,8 @@ __global__ __launch_bounds__(256) void view_classify_kernel(const vert12* __rest
     const int t = chunk * 256 + int(threadIdx.x);
     const int tt = t < n_tris ? t : 0;
     const rm_vert va = load_vert(tvv, tris[3 * tt]), vb = load_vert(tvv, tris[3 * tt + 1]), vc = load_vert(tvv, tris[3 * tt + 2]);
-    const int lane = int(threadIdx.x) & 63;
     const bool big = t < n_tris && view_classify_one(view, t, va, vb, vc, size, keys, counts);
-    const unsigned long long m = __ballot(big);
-    if (m) {  // (wave-uniform) one atomic per wave appends its big triangles
-        const int leader = __ffsll(static_cast<long long>(m)) - 1;
-        int base = 0;
-        if (lane == leader) base = atomicAdd(&n_big[view], __popcll(m));
-        base = __shfl(base, leader);
-        if (big) big_list[size_t(view) * n_tris + base + __popcll(m & ((1ull << lane) - 1ull))] = t;
-    }
+    append_big(big, t, view, n_tris, n_big, big_list);
 }
 
 // exclusive prefix sum over a view's tile counters (up to 16 384): a thread sums its run of `per` counters, the 256 run sums
@@ -134,16 +118,7 @@ __global__ void view_bin_fill_kernel(const vert12* __restrict__ tv, const int32_
     for (int k = wg * 256 + int(threadIdx.x); k < n; k += FILL_WGS * 256) {
         const int t = big_list[size_t(view) * n_tris + k];
         const rm_tri tr = view_load_tri(tv + size_t(view) * n_verts, tris, t, size);
-        const int tx0 = tr.ix0 / RM_TILE, tx1 = tr.ix1 / RM_TILE, ty0 = tr.iy0 / RM_TILE, ty1 = tr.iy1 / RM_TILE;
-        for (int ty = ty0; ty <= ty1; ++ty)
-            for (int tx = tx0; tx <= tx1; ++tx) {
-                const size_t tile = size_t(view) * tiles_x * tiles_x + ty * tiles_x + tx;
-                const int pos = offsets[tile] + atomicAdd(&cursors[tile], 1);
-                if (pos >= 0 && pos < cap)
-                    bins[size_t(view) * cap + pos] = t;
-                else
-                    *overflow = 1;
-            }
+        scatter_tile_range<size_t>(view, tiles_x, offsets, cursors, bins, cap, overflow, tr.ix0, tr.ix1, tr.iy0, tr.iy1, t);
     }
 }
 
@@ -174,24 +149,15 @@ __global__ __launch_bounds__(256) void view_tile_kernel(
     __shared__ int s_sph_id[VIEW_SPHERE_CAP];
     __shared__ int s_wave[4];
     __shared__ int s_cnt[VIEW_COUNT_SPAN];
-    const int tiles_x = size / RM_TILE, tiles = tiles_x * tiles_x;
+    const int tiles_x = size / RM_TILE;
     int view, tile;
-    if (!view_chunk(tiles, n_views, &view, &tile)) return;
-    const size_t vt = size_t(view) * tiles + tile;
+    if (!view_chunk(tiles_x * tiles_x, n_views, &view, &tile)) return;
     const int tid = threadIdx.x;
-    const int tx0 = (tile % tiles_x) * RM_TILE, ty0 = (tile / tiles_x) * RM_TILE;
-    const int i = tx0 + (tid & (RM_TILE - 1));
-    const int j = ty0 + (tid >> 4);
-    const vert12* const tvv = tv + size_t(view) * n_verts;
-    const int n = min(counts[vt], cap - offsets[vt]);
-    const int* const list = bins + size_t(view) * cap + offsets[vt];
+    const auto [tx0, ty0, i, j, tvv, n, list] = tile_prologue<size_t>(view, tile, tiles_x, tv, n_verts, counts, offsets, bins, cap);
     const view_frame frame = frames[view];
 
     uint64_t best = keys[(size_t(view) * size + j) * size + i];  // what the small triangles left
-    if (blockIdx.x == 0 && tid == 0) {  // the overflow flag of the kernels before this one, to the host's pinned word
-        __atomic_store_n(overflow_host, *overflow, __ATOMIC_RELAXED);
-        __threadfence_system();
-    }
+    publish_overflow(overflow, overflow_host);
 
     best = view_tile_resolve(best, tvv, tris, list, n, size, i, j, tid, s_tri, s_id);
     float zbest;
@@ -215,19 +181,14 @@ int mvlm_view_launch_stages(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* 
     const std::string no_scratch = std::string(what) + ": scratch allocation failed";
     const int V = mesh->n_verts, T = mesh->n_tris;
     const int tiles_x = size / RM_TILE, tiles = tiles_x * tiles_x;
-    const int cap = 4 * T + 8 * tiles;  // tile-list entries per view; larger lists raise an error (mvlm_render_check)
-    const size_t n_ctr = size_t(n_views) * tiles;
-    const size_t ctr_ints = 2 * n_ctr + n_views + 4;  // counts | cursors | n_big | overflow: one memset clears them
     const size_t key_bytes = size_t(n_views) * size * size * sizeof(unsigned long long);
     auto* tv = static_cast<vert12*>(ctx->get_scratch("view.tv", size_t(n_views) * V * sizeof(vert12)));
     auto* rot = static_cast<double*>(ctx->get_scratch("view.rot", size_t(n_views) * 9 * sizeof(double)));
     auto* frames = static_cast<view_frame*>(ctx->get_scratch("view.frames", size_t(n_views) * sizeof(view_frame)));
-    auto* ctr = static_cast<int*>(ctx->get_scratch("view.ctr", ctr_ints * sizeof(int)));
-    auto* offsets = static_cast<int*>(ctx->get_scratch("view.off", n_ctr * sizeof(int)));
-    auto* bins = static_cast<int*>(ctx->get_scratch("view.bins", size_t(n_views) * cap * sizeof(int)));
-    auto* big_list = static_cast<int*>(ctx->get_scratch("view.big", size_t(n_views) * T * sizeof(int)));
+    raster_bins& b = out->bins;  // (tile-list entries per view: 4 T + 8 tiles)
+    const bool have_bins = raster_bins_scratch(ctx, "view", n_views, tiles, T, 4 * T + 8 * tiles, &b);
     auto* keys = static_cast<unsigned long long*>(ctx->get_scratch("view.keys", key_bytes));
-    MVLM_REQUIRE(ctx, tv && rot && frames && ctr && offsets && bins && big_list && keys, no_scratch);
+    MVLM_REQUIRE(ctx, tv && rot && frames && have_bins && keys, no_scratch);
     double* lm = nullptr;
     uint8_t* lm_rgb = nullptr;
     rv_sphere* spheres = nullptr;
@@ -240,10 +201,6 @@ int mvlm_view_launch_stages(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* 
             MVLM_REQUIRE(ctx, lm_rgb, no_scratch);
         }
     }
-    int* counts = ctr;
-    int* cursors = ctr + n_ctr;
-    int* n_big = ctr + 2 * n_ctr;
-    int* overflow = n_big + n_views;
     hipStream_t st = ctx->stream;
     // mvlm_render_set_profiling: events between the stages, the first in front of the copies and fills (mvlm_landmark_view_stage_ms,
     // mvlm_ray_view_stage_ms)
@@ -264,23 +221,20 @@ int mvlm_view_launch_stages(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* 
         if (lm_rgb) MVLM_CHECK_HIP(ctx, hipMemcpyAsync(lm_rgb, lm_rgb_host, size_t(n_lm) * 3, hipMemcpyHostToDevice, st));
         if (lm_pixels_dev) MVLM_CHECK_HIP(ctx, hipMemsetAsync(lm_pixels_dev, 0, size_t(n_views) * n_lm * sizeof(int32_t), st));
     }
-    MVLM_CHECK_HIP(ctx, hipMemsetAsync(ctr, 0, ctr_ints * sizeof(int), st));
+    MVLM_CHECK_HIP(ctx, hipMemsetAsync(b.counts, 0, b.ctr_ints * sizeof(int), st));
     MVLM_CHECK_HIP(ctx, hipMemsetAsync(keys, 0xFF, key_bytes, st));  // RM_KEY_EMPTY everywhere, in every call
-    if (!ctx->render_overflow_host) {
-        MVLM_CHECK_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->render_overflow_host), sizeof(int)));
-        *ctx->render_overflow_host = 0;
-    }
+    MVLM_REQUIRE(ctx, render_overflow_word(ctx), std::string(what) + ": pinned allocation failed");
     if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[1], st));
     hipLaunchKernelGGL(view_transform_kernel, dim3(view_chunk_grid((V + 255) / 256, n_views)), dim3(256), 0, st, mesh->verts, V, rot,
                        frames, n_views, ctx->render_subpixel_bits, tv);
     if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[2], st));
     hipLaunchKernelGGL(view_classify_kernel, dim3(view_chunk_grid((T + 255) / 256, n_views)), dim3(256), 0, st, tv, mesh->tris, V, T,
-                       n_views, size, keys, counts, n_big, big_list);
+                       n_views, size, keys, b.counts, b.n_big, b.big_list);
     if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[3], st));
-    hipLaunchKernelGGL(view_scan_kernel, dim3(n_views), dim3(256), 0, st, counts, offsets, tiles, cap, overflow);
+    hipLaunchKernelGGL(view_scan_kernel, dim3(n_views), dim3(256), 0, st, b.counts, b.offsets, tiles, b.cap, b.overflow);
     if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[4], st));
     hipLaunchKernelGGL(view_bin_fill_kernel, dim3(view_chunk_grid(FILL_WGS, n_views)), dim3(256), 0, st, tv, mesh->tris, V, T, n_views,
-                       size, n_big, big_list, offsets, cursors, bins, cap, overflow);
+                       size, b.n_big, b.big_list, b.offsets, b.cursors, b.bins, b.cap, b.overflow);
     if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[5], st));
     if (n_lm > 0)
         hipLaunchKernelGGL(view_project_kernel, dim3((n_views * n_lm + 255) / 256), dim3(256), 0, st, lm, lm_rgb, n_lm, rot, frames,
@@ -289,12 +243,7 @@ int mvlm_view_launch_stages(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* 
     out->tv = tv;
     out->frames = frames;
     out->rot = rot;
-    out->counts = counts;
-    out->offsets = offsets;
-    out->bins = bins;
-    out->cap = cap;
     out->keys = keys;
-    out->overflow = overflow;
     out->spheres = spheres;
     out->vcol = ctx->render_shading == 0 && mesh->colors && !(mesh->tex && mesh->uvs) ? mesh->colors : nullptr;
     out->ev = ev;
@@ -312,9 +261,9 @@ int mvlm_launch_landmark_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double
         return 1;
     const int tiles_x = size / RM_TILE, tiles = tiles_x * tiles_x;
     hipLaunchKernelGGL(view_tile_kernel, dim3(view_chunk_grid(tiles, n_views)), dim3(256), 0, ctx->stream, s.tv, mesh->tris, mesh->uvs,
-                       mesh->tex, mesh->tex_w, mesh->tex_h, reinterpret_cast<const uchar4*>(s.vcol), mesh->n_verts, s.counts,
-                       s.offsets, s.bins, s.cap, s.keys, s.frames, ctx->render_shading, n_views, size, s.spheres, n_lm,
-                       lm_pixels_dev, s.overflow, ctx->render_overflow_host, reinterpret_cast<uint32_t*>(out_dev));
+                       mesh->tex, mesh->tex_w, mesh->tex_h, reinterpret_cast<const uchar4*>(s.vcol), mesh->n_verts, s.bins.counts,
+                       s.bins.offsets, s.bins.bins, s.bins.cap, s.keys, s.frames, ctx->render_shading, n_views, size, s.spheres, n_lm,
+                       lm_pixels_dev, s.bins.overflow, ctx->render_overflow_host, reinterpret_cast<uint32_t*>(out_dev));
     if (s.ev) MVLM_CHECK_HIP(ctx, hipEventRecord(s.ev[7], ctx->stream));
     MVLM_CHECK_HIP(ctx, hipGetLastError());
     ctx->view_events_valid = s.ev != nullptr;

@@ -71,18 +71,11 @@ __device__ __forceinline__ uint32_t view_tile_shade(uint64_t best, const vert12*
             const uint32_t g = uint32_t(rv_geometry_u8(&tr, rv_geometry_kz(size, frame.half)));
             rgb = g | (g << 8) | (g << 16);
         } else if (colors) {
-            const uchar4 c0 = colors[a], c1 = colors[b], c2 = colors[c];
-            const int r = rm_color_u8(rm_interp(0.f, b1, b2, float(c0.x) / 255.0f, float(c1.x) / 255.0f, float(c2.x) / 255.0f));
-            const int g = rm_color_u8(rm_interp(0.f, b1, b2, float(c0.y) / 255.0f, float(c1.y) / 255.0f, float(c2.y) / 255.0f));
-            const int bl = rm_color_u8(rm_interp(0.f, b1, b2, float(c0.z) / 255.0f, float(c1.z) / 255.0f, float(c2.z) / 255.0f));
-            rgb = uint32_t(r) | (uint32_t(g) << 8) | (uint32_t(bl) << 16);
+            rgb = vertex_colour(colors, a, b, c, b1, b2);
         } else if (tex && uvs) {
             const float u = rm_interp(b0, b1, b2, uvs[2 * a], uvs[2 * b], uvs[2 * c]);
             const float v = rm_interp(b0, b1, b2, uvs[2 * a + 1], uvs[2 * b + 1], uvs[2 * c + 1]);
-            // one (unaligned) 4-byte load per texel: the buffer carries 4 spare bytes behind the last one (api.hip)
-            uint32_t texel;
-            __builtin_memcpy(&texel, tex + size_t(rm_texel(u, v, tex_w, tex_h)) * 3, 4);
-            rgb = texel & 0xFFFFFFu;
+            rgb = fetch_texel(tex, u, v, tex_w, tex_h);
         }
         zbest = rm_key_z(best);
     }
@@ -114,7 +107,7 @@ __device__ __forceinline__ int view_tile_spheres(const rv_sphere* __restrict__ s
         __syncthreads();  // (the previous round's walk is over)
         if (lane == 0) s_wave[wave] = __popcll(m);
         __syncthreads();
-        int off = 0, total = 0;
+        int off = 0, total = 0;  // (as in rays_tile_kernel; why this is not a shared helper: raster_bins.h)
         for (int w = 0; w < 4; ++w) {
             off += w < wave ? s_wave[w] : 0;
             total += s_wave[w];
@@ -163,12 +156,8 @@ struct mvlm_view_stages {
     const vert12* tv;
     const view_frame* frames;
     const double* rot;
-    const int* counts;
-    const int* offsets;
-    const int* bins;
-    int cap;
+    raster_bins bins;  // counters, offsets, lists and the overflow flag (raster_bins.h)
     const unsigned long long* keys;
-    const int* overflow;
     const rv_sphere* spheres;  // null when n_lm == 0
     const uint8_t* vcol;       // the per-vertex colours the tile stage shades with, or null
     hipEvent_t* ev;            // null unless render profiling is on: [0..6] recorded, the caller records the rest

@@ -195,6 +195,38 @@ def test_geometry_shading_and_four_subpixel_bits_follow_the_model(model):
         np.testing.assert_array_equal(counts, wc)
 
 
+# ---- list overflow ----------------------------------------------------------------------------------------------------------
+def _window_filling_triangles(n=16):
+    """n triangles that each cover the whole window of a frame of half 50 about the origin (test_gpu_round6.py's overflow mesh)"""
+    from mvlm_amd.utils import Mesh
+
+    rs = np.random.RandomState(2)
+    verts = np.concatenate([np.array([[-400, -400, z], [400, -400, z], [0, 600, z]], np.float32) for z in rs.uniform(-50, 50, n)])
+    return Mesh(verts, np.arange(3 * n, dtype=np.int32).reshape(n, 3))
+
+
+def test_list_overflow_is_reported_and_the_next_view_is_clean(model):
+    """At S = 64 a view has 16 tiles and 4 * 16 + 8 * 16 = 192 list entries; 16 big triangles on all 16 tiles ask for 256.  The
+    call returns 0 (the scatter drops what does not fit), mvlm_render_check says "overflowed", and the view after it on the same
+    renderer is the model's bit for bit with a clean check."""
+    from mvlm_amd import _lib
+
+    r = _renderer()
+    rc, _, _ = _call(r, _window_filling_triangles(), FRONT, 64, (0.0, 0.0, 50.0))
+    assert rc == 0
+    with pytest.raises(_lib.MvlmHipError, match="overflowed"):
+        r.check()
+    sc = SCENES["face40"]
+    mesh, extra = _mesh("face40", "textured")
+    lm = _face_landmarks(84)
+    want, want_counts, winner = model(sc["verts"], sc["tris"], extra["uvs"], extra["texture"], FRONT, 64, frame=view_model.NETWORK_FRAME,
+                                      landmarks=lm, radius=4.0)
+    got, counts = _view(r, mesh, FRONT, 64, view_model.NETWORK_FRAME, lm, 4.0)   # (_view's r.check() is clean)
+    np.testing.assert_array_equal(got, want)
+    np.testing.assert_array_equal(counts, want_counts)
+    assert (winner >= 0).any() and (winner <= -2).any()
+
+
 # ---- bad arguments ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("what", ["size_250", "size_4096", "half_0", "nan_landmark", "negative_radius", "nan_frame", "views_129"])
 def test_bad_arguments_return_an_error_and_launch_nothing(what):

@@ -293,6 +293,33 @@ def test_geometry_shading_and_four_subpixel_bits_follow_the_model(model, face_ra
     assert (ray_model.ray_of(winner) >= 0).any()
 
 
+# ---- list overflow ----------------------------------------------------------------------------------------------------------
+def test_list_overflow_is_reported_and_the_next_view_is_clean(model, face_rays):
+    """At S = 64 a view has 16 tiles and 4 * 16 + 8 * 16 = 192 list entries; 16 big triangles on all 16 tiles ask for 256.  The
+    call returns 0 (the scatter drops what does not fit), mvlm_render_check says "overflowed", and the ray view after it on the
+    same renderer is the model's bit for bit with a clean check."""
+    from mvlm_amd import _lib
+    from mvlm_amd.utils import Mesh
+
+    n = 16  # test_gpu_round6.py's overflow triangles: each covers the whole window of a frame of half 50 about the origin
+    rs = np.random.RandomState(2)
+    verts = np.concatenate([np.array([[-400, -400, z], [400, -400, z], [0, 600, z]], np.float32) for z in rs.uniform(-50, 50, n)])
+    huge = Mesh(verts, np.arange(3 * n, dtype=np.int32).reshape(n, 3))
+    r = _renderer()
+    rc, _, _, _ = _call(r, huge, FRONT, 64, (0.0, 0.0, 50.0))
+    assert rc == 0
+    with pytest.raises(_lib.MvlmHipError, match="overflowed"):
+        r.check()
+    sc = SCENES["face40"]
+    mesh, extra = _mesh("face40", "textured")
+    lm = view_model.surface_landmarks(sc["verts"], 84)
+    kw = dict(landmarks=lm, radius=4.0, starts=face_rays[0][:40], ends=face_rays[1][:40], ray_radius=0.5)
+    w_img, w_cnt, w_rcnt, winner, _ = model(sc["verts"], sc["tris"], sc["uvs"], sc["tex"], FRONT, 64, frame=view_model.NETWORK_FRAME, **kw)
+    got = _view(r, mesh, FRONT, 64, view_model.NETWORK_FRAME, **kw)   # (_view's r.check() is clean)
+    _check((w_img, w_cnt, w_rcnt), got, winner)
+    assert (winner >= 0).any() and (ray_model.ray_of(winner) >= 0).any()
+
+
 # ---- equal to mvlm_render_landmark_view --------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mode", ["textured", "vcolor", "white"])
 def test_no_rays_is_the_landmark_view_byte_for_byte(mode):
