@@ -102,6 +102,37 @@ int mvlm_mesh_upload(mvlm_ctx* ctx, const float* verts_host, const float* uvs_ho
  * A mesh with a texture and uvs renders with its texture alone (VTK would multiply texel and colour: not built); geometry shading and the
  * depth plane never see colours.  Same staging, copy stream and ready event as the mesh upload; may run on a reader thread. */
 int mvlm_mesh_upload_colors(mvlm_ctx* ctx, mvlm_mesh* mesh, const uint8_t* rgb_host, int n_verts);
+/* ---- point clouds: a scan with points and no faces ---------------------------------
+ * mvlm_mesh_upload with n_tris == 0 (tris_host may be NULL) makes a POINT MESH; uvs and texture arguments are ignored, and the
+ * JPEG / texture upload entries refuse n_tris == 0.  mvlm_mesh_upload_colors works as for any mesh.  The reference has no
+ * such path (vtkOBJReader yields no cells: white views, nothing to snap to), so the contract is this build's own
+ * (csrc/raster_points_math.h, DESIGN.md 5.1 "Point clouds"):
+ *   - mvlm_render draws every point as a SPLAT: position and depth from the mesh path's transform, a disc of R =
+ *     floor(r * 256 / 300 * 256 + 0.5) steps of 1/256 pixel that covers the pixel centres with dx^2 + dy^2 <= R^2, a depth that
+ *     rises towards the rim, z_pix = z + (float)d2 * c with c = (float)(r / 1500 / R^2) - so neighbouring splats share the
+ *     screen like a Voronoi diagram - clipped to [0,1]; the least z_pix wins a pixel, the higher point id on ties; RGB is
+ *     the winner's colour (white without colours), the depth plane its z_pix.  A non-finite point draws nothing.
+ *   - mvlm_project_to_surface returns the NEAREST POINT's own coordinates (float64 distances, lowest id on ties, non-finite
+ *     points never, a non-finite landmark passed through).
+ *   - refused with an argument error before anything is launched: mvlm_render with shading 1 (geometry) or 4 multisamples,
+ *     mvlm_render_landmark_view, mvlm_render_ray_view, mvlm_clip_rays_to_mesh, mvlm_surface_attach.
+ * The radius r (model units) is per mesh: at upload the automatic one, mvlm_points_auto_radius of the uploaded points;
+ * mvlm_mesh_set_point_radius replaces it - an error outside 0.75..8 pixels (0.87890625..9.375 model units) or on a mesh with
+ * triangles; mvlm_mesh_point_radius reads it (non-zero for a mesh with triangles). */
+int mvlm_mesh_set_point_radius(mvlm_ctx* ctx, mvlm_mesh* mesh, double r_model_units);
+int mvlm_mesh_point_radius(const mvlm_mesh* mesh, double* r_model_units);
+/* The automatic radius; host only, no ctx, no GPU.  verts f32[n,3].  Bounding box of the points whose three coordinates are
+ * finite, extents sorted ex >= ey >= ez, s = sqrt(ex * ey / n_finite), r = clamp(1.25 s, 0.75, 8.0) * 300 / 256: a regular grid
+ * of spacing s leaves no pixel centre farther than 0.71 s from a point and rotation only shrinks projected spacing; a dense
+ * scan lands on the 0.75 pixel floor, as does a cloud with s = 0 (one point, collinear points, no finite point). */
+int mvlm_points_auto_radius(const float* verts_host, int n, double* r_model_units);
+/* measuring hooks: the splat kernel's counting form, and what the last counted render saw (pixels past coverage and clip;
+ * atomics issued - the others found a smaller key stored already).  mvlm_points_get_stats synchronises the stream. */
+int mvlm_points_set_counting(mvlm_ctx* ctx, int enabled);
+int mvlm_points_get_stats(mvlm_ctx* ctx, unsigned long long* covered, unsigned long long* issued);
+/* ms2[0], ms2[1]: milliseconds of the splat and of the tile kernel of the last cloud render made while
+ * mvlm_render_set_profiling was on; synchronises the stream. */
+int mvlm_points_stage_ms(mvlm_ctx* ctx, float* ms2);
 void mvlm_mesh_free(mvlm_ctx* ctx, mvlm_mesh* mesh);
 
 /* ---- JPEG texture decoded on the device (replaces vtkJPEGReader in obj_to_actor, utils3d.py:28-34 / :42-48, and in
@@ -424,7 +455,7 @@ int mvlm_consensus_report(mvlm_ctx* ctx, const double* starts_dev, const double*
                           double* stats_dev, int32_t* counts_dev, double* dist2_dev, uint8_t* flags_dev);
 
 /* ---- surface snap (replaces estimator3d.py:252-285) ------------------------------ */
-/* pts_dev f64[NL,3] -> out_dev f64[NL,3]: closest point on the triangle surface */
+/* pts_dev f64[NL,3] -> out_dev f64[NL,3]: closest point on the triangle surface (of a point mesh: the nearest point) */
 int mvlm_project_to_surface(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* pts_dev, int n_points,
                             double* out_dev);
 

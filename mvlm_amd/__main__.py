@@ -64,6 +64,9 @@ def build_parser() -> argparse.ArgumentParser:
                              "scan: the mesh, every view's ray for every landmark clipped to its first hit with the surface, and the "
                              "landmarks, from the front and from 60 degrees left and right (with --report the rays are green where the "
                              "consensus used them, orange where it kept but did not use them, grey where the score filter dropped them)")
+    parser.add_argument("--point-radius", type=float, default=None, metavar="MM",
+                        help="splat radius, in model units, of scans that have points but no faces (point clouds): 0.88 to 9.375, "
+                             "i.e. 0.75 to 8 pixels of a view; default: automatic, from the spacing of the points (DESIGN.md 5.1)")
     parser.add_argument("--png-encoder", choices=("host", "device"), default="host",
                         help="who makes the PNG files of --visualize-img and --visualize-rays: 'host' copies the picture to the host "
                              "and encodes it with Pillow; 'device' filters and compresses it on the GPU and copies only the file's "
@@ -114,6 +117,8 @@ def main(argv=None) -> int:
     if args.visualize_rays:
         extra["visualize_rays_img"] = True
         extra["visualize_size"] = args.visualize_size
+    if args.point_radius is not None:
+        extra["point_radius"] = args.point_radius
     if args.png_encoder != "host":
         extra["view_png_encoder"] = args.png_encoder
     if args.config is not None:

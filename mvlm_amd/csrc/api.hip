@@ -8,6 +8,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "raster_points_math.h"
 #include "raster_view_math.h"
 
 void* mvlm_ctx::get_scratch(const char* name, size_t bytes) {
@@ -85,6 +86,8 @@ extern "C" void mvlm_ctx_destroy(mvlm_ctx* ctx) {
     for (auto e : ctx->view_events)
         if (e) hipEventDestroy(e);
     for (auto e : ctx->png_events)
+        if (e) hipEventDestroy(e);
+    for (auto e : ctx->points_events)
         if (e) hipEventDestroy(e);
     for (auto e : ctx->cnn.sync_events)
         if (e) hipEventDestroy(e);
@@ -186,7 +189,13 @@ static int mesh_upload_impl(mvlm_ctx* ctx, const float* verts_host, const float*
     // pick, the asynchronous copies and the event records.
     MVLM_REQUIRE(ctx, out, "mesh_upload: null output");
     *out = nullptr;
-    MVLM_REQUIRE(ctx, verts_host && tris_host && n_verts > 0 && n_tris > 0, "mesh_upload: mesh does not contain any points");
+    // n_tris == 0 (tris_host may be null): a point mesh - the points alone, drawn as splats and snapped to the nearest point
+    MVLM_REQUIRE(ctx, verts_host && n_verts > 0 && n_tris >= 0 && (tris_host || n_tris == 0), "mesh_upload: mesh does not contain any points");
+    MVLM_REQUIRE(ctx, n_tris > 0 || !(jpeg || pre), "mesh_upload: a point cloud (n_tris == 0) takes no texture");
+    if (n_tris == 0) {  // a texture or uvs on a faceless mesh are ignored
+        uvs_host = nullptr;
+        tex_host = nullptr;
+    }
     MVLM_REQUIRE(ctx, !(tex_host || jpeg || pre) || (tex_h > 0 && tex_w > 0), "mesh_upload: bad texture size");
     for (long i = 0; i < 3l * n_tris; ++i)
         MVLM_REQUIRE(ctx, tris_host[i] >= 0 && tris_host[i] < n_verts, "mesh_upload: triangle index out of range");
@@ -235,6 +244,11 @@ static int mesh_upload_impl(mvlm_ctx* ctx, const float* verts_host, const float*
     m->uid = next_uid.fetch_add(1);
     m->n_verts = n_verts;
     m->n_tris = n_tris;
+    if (n_tris == 0) {  // the automatic radius, from the points as uploaded
+        (void)mvlm_points_auto_radius(verts_host, n_verts, &m->point_radius);
+        (void)rp_radius_steps(m->point_radius, &m->point_R);  // (inside the admitted range by construction)
+        m->point_c = rp_depth_coeff(m->point_radius, m->point_R);
+    }
     void** dst[4] = {(void**)&m->verts, (void**)&m->uvs, (void**)&m->tris, (void**)&m->tex};
     bool ok = true;
     {
@@ -311,6 +325,7 @@ extern "C" int mvlm_mesh_upload_jpeg(mvlm_ctx* ctx, const float* verts_host, con
                                      const int32_t* tris_host, int n_tris, const uint8_t* jpeg, size_t jpeg_bytes, mvlm_mesh** out) {
     MVLM_REQUIRE(ctx, out, "mesh_upload_jpeg: null output");
     *out = nullptr;
+    MVLM_REQUIRE(ctx, n_tris != 0, "mesh_upload_jpeg: a point cloud (n_tris == 0) takes no texture");
     MVLM_REQUIRE(ctx, jpeg && jpeg_bytes > 0, "mesh_upload_jpeg: no JPEG");
     std::unique_ptr<MvlmJpegPlan, void (*)(MvlmJpegPlan*)> plan(mvlm_jpeg_plan_new(), mvlm_jpeg_plan_delete);
     std::string w;
@@ -456,6 +471,7 @@ extern "C" int mvlm_mesh_upload_texture(mvlm_ctx* ctx, const float* verts_host, 
                                         const int32_t* tris_host, int n_tris, mvlm_texture* tex, int* consumed, mvlm_mesh** out) {
     if (consumed) *consumed = 0;
     MVLM_REQUIRE(ctx, tex && tex->dev, "mesh_upload_texture: no texture");
+    MVLM_REQUIRE(ctx, n_tris != 0, "mesh_upload_texture: a point cloud (n_tris == 0) takes no texture");
     const bool will_consume = uvs_host != nullptr;
     const int rc = mesh_upload_impl(ctx, verts_host, uvs_host, n_verts, tris_host, n_tris, nullptr, tex->h, tex->w, nullptr, nullptr, 0, out, tex);
     if (rc == 0 && will_consume && consumed) *consumed = 1;
@@ -531,6 +547,61 @@ extern "C" int mvlm_mesh_upload_colors(mvlm_ctx* ctx, mvlm_mesh* m, const uint8_
     }
     if (ok) m->colors = static_cast<uint8_t*>(dst);
     MVLM_REQUIRE(ctx, ok, "mesh_upload_colors: device allocation / copy failed");
+    return 0;
+}
+
+// The splat radius of a point mesh, in model units (raster_points_math.h): admitted from 0.75 to 8 pixels of the 256-pixel window
+// that shows 300 units.  Renders enqueued before the call keep the radius they were launched with.
+extern "C" int mvlm_mesh_set_point_radius(mvlm_ctx* ctx, mvlm_mesh* m, double r_model_units) {
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    MVLM_REQUIRE(ctx, m, "mesh_set_point_radius: null mesh");
+    MVLM_REQUIRE(ctx, m->n_tris == 0, "mesh_set_point_radius: the mesh has triangles (a radius belongs to a point cloud)");
+    int32_t R = 0;
+    MVLM_REQUIRE(ctx, rp_radius_steps(r_model_units, &R),
+                 "mesh_set_point_radius: the radius must be 0.75 to 8 pixels, i.e. 0.87890625 to 9.375 model units (" +
+                     std::to_string(r_model_units) + " given)");
+    m->point_radius = r_model_units;
+    m->point_R = R;
+    m->point_c = rp_depth_coeff(r_model_units, R);
+    return 0;
+}
+
+extern "C" int mvlm_mesh_point_radius(const mvlm_mesh* m, double* r_model_units) {
+    if (!m || !r_model_units || m->n_tris != 0) return 1;
+    *r_model_units = m->point_radius;
+    return 0;
+}
+
+// Measuring hook (tools/points_bench.py): with counting on, a cloud's render runs the splat kernel's counting form;
+// mvlm_points_get_stats waits for the stream and returns what the LAST such render counted - pixels that passed coverage and
+// clip, and the atomics issued for them (the rest found a smaller key in place and skipped theirs).
+extern "C" int mvlm_points_set_counting(mvlm_ctx* ctx, int enabled) {
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    ctx->points_counting = enabled != 0;
+    return 0;
+}
+
+extern "C" int mvlm_points_get_stats(mvlm_ctx* ctx, unsigned long long* covered, unsigned long long* issued) {
+    MVLM_ENTER(ctx);
+    MVLM_REQUIRE(ctx, covered && issued, "points_get_stats: null pointer");
+    const auto it = ctx->scratch.find("points.stats");
+    MVLM_REQUIRE(ctx, it != ctx->scratch.end() && it->second.first, "points_get_stats: no cloud has been rendered with counting on");
+    unsigned long long host[2] = {0, 0};
+    MVLM_CHECK_HIP(ctx, hipMemcpyAsync(host, it->second.first, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
+    MVLM_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *covered = host[0];
+    *issued = host[1];
+    return 0;
+}
+
+// Milliseconds of the last cloud render's two kernels - splat, tile - while mvlm_render_set_profiling is on; waits for the stream.
+extern "C" int mvlm_points_stage_ms(mvlm_ctx* ctx, float* ms2) {
+    MVLM_ENTER(ctx);
+    MVLM_REQUIRE(ctx, ms2, "points_stage_ms: null pointer");
+    MVLM_REQUIRE(ctx, ctx->points_events_valid && ctx->points_events.size() >= 3,
+                 "points_stage_ms: no point cloud was rendered with render profiling on");
+    MVLM_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < 2; ++k) MVLM_CHECK_HIP(ctx, hipEventElapsedTime(&ms2[k], ctx->points_events[k], ctx->points_events[k + 1]));
     return 0;
 }
 
@@ -887,7 +958,8 @@ static int view_check_arguments(mvlm_ctx* ctx, const std::string& what, const mv
                                 int size, const float* frame_host, const double* landmarks_host, int n_lm, float radius,
                                 const uint8_t* out_dev, std::vector<float>& frames) {
     MVLM_REQUIRE(ctx, mesh && rot_host && frame_host && out_dev && n_views > 0, what + ": bad arguments");
-    MVLM_REQUIRE(ctx, mesh->n_verts > 0 && mesh->n_tris > 0, what + ": empty mesh");
+    MVLM_REQUIRE(ctx, mesh->n_verts > 0, what + ": empty mesh");
+    MVLM_REQUIRE(ctx, mesh->n_tris > 0, what + ": a point cloud is not supported here (the mesh has no triangles)");
     MVLM_REQUIRE(ctx, size >= RV_MIN_SIZE && size <= RV_MAX_SIZE && size % RM_TILE == 0,
                  what + ": size must be a multiple of 16 in 64..2048 (" + std::to_string(size) + " given)");
     MVLM_REQUIRE(ctx, n_views <= RV_MAX_VIEWS, what + ": at most 128 views per call (" + std::to_string(n_views) + " given)");

@@ -232,6 +232,11 @@ struct mvlm_mesh {
     uint8_t* tex = nullptr;   // [H,W,3] or null
     uint8_t* colors = nullptr;  // [V,4] per-vertex r g b 255 (one aligned 4-byte load per vertex) or null: mvlm_mesh_upload_colors
     int n_verts = 0, n_tris = 0, tex_h = 0, tex_w = 0;
+    // a point mesh (n_tris == 0, tris == null; raster_points_math.h): the splat radius in model units, the same in lattice
+    // steps and the paraboloid's coefficient - the automatic radius at upload, mvlm_mesh_set_point_radius replaces it
+    double point_radius = 0.0;
+    int32_t point_R = 0;
+    float point_c = 0.f;
     unsigned long long uid = 0;  // unique per upload (an address can be recycled): key of per-mesh derived data a context keeps
     size_t cap[5] = {0, 0, 0, 0, 0};  // allocation sizes of verts / uvs / tris / tex / colors (for the ctx's mesh pool)
     // recorded on the context's upload stream behind the host-to-device copies (again behind the colours' copy, when they
@@ -304,6 +309,10 @@ struct mvlm_ctx {
     int render_multisamples = 0;   // 0: one sample at the pixel centre (the default contract); 4: four samples per pixel
     int render_shading = 0;  // 0: unlit nearest-texel RGB (reference), 1: build-defined geometry shading
     int* render_overflow_host = nullptr;  // pinned; written asynchronously by mvlm_render
+    bool points_counting = false;  // mvlm_points_set_counting: a cloud's splat kernel also counts covered pixels and atomics
+    // under render profiling, round the two kernels of a cloud's render: before the splats, between, behind the tile stage
+    std::vector<hipEvent_t> points_events;
+    bool points_events_valid = false;
     bool render_profiling = false;        // mvlm_render_set_profiling: HIP events around each render's kernels
     std::vector<RenderProfileRec> render_prof;
     std::vector<hipEvent_t> render_events;
@@ -448,6 +457,11 @@ int mvlm_launch_ray_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot
 // for an entry point that holds the context; its final kernel follows (mvlm_project_to_surface, mvlm_surface_attach)
 int mvlm_project_partials(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* pts_dev, int n_points, int* n_chunks_out,
                           const double** part_d_out, const int** part_t_out);
+
+// surface_points.hip: the snap of a point mesh (n_tris == 0) - the nearest point - for mvlm_project_to_surface, which holds the context
+int mvlm_points_nearest(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* pts_dev, int n_points, double* out_dev);
+// raster_points.hip: the automatic splat radius of a cloud (host only; exported, include/mvlm_hip.h)
+extern "C" int mvlm_points_auto_radius(const float* verts, int n, double* r_out);
 
 // small kernels (misc.hip)
 int mvlm_launch_pack_input(mvlm_ctx* ctx, const float* images, int n, const int* sel4, int c, float* out);

@@ -188,13 +188,24 @@ __global__ __launch_bounds__(256) void tile_kernel(const vert12* __restrict__ tv
 extern "C" int mvlm_render(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot_host, int n_views, float* out_dev) {
     MVLM_ENTER(ctx);
     MVLM_REQUIRE(ctx, mesh && rot_host && out_dev && n_views > 0, "render: bad arguments");
-    MVLM_REQUIRE(ctx, mesh->n_verts > 0 && mesh->n_tris > 0, "render: empty mesh");
+    MVLM_REQUIRE(ctx, mesh->n_verts > 0 && mesh->n_tris >= 0, "render: empty mesh");
+    // A point mesh (n_tris == 0) is drawn as splats by the kernels of raster_points.hip; what it does not have is refused here,
+    // before anything is enqueued.
+    const bool cloud = mesh->n_tris == 0;
+    MVLM_REQUIRE(ctx, !cloud || ctx->render_shading == 0,
+                 "render: geometry shading of a point cloud is not supported (it needs normals, a cloud has none)");
+    MVLM_REQUIRE(ctx, !cloud || ctx->render_multisamples == 0, "render: multisampled rendering of a point cloud is not supported");
+    MVLM_REQUIRE(ctx, !cloud || n_views <= 65535, "render: at most 65535 views of a point cloud per call");
     if (mvlm_mesh_wait_ready(ctx, mesh, ctx->stream)) return 1;  // the upload runs on a stream of its own
     const int V = mesh->n_verts, T = mesh->n_tris;
-    auto* tv = static_cast<vert12*>(ctx->get_scratch("raster.tv", size_t(n_views) * V * sizeof(vert12)));
+    vert12* tv = nullptr;
     auto* rot = static_cast<double*>(ctx->get_scratch("raster.rot", size_t(n_views) * 9 * sizeof(double)));
     raster_bins b;  // (tile-list entries per view: 4 T + 16 384)
-    const bool have_bins = raster_bins_scratch(ctx, "raster", n_views, TILES, T, 4 * T + 16384, &b);
+    bool have_bins = true;
+    if (!cloud) {  // (a cloud's splats go straight to the key plane: no transformed vertices, no bins)
+        tv = static_cast<vert12*>(ctx->get_scratch("raster.tv", size_t(n_views) * V * sizeof(vert12)));
+        have_bins = raster_bins_scratch(ctx, "raster", n_views, TILES, T, 4 * T + 16384, &b);
+    }
     // one key per pixel, or S per pixel in a plane of its own when multisampling (allocated only then)
     const int S = ctx->render_multisamples;
     // per-vertex colours shade the RGB planes of the unlit render of a mesh without a usable texture
@@ -202,9 +213,15 @@ extern "C" int mvlm_render(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* r
     const char* const key_name = S ? "raster.keys4" : "raster.keys";
     const size_t key_bytes = size_t(n_views) * RM_SIZE * RM_SIZE * size_t(S ? S : 1) * sizeof(unsigned long long);
     auto* keys = static_cast<unsigned long long*>(ctx->get_scratch(key_name, key_bytes));
-    MVLM_REQUIRE(ctx, tv && rot && have_bins && keys, "render: scratch allocation failed");
+    MVLM_REQUIRE(ctx, (cloud || tv) && rot && have_bins && keys, "render: scratch allocation failed");
+    unsigned long long* point_stats = nullptr;  // (mvlm_points_set_counting: the splat kernel's measuring form)
+    if (cloud && ctx->points_counting) {
+        point_stats = static_cast<unsigned long long*>(ctx->get_scratch("points.stats", 2 * sizeof(unsigned long long)));
+        MVLM_REQUIRE(ctx, point_stats, "render: scratch allocation failed");
+    }
     MVLM_CHECK_HIP(ctx, hipMemcpyAsync(rot, rot_host, size_t(n_views) * 9 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    MVLM_CHECK_HIP(ctx, hipMemsetAsync(b.counts, 0, b.ctr_ints * sizeof(int), ctx->stream));
+    if (!cloud) MVLM_CHECK_HIP(ctx, hipMemsetAsync(b.counts, 0, b.ctr_ints * sizeof(int), ctx->stream));
+    if (point_stats) MVLM_CHECK_HIP(ctx, hipMemsetAsync(point_stats, 0, 2 * sizeof(unsigned long long), ctx->stream));
     // The key plane is EMPTY between renders (tile_kernel clears what it reads); it is filled here only when the buffer is new
     // or a render did not run to its end.  `clean` = the buffer and capacity it was last known clean at: a buffer that
     // get_scratch replaced (after a failed allocation, say) is filled even when its size is the old one.
@@ -227,25 +244,44 @@ extern "C" int mvlm_render(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* r
         ctx->render_event_cursor += 2;
         MVLM_CHECK_HIP(ctx, hipEventRecord(e0, ctx->stream));
     }
-    hipLaunchKernelGGL(transform_kernel, dim3(view_chunk_grid((V + 255) / 256, n_views)), dim3(256), 0, ctx->stream,
-                       mesh->verts, V, rot, n_views, ctx->render_subpixel_bits, tv);
-    if (S == 0) {
-        hipLaunchKernelGGL(classify_kernel<CLASSIFY_TPT>, dim3(view_chunk_grid((T + 256 * CLASSIFY_TPT - 1) / (256 * CLASSIFY_TPT), n_views)), dim3(256), 0,
-                           ctx->stream, tv, mesh->tris, V, T, n_views, keys, b.counts, b.n_big, b.big_list);
-        hipLaunchKernelGGL(scan_kernel, dim3(n_views), dim3(TILES), 0, ctx->stream, b.counts, b.offsets, b.cap, b.overflow);
-        hipLaunchKernelGGL(bin_fill_kernel, dim3(view_chunk_grid(FILL_WGS, n_views)), dim3(256), 0, ctx->stream, tv,
-                           mesh->tris, V, T, n_views, b.n_big, b.big_list, b.offsets, b.cursors, b.bins, b.cap, b.overflow);
-        if (vcol)
-            raster_vc_tile(ctx->stream, 0, tv, mesh->tris, vcol, V, n_views, b, keys, ctx->render_shading, overflow_host, out_dev);
-        else
-            hipLaunchKernelGGL(tile_kernel, dim3(view_chunk_grid(TILES, n_views)), dim3(256), 0, ctx->stream, tv, mesh->tris,
-                               mesh->uvs, mesh->tex, mesh->tex_w, mesh->tex_h, V, b.counts, b.offsets, b.bins, b.cap, keys,
-                               ctx->render_shading, n_views, b.overflow, overflow_host, out_dev);
-    } else {  // S == 4 (mvlm_set_render_multisamples admits nothing else): the kernels of raster_ms.hip
-        raster_ms_classify(ctx->stream, S, tv, mesh->tris, V, T, n_views, keys, b);
-        hipLaunchKernelGGL(scan_kernel, dim3(n_views), dim3(TILES), 0, ctx->stream, b.counts, b.offsets, b.cap, b.overflow);
-        raster_ms_bin_and_tile(ctx->stream, S, tv, mesh->tris, mesh->uvs, mesh->tex, mesh->tex_w, mesh->tex_h, V, T, n_views, b,
-                               keys, ctx->render_shading, overflow_host, out_dev, vcol);
+    if (cloud) {
+        hipEvent_t* pev = nullptr;  // (profiling: events of the cloud's own round its two kernels, mvlm_points_stage_ms)
+        ctx->points_events_valid = false;
+        if (ctx->render_profiling) {
+            ctx->points_events.resize(3, nullptr);
+            for (hipEvent_t& e : ctx->points_events)
+                if (!e) MVLM_CHECK_HIP(ctx, hipEventCreate(&e));
+            pev = ctx->points_events.data();
+            MVLM_CHECK_HIP(ctx, hipEventRecord(pev[0], ctx->stream));
+        }
+        // per-point colours shade the RGB planes (white without them); a texture or uvs on a faceless mesh are ignored
+        raster_points_launch(ctx->stream, mesh->verts, mesh->colors, V, rot, n_views, ctx->render_subpixel_bits, mesh->point_R,
+                             mesh->point_c, keys, point_stats, overflow_host, out_dev, pev ? pev[1] : nullptr);
+        if (pev) {
+            MVLM_CHECK_HIP(ctx, hipEventRecord(pev[2], ctx->stream));
+            ctx->points_events_valid = true;
+        }
+    } else {
+        hipLaunchKernelGGL(transform_kernel, dim3(view_chunk_grid((V + 255) / 256, n_views)), dim3(256), 0, ctx->stream,
+                           mesh->verts, V, rot, n_views, ctx->render_subpixel_bits, tv);
+        if (S == 0) {
+            hipLaunchKernelGGL(classify_kernel<CLASSIFY_TPT>, dim3(view_chunk_grid((T + 256 * CLASSIFY_TPT - 1) / (256 * CLASSIFY_TPT), n_views)), dim3(256), 0,
+                               ctx->stream, tv, mesh->tris, V, T, n_views, keys, b.counts, b.n_big, b.big_list);
+            hipLaunchKernelGGL(scan_kernel, dim3(n_views), dim3(TILES), 0, ctx->stream, b.counts, b.offsets, b.cap, b.overflow);
+            hipLaunchKernelGGL(bin_fill_kernel, dim3(view_chunk_grid(FILL_WGS, n_views)), dim3(256), 0, ctx->stream, tv,
+                               mesh->tris, V, T, n_views, b.n_big, b.big_list, b.offsets, b.cursors, b.bins, b.cap, b.overflow);
+            if (vcol)
+                raster_vc_tile(ctx->stream, 0, tv, mesh->tris, vcol, V, n_views, b, keys, ctx->render_shading, overflow_host, out_dev);
+            else
+                hipLaunchKernelGGL(tile_kernel, dim3(view_chunk_grid(TILES, n_views)), dim3(256), 0, ctx->stream, tv, mesh->tris,
+                                   mesh->uvs, mesh->tex, mesh->tex_w, mesh->tex_h, V, b.counts, b.offsets, b.bins, b.cap, keys,
+                                   ctx->render_shading, n_views, b.overflow, overflow_host, out_dev);
+        } else {  // S == 4 (mvlm_set_render_multisamples admits nothing else): the kernels of raster_ms.hip
+            raster_ms_classify(ctx->stream, S, tv, mesh->tris, V, T, n_views, keys, b);
+            hipLaunchKernelGGL(scan_kernel, dim3(n_views), dim3(TILES), 0, ctx->stream, b.counts, b.offsets, b.cap, b.overflow);
+            raster_ms_bin_and_tile(ctx->stream, S, tv, mesh->tris, mesh->uvs, mesh->tex, mesh->tex_w, mesh->tex_h, V, T, n_views, b,
+                                   keys, ctx->render_shading, overflow_host, out_dev, vcol);
+        }
     }
     MVLM_CHECK_HIP(ctx, hipGetLastError());
     clean = mvlm_ctx::KeyPlaneState{keys, keys_cap};

@@ -85,5 +85,12 @@ void raster_ms_bin_and_tile(hipStream_t stream, int samples, const void* tv, con
 // or 4 (in place of tile_ms_kernel, behind raster_ms.hip's bin fill).
 void raster_vc_tile(hipStream_t stream, int samples, const void* tv, const int32_t* tris, const uint8_t* colors, int n_verts,
                     int n_views, const raster_bins& b, unsigned long long* keys, int shading, int* overflow_host, float* out);
+// The two kernels of a point mesh's render (raster_points.hip): splats into `keys`, then the tile stage, which hands the key plane
+// back EMPTY.  `rot` f64[n_views,9] on the device; R / c: the mesh's radius in lattice steps and its depth coefficient
+// (raster_points_math.h); `colors` u8[n_points,4] on the device or null (white); `stats` null, or two device counters the splat
+// kernel's measuring form adds to (covered pixels, atomics issued); `between`: null, or an event to record between the two kernels.
+void raster_points_launch(hipStream_t stream, const float* verts, const uint8_t* colors, int n_points, const double* rot,
+                          int n_views, int sub_bits, int R, float c, unsigned long long* keys, unsigned long long* stats,
+                          int* overflow_host, float* out, hipEvent_t between);
 
 #endif

@@ -383,7 +383,7 @@ extern "C" int mvlm_clip_rays_to_mesh(mvlm_ctx* ctx, const mvlm_mesh* mesh, cons
                                       const double* ends_dev, int n_rays, double* new_ends_dev, uint8_t* hit_dev) {
     MVLM_ENTER(ctx);
     MVLM_REQUIRE(ctx, mesh && starts_dev && ends_dev && new_ends_dev && n_rays > 0, "clip_rays_to_mesh: bad arguments");
-    MVLM_REQUIRE(ctx, mesh->n_tris > 0, "clip_rays_to_mesh: empty mesh");
+    MVLM_REQUIRE(ctx, mesh->n_tris > 0, "clip_rays_to_mesh: ray clipping against a point cloud is not supported (the mesh has no triangles)");
     if (mvlm_mesh_wait_ready(ctx, mesh, ctx->stream)) return 1;
     const int groups = (n_rays + RAYS_PER_GROUP - 1) / RAYS_PER_GROUP;
     hipLaunchKernelGGL(clip_rays_kernel, dim3(groups), dim3(256), 0, ctx->stream, mesh->verts, mesh->tris, mesh->n_tris,
@@ -439,7 +439,8 @@ extern "C" int mvlm_project_to_surface(mvlm_ctx* ctx, const mvlm_mesh* mesh, con
                                        double* out_dev) {
     MVLM_ENTER(ctx);
     MVLM_REQUIRE(ctx, mesh && pts_dev && out_dev && n_points > 0, "project_to_surface: bad arguments");
-    MVLM_REQUIRE(ctx, mesh->n_tris > 0, "project_to_surface: empty mesh");
+    MVLM_REQUIRE(ctx, mesh->n_verts > 0 && mesh->n_tris >= 0, "project_to_surface: empty mesh");
+    if (mesh->n_tris == 0) return mvlm_points_nearest(ctx, mesh, pts_dev, n_points, out_dev);  // a point mesh: surface_points.hip
     int n_chunks = 0;
     const double* part_d = nullptr;
     const int* part_t = nullptr;

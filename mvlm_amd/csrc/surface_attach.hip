@@ -111,7 +111,7 @@ extern "C" int mvlm_surface_attach(mvlm_ctx* ctx, const mvlm_mesh* mesh, const d
     MVLM_ENTER(ctx);
     MVLM_REQUIRE(ctx, mesh && pts_dev && snapped_dev && tri_dev && bary_dev && uv_dev && n_points > 0,
                  "surface_attach: bad arguments");
-    MVLM_REQUIRE(ctx, mesh->n_tris > 0, "surface_attach: empty mesh");
+    MVLM_REQUIRE(ctx, mesh->n_tris > 0, "surface_attach: the surface attachment of a point cloud is not supported (the mesh has no triangles)");
     int n_chunks = 0;
     const double* part_d = nullptr;
     const int* part_t = nullptr;

@@ -93,7 +93,7 @@ class Pipeline(abc.ABC):
                  verbose: bool = True, render_multisamples: int = 0, landmark_report: bool = False,
                  visualize_img: bool = False, visualize_size: int = 1024, visualize_name: str | None = None,
                  visualize_rays_img: bool = False, visualize_rays_poses=((0, 0, 0), (0, 60, 0), (0, -60, 0)),
-                 view_png_encoder: str = "host"):
+                 view_png_encoder: str = "host", point_radius: float | None = None):
         self.render_image_stack = render_image_stack
         self.render_image_folder = render_image_folder
         self.n_views = n_views
@@ -158,8 +158,9 @@ class Pipeline(abc.ABC):
             if torch.cuda.is_available():
                 torch.cuda.set_device(device)
         # render_multisamples: samples per pixel of the renderer (HipRenderer3D.multisamples: 0 or 4)
+        # point_radius: splat radius (model units) of scans without faces - point clouds -, None = automatic (HipRenderer3D)
         self.renderer_3d = HipRenderer3D(image_size=(256, 256), offscreen=offscreen, n_views=n_views, device=device,
-                                         verbose=verbose, multisamples=render_multisamples)
+                                         verbose=verbose, multisamples=render_multisamples, point_radius=point_radius)
         self.estimator_3d = HipEstimator3D(device=device, verbose=verbose)
         self.predictor_2d = None  # will be assigned externally
 
@@ -190,6 +191,24 @@ class Pipeline(abc.ABC):
         if self.renderer_3d.shading == "geometry":
             return False  # planes 0..2 carry the build-defined geometry shading
         return any(int(c) < 3 for c in sel)
+
+    def _check_cloud(self, mesh) -> None:
+        """A scan without faces - a point cloud - is rendered as splats and snapped to its nearest point; what a cloud does
+        not have is said here, before the GPU section, instead of by the call that would meet it."""
+        if mesh is None or getattr(mesh, "n_tris", 1) != 0:
+            return
+        name = getattr(mesh, "path", None) or "the mesh"
+        if self.landmark_report:
+            raise ValueError(f"{name} is a point cloud: landmark_report is not supported (the surface attachment needs triangles)")
+        if self.visualize_img:
+            raise ValueError(f"{name} is a point cloud: visualize_img is not supported (the landmark view draws triangles)")
+        if self.visualize_rays_img:
+            raise ValueError(f"{name} is a point cloud: visualize_rays_img is not supported (the ray view draws triangles)")
+        r3 = self.renderer_3d
+        if getattr(r3, "multisamples", 0):
+            raise ValueError(f"{name} is a point cloud: multisampled rendering (render_multisamples=4) is not supported")
+        if getattr(r3, "shading", "texture") == "geometry":
+            raise ValueError(f"{name} is a point cloud: a geometry image mode is not supported (geometry shading needs normals)")
 
     def _to_original(self, mesh, landmarks):
         """Landmarks found on a pre-aligned mesh -> the file's own coordinates (utils3d.py:505-527)."""
@@ -266,8 +285,8 @@ class Pipeline(abc.ABC):
 
             t0 = time.perf_counter()
             mesh = self.renderer_3d.load_mesh(self.renderer_3d._check_file(file_name), load_texture=self._texture_needed())
-            if mesh.n_tris > 0:
-                upload_mesh(self.renderer_3d.ctx, mesh)  # (thread-safe beside a launching thread: include/mvlm_hip.h)
+            self._check_cloud(mesh)
+            upload_mesh(self.renderer_3d.ctx, mesh)  # (thread-safe beside a launching thread: include/mvlm_hip.h)
             load_seconds = time.perf_counter() - t0
         with self._lock:
             self._rays = None
@@ -379,6 +398,7 @@ class Pipeline(abc.ABC):
         import torch
 
         r3, p2, e3 = self.renderer_3d, self.predictor_2d, self.estimator_3d
+        self._check_cloud(mesh)
         n_total = int(transform_stack.shape[0])
         sharded = self.shard_views and parallel.is_distributed()
         rank, world = parallel.rank_world() if sharded else (0, 1)
@@ -616,7 +636,8 @@ class Pipeline(abc.ABC):
         from ..utils.prealign import aligned
 
         meshes = [aligned(m, self.pre_align) for m in meshes]
-        if not self._groupable(k):
+        # (a point cloud among them: the scans go one by one - grouping clouds is not built)
+        if not self._groupable(k) or any(m.n_tris == 0 for m in meshes):
             out = []
             for m in meshes:
                 landmarks, err = self.predict_mesh_device(m, pose_fn())
@@ -715,10 +736,10 @@ class Pipeline(abc.ABC):
             if not f.exists():
                 return None
             mesh = self.renderer_3d.load_mesh(self.renderer_3d._check_file(f), load_texture=load_texture)  # pre-aligned here, uploaded once
-            if mesh.n_tris > 0:
-                # device copy from the reader thread too: pinned staging + a copy stream of the library's own, so the
-                # transfer runs beside the current scan's kernels (mvlm_mesh_upload); the renderer waits for its event
-                upload_mesh(self.renderer_3d.ctx, mesh)
+            self._check_cloud(mesh)
+            # device copy from the reader thread too: pinned staging + a copy stream of the library's own, so the
+            # transfer runs beside the current scan's kernels (mvlm_mesh_upload); the renderer waits for its event
+            upload_mesh(self.renderer_3d.ctx, mesh)
             return mesh
 
         if readers is None:
@@ -827,6 +848,7 @@ class Pipeline(abc.ABC):
                 image_stack, transform_stack, pd = self.renderer_3d.multiview_render(file_name, load_texture=self._texture_needed())
             else:
                 image_stack, transform_stack, pd = self.renderer_3d.multiview_render(file_name)
+        self._check_cloud(pd)
         if self.render_image_stack:
             self.visualize_image_stack(image_stack, file_name)
         with tm.stage("prediction"):

@@ -283,7 +283,8 @@ class HipEstimator3D:
         handle = upload_mesh(self.ctx, mesh)
         self.ctx.check(self.ctx.lib.mvlm_surface_attach(
             self.ctx.handle, handle, C.c_void_p(pts.data_ptr()), n, C.c_void_p(views["snapped"].data_ptr()),
-            C.c_void_p(views["tri"].data_ptr()), C.c_void_p(views["bary"].data_ptr()), C.c_void_p(views["uv"].data_ptr())))
+            C.c_void_p(views["tri"].data_ptr()), C.c_void_p(views["bary"].data_ptr()), C.c_void_p(views["uv"].data_ptr())),
+            ValueError if mesh.n_tris == 0 else _lib.MvlmHipError)  # (a point cloud has no triangle to attach to: an argument error)
         return views
 
     def project_device(self, mesh: Mesh, landmarks_dev, out=None):
@@ -309,7 +310,7 @@ class HipEstimator3D:
             self.ctx.bind_current_stream(torch, dev)
             self.ctx.check(self.ctx.lib.mvlm_clip_rays_to_mesh(
                 self.ctx.handle, handle, C.c_void_p(s.data_ptr()), C.c_void_p(e.data_ptr()), n, C.c_void_p(out.data_ptr()),
-                C.c_void_p(hit.data_ptr())))
+                C.c_void_p(hit.data_ptr())), ValueError if mesh.n_tris == 0 else _lib.MvlmHipError)  # (a point cloud: refused)
         return out, hit
 
     def clip_rays_to_mesh(self, pd, line_starts: np.ndarray, line_ends: np.ndarray):

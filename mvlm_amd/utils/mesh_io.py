@@ -40,6 +40,10 @@ class Mesh:
     # RGB planes of the unlit render when the mesh has no usable texture (no uvs or no texture image); a textured mesh
     # renders with its texture alone, geometry shading and the depth plane never see them.
     colors: np.ndarray | None = None
+    # A mesh without triangles is a POINT CLOUD: it is rendered as splats and landmarks snap to its nearest point (DESIGN.md
+    # 5.1, "Point clouds").  The splat radius in model units, 0.75 to 8 pixels of the 256-pixel window over 300 units
+    # (0.879 .. 9.375); None = the automatic one, from the spacing of the uploaded points.  Ignored on a mesh with triangles.
+    point_radius: float | None = None
 
     @property
     def n_verts(self) -> int:
@@ -184,7 +188,7 @@ def _read_obj_python(path: Path):
         raise ValueError(f"File {path} does not contain any points.")  # utils3d.py:20-21
     pos_a = np.asarray(pos, dtype=np.float32).reshape(-1, 3)
     if len(tris) == 0:
-        # a point cloud: keep the points, nothing to render or to snap to
+        # a point cloud: the points (and their colours) alone - rendered as splats, snapped to the nearest point
         return pos_a, np.zeros((0, 3), np.int32), None, None if col is None else np.asarray(col, np.uint8).reshape(-1, 3)
     v_idx = np.asarray(out_v, dtype=np.int64)
     if v_idx.min() < 0 or v_idx.max() >= len(pos):

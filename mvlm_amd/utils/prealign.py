@@ -48,7 +48,8 @@ def apply_prealign(mesh: Mesh, cfg: dict) -> tuple[Mesh, np.ndarray]:
     v = mesh.verts.astype(np.float64) @ m[:3, :3].T + m[:3, 3]
     # (a texture that is still the JPEG file's bytes stays that way: the upload decodes it on the device)
     out = Mesh(v.astype(np.float32), mesh.tris, mesh.uvs, getattr(mesh, "_texture", None), mesh.path, to_original=m,
-               texture_jpeg=mesh.texture_jpeg, colors=mesh.colors)
+               texture_jpeg=mesh.texture_jpeg, colors=mesh.colors,
+               point_radius=mesh.point_radius)  # (a cloud's automatic radius is computed on these points, at upload)
     if hasattr(mesh, "_colors_wanted"):
         out._colors_wanted = mesh._colors_wanted
     out._texture_ahead = getattr(mesh, "_texture_ahead", None)  # (a texture decoded ahead moves to the copy that is uploaded)
@@ -71,6 +72,8 @@ def write_pre_aligned(mesh: Mesh, path) -> None:
         f.write("# vtk DataFile Version 3.0\npre-aligned mesh\nASCII\nDATASET POLYDATA\n")
         f.write(f"POINTS {mesh.n_verts} float\n")
         np.savetxt(f, mesh.verts, fmt="%.9g")
+        if mesh.n_tris == 0:  # a point cloud: the points alone
+            return
         f.write(f"POLYGONS {mesh.n_tris} {4 * mesh.n_tris}\n")
         np.savetxt(f, np.concatenate([np.full((mesh.n_tris, 1), 3, np.int64), mesh.tris.astype(np.int64)], axis=1), fmt="%d")
 

@@ -78,16 +78,22 @@ def upload_mesh(ctx: "_lib.Context", mesh: Mesh) -> C.c_void_p:
     key = id(ctx)
     ent = mesh._device.get(key)
     if ent is not None:
+        if mesh.n_tris == 0 and ent[3] != mesh.point_radius:  # the cloud's radius was changed after the upload
+            _set_point_radius(ctx, ent[0], mesh)
+            mesh._device[key] = ent[:3] + (mesh.point_radius,)
         return ent[0]
-    if mesh.n_tris == 0:
-        raise ValueError("mesh has no triangles to render")
+    cloud = mesh.n_tris == 0  # a point cloud: the points (and their colours) alone; uvs and texture are ignored
     verts = np.ascontiguousarray(mesh.verts, dtype=np.float32)
     tris = np.ascontiguousarray(mesh.tris, dtype=np.int32)
-    uvs = None if mesh.uvs is None else np.ascontiguousarray(mesh.uvs, dtype=np.float32)
+    uvs = None if mesh.uvs is None or cloud else np.ascontiguousarray(mesh.uvs, dtype=np.float32)
     handle = C.c_void_p()
     uploaded = False
-    ahead = getattr(mesh, "_texture_ahead", None)
-    if ahead is not None and ahead.ctx is ctx and ahead.handle:
+    ahead = None if cloud else getattr(mesh, "_texture_ahead", None)
+    if cloud:
+        ctx.check(ctx.lib.mvlm_mesh_upload(ctx.handle, _lib.as_ptr(verts, C.c_float), None, mesh.n_verts, None, 0, None, 0, 0,
+                                           C.byref(handle)), ValueError)
+        uploaded = True
+    elif ahead is not None and ahead.ctx is ctx and ahead.handle:
         # the texture was decoded on the device while the geometry was parsed (HipRenderer3D.load_mesh): its buffer
         # becomes the mesh's
         consumed = C.c_int(0)
@@ -137,8 +143,22 @@ def upload_mesh(ctx: "_lib.Context", mesh: Mesh) -> C.c_void_p:
         if colors.shape != (mesh.n_verts, 3):
             raise ValueError(f"mesh colours must be uint8 [V,3] with V = {mesh.n_verts}, not {colors.shape}")
         ctx.check(ctx.lib.mvlm_mesh_upload_colors(ctx.handle, handle, _lib.as_ptr(colors, C.c_uint8), mesh.n_verts), ValueError)
-    mesh._device[key] = (handle, owner, send_colors)  # (the third entry: were colours uploaded with it?)
+    if cloud and mesh.point_radius is not None:
+        _set_point_radius(ctx, handle, mesh)
+    # (the third entry: were colours uploaded with it?  the fourth: the point radius the device copy has, None = automatic)
+    mesh._device[key] = (handle, owner, send_colors, mesh.point_radius if cloud else None)
     return handle
+
+
+def _set_point_radius(ctx: "_lib.Context", handle, mesh: Mesh) -> None:
+    """Give a cloud's device copy the radius its Mesh names (None: the automatic one of its points)."""
+    r = mesh.point_radius
+    if r is None:
+        verts = np.ascontiguousarray(mesh.verts, dtype=np.float32)
+        auto = C.c_double()
+        ctx.lib.mvlm_points_auto_radius(_lib.as_ptr(verts, C.c_float), mesh.n_verts, C.byref(auto))
+        r = auto.value
+    ctx.check(ctx.lib.mvlm_mesh_set_point_radius(ctx.handle, handle, C.c_double(float(r))), ValueError)
 
 
 class _DevicePointer:
@@ -184,7 +204,8 @@ class HipRenderer3D:
                  min_x_angle: int = -40, max_x_angle: int = 40, min_y_angle: int = -80, max_y_angle: int = 80,
                  min_z_angle: int = -20, max_z_angle: int = 20, min_scale: float = 1.4, max_scale: float = 1.9,
                  min_tx: int = -20, max_tx: int = 20, min_ty: int = -20, max_ty: int = 20, device: int = 0,
-                 verbose: bool = True, shading: str = "texture", subpixel_bits: int = 8, multisamples: int = 0):
+                 verbose: bool = True, shading: str = "texture", subpixel_bits: int = 8, multisamples: int = 0,
+                 point_radius: float | None = None):
         if tuple(image_size) != (256, 256):
             raise ValueError("the HIP renderer is built for 256x256 views (general_pipeline.py:57)")
         self.n_views = n_views
@@ -211,6 +232,9 @@ class HipRenderer3D:
         # samples per pixel (vtkRenderWindow.MultiSamples, which the reference leaves to VTK's default): 0 = one at the pixel
         # centre (the default contract), 4 = four, resolved like the OpenGL behind tests/golden/gl_raster_msaa4.npz
         self.multisamples = multisamples
+        # splat radius (model units) of the point clouds - scans without faces - that load_mesh reads: None = automatic, from
+        # the spacing of the points (Mesh.point_radius, which a Mesh handed to render_device carries itself)
+        self.point_radius = None if point_radius is None else float(point_radius)
         # "pre-align" block of a Deep-MVLM config (utils/prealign.py; utils3d.py:465-503): applied to every mesh this
         # renderer loads, the mesh handle it returns carries the matrix (Mesh.to_original)
         self.pre_align: dict | None = None
@@ -268,8 +292,9 @@ class HipRenderer3D:
             self.ctx.check(self.ctx.lib.mvlm_set_render_subpixel_bits(self.ctx.handle, mode[1]))
             self.ctx.check(self.ctx.lib.mvlm_set_render_multisamples(self.ctx.handle, mode[2]))
             self.ctx._render_mode = mode
+        # (a cloud's refusals - geometry shading, multisampling - are argument errors, said before anything is launched)
         self.ctx.check(self.ctx.lib.mvlm_render(self.ctx.handle, handle, _lib.as_ptr(rot, C.c_double), n,
-                                                C.c_void_p(out.data_ptr())))
+                                                C.c_void_p(out.data_ptr())), ValueError if mesh.n_tris == 0 else _lib.MvlmHipError)
         return out
 
     # ---- landmark view (utils/viewer.py's offscreen window) ----------------------------------
@@ -556,7 +581,7 @@ class HipRenderer3D:
             mesh = load_obj(file_name, load_texture=load_texture, decode=self.texture_decode)
             if not load_texture:
                 mesh._colors_wanted = False  # nobody reads an RGB plane: per-point colours are not uploaded either
-            return aligned(mesh, self.pre_align)
+            return aligned(self._with_point_radius(mesh), self.pre_align)
         # The texture is decoded on the device by a second thread (read the .jpg, unstuff, GPU decode: 1.8 ms at 2048^2)
         # while this one parses the geometry (2.7 ms): the scan is ready when the slower of the two is.
         import threading
@@ -593,7 +618,13 @@ class HipRenderer3D:
                 mesh._texture = box[3]
                 if box[3] is None:
                     mesh.texture_jpeg = None
-        return aligned(mesh, self.pre_align)
+        return aligned(self._with_point_radius(mesh), self.pre_align)
+
+    def _with_point_radius(self, mesh: Mesh) -> Mesh:
+        """A cloud read from a file gets the renderer's radius (None leaves the automatic one)."""
+        if mesh.n_tris == 0 and self.point_radius is not None:
+            mesh.point_radius = self.point_radius
+        return mesh
 
     def multiview_render_device(self, file_or_mesh, transformation_stack=None):
         """Same, but the image stack stays in HBM (used by the fused pipeline path)."""
