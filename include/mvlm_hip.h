@@ -250,6 +250,39 @@ int mvlm_render_ray_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot
  * (copies and fills, transform, classify, scan, bin fill, landmark projection), the ray projection, the tile kernel. */
 int mvlm_ray_view_stage_ms(mvlm_ctx* ctx, float* ms8);
 
+/* ---- view sheet (replaces Predictor2D.draw_image_with_landmarks, prediction/predictor2d.py:29-53, for all views at once) ---- */
+/* The layout of a sheet of n_views views ("View sheet"): cols columns (cols_in, or ceil(sqrt(n_views)) when
+ * cols_in is 0), rows = ceil(n_views / cols), view v in cell (v / cols, v % cols), a cell 256 * scale pixels a side, gap pixels
+ * between cells and around the sheet: width = cols * 256 * scale + (cols + 1) * gap, height likewise with rows.  Host only: no
+ * context, no GPU.  0, or non-zero with the reason in why (may be NULL): n_views < 1, cols_in < 0, scale outside 1..4, gap outside
+ * 0..16, or a width or height above 4096 (mvlm_png_encode's limit) - that message names the largest scale that fits. */
+int mvlm_view_sheet_layout(int n_views, int cols_in, int scale, int gap, int* cols, int* rows, int* width, int* height, char* why,
+                           int why_len);
+/* The sheet: every view of the stack in its cell, each sheet pixel (x, y) of a cell showing view pixel (y / scale, x / scale) - planes
+ * 0..2 as bytes (background 0) or plane 3 as a grey (background 1), a byte being (int)(p * 255 + 0.5) in float32 - gaps and cells
+ * beyond n_views grey (128, 128, 128), then per (view, landmark) the residual and the marker:
+ *   images_dev f32[n_views,256,256,4]  mvlm_render's stack, on the device
+ *   maxima_dev f32[n_lm,n_views,3]     (a, b, score) as mvlm_cnn_maxima leaves them, on the device; NULL: the views alone.  The
+ *                               marker stands at X = b, Y = a + 1 view pixels from the cell's left and top edge - where the
+ *                               prediction's ray pierces the image - and covers the sheet pixels whose centre (i + 0.5, j + 0.5)
+ *                               has dx^2 + dy^2 <= (marker_radius * scale)^2, dx = (i + 0.5) - scale * X; a non-finite a, b or
+ *                               score draws nothing
+ *   rot_host f64[n_views,9], landmarks_host f64[n_lm,3]  both or neither (NULL): the consensus landmarks in the space the mesh
+ *                               was uploaded in.  q = M p, X' = (q.x + 150) * 256 / 300, Y' = 256 - (q.y + 150) * 256 / 300; the
+ *                               segment marker -> (X', Y') is drawn red, max(0.5, scale / 2) sheet pixels to either side; a
+ *                               non-finite landmark draws no segment
+ *   lm_rgb_host u8[n_lm,3]      a colour per landmark, NULL = blue (0, 0, 255)
+ *   used_host u8[n_lm,n_views]  0: the marker is a ring, the outer max(1, scale) sheet pixels of its disc; NULL = all used
+ *   marker_radius               in view pixels, finite, 0.5..16
+ *   out_dev u8[height,width,4]  RGBA, alpha 255, top row first (mvlm_view_sheet_layout gives the extents)
+ * Order: background, residuals, markers; in landmark order within each, the later one wins.  Markers and residuals are clipped to
+ * their cell.  All of it in float64, in the operation order of csrc/view_sheet_math.h.  A bad layout, background, radius, n_lm outside
+ * 0..65536, a non-finite rotation or a NULL images_dev / out_dev set an error that starts with "view sheet:" and launch nothing.
+ * Only enqueues work on the launch stream. */
+int mvlm_render_view_sheet(mvlm_ctx* ctx, const float* images_dev, int n_views, const float* maxima_dev, int n_lm,
+                           const double* rot_host, const double* landmarks_host, const uint8_t* lm_rgb_host, const uint8_t* used_host,
+                           int background, int cols_in, int scale, int gap, double marker_radius, uint8_t* out_dev);
+
 /* ---- PNG on the device (the views' files without the picture crossing to the host) ---- */
 /* Bytes that hold any file mvlm_png_encode writes for a picture of height x width (each 1..4096): the filtered stream
  * height * (1 + 3 * width), 10 bytes per 32 768-byte segment of it (5 of a stored block's header, 5 of the flush), and 63 of

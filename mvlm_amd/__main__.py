@@ -64,6 +64,13 @@ def build_parser() -> argparse.ArgumentParser:
                              "scan: the mesh, every view's ray for every landmark clipped to its first hit with the surface, and the "
                              "landmarks, from the front and from 60 degrees left and right (with --report the rays are green where the "
                              "consensus used them, orange where it kept but did not use them, grey where the score filter dropped them)")
+    parser.add_argument("--visualize-sheet", action="store_true",
+                        help="write visualization/<stem>_<pipeline>_views.png under the working directory for every scan: all rendered "
+                             "views in one picture, a marker where the network put each landmark in each view and a red line from it "
+                             "to where the final landmark projects in that view (with --report a view the score filter dropped gets a "
+                             "ring, and the markers carry the RANSAC branch colours)")
+    parser.add_argument("--sheet-scale", type=int, default=1, choices=(1, 2, 3, 4),
+                        help="sheet pixels per view pixel of --visualize-sheet (the sheet may not exceed 4096 pixels a side)")
     parser.add_argument("--point-radius", type=float, default=None, metavar="MM",
                         help="splat radius, in model units, of scans that have points but no faces (point clouds): 0.88 to 9.375, "
                              "i.e. 0.75 to 8 pixels of a view; default: automatic, from the spacing of the points (DESIGN.md 5.1)")
@@ -117,6 +124,9 @@ def main(argv=None) -> int:
     if args.visualize_rays:
         extra["visualize_rays_img"] = True
         extra["visualize_size"] = args.visualize_size
+    if args.visualize_sheet:
+        extra["visualize_sheet"] = True
+        extra["sheet_scale"] = args.sheet_scale
     if args.point_radius is not None:
         extra["point_radius"] = args.point_radius
     if args.png_encoder != "host":

@@ -93,7 +93,8 @@ class Pipeline(abc.ABC):
                  verbose: bool = True, render_multisamples: int = 0, landmark_report: bool = False,
                  visualize_img: bool = False, visualize_size: int = 1024, visualize_name: str | None = None,
                  visualize_rays_img: bool = False, visualize_rays_poses=((0, 0, 0), (0, 60, 0), (0, -60, 0)),
-                 view_png_encoder: str = "host", point_radius: float | None = None):
+                 view_png_encoder: str = "host", point_radius: float | None = None, visualize_sheet: bool = False,
+                 sheet_scale: int = 1):
         self.render_image_stack = render_image_stack
         self.render_image_folder = render_image_folder
         self.n_views = n_views
@@ -139,6 +140,21 @@ class Pipeline(abc.ABC):
         # its own has no file name, draws nothing and leaves nothing behind
         self._ray_view = None
         self._keep_ray_view = False
+        # visualize_sheet: after every successful prediction the views the network saw are drawn side by side, with a marker where
+        # it put each landmark in each view and a red residual to where the final landmark projects there (the reference's
+        # Predictor2D.draw_image_with_landmarks for all views; HipRenderer3D.render_view_sheet), from this pass's own device
+        # buffers, into visualization/<stem>_<visualize_name>_views.png; sheet_scale 1..4 sheet pixels per view pixel.  With
+        # landmark_report a view the score filter dropped gets a ring and the markers carry the report's branch colours.  Off (the
+        # default): nothing of it is launched, allocated or copied.
+        self.visualize_sheet = bool(visualize_sheet)
+        self.sheet_scale = sheet_scale
+        self.last_sheet_path = None
+        if self.visualize_sheet:
+            if isinstance(sheet_scale, bool) or not isinstance(sheet_scale, (int, np.integer)) or not 1 <= sheet_scale <= 4:
+                raise ValueError(f"sheet_scale must be an integer in 1..4, not {sheet_scale!r}")
+            self.sheet_scale = int(sheet_scale)
+            if n_views is not None:  # (a sheet beyond 4096 pixels a side: said here, with the scale that fits)
+                HipRenderer3D.view_sheet_layout(int(n_views), None, self.sheet_scale)
         if (self.visualize_img or self.visualize_rays_img) and (self.visualize_size < 64 or self.visualize_size > 2048 or self.visualize_size % 16):
             raise ValueError(f"visualize_size must be a multiple of 16 in 64..2048, not {visualize_size}")
         name = type(self).__name__.lower()
@@ -399,6 +415,8 @@ class Pipeline(abc.ABC):
 
         r3, p2, e3 = self.renderer_3d, self.predictor_2d, self.estimator_3d
         self._check_cloud(mesh)
+        if self.visualize_sheet:
+            self._check_visualize()
         n_total = int(transform_stack.shape[0])
         sharded = self.shard_views and parallel.is_distributed()
         rank, world = parallel.rank_world() if sharded else (0, 1)
@@ -474,6 +492,7 @@ class Pipeline(abc.ABC):
             else:
                 maxima = torch.empty((p2.get_lm_count(), 0, 3), dtype=torch.float32,
                                      device=torch.device("cuda", self.device))
+            sheet_images = images if self.visualize_sheet else None  # (the stack stays where it is until the sheet is drawn)
             del images
             if sharded:
                 maxima = parallel.all_gather_views(maxima, n_total)
@@ -555,13 +574,24 @@ class Pipeline(abc.ABC):
         self.last_error = error
         if self.visualize_img and (not sharded or rank == 0):  # (sharded: every rank holds the result, one draws)
             self._draw_landmark_view(mesh, landmarks, self.last_report if layout is not None else None)  # (THIS pass's report)
+        if self.visualize_sheet and sheet_images is not None:
+            keep = None if kept_views is None else torch.from_numpy(np.asarray(kept_views)).to(sheet_images.device)
+            self._draw_view_sheet(mesh, sheet_images if keep is None else sheet_images.index_select(0, keep), maxima,
+                                  rot if kept_views is None else rot[kept_views], landmarks,
+                                  self.last_report if layout is not None else None)
         if self._keep_ray_view and (not sharded or rank == 0):  # drawn by _after_prediction, which knows the file and the selection
             self._ray_view = (mesh, starts, ends, landmarks, self.last_report if layout is not None else None)
         return landmarks, error
 
     def _check_visualize(self):
-        """``visualize_img`` and ``visualize_rays_img`` need the renderer that holds the mesh on the device: said before the
-        prediction, not after it."""
+        """``visualize_img`` and ``visualize_rays_img`` need the renderer that holds the mesh on the device, ``visualize_sheet`` the
+        one that draws it - and all the views in one process: said before the prediction, not after it."""
+        if self.visualize_sheet and not isinstance(self.renderer_3d, HipRenderer3D):
+            raise ValueError("visualize_sheet needs a HipRenderer3D in the renderer slot (it draws the sheet), "
+                             f"not {type(self.renderer_3d).__name__}")
+        if self.visualize_sheet and self.shard_views and parallel.is_distributed():
+            raise ValueError("visualize_sheet is not supported with shard_views in a distributed run: a rank holds only its slice "
+                             "of the views")
         if self.visualize_rays_img and not isinstance(self.renderer_3d, HipRenderer3D):
             raise ValueError("visualize_rays_img needs a HipRenderer3D in the renderer slot (it draws the mesh resident on the "
                              f"device), not {type(self.renderer_3d).__name__}")
@@ -598,6 +628,35 @@ class Pipeline(abc.ABC):
         self._say(f"[Pipeline] landmark view written to {self.last_view_path}")
         return self.last_view_path
 
+    def _draw_view_sheet(self, mesh, images, maxima, rot, landmarks, report=None):
+        """``visualize_sheet``: the views of THIS pass (a device stack [N,256,256,4] or the slot protocol's numpy one), their maxima
+        [NL,N,3], the views' rotations and the landmarks in the space the mesh was uploaded in, drawn by
+        ``HipRenderer3D.render_view_sheet``; the background is the planes the predictor read.  ``report``: the LandmarkReport of this
+        prediction (its survivor flags make rings, its branches colour the markers) or None."""
+        from ..utils.viewer import view_sheet_path, write_view_png
+
+        if landmarks is None:
+            return None
+        self._check_visualize()
+        with self._timer.stage("visualize_sheet"):
+            colours = used = None
+            if report is not None:
+                colours = report.branch_colours()
+                used = ((np.asarray(report.view_flags) & LandmarkReport.VIEW_KEPT) != 0).astype(np.uint8)
+            out_path = view_sheet_path(getattr(mesh, "path", None) or "mesh.obj", self.visualize_name)
+            if hasattr(maxima, "data_ptr"):
+                maxima = maxima.float()  # (a detector's device maxima may be float64; the network's are float32 already)
+            args = dict(maxima=maxima, rot=rot, landmarks=np.asarray(landmarks, dtype=np.float64).reshape(-1, 3), colors=colours,
+                        used=used, background="auto", scale=self.sheet_scale, chan_sel=getattr(self.predictor_2d, "chan_sel", None))
+            if self.view_png_encoder == "device":  # the picture stays on the device
+                image = self.renderer_3d.render_view_sheet_device(images, **args)
+                self.last_sheet_path = write_view_png(image, out_path, encoder="device", renderer=self.renderer_3d)
+                self.renderer_3d.check()
+            else:
+                self.last_sheet_path = write_view_png(self.renderer_3d.render_view_sheet(images, **args), out_path)
+        self._say(f"[Pipeline] view sheet written to {self.last_sheet_path}")
+        return self.last_sheet_path
+
     def _groupable(self, n_scans: int) -> bool:
         """Can ``n_scans`` scans share one network pass (predict_meshes_device)?"""
         p2, e3 = self.predictor_2d, self.estimator_3d
@@ -609,8 +668,8 @@ class Pipeline(abc.ABC):
             return False
         if self.landmark_report:
             return False  # one report per scan, made by the scan's own pass
-        if self.visualize_img or self.visualize_rays_img:
-            return False  # one picture per scan, drawn by the scan's own pass while its mesh is resident
+        if self.visualize_img or self.visualize_rays_img or self.visualize_sheet:
+            return False  # one picture per scan, drawn by the scan's own pass while its mesh (its views) are resident
         n = int(self.renderer_3d.n_views)
         return e3.expected_counts(p2.get_lm_count(), n) is not None and n_scans * n <= (p2.device_batch or 128)
 
@@ -889,6 +948,12 @@ class Pipeline(abc.ABC):
                                               view_indices=np.nonzero(kept)[0] if kept.dtype == bool else kept)
         if self.visualize_img:  # behind the report: the spheres carry THIS scan's branches
             self._draw_landmark_view(pd, drawn, self.last_report if arrays is not None else None)
+        if self.visualize_sheet:
+            from ..utils.render3d import view_rotations
+
+            self._draw_view_sheet(pd, np.asarray(image_stack, dtype=np.float32),
+                                  np.asarray(landmark_stack, dtype=np.float32), view_rotations(np.asarray(transform_stack)), drawn,
+                                  self.last_report if arrays is not None else None)
         if self._keep_ray_view:
             self._ray_view = (pd, np.asarray(lines_s), np.asarray(lines_e), drawn, self.last_report if arrays is not None else None)
         return landmarks

@@ -478,6 +478,123 @@ class HipRenderer3D:
         self.check()
         return (image, counts, ray_counts) if return_pixels else image
 
+    # ---- view sheet (prediction/predictor2d.py's draw_image_with_landmarks, all views in one picture) ----------
+    @staticmethod
+    def view_sheet_layout(n_views: int, cols=None, scale: int = 1, gap: int = 2) -> tuple:
+        """(cols, rows, width, height) of a sheet of ``n_views`` views (mvlm_view_sheet_layout; no GPU): ``cols`` columns, default
+        ceil(sqrt(n_views)), cells of 256 * scale pixels, ``gap`` pixels between them and around the sheet.  ValueError with the
+        library's reason for what does not fit (a side above 4096: the message names the largest scale that does)."""
+        for name, value in (("n_views", n_views), ("scale", scale), ("gap", gap)) + ((("cols", cols),) if cols is not None else ()):
+            if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+                raise ValueError(f"view sheet: {name} must be an integer, not {value!r}")
+        if cols is not None and cols < 1:
+            raise ValueError(f"view sheet: cols must be at least 1 ({cols} given)")
+        out = [C.c_int() for _ in range(4)]
+        why = C.create_string_buffer(512)
+        rc = _lib.load().mvlm_view_sheet_layout(int(n_views), 0 if cols is None else int(cols), int(scale), int(gap),
+                                                *[C.byref(o) for o in out], why, len(why))
+        if rc != 0:
+            raise ValueError(f"view sheet: {why.value.decode()}")
+        return tuple(int(o.value) for o in out)
+
+    def _sheet_tensor(self, x, what, dtype, dev, shape_ok, shape_words):
+        """A view-sheet input on the renderer's device: a tensor is taken where it lies (dtype, device and shape checked), anything
+        else is made a numpy array of that dtype and uploaded."""
+        import torch
+
+        if hasattr(x, "data_ptr"):
+            if x.dtype != dtype:
+                raise ValueError(f"view sheet: {what} must be {dtype}, not {x.dtype}")
+            if x.device != dev:
+                raise ValueError(f"view sheet: {what} lives on {x.device}, the renderer on {dev}")
+            t = x
+        else:
+            try:
+                a = np.ascontiguousarray(x, dtype={torch.float32: np.float32}[dtype])
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"view sheet: {what} is not a numeric array ({e})") from None
+            t = None if not shape_ok(a.shape) else torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
+        if t is None or not shape_ok(tuple(t.shape)):
+            raise ValueError(f"view sheet: {what} must be {shape_words}, not {tuple(np.shape(x) if t is None else t.shape)}")
+        return t.contiguous()
+
+    def render_view_sheet_device(self, images, maxima=None, rot=None, landmarks=None, colors=None, used=None, background="rgb",
+                                 cols=None, scale: int = 1, gap: int = 2, marker_radius: float = 2.0, chan_sel=None):
+        """``render_view_sheet`` with the picture left on the device: uint8 [H,W,4] RGBA, the layout ``encode_png`` takes.  Only
+        enqueues work."""
+        import torch
+
+        dev = torch.device("cuda", self.ctx.device)
+        images = self._sheet_tensor(images, "images", torch.float32, dev, lambda s: len(s) == 4 and s[0] >= 1 and tuple(s[1:]) == (256, 256, 4),
+                                    "float32 [N,256,256,4]")
+        n = int(images.shape[0])
+        _, _, width, height = self.view_sheet_layout(n, cols, scale, gap)
+        nl = 0
+        if maxima is not None:
+            maxima = self._sheet_tensor(maxima, "maxima", torch.float32, dev, lambda s: len(s) == 3 and s[1] == n and s[2] == 3,
+                                        f"float32 [NL,{n},3]")
+            nl = int(maxima.shape[0])
+            if nl > 65536:
+                raise ValueError(f"view sheet: at most 65536 landmarks, not {nl}")
+
+        def host(x, what, dtype, shape, words):
+            if x is None:
+                return None
+            if hasattr(x, "data_ptr"):
+                x = x.detach().cpu().numpy()
+            try:
+                a = np.ascontiguousarray(x, dtype=dtype)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"view sheet: {what} is not a numeric array ({e})") from None
+            if a.size != int(np.prod(shape)) or a.ndim < 1 or (a.ndim > 1 and a.shape[0] != shape[0]):
+                raise ValueError(f"view sheet: {what} must be {words}, not {a.shape}")
+            return np.ascontiguousarray(a.reshape(shape))
+
+        rot = host(rot, "rot", np.float64, (n, 9), f"float64 [{n},3,3]")
+        landmarks = host(landmarks, "landmarks", np.float64, (nl, 3), f"float64 [{nl},3]")
+        colors = host(colors, "colors", np.uint8, (nl, 3), f"uint8 [{nl},3]")
+        used = host(used, "used", np.uint8, (nl, n), f"uint8 [{nl},{n}]")
+        if rot is not None and not np.isfinite(rot).all():
+            raise ValueError("view sheet: non-finite rotation")
+        if background == "auto":  # the planes the predictor read (Pipeline passes its chan_sel); unknown: the RGB planes
+            background = "rgb" if chan_sel is None or any(int(c) < 3 for c in chan_sel) else "depth"
+        if background not in ("rgb", "depth"):
+            raise ValueError(f'view sheet: background must be "rgb", "depth" or "auto", not {background!r}')
+        try:
+            marker_radius = float(marker_radius)
+        except (TypeError, ValueError):
+            raise ValueError(f"view sheet: marker_radius must be a number, not {marker_radius!r}") from None
+        if not np.isfinite(marker_radius) or not 0.5 <= marker_radius <= 16.0:
+            raise ValueError(f"view sheet: marker_radius must be finite and in 0.5..16, not {marker_radius}")
+        out = torch.empty((height, width, 4), dtype=torch.uint8, device=dev)
+        residuals = nl > 0 and rot is not None and landmarks is not None
+        self.ctx.bind_current_stream(torch, dev)
+        self.ctx.check(self.ctx.lib.mvlm_render_view_sheet(
+            self.ctx.handle, C.c_void_p(images.data_ptr()), n, C.c_void_p(maxima.data_ptr()) if nl else None, nl,
+            _lib.as_ptr(rot, C.c_double) if residuals else None, _lib.as_ptr(landmarks, C.c_double) if residuals else None,
+            _lib.as_ptr(colors, C.c_uint8) if nl and colors is not None else None,
+            _lib.as_ptr(used, C.c_uint8) if nl and used is not None else None, 1 if background == "depth" else 0,
+            0 if cols is None else int(cols), int(scale), int(gap), C.c_double(marker_radius), C.c_void_p(out.data_ptr())), ValueError)
+        self._sheet_keepalive = (images, maxima)  # (read by the enqueued kernels)
+        return out
+
+    def render_view_sheet(self, images, maxima=None, rot=None, landmarks=None, colors=None, used=None, background="rgb", cols=None,
+                          scale: int = 1, gap: int = 2, marker_radius: float = 2.0, chan_sel=None):
+        """Every rendered view in one picture with the network's 2-D predictions on it - the reference's
+        ``Predictor2D.draw_image_with_landmarks`` for all views at once: uint8 [H,W,3].  ``images`` float32 [N,256,256,4]
+        (``render_device``'s stack), ``maxima`` float32 [NL,N,3] (``predict_device``'s) - tensors on the renderer's device, or numpy
+        arrays, which are uploaded.  A marker of ``marker_radius`` view pixels stands where each prediction's ray pierces its view
+        (a ring where ``used`` uint8 [NL,N] is 0), in ``colors`` uint8 [NL,3] (default blue); with ``rot`` float64 [N,3,3] (``view_rotations``)
+        and ``landmarks`` float64 [NL,3] (the space the mesh was uploaded in) a red residual runs from each marker to where its landmark
+        projects in that view.  ``background``: "rgb", "depth", or "auto" (depth when ``chan_sel`` names no plane below 3).  Views sit
+        in ``cols`` columns (default ceil(sqrt(N))), ``scale`` 1..4 sheet pixels per view pixel, ``gap`` 0..16 grey pixels between
+        them ("View sheet")."""
+        out = self.render_view_sheet_device(images, maxima, rot, landmarks, colors, used, background, cols, scale, gap, marker_radius,
+                                            chan_sel)
+        image = out.cpu().numpy()[..., :3].copy()
+        self.check()
+        return image
+
     # ---- PNG on the device -------------------------------------------------------------------
     @staticmethod
     def png_bound(height: int, width: int) -> int:

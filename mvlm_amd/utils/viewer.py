@@ -12,13 +12,19 @@ from pathlib import Path
 
 import numpy as np
 
-__all__ = ["LandmarkViewer", "RayVisualizer", "RayVisualizerConfig", "view_path", "write_view_png"]
+__all__ = ["LandmarkViewer", "RayVisualizer", "RayVisualizerConfig", "view_path", "view_sheet_path", "write_view_png"]
 
 
 def view_path(filename, pname: str | None = None) -> Path:
     """``visualization/<stem>[_<pname>].png`` relative to the working directory (viewer.py:89-92)."""
     suffix = f"_{pname}" if pname else ""
     return Path("visualization") / f"{Path(filename).stem}{suffix}.png"
+
+
+def view_sheet_path(filename, pname: str | None = None) -> Path:
+    """``visualization/<stem>[_<pname>]_views.png`` relative to the working directory: the view sheet beside the landmark view."""
+    suffix = f"_{pname}" if pname else ""
+    return Path("visualization") / f"{Path(filename).stem}{suffix}_views.png"
 
 
 PNG_ENCODERS = ("host", "device")
