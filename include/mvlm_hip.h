@@ -367,6 +367,18 @@ int mvlm_pack_winograd_weights(const float* w9_host, int cin_pad, int cout_pad, 
  * ky, float64 arithmetic, one rounding). */
 int mvlm_cnn_set_winograd4(mvlm_ctx* ctx, int mode);
 int mvlm_pack_winograd4_weights(const float* w9_host, int cin_pad, int cout_pad, float* w18_host);
+/* The workgroup shape of that tile's launches.  A launch of code 2048 whose padded output channels are a multiple of 64 runs on
+ * the wide shape - 64 output channels x 8 rows x 32 pixels, one staged input tile for two 32-channel halves - and every other
+ * one on the 32 x 16 shape; the variant code, the FLOPs of a profile record and every output bit are the same either way.
+ *   mvlm_cnn_set_winograd4_wide: 1 (default) as above, 0 the 32 x 16 shape on every launch; other values are refused.  A new
+ *     context takes MVLM_WINOGRAD4_WIDE (0 | 1) from the environment.  The few (shape, kind) keys that measured slower on the wide
+ *     shape inside the network (csrc/conv_wino4_wide_hold.h) stay on the 32 x 16 shape under either setting.
+ *   mvlm_conv_wino4_wide_serves: 1 where a launch of this shape on code 2048 takes the wide shape while the switch is on.
+ *   mvlm_conv_wino4_wide_launches: *count = launches issued on the wide shape by this context so far (host counter; a graph
+ *     replay issues none); reset != 0 sets it to zero afterwards. */
+int mvlm_cnn_set_winograd4_wide(mvlm_ctx* ctx, int on);
+int mvlm_conv_wino4_wide_serves(int ksize, int cin_pad, int cout_pad, int size);
+int mvlm_conv_wino4_wide_launches(mvlm_ctx* ctx, int64_t* count, int reset);
 int mvlm_cnn_execution_stats(mvlm_ctx* ctx, int64_t* eager_runs, int64_t* graph_captures, int64_t* graph_replays,
                              int64_t* graph_failures);
 /* OPT-IN reduced-cost arithmetic ("fast" precision, mvlm_amd/csrc/conv_fast.hip): the big 3x3 layers (input channels a

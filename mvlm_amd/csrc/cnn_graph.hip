@@ -1008,6 +1008,24 @@ extern "C" int mvlm_cnn_set_winograd4(mvlm_ctx* ctx, int mode) {
     return set_winograd_mode(ctx, &mvlm_ctx::conv_winograd4, mode, "cnn_set_winograd4: 0 never, 1 the measured table (default), 2 every layer the F(4,3) Winograd tile can serve");
 }
 
+// the workgroup shape of the F(4,3) tile's launches (captured graphs encode the kernels)
+extern "C" int mvlm_cnn_set_winograd4_wide(mvlm_ctx* ctx, int on) {
+    MVLM_ENTER(ctx);
+    MVLM_REQUIRE(ctx, on == 0 || on == 1, "cnn_set_winograd4_wide: 0 the 32 x 16 shape on every launch, 1 the wide shape where the output channels come in 64s (default)");
+    if (on != ctx->conv_winograd4_wide) ctx->cnn.drop_graphs();
+    ctx->conv_winograd4_wide = on;
+    return 0;
+}
+
+// launches issued on the wide shape since the context was made or the count was last reset (a host counter: a launch that a
+// captured graph replays was counted once, at its capture)
+extern "C" int mvlm_conv_wino4_wide_launches(mvlm_ctx* ctx, int64_t* count, int reset) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (count) *count = ctx->conv_wino4_wide_launches;
+    if (reset) ctx->conv_wino4_wide_launches = 0;
+    return 0;
+}
+
 extern "C" int mvlm_cnn_execution_stats(mvlm_ctx* ctx, int64_t* eager_runs, int64_t* graph_captures,
                                         int64_t* graph_replays, int64_t* graph_failures) {
     std::lock_guard<std::mutex> lk(ctx->mu);

@@ -292,10 +292,14 @@ struct mvlm_ctx {
     // the F(4,3) Winograd tile, where Winograd mode is not 0 and the launch carries ConvArgs::w_wino4: 0 never, 1 where the measured
     // table (conv_tuned_wino4.h) has an entry and Winograd mode is 1, 2 every layer the tile can serve (tests); MVLM_WINOGRAD4 (default 1)
     int conv_winograd4 = [] { const char* e = getenv("MVLM_WINOGRAD4"); return (e && e[0] >= '0' && e[0] <= '2' && !e[1]) ? e[0] - '0' : 1; }();
+    // the workgroup shape of the F(4,3) tile's launches (conv_inst_q0.hip: mvlm_conv_launch_wino4): 1 the wide shape, 64 output channels
+    // x 8 rows on one staged input tile, where cout_pad is a multiple of 64; 0 the 32 x 16 shape on every launch; MVLM_WINOGRAD4_WIDE (default 1)
+    int conv_winograd4_wide = [] { const char* e = getenv("MVLM_WINOGRAD4_WIDE"); return (e && e[0] >= '0' && e[0] <= '1' && !e[1]) ? e[0] - '0' : 1; }();
+    long long conv_wino4_wide_launches = 0;  // launches issued on the wide shape (mvlm_conv_wino4_wide_launches)
     std::vector<ConvOverride> conv_overrides;  // tools/tune_in_network.py: kernel variant per (shape, kind), before any table
     // Conv kernels whose launch attributes are set on this ctx's device.  The 64 bits: a base variant's bit is its id (all below
-    // MVLM_CONV_FAST_ATTR_BIT0, none MVLM_CONV_WINO4_ATTR_BIT: conv_mfma.hip asserts it), the F(4,3) tile has bit 41, the fast
-    // kernels (conv_fast.hip) the bits from 54 on.
+    // MVLM_CONV_FAST_ATTR_BIT0, none MVLM_CONV_WINO4_ATTR_BIT or MVLM_CONV_WINO4_WIDE_ATTR_BIT: conv_mfma.hip asserts it), the F(4,3)
+    // tile has bit 41 and its wide shape bit 42, the fast kernels (conv_fast.hip) the bits from 54 on.
     unsigned long long conv_attr_mask = 0;
     // a depth-key plane's buffer and capacity when it was last left all-EMPTY ({nullptr, 0}: not known clean); keyed on both,
     // so a buffer that get_scratch replaced by one of the same size is filled again
@@ -438,7 +442,11 @@ int mvlm_launch_conv_fast(mvlm_ctx* ctx, const ConvArgs& a, const unsigned short
 // the F(4,3) Winograd tile (conv3x3q_c32_t16x32): a code beyond the base ids and their K-part forms (0..1023) and below the pair
 // flag - a row of the variant table like the others (conv_mfma.hip: decode_variant reads the code), and a bit of conv_attr_mask
 constexpr int MVLM_CONV_VARIANT_WINO4 = 2048;
-constexpr int MVLM_CONV_WINO4_ATTR_BIT = 41, MVLM_CONV_FAST_ATTR_BIT0 = 54;
+constexpr int MVLM_CONV_WINO4_ATTR_BIT = 41, MVLM_CONV_WINO4_WIDE_ATTR_BIT = 42, MVLM_CONV_FAST_ATTR_BIT0 = 54;
+// The wide shape of that tile (conv_inst_q1.hip: 64 output channels x 8 rows x 32 pixels on one staged input tile) is no variant of
+// its own: code 2048's launcher takes it where the context's switch is on and the layer's output channels come in 64s.  Everything
+// else about the layer is what the 32 x 16 shape asks, so this is asked of launches already routed to code 2048.
+inline bool mvlm_conv_wino4_wide_shape_ok(int cout_pad, int H) { return cout_pad > 0 && cout_pad % 64 == 0 && H % 16 == 0; }
 constexpr int MVLM_CONV_VARIANT_FAST = 62;    // id reported for launches of the bf16x3 kernel
 constexpr int MVLM_CONV_VARIANT_FAST16 = 61;  // ... of the f16x2 kernel
 

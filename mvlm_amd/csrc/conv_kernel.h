@@ -72,6 +72,11 @@ struct Cfg {
     static constexpr bool HAS_AMAX = NIMG == 1 && TW == 32 && TRI == 8 && KS != 1 && (COUT_T == 80 || COUT_T == 96 || (COUT_T == 84 && KS == 2));
     static constexpr int NT = SPLITK ? PIX_T / 32 : PIX_T / 4 / 32;  // split-K: every wave multiplies all (one or two) 32-pixel columns
     static constexpr int NT16 = TAIL16 ? 2 * NT : 1;  // 16-pixel column groups of a wave
+    // The epilogue's geometry, apart from the staging geometry above: a wave finishes EMT 32-row cout tiles x ENT 32-pixel columns,
+    // EPIX consecutive pixels of the tile, out of ECOUT channels.  They differ on the wide F(4,3) shape only (WINO4 with 64 output
+    // channels: wave w = cout half w >> 1, row quad w & 1), whose wave holds what the narrow shape's does - one quad of 32 channels.
+    static constexpr bool WIDE4 = WINO4 && COUT_T == 64;
+    static constexpr int EMT = WIDE4 ? 1 : MT, ENT = WIDE4 ? 4 : NT, EPIX = WIDE4 ? 128 : PIX_T / 4, ECOUT = WIDE4 ? 32 : COUT_T;
     static constexpr int KSTEPS = (WINO || WINO4) ? 3 * CK / 2 : TAPS * CKW / 2;  // WINO: (kx, channel pair), four GEMMs per step (WINO4: six)
     static constexpr int WP = PIX_T / 4 / 64;              // WINO: row pairs of a wave
     static constexpr int WJOBS = CK * (WINO4 ? TRI / 4 : TRI / 2) * PW;  // WINO: staging jobs of a chunk = (channel, row pair, x); WINO4: (channel, row quad, x)
@@ -105,8 +110,8 @@ struct Cfg {
     static_assert(CK % 2 == 0, "the f32 MFMA consumes two k values per step");
     static_assert(!WINO || (!SPLITK && TW == 32 && NIMG == 1 && PIX_T % 256 == 0 && COUT_T % 32 == 0),
                   "Winograd tiles: 32-pixel rows, one image, whole row pairs per wave, no strips");
-    static_assert(!WINO4 || (!SPLITK && TW == 32 && NIMG == 1 && PIX_T == 512 && COUT_T == 32),
-                  "F(4,3) Winograd tile: 32-pixel rows, one image, one row quad per wave, one 32-row cout tile");
+    static_assert(!WINO4 || (!SPLITK && TW == 32 && NIMG == 1 && COUT_T % 32 == 0 && TRI % 4 == 0 && (COUT_T / 32) * (TRI / 4) == 4),
+                  "F(4,3) Winograd tile: 32-pixel rows, one image, one row quad and one 32-row cout tile per wave: 32 x 16 rows or 64 x 8");
     static_assert(LDS_BYTES <= 160 * 1024, "two stages must fit the CU's 160 KiB LDS");
 };
 
@@ -658,6 +663,8 @@ __device__ __forceinline__ void wino_main(const ConvArgs& a, float* smem, const 
 //   o0 = (m0 + s) + (m3 + m4)    o1 = d + (2 m3 - m4 / 2)    o2 = s + (4 m3 + m4 / 4)    o3 = (d + (8 m3 - m4 / 8)) + m5
 // A channel's plane of a stage is [q][x][4] (v0..v3, one 16-byte write and read) followed by [q][x][2] (v4, v5, 8 bytes):
 // neighbouring lanes read neighbouring 16- / 8-byte words.  The weight slice is [t * 3 + kx][cin][cout] as in global memory.
+// The wide shape (Cfg::WIDE4: 64 cout x 8 rows x 32 pixels) runs the same program with wave w = (cout half w >> 1, row quad w & 1): two
+// waves read the same staged quad against the two 32-channel halves of a 64-channel weight slice, so a staging job serves twice the MFMAs.
 // Staging job = one (channel, row quad, x) of a chunk: six loads, one BatchNorm pair, two LDS writes.  Masks, repeated jobs,
 // the neutral BatchNorm pair and the padded last chunk are handled as for the F(2,3) tiles (see WinoStage).
 template <class C>
@@ -841,11 +848,13 @@ __device__ __forceinline__ void wino4_mask_tail(const ConvArgs& a, int cb, int t
 // only one that can hold channels beyond cin) staged after wino4_mask_tail().
 template <class C>
 __device__ __forceinline__ void wino4_main(const ConvArgs& a, float* smem, const int tid, const int y0, const int x0, const int b0,
-                                           const int co0, const unsigned HWin, const int woff, f32x16 (&acc)[C::MT][C::NT], long long* t_loop) {
+                                           const int co0, const unsigned HWin, const int woff, f32x16 (&acc)[C::EMT][C::ENT], long long* t_loop) {
     static_assert(!C::WINO4 || 256 * C::X_ITERS - C::WJOBS <= C::WJOBS, "a lane without a job repeats an earlier job");
-    static_assert(!C::WINO4 || (C::TRI % 4 == 0 && C::NT == 4 && C::MT == 1), "one row quad per wave; rows 4q .. 4q + 3 of a tile share one mask");
+    static_assert(!C::WINO4 || (C::TRI % 4 == 0 && C::ENT == 4 && C::EMT == 1), "one row quad per wave; rows 4q .. 4q + 3 of a tile share one mask");
     static_assert(!C::WINO4 || (C::WT / 4 > 256 * (C::W_ITERS - 1) && C::WT / 4 >= 256), "a lane without a float4 repeats its previous one");
     const int lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
+    const int wq = C::WIDE4 ? (wave & 1) : wave;  // the wave's row quad ...
+    const int wh = C::WIDE4 ? (wave >> 1) : 0;    // ... and its 32-row half of the staged cout tile
     Wino4Stage<C> ws;
     constexpr int JPC = (C::TRI / 4) * C::PW;  // jobs per channel
     constexpr int Q4 = JPC * 4;                // floats of a channel's [q][x][4] part
@@ -881,14 +890,14 @@ __device__ __forceinline__ void wino4_main(const ConvArgs& a, float* smem, const
         ws.wlds[i] = f;
     }
     ws.floor = __int_as_float(__builtin_amdgcn_readfirstlane(a.pre_scale != nullptr ? 0 : int(0xFF800000u)));  // (a scalar)
-    ws.abase = woff;
+    ws.abase = woff + 32 * wh;
     wino_opaque(ws.abase);
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
         for (int cp = 0; cp < C::CK / 2; ++cp) {
-            ws.bbase4[s][cp] = s * C::STAGE + (2 * cp + half) * C::PLANE + (wave * C::PW + l31) * 4;
-            ws.bbase2[s][cp] = s * C::STAGE + (2 * cp + half) * C::PLANE + Q4 + (wave * C::PW + l31) * 2;
+            ws.bbase4[s][cp] = s * C::STAGE + (2 * cp + half) * C::PLANE + (wq * C::PW + l31) * 4;
+            ws.bbase2[s][cp] = s * C::STAGE + (2 * cp + half) * C::PLANE + Q4 + (wq * C::PW + l31) * 2;
             wino_opaque(ws.bbase4[s][cp]);
             wino_opaque(ws.bbase2[s][cp]);
         }
@@ -1071,11 +1080,11 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a_in, const int tiles_
     }
     const int woff = C::XT_PAD + half * C::COUT_T + l31 + (C::SPLITK ? wave * C::CKW * C::COUT_T : 0);
 
-    f32x16 acc[C::MT][C::NT];
+    f32x16 acc[C::EMT][C::ENT];
 #pragma unroll
-    for (int m = 0; m < C::MT; ++m)
+    for (int m = 0; m < C::EMT; ++m)
 #pragma unroll
-        for (int n = 0; n < C::NT; ++n) acc[m][n] = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int n = 0; n < C::ENT; ++n) acc[m][n] = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     // 16-row strip (TAIL16): lane l multiplies channel 32*MT + (l & 15) with k = l >> 4 of a tap's four
     // channels; result register i of column group j is channel 32*MT + 4*(l >> 4) + i at pixel 16*j + (l & 15)
     const int q16 = lane >> 4, i16 = lane & 15;
@@ -1194,10 +1203,10 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a_in, const int tiles_
 #if defined(MVLM_ABLATE_NO_EPILOGUE)  // timing experiment only: wrong results
     {
         float sacc = 0.f;
-        static_for<0, C::MT>([&](auto mc) {
+        static_for<0, C::EMT>([&](auto mc) {
             constexpr int m = decltype(mc)::value;
 #pragma unroll
-            for (int n = 0; n < C::NT; ++n)
+            for (int n = 0; n < C::ENT; ++n)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) sacc += acc[m][n][r];
         });
@@ -1444,19 +1453,23 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a_in, const int tiles_
     // Addresses are wave-uniform channel bases (scalar registers) + one 32-bit per-lane offset per
     // tensor and pixel column, so an element costs a load/add/store, not 64-bit vector arithmetic.
     const unsigned HW = unsigned(H) * unsigned(W);
-    bool lane_ok[C::NT];
-    int ppix[C::NT];
-    unsigned o_raw[C::NT], o_r1[C::NT], o_r2[C::NT], o_out[C::NT], o_skip[C::NT];
+    // the wave's place in the epilogue's geometry (Cfg::EMT ...): the wide F(4,3) shape's wave finishes row quad wave & 1 of the
+    // cout half wave >> 1, every other tile's wave its quarter of the pixels of all channels
+    const int ewave = C::WIDE4 ? (wave & 1) : wave;
+    const int eco0 = C::WIDE4 ? co0 + 32 * (wave >> 1) : co0;
+    bool lane_ok[C::ENT];
+    int ppix[C::ENT];
+    unsigned o_raw[C::ENT], o_r1[C::ENT], o_r2[C::ENT], o_out[C::ENT], o_skip[C::ENT];
     // fused 2x2 max-pool: the rows of a pair are two pixel registers of one lane (n, n+1), the columns two
     // neighbouring lanes, so it needs 32-pixel tile rows, one image per tile and an even row count per wave
-    constexpr bool CAN_POOL = !C::SPLITK && C::TW == 32 && C::NIMG == 1 && C::NT % 2 == 0;
+    constexpr bool CAN_POOL = !C::SPLITK && C::TW == 32 && C::NIMG == 1 && C::ENT % 2 == 0;
     constexpr bool POOLS = C::POOL_SMALL;  // narrow tiles: partner lanes l ^ TW (row) and l ^ 1 (column), see Cfg
-    unsigned o_pool[C::NT / 2 > 0 ? C::NT / 2 : 1];
-    unsigned o_pool_s[POOLS ? C::NT : 1];
+    unsigned o_pool[C::ENT / 2 > 0 ? C::ENT / 2 : 1];
+    unsigned o_pool_s[POOLS ? C::ENT : 1];
     const bool pool_writer = (l31 & (C::TW & 31)) == 0 && (l31 & 1) == 0;
 #pragma unroll
-    for (int n = 0; n < C::NT; ++n) {
-        const int p = (C::SPLITK ? 0 : wave * (C::PIX_T / 4)) + n * 32 + l31;
+    for (int n = 0; n < C::ENT; ++n) {
+        const int p = (C::SPLITK ? 0 : ewave * C::EPIX) + n * 32 + l31;
         const int rr = p / C::TW;
         const int b = b0 + rr / C::TRI;
         const int y = y0 + rr % C::TRI, x = x0 + p % C::TW;
@@ -1490,8 +1503,8 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a_in, const int tiles_
     // addresses) before group g is finished and stored, so a load's latency is paid once per
     // group of 4*NT elements instead of once per element, and the feature flags cost one
     // wave-uniform branch per group.
-    constexpr int GE = 4 * C::NT;       // elements per group
-    constexpr int NG = C::MT * 4;       // groups per wave
+    constexpr int GE = 4 * C::ENT;       // elements per group
+    constexpr int NG = C::EMT * 4;       // groups per wave
     auto epilogue = [&](auto full_c) __attribute__((always_inline)) {
         constexpr bool FULL = decltype(full_c)::value;  // every channel row of this tile exists
         // The tensors may share storage (a block adds into its own residual slice in place, the
@@ -1506,7 +1519,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a_in, const int tiles_
         float* __restrict__ const t_out = a.out;
         float* __restrict__ const t_pool = a.pool_out;
         float resv[2][GE];
-        auto group_base = [&](int g) { return co0 + (g >> 2) * 32 + 8 * (g & 3); };  // wave-uniform first channel
+        auto group_base = [&](int g) { return eco0 + (g >> 2) * 32 + 8 * (g & 3); };  // wave-uniform first channel
         auto load_group = [&](auto gc, float (&dst)[GE]) {
             constexpr int g = decltype(gc)::value;
             if (a.res1) {
@@ -1517,7 +1530,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a_in, const int tiles_
                     const int cs = (FULL || cs0 + j + 4 < a.cout) ? cs0 + j : 0;
                     const float* const p1 = t_res1 + size_t(cs) * HW;
 #pragma unroll
-                    for (int n = 0; n < C::NT; ++n) dst[j * C::NT + n] = p1[o_r1[n]];
+                    for (int n = 0; n < C::ENT; ++n) dst[j * C::ENT + n] = p1[o_r1[n]];
                 }
                 if (a.res2) {
 #pragma unroll
@@ -1525,7 +1538,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a_in, const int tiles_
                         const int cs = (FULL || cs0 + j + 4 < a.cout) ? cs0 + j : 0;
                         const float* const p2 = t_res2 + size_t(cs) * HW;
 #pragma unroll
-                        for (int n = 0; n < C::NT; ++n) dst[j * C::NT + n] += p2[o_r2[n]];
+                        for (int n = 0; n < C::ENT; ++n) dst[j * C::ENT + n] += p2[o_r2[n]];
                     }
                 }
             }
@@ -1554,11 +1567,11 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a_in, const int tiles_
             for (int j = 0; j < 4; ++j) {
                 okc[j] = FULL || cl + j < a.cout;
 #pragma unroll
-                for (int n = 0; n < C::NT; ++n) {
+                for (int n = 0; n < C::ENT; ++n) {
                     float v = acc[m][n][4 * rg + j];
                     if (a.bias) v += bias4[j];
                     if (a.post_scale) v = fmaxf(fmaf(v, ps4[j], pt4[j]), 0.f);
-                    vals[j * C::NT + n] = v;
+                    vals[j * C::ENT + n] = v;
                 }
             }
             if (a.out_raw) {
@@ -1566,8 +1579,8 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a_in, const int tiles_
                 for (int j = 0; j < 4; ++j) {
                     float* const p = t_raw + size_t(cs0 + j) * HW;
 #pragma unroll
-                    for (int n = 0; n < C::NT; ++n)
-                        if (okc[j] && lane_ok[n]) p[o_raw[n]] = vals[j * C::NT + n];
+                    for (int n = 0; n < C::ENT; ++n)
+                        if (okc[j] && lane_ok[n]) p[o_raw[n]] = vals[j * C::ENT + n];
                 }
             }
             if (a.res1) {
@@ -1580,8 +1593,8 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a_in, const int tiles_
                     for (int j = 0; j < 4; ++j) {
                         float* const p = t_pool + size_t(cs0 + j) * (HW / 4);
 #pragma unroll
-                        for (int q = 0; q < C::NT / 2; ++q) {
-                            const float v2 = fmaxf(vals[j * C::NT + 2 * q], vals[j * C::NT + 2 * q + 1]);
+                        for (int q = 0; q < C::ENT / 2; ++q) {
+                            const float v2 = fmaxf(vals[j * C::ENT + 2 * q], vals[j * C::ENT + 2 * q + 1]);
                             const int vi = __float_as_int(v2);
                             const float other = __int_as_float(__builtin_amdgcn_update_dpp(vi, vi, 0xB1, 0xf, 0xf, false));  // lane ^ 1
                             if (okc[j] && (l31 & 1) == 0) p[o_pool[q]] = fmaxf(v2, other);
@@ -1595,8 +1608,8 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a_in, const int tiles_
                     for (int j = 0; j < 4; ++j) {
                         float* const p = t_pool + size_t(cs0 + j) * (HW / 4);
 #pragma unroll
-                        for (int n = 0; n < C::NT; ++n) {
-                            const float m1 = fmaxf(vals[j * C::NT + n], __shfl_xor(vals[j * C::NT + n], C::TW));
+                        for (int n = 0; n < C::ENT; ++n) {
+                            const float m1 = fmaxf(vals[j * C::ENT + n], __shfl_xor(vals[j * C::ENT + n], C::TW));
                             const int mi = __float_as_int(m1);
                             const float m2 = fmaxf(m1, __int_as_float(__builtin_amdgcn_update_dpp(mi, mi, 0xB1, 0xf, 0xf, false)));  // lane ^ 1
                             if (okc[j] && lane_ok[n] && pool_writer) p[o_pool_s[n]] = m2;
@@ -1610,8 +1623,8 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a_in, const int tiles_
                     for (int j = 0; j < 4; ++j) {
                         float* const p = t_out + size_t(cs0 + j) * HW * (a.up_out ? 4 : 1);
 #pragma unroll
-                        for (int n = 0; n < C::NT; ++n)
-                            if (okc[j] && lane_ok[n]) p[o_out[n]] = vals[j * C::NT + n];
+                        for (int n = 0; n < C::ENT; ++n)
+                            if (okc[j] && lane_ok[n]) p[o_out[n]] = vals[j * C::ENT + n];
                     }
                 } else {
                     const unsigned W2 = 2u * unsigned(W);
@@ -1621,16 +1634,16 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a_in, const int tiles_
                         const int cs = okc[j] ? cs0 + j : 0;
                         const float* const ps = t_skip + size_t(cs) * HW * 4;
                         float* const p = t_out + size_t(cs0 + j) * HW * 4;
-                        float2 s0[C::NT], s1[C::NT];
+                        float2 s0[C::ENT], s1[C::ENT];
 #pragma unroll
-                        for (int n = 0; n < C::NT; ++n) {
+                        for (int n = 0; n < C::ENT; ++n) {
                             s0[n] = *reinterpret_cast<const float2*>(ps + o_skip[n]);
                             s1[n] = *reinterpret_cast<const float2*>(ps + o_skip[n] + W2);
                         }
 #pragma unroll
-                        for (int n = 0; n < C::NT; ++n) {
+                        for (int n = 0; n < C::ENT; ++n) {
                             if (okc[j] && lane_ok[n]) {
-                                const float v = vals[j * C::NT + n];
+                                const float v = vals[j * C::ENT + n];
                                 *reinterpret_cast<float2*>(p + o_out[n]) = make_float2(v + s0[n].x, v + s0[n].y);
                                 *reinterpret_cast<float2*>(p + o_out[n] + W2) = make_float2(v + s1[n].x, v + s1[n].y);
                             }
@@ -1665,22 +1678,22 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a_in, const int tiles_
         float resv[RING][GE];
         float resv2[RES2 ? RING : 1][GE];
         f32x4 bias_r[2], ps_r[2], pt_r[2];
-        auto chan0 = [&](int g) { return co0 + (g >> 2) * 32 + 8 * (g & 3); };  // wave-uniform first channel
+        auto chan0 = [&](int g) { return eco0 + (g >> 2) * 32 + 8 * (g & 3); };  // wave-uniform first channel
         auto ld_res = [&](auto gc) __attribute__((always_inline)) {
             constexpr int g = decltype(gc)::value;
             if constexpr (RES) {
                 static_for<0, 4>([&](auto jc) {
                     constexpr int j = decltype(jc)::value;
                     const float* const p1 = a.res1 + size_t(chan0(g) + j) * HW;
-                    static_for<0, C::NT>([&](auto nc) {
+                    static_for<0, C::ENT>([&](auto nc) {
                         constexpr int n = decltype(nc)::value;
-                        resv[g % RING][j * C::NT + n] = p1[o_r1[n]];
+                        resv[g % RING][j * C::ENT + n] = p1[o_r1[n]];
                     });
                     if constexpr (RES2) {
                         const float* const p2 = a.res2 + size_t(chan0(g) + j) * HW;
-                        static_for<0, C::NT>([&](auto nc) {
+                        static_for<0, C::ENT>([&](auto nc) {
                             constexpr int n = decltype(nc)::value;
-                            resv2[g % RING][j * C::NT + n] = p2[o_r2[n]];
+                            resv2[g % RING][j * C::ENT + n] = p2[o_r2[n]];
                         });
                     }
                 });
@@ -1705,8 +1718,8 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a_in, const int tiles_
             // the group's 2x2 blocks of the skip tensor, SK_CH channels at a time, requested before those channels' other
             // work (two where the registers allow it: pipelining a channel ahead, or a whole group at once, spilled on the
             // 168-register tiles)
-            constexpr int SK_CH = (C::MIN_BLOCKS_PER_CU == 2 && C::NT <= 2) ? 2 : 1;
-            float2 sk0[SCAT ? SK_CH * C::NT : 1], sk1[SCAT ? SK_CH * C::NT : 1];
+            constexpr int SK_CH = (C::MIN_BLOCKS_PER_CU == 2 && C::ENT <= 2) ? 2 : 1;
+            float2 sk0[SCAT ? SK_CH * C::ENT : 1], sk1[SCAT ? SK_CH * C::ENT : 1];
             auto ld_skip = [&](auto hc) __attribute__((always_inline)) {
                 constexpr int h = decltype(hc)::value;  // channels SK_CH h ... of the group
                 if constexpr (SCAT) {
@@ -1714,10 +1727,10 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a_in, const int tiles_
                     static_for<0, SK_CH>([&](auto jc) {
                         constexpr int jj = decltype(jc)::value, j = SK_CH * h + jj;
                         const float* const ps = a.skip + size_t(cs0 + j) * HW * 4;
-                        static_for<0, C::NT>([&](auto nc) {
+                        static_for<0, C::ENT>([&](auto nc) {
                             constexpr int n = decltype(nc)::value;
-                            sk0[jj * C::NT + n] = *reinterpret_cast<const float2*>(ps + o_skip[n]);
-                            sk1[jj * C::NT + n] = *reinterpret_cast<const float2*>(ps + o_skip[n] + W2);
+                            sk0[jj * C::ENT + n] = *reinterpret_cast<const float2*>(ps + o_skip[n]);
+                            sk1[jj * C::ENT + n] = *reinterpret_cast<const float2*>(ps + o_skip[n] + W2);
                         });
                     });
                 }
@@ -1727,21 +1740,21 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a_in, const int tiles_
             float vals[GE];
             static_for<0, 4>([&](auto jc) {
                 constexpr int j = decltype(jc)::value;
-                static_for<0, C::NT>([&](auto nc) {
+                static_for<0, C::ENT>([&](auto nc) {
                     constexpr int n = decltype(nc)::value;
                     float v = acc[m][n][4 * rg + j];
                     if constexpr (PAR >= 1) v += bias_r[g & 1][j];
                     if constexpr (PAR == 2) v = fmaxf(fmaf(v, ps_r[g & 1][j], pt_r[g & 1][j]), 0.f);
-                    vals[j * C::NT + n] = v;
+                    vals[j * C::ENT + n] = v;
                 });
             });
             if constexpr (RAW) {
                 static_for<0, 4>([&](auto jc) {
                     constexpr int j = decltype(jc)::value;
                     float* const p = a.out_raw + size_t(cs0 + j) * HW;
-                    static_for<0, C::NT>([&](auto nc) {
+                    static_for<0, C::ENT>([&](auto nc) {
                         constexpr int n = decltype(nc)::value;
-                        if (lane_ok[n]) p[o_raw[n]] = vals[j * C::NT + n];
+                        if (lane_ok[n]) p[o_raw[n]] = vals[j * C::ENT + n];
                     });
                 });
             }
@@ -1754,9 +1767,9 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a_in, const int tiles_
                 static_for<0, 4>([&](auto jc) {
                     constexpr int j = decltype(jc)::value;
                     float* const p = a.pool_out + size_t(cs0 + j) * (HW / 4);
-                    static_for<0, C::NT / 2>([&](auto qc) {
+                    static_for<0, C::ENT / 2>([&](auto qc) {
                         constexpr int q = decltype(qc)::value;
-                        const float v2 = fmaxf(vals[j * C::NT + 2 * q], vals[j * C::NT + 2 * q + 1]);
+                        const float v2 = fmaxf(vals[j * C::ENT + 2 * q], vals[j * C::ENT + 2 * q + 1]);
                         const int vi = __float_as_int(v2);
                         const float other = __int_as_float(__builtin_amdgcn_update_dpp(vi, vi, 0xB1, 0xf, 0xf, false));  // lane ^ 1
                         if ((l31 & 1) == 0) p[o_pool[q]] = fmaxf(v2, other);
@@ -1767,9 +1780,9 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a_in, const int tiles_
                 static_for<0, 4>([&](auto jc) {
                     constexpr int j = decltype(jc)::value;
                     float* const p = a.pool_out + size_t(cs0 + j) * (HW / 4);
-                    static_for<0, C::NT>([&](auto nc) {
+                    static_for<0, C::ENT>([&](auto nc) {
                         constexpr int n = decltype(nc)::value;
-                        const float m1 = fmaxf(vals[j * C::NT + n], __shfl_xor(vals[j * C::NT + n], C::TW));
+                        const float m1 = fmaxf(vals[j * C::ENT + n], __shfl_xor(vals[j * C::ENT + n], C::TW));
                         const int mi = __float_as_int(m1);
                         const float m2 = fmaxf(m1, __int_as_float(__builtin_amdgcn_update_dpp(mi, mi, 0xB1, 0xf, 0xf, false)));  // lane ^ 1
                         if (lane_ok[n] && pool_writer) p[o_pool_s[n]] = m2;
@@ -1783,11 +1796,11 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a_in, const int tiles_
                     if constexpr (SK_CH == 1) ld_skip(jc);
                     if constexpr (SK_CH == 2 && j == 2) ld_skip(std::integral_constant<int, 1>{});
                     float* const p = a.out + size_t(cs0 + j) * HW * 4;
-                    static_for<0, C::NT>([&](auto nc) {
+                    static_for<0, C::ENT>([&](auto nc) {
                         constexpr int n = decltype(nc)::value;
                         if (lane_ok[n]) {
-                            const float v = vals[j * C::NT + n];
-                            const float2 s0 = sk0[(j % SK_CH) * C::NT + n], s1 = sk1[(j % SK_CH) * C::NT + n];
+                            const float v = vals[j * C::ENT + n];
+                            const float2 s0 = sk0[(j % SK_CH) * C::ENT + n], s1 = sk1[(j % SK_CH) * C::ENT + n];
                             *reinterpret_cast<float2*>(p + o_out[n]) = make_float2(v + s0.x, v + s0.y);
                             *reinterpret_cast<float2*>(p + o_out[n] + W2) = make_float2(v + s1.x, v + s1.y);
                         }
@@ -1797,9 +1810,9 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a_in, const int tiles_
                 static_for<0, 4>([&](auto jc) {
                     constexpr int j = decltype(jc)::value;
                     float* const p = a.out + size_t(cs0 + j) * HW;
-                    static_for<0, C::NT>([&](auto nc) {
+                    static_for<0, C::ENT>([&](auto nc) {
                         constexpr int n = decltype(nc)::value;
-                        if (lane_ok[n]) p[o_out[n]] = vals[j * C::NT + n];
+                        if (lane_ok[n]) p[o_out[n]] = vals[j * C::ENT + n];
                     });
                 });
             }
@@ -1809,7 +1822,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a_in, const int tiles_
     using F_ = std::false_type;
     using P0 = std::integral_constant<int, 0>;
     using P2 = std::integral_constant<int, 2>;
-    const bool full_tile = co0 + C::COUT_T <= a.cout;
+    const bool full_tile = eco0 + C::ECOUT <= a.cout;
     const bool has_raw = a.out_raw != nullptr, has_res = a.res1 != nullptr, has_pool = a.pool_out != nullptr;
     const bool scat = a.up_out == 1 && a.skip != nullptr && a.out != nullptr;
     const bool fast_ok = full_tile && !C::SPLITK && (a.out || has_pool) && (!a.up_out || scat) && (!a.skip || scat) && (CAN_POOL || POOLS || !has_pool);

@@ -103,8 +103,8 @@ constexpr int MAX_VARIANT_ID = 64;  // base ids live in the low byte of a varian
 template <int ID, class V>
 constexpr ConvVariantInfo variant_info(const char* name, int (*launch)(mvlm_ctx*, const ConvArgs&),
                                        int (*launch_pair)(mvlm_ctx*, const ConvArgs&, const ConvArgs&)) {
-    static_assert(ID == MVLM_CONV_VARIANT_WINO4 || (ID >= 0 && ID < MVLM_CONV_FAST_ATTR_BIT0 && ID != MVLM_CONV_WINO4_ATTR_BIT),
-                  "base ids are below the fast kernels' attribute bits and leave the F(4,3) tile's free");
+    static_assert(ID == MVLM_CONV_VARIANT_WINO4 || (ID >= 0 && ID < MVLM_CONV_FAST_ATTR_BIT0 && ID != MVLM_CONV_WINO4_ATTR_BIT && ID != MVLM_CONV_WINO4_WIDE_ATTR_BIT),
+                  "base ids are below the fast kernels' attribute bits and leave the F(4,3) tile's two free");
     static_assert((ID == MVLM_CONV_VARIANT_WINO4) == V::WINO4, "the F(4,3) tile has the code of its own, and nothing else has");
     return {ID, name, V::KS, V::TW, V::TRI, V::NIMG, V::COUT_T, V::CK, V::PIX_T, V::NT, V::BN_MAXC,
             V::WINO ? MVLM_WINO_F23 : V::WINO4 ? MVLM_WINO_F43 : -1, V::SPLITK, V::TAIL16, V::PAIRABLE, V::CAN_POOL_ANY, V::HAS_IN2, launch, launch_pair};
@@ -482,6 +482,12 @@ extern "C" int mvlm_conv_variant_serves(int variant, int ksize, int cin_pad, int
     const bool bn_fits = t->form < 0 || cin_pad <= t->BN_MAXC;                      // (as wino_candidate; the direct tiles check it at the launch)
     const bool parts_ok = parts == 1 || (t->SPLITK && t->PIX_T == 32 && cin_pad % (parts * t->CK) == 0);
     return residual_block_tile && bn_fits && parts_ok;
+}
+
+// Would a launch of this shape on the F(4,3) tile (code 2048) take the wide workgroup shape while the context's switch is on?
+// A pure query: what the tile serves at all, and output channels in 64s (common.h: mvlm_conv_wino4_wide_shape_ok).
+extern "C" int mvlm_conv_wino4_wide_serves(int ksize, int cin_pad, int cout_pad, int size) {
+    return mvlm_conv_variant_serves(MVLM_CONV_VARIANT_WINO4, ksize, cin_pad, cout_pad, size, 0) && mvlm_conv_wino4_wide_shape_ok(cout_pad, size);
 }
 
 // kernel variant for every launch of this (shape, kind) on this context, ahead of all tables; variant < 0 removes the

@@ -76,6 +76,12 @@
 // a row of the variant table like every variant below (conv_mfma.hip: VARIANTS, decode_variant).
 #define MVLM_CONV_WINO4_NAME "conv3x3q_c32_t16x32"
 #define MVLM_CONV_WINO4_CFG Cfg<32, 32, 16, 1, 34, 4>
+// The same tile's wide workgroup shape: 64 cout x 8 rows x 32 pixels, wave w = (cout half w >> 1, row quad w & 1).  A staged
+// input tile then serves 64 output channels instead of 32: half the staging jobs (loads, BatchNorm, transform, LDS writes) per
+// MFMA, the same six accumulators per wave, the same workgroup count per layer and every output bit the same.  No variant code
+// of its own: mvlm_conv_launch_wino4 takes it where cout_pad % 64 == 0 and mvlm_cnn_set_winograd4_wide is on.  Instantiated in
+// conv_inst_q1.hip, built into build/wino4w/ (occupancy table tests/golden/kernel_occupancy_wino4w.json).
+#define MVLM_CONV_WINO4_WIDE_CFG Cfg<64, 32, 8, 1, 34, 4>
 #define MVLM_CONV_VARIANTS(X) \
     MVLM_CONV_VARIANTS_G0(X) MVLM_CONV_VARIANTS_G1(X) MVLM_CONV_VARIANTS_G2(X) MVLM_CONV_VARIANTS_G3(X) MVLM_CONV_VARIANTS_G4(X) MVLM_CONV_VARIANTS_G5(X) MVLM_CONV_VARIANTS_G6(X) MVLM_CONV_VARIANTS_G7(X) MVLM_CONV_VARIANTS_G8(X) MVLM_CONV_VARIANTS_G9(X) MVLM_CONV_VARIANTS_G10(X) MVLM_CONV_VARIANTS_G11(X) MVLM_CONV_VARIANTS_G12(X) MVLM_CONV_VARIANTS_G13(X) MVLM_CONV_VARIANTS_G14(X) MVLM_CONV_VARIANTS_G15(X) MVLM_CONV_VARIANTS_W0(X)
 #define MVLM_CONV_N_GROUPS 16

@@ -2,15 +2,16 @@
 """Instruction mix of the steady-state K loop of every convolution kernel of the built library objects.
 
     tools/conv_loop_mix.py            print the table
-    tools/conv_loop_mix.py --write    rewrite tests/golden/conv_loop_mix_wino.json and conv_loop_mix_wino4.json (the Winograd kernels' rows)
-                                      from the build
+    tools/conv_loop_mix.py --write    rewrite tests/golden/conv_loop_mix_wino.json, conv_loop_mix_wino4.json and
+                                      conv_loop_mix_wino4w.json (the Winograd kernels' rows) from the build
 
 A convolution tile is compute-bound by construction: what it loses against the matrix peak is time its waves spend issuing
 anything but MFMAs inside the K loop (addresses, staging arithmetic, LDS traffic, waits, branches).  The ratio of those to the
 MFMAs can be read off the object file, before any GPU time is spent.  The steady-state loop of a kernel is the innermost
 backward branch whose body holds MFMAs and a barrier (the loop over K-chunks); where a kernel has several, the one with the most
 MFMAs.  Instructions are classed by the prefix of their mnemonic.  tests/test_winograd_loop_mix.py holds the Winograd kernel
-to the committed row, tests/test_winograd4_loop_mix.py the F(4,3) kernel (build/wino4/) to its own."""
+to the committed row, tests/test_winograd4_loop_mix.py the F(4,3) kernel (build/wino4/) to its own,
+tests/test_winograd4_wide_loop_mix.py that kernel's wide workgroup shape (build/wino4w/) to its own."""
 import json
 import re
 import subprocess
@@ -23,9 +24,10 @@ LLVM = Path("/opt/rocm/lib/llvm/bin")
 BUILD = REPO / "mvlm_amd" / "csrc" / "build"
 WINO_TABLE = REPO / "tests" / "golden" / "conv_loop_mix_wino.json"
 WINO4_TABLE = REPO / "tests" / "golden" / "conv_loop_mix_wino4.json"
+WINO4W_TABLE = REPO / "tests" / "golden" / "conv_loop_mix_wino4w.json"
 CLASSES = ("valu", "lds_read", "lds_write", "global_load", "scalar", "wait", "other")
 MFMAS_PER_CHUNK_WINO = 48  # a 4-channel group of the 64 x (8 x 32) Winograd tile: 6 k-steps x 2 cout tiles x 4 GEMMs
-MFMAS_PER_CHUNK_WINO4 = 36  # a 4-channel group of the 32 x (16 x 32) F(4,3) tile: 6 k-steps x 6 GEMMs
+MFMAS_PER_CHUNK_WINO4 = 36  # a 4-channel group of the 32 x (16 x 32) F(4,3) tile, and of its 64 x (8 x 32) shape: 6 k-steps x 6 GEMMs
 
 _INSN = re.compile(r"^\s*([a-z][a-z0-9_]+)\s.*//\s*([0-9A-Fa-f]+):")
 _SYM = re.compile(r"^([0-9a-f]+) <(\S+)>:")
@@ -125,14 +127,14 @@ def build_table(objdir: Path = BUILD) -> dict:
 
 if __name__ == "__main__":
     if "--write" in sys.argv:
-        for path, objdir in ((WINO_TABLE, BUILD / "wino"), (WINO4_TABLE, BUILD / "wino4")):
+        for path, objdir in ((WINO_TABLE, BUILD / "wino"), (WINO4_TABLE, BUILD / "wino4"), (WINO4W_TABLE, BUILD / "wino4w")):
             rows = build_table(objdir)
             path.write_text(json.dumps(rows, indent=1) + "\n")
             print(f"{len(rows)} kernels -> {path}")
     else:
         hdr = f"{'mfma':>5s} {'other':>6s} {'/mfma':>6s} {'barr':>5s} " + " ".join(f"{c:>11s}" for c in CLASSES)
         print(hdr + "  kernel")
-        for objdir in (BUILD, BUILD / "wino", BUILD / "wino4"):
+        for objdir in (BUILD, BUILD / "wino", BUILD / "wino4", BUILD / "wino4w"):
             for k, v in build_table(objdir).items():
                 print(f"{v['mfma']:5d} {v['non_mfma']:6d} {v['non_mfma_per_mfma']:6.2f} {v['barriers']:5d} " +
                       " ".join(f"{v[c]:11d}" for c in CLASSES) + f"  {k}")

@@ -30,16 +30,20 @@ CASES = [  # name, cin, cout, size, k, batch, pre-BN, residual, bias+post-BN  (M
     ("winograd     256->128 @128 (w64)", 256, 128, 128, 3, 64, True, True, False, 40),
     ("winograd     128-> 64 @128 (w64)", 128, 64, 128, 3, 64, True, True, False, 40),
     ("winograd      64-> 64 @ 64 (w64)", 64, 64, 64, 3, 64, True, True, False, 40),
-    # the F(4,3) Winograd tile (variant code 2048, conv3x3q_c32_t16x32), forced
-    ("winograd4    256->128 @128 (q32)", 256, 128, 128, 3, 64, True, True, False, 2048),
-    ("winograd4    128-> 64 @128 (q32)", 128, 64, 128, 3, 64, True, True, False, 2048),
-    ("winograd4     64-> 64 @ 64 (q32)", 64, 64, 64, 3, 64, True, True, False, 2048),
-    ("winograd4     64-> 32 @256 (q32)", 64, 32, 256, 3, 64, True, True, False, 2048),
+    # the F(4,3) Winograd tile (variant code 2048, conv3x3q_c32_t16x32), forced; the last field is mvlm_cnn_set_winograd4_wide:
+    # q32 the 32 x 16 workgroup shape, q64 the wide one (64 output channels x 8 rows; a 32-channel layer has the first only)
+    ("winograd4    256->128 @128 (q32)", 256, 128, 128, 3, 64, True, True, False, 2048, 0),
+    ("winograd4    128-> 64 @128 (q32)", 128, 64, 128, 3, 64, True, True, False, 2048, 0),
+    ("winograd4     64-> 64 @ 64 (q32)", 64, 64, 64, 3, 64, True, True, False, 2048, 0),
+    ("winograd4     64-> 32 @256 (q32)", 64, 32, 256, 3, 64, True, True, False, 2048, 0),
+    ("winograd4    256->128 @128 (q64)", 256, 128, 128, 3, 64, True, True, False, 2048, 1),
+    ("winograd4    128-> 64 @128 (q64)", 128, 64, 128, 3, 64, True, True, False, 2048, 1),
+    ("winograd4     64-> 64 @ 64 (q64)", 64, 64, 64, 3, 64, True, True, False, 2048, 1),
     ("direct        64-> 32 @256 (c32)", 64, 32, 256, 3, 64, True, True, False, 3),
 ]
 
 
-SMALL = [  # the latency-bound levels of a 12-view batch (MVLM_PHASE_CASES=small; MVLM_PHASE_CASES=winograd: the forced Winograd cases alone)
+SMALL = [  # the latency-bound levels of a 12-view batch (MVLM_PHASE_CASES=small; MVLM_PHASE_CASES=winograd: the forced Winograd cases alone, winograd4: the F(4,3) tile's)
     ("block conv1  256->128 @ 32 B12", 256, 128, 32, 3, 12, True, True, False),
     ("block conv2  128-> 64 @ 32 B12", 128, 64, 32, 3, 12, True, True, False),
     ("block conv1  256->128 @ 16 B12", 256, 128, 16, 3, 12, True, True, False),
@@ -67,6 +71,8 @@ def main():
     print(f"{'layer':40s} {'ms':>7s} {'TFLOP/s':>8s} | per workgroup, wave 0: prologue / K loop / epilogue (cycles, share)")
     if os.environ.get("MVLM_PHASE_CASES") == "winograd":
         CASES = [c for c in CASES if len(c) > 9]
+    if os.environ.get("MVLM_PHASE_CASES") == "winograd4":
+        CASES = [c for c in CASES if len(c) > 9 and c[9] == 2048]
     for name, cin, cout, size, k, batch, pre, res, post, *forced in CASES:
         batch = int(os.environ.get("MVLM_PHASE_BATCH", batch))
         x = torch.randn(batch, cin, size, size, device="cuda")
@@ -85,6 +91,8 @@ def main():
             e0.record()
             if forced:
                 ctx.check(ctx.lib.mvlm_conv_force_variant(ctx.handle, forced[0]))
+            if len(forced) > 1:
+                ctx.check(ctx.lib.mvlm_cnn_set_winograd4_wide(ctx.handle, forced[1]))
             try:
                 ctx.check(ctx.lib.mvlm_conv2d(ctx.handle, C.c_void_p(x.data_ptr()), batch, cin, size, size, f(w), cout, k, f(b),
                                               f(ps), f(pt), f(qs), f(qt), C.c_void_p(r.data_ptr()) if res else None, 0,
@@ -92,6 +100,8 @@ def main():
             finally:
                 if forced:
                     ctx.check(ctx.lib.mvlm_conv_force_variant(ctx.handle, -1))
+                if len(forced) > 1:
+                    ctx.check(ctx.lib.mvlm_cnn_set_winograd4_wide(ctx.handle, 1))
             e1.record()
             torch.cuda.synchronize()
             times.append(e0.elapsed_time(e1))

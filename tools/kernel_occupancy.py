@@ -4,7 +4,8 @@
     tools/kernel_occupancy.py            print the table
     tools/kernel_occupancy.py --write    rewrite tests/golden/kernel_occupancy.json (and kernel_occupancy_msaa.json,
                                          kernel_occupancy_vcolor.json, kernel_occupancy_wino.json,
-                                         kernel_occupancy_wino4.json, kernel_occupancy_report.json,
+                                         kernel_occupancy_wino4.json, kernel_occupancy_wino4w.json,
+                                         kernel_occupancy_report.json,
                                          kernel_occupancy_view.json, kernel_occupancy_rays.json,
                                          kernel_occupancy_png.json, kernel_occupancy_points.json,
                                          kernel_occupancy_sheet.json) from the build
@@ -18,7 +19,8 @@ rasteriser's kernels are built into an object directory of their own (build/msaa
 tests/golden/kernel_occupancy_msaa.json, held to the same rule by tests/test_msaa_occupancy.py; so are the tile kernels that
 shade with per-vertex colours (build/vcolor/, kernel_occupancy_vcolor.json, tests/test_vcolor_occupancy.py) and the Winograd convolution
 tiles (build/wino/, tests/golden/kernel_occupancy_wino.json, tests/test_winograd_occupancy.py), the F(4,3) Winograd tile
-(build/wino4/, tests/golden/kernel_occupancy_wino4.json, tests/test_winograd4_occupancy.py) and the two kernels of the opt-in
+(build/wino4/, tests/golden/kernel_occupancy_wino4.json, tests/test_winograd4_occupancy.py), its wide workgroup shape
+(build/wino4w/, tests/golden/kernel_occupancy_wino4w.json, tests/test_winograd4_wide_occupancy.py) and the two kernels of the opt-in
 landmark report (build/report/, tests/golden/kernel_occupancy_report.json, tests/test_report_occupancy.py) and the six kernels
 of the landmark view (build/view/, tests/golden/kernel_occupancy_view.json, tests/test_view_occupancy.py), whose table also
 records the bytes of scratch memory per work-item (0); likewise the two kernels of the ray view (build/rays/,
@@ -40,6 +42,7 @@ MSAA_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_msaa.json"
 VCOLOR_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_vcolor.json"
 WINO_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_wino.json"
 WINO4_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_wino4.json"
+WINO4W_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_wino4w.json"
 REPORT_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_report.json"
 VIEW_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_view.json"
 RAYS_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_rays.json"
@@ -91,7 +94,7 @@ def build_table(objdir: Path = BUILD) -> dict:
 
 if __name__ == "__main__":
     for table_path, objdir in ((TABLE, BUILD), (MSAA_TABLE, BUILD / "msaa"), (VCOLOR_TABLE, BUILD / "vcolor"),
-                                (WINO_TABLE, BUILD / "wino"), (WINO4_TABLE, BUILD / "wino4"), (REPORT_TABLE, BUILD / "report"),
+                                (WINO_TABLE, BUILD / "wino"), (WINO4_TABLE, BUILD / "wino4"), (WINO4W_TABLE, BUILD / "wino4w"), (REPORT_TABLE, BUILD / "report"),
                                 (VIEW_TABLE, BUILD / "view"), (RAYS_TABLE, BUILD / "rays"), (PNG_TABLE, BUILD / "png"),
                                 (POINTS_TABLE, BUILD / "points"), (SHEET_TABLE, BUILD / "sheet")):
         t = build_table(objdir)

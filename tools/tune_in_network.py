@@ -22,6 +22,15 @@ the key won at every tuned batch above it.
 --winograd4: the table of the F(4,3) Winograd tile (conv_tuned_wino4.h), the same way, but starting from what runs without that
 tile: the default Winograd mode (1, the table conv_tuned_wino.h) with the F(4,3) switch at 0.  A key is switched where the tile
 beats the F(2,3) tile, the pair launch or the direct tile that serves it otherwise.
+
+--winograd4-wide: no table, a comparison.  Per batch (default 96,12) the default pass is timed with the F(4,3) tile's workgroup
+shape switch (mvlm_cnn_set_winograd4_wide) at 0 and at 1, alternating, and every (shape, kind) whose launches on code 2048 the
+wide shape takes (mvlm_conv_wino4_wide_serves) is listed with its time per pass under either setting, then the sum of the
+convolution kernels of a pass.  A key that the wide shape makes slower by more than --min-gain is marked; --write-header lists
+the keys marked at the largest batch in conv_wino4_wide_hold.h, which the tile's launcher keeps on the 32 x 16 shape.  A key the
+header already holds runs on that shape under either setting here and cannot be marked again, so its row is carried over: to
+measure it afresh, take it out of the header and build first.  --f43-mode 2 (default) puts every key the tile serves on it, 1
+leaves the pass to the measured table (no launch of the tile below 96 views).
 """
 from __future__ import annotations
 
@@ -40,6 +49,7 @@ sys.path.insert(0, str(REPO))
 HEADER = REPO / "mvlm_amd" / "csrc" / "conv_tuned_net.h"
 WINO_HEADER = REPO / "mvlm_amd" / "csrc" / "conv_tuned_wino.h"
 WINO4_HEADER = REPO / "mvlm_amd" / "csrc" / "conv_tuned_wino4.h"
+WIDE_HOLD_HEADER = REPO / "mvlm_amd" / "csrc" / "conv_wino4_wide_hold.h"
 CAP = 1024
 
 
@@ -85,7 +95,7 @@ def key_time(runs, key):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--batches", default="1,2,3,4,5,6,7,8,9,10,11,12,13,14,15,16,20,24,32,48,64,96,128")
+    ap.add_argument("--batches", default=ap_default_batches())
     ap.add_argument("--nets", default="dtu3d:geometry+depth,bu3dfe:RGB+depth")
     ap.add_argument("--write-header", action="store_true")
     ap.add_argument("--merge", action="store_true", help="keep the entries of the existing header that this run does not re-measure")
@@ -95,6 +105,8 @@ def main():
     ap.add_argument("--max-size", type=int, default=256, help="only keys of feature maps up to this size (re-tuning the small levels)")
     ap.add_argument("--winograd", action="store_true", help="tune the Winograd tiles' table (conv_tuned_wino.h) instead")
     ap.add_argument("--winograd4", action="store_true", help="tune the F(4,3) Winograd tile's table (conv_tuned_wino4.h) instead")
+    ap.add_argument("--winograd4-wide", action="store_true", help="time every key the F(4,3) tile's wide workgroup shape serves with the switch at 0 and 1")
+    ap.add_argument("--f43-mode", type=int, default=2, help="--winograd4-wide: the F(4,3) mode of the compared passes (2 every served key, 1 the table)")
     ap.add_argument("--hold-min-batch", type=int, default=0,
                     help="--winograd4: write no row below this many views, whatever won there (the header says so and why)")
     ap.add_argument("--header-from", default="", help="--winograd / --winograd4: write the header from this earlier --out JSON, without tuning")
@@ -104,6 +116,8 @@ def main():
         return write_wino_header(rows, sorted({r["batch"] for r in rows}), None, args.winograd4, args.hold_min_batch)
     if args.winograd or args.winograd4:
         return tune_winograd(args, four=args.winograd4)
+    if args.winograd4_wide:
+        return compare_wide(args)
 
     import torch
 
@@ -283,6 +297,95 @@ def tune_winograd(args, four=False):
     Path(args.out).write_text(json.dumps(rows, indent=0))
     if args.write_header:
         write_wino_header(rows, batches, Path(args.out).parent, four, args.hold_min_batch)
+
+
+def compare_wide(args):
+    import torch
+
+    from mvlm_amd.prediction import BU3DFEPredictor, DTU3DPredictor
+
+    rows = []
+    batches = [96, 12] if args.batches == ap_default_batches() else [int(b) for b in args.batches.split(",")]
+    for net in args.nets.split(","):
+        name, mode = net.split(":")
+        pred = (DTU3DPredictor if name == "dtu3d" else BU3DFEPredictor)(image_mode=mode, weights="synthetic:0", verbose=False)
+        ctx, lib = pred.ctx, pred.ctx.lib
+        nl = pred.get_lm_count()
+        ctx.check(lib.mvlm_cnn_set_winograd(ctx.handle, 1))
+        ctx.check(lib.mvlm_cnn_set_winograd4(ctx.handle, args.f43_mode))
+        for batch in batches:
+            rs = np.random.RandomState(batch)
+            images = torch.from_numpy(rs.rand(batch, 256, 256, 4).astype(np.float32)).cuda()
+            out = torch.empty((nl, batch, 3), dtype=torch.float32, device="cuda")
+            pred.set_execution(graphs=False)
+            runs = {0: [], 1: []}
+            for on in (0, 1):  # first use of either shape: launch attributes, workspace
+                ctx.check(lib.mvlm_cnn_set_winograd4_wide(ctx.handle, on))
+                pred.predict_device(images, out=out)
+            ctx.check(lib.mvlm_cnn_set_profiling(ctx.handle, 1))
+            for _ in range(args.passes):
+                for on in (0, 1):
+                    ctx.check(lib.mvlm_cnn_set_winograd4_wide(ctx.handle, on))
+                    runs[on] += profile_pass(pred, images, out, 1)
+            ctx.check(lib.mvlm_cnn_set_profiling(ctx.handle, 0))
+            ctx.check(lib.mvlm_cnn_set_winograd4_wide(ctx.handle, 1))
+            rec = {on: min_records(runs[on]) for on in (0, 1)}
+            assert [(s, v) for s, v, _, _ in rec[0]] == [(s, v) for s, v, _, _ in rec[1]]  # the switch moves no launch to another code
+            keys = {on: defaultdict(float) for on in (0, 1)}
+            count = defaultdict(int)
+            for on in (0, 1):
+                for s, v, t, sh in rec[on]:
+                    if s >= 0 and v == WINO4_CODE and lib.mvlm_conv_wino4_wide_serves(*sh[:4]):
+                        keys[on][sh[:5]] += t
+                        count[sh[:5]] += on
+            for key in sorted(keys[0], key=lambda k: -keys[0][k]):
+                us0, us1 = keys[0][key], keys[1][key]
+                slower = us1 > (1.0 + args.min_gain) * us0
+                rows.append(dict(net=net, batch=batch, key=list(key), launches=count[key], narrow_us=round(us0, 1), wide_us=round(us1, 1), slower=bool(slower)))
+                print(f"{net} B{batch:3d} {key[1]:3d}->{key[2]:3d} @{key[3]:3d} kind {key[4]}  {count[key]:2d} launches  narrow {us0:9.1f} us  wide {us1:9.1f} us  "
+                      f"{us0 / us1:5.2f}x{'  <-- slower on the wide shape' if slower else ''}", flush=True)
+            tot = {on: sum(t for _, _, t, _ in rec[on]) for on in (0, 1)}
+            f43 = {on: sum(t for _, v, t, _ in rec[on] if v == WINO4_CODE) for on in (0, 1)}
+            print(f"== {net} batch {batch}, F(4,3) mode {args.f43_mode}: conv kernels of a pass {tot[0] / 1e3:.3f} ms -> {tot[1] / 1e3:.3f} ms with the wide shape "
+                  f"(launches on code 2048: {f43[0] / 1e3:.3f} -> {f43[1] / 1e3:.3f} ms; keys served wide: {sum(keys[0].values()) / 1e3:.3f} -> {sum(keys[1].values()) / 1e3:.3f} ms)", flush=True)
+            rows.append(dict(net=net, batch=batch, summary=True, before_us=round(tot[0], 1), after_us=round(tot[1], 1)))
+            del images, out
+        ctx.check(lib.mvlm_cnn_set_winograd4(ctx.handle, 1))
+        del pred
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(args.out).write_text(json.dumps(rows, indent=0))
+    if args.write_header:
+        write_wide_hold_header(rows, max(batches))
+
+
+def write_wide_hold_header(rows, batch):
+    """the keys (cin_pad, cout_pad, size, kind) slower on the wide shape at `batch` views in any net, and the rows the header had"""
+    import re
+
+    held = {}
+    if WIDE_HOLD_HEADER.exists():
+        for m in re.finditer(r"^    \{(\d+), (\d+), (\d+), (\d+)\},\s*//(.*)$", WIDE_HOLD_HEADER.read_text(), re.M):
+            if int(m.group(1)):  # (not the end row)
+                held[tuple(int(v) for v in m.groups()[:4])] = m.group(5).strip()
+    for r in rows:
+        if not r.get("summary") and r["batch"] == batch and r["slower"]:
+            held[tuple(r["key"][1:5])] = f"B{batch} {r['launches']} launches: narrow {r['narrow_us']} us, wide {r['wide_us']} us [{r['net']}]"
+    lines = ["// GENERATED by tools/tune_in_network.py --winograd4-wide --write-header on an MI355X: the (shape, kind) keys whose launches on the",
+             "// F(4,3) tile ran slower on its wide workgroup shape than on the 32 x 16 shape INSIDE a forward pass, by more than 2 %.  The tile's",
+             "// launcher (conv_inst_q0.hip) keeps them on the 32 x 16 shape; every other launch with output channels in 64s takes the wide one.",
+             "// {cin_pad, cout_pad, size, kind}",
+             "#ifndef MVLM_CONV_WINO4_WIDE_HOLD_H", "#define MVLM_CONV_WINO4_WIDE_HOLD_H",
+             "struct ConvWino4WideHold {", "    short cin_pad, cout_pad, size, kind;", "};",
+             "static const ConvWino4WideHold MVLM_CONV_WINO4_WIDE_HOLD[] = {"]
+    lines += [f"    {{{k[0]}, {k[1]}, {k[2]}, {k[3]}}},  // {note}" for k, note in sorted(held.items())]
+    lines += ["    {0, 0, 0, 0},  // (end: no layer has zero channels)", "};",
+              f"static const int MVLM_CONV_WINO4_WIDE_HOLD_N = {len(held)};", "#endif", ""]
+    WIDE_HOLD_HEADER.write_text("\n".join(lines))
+    print(f"{len(held)} keys -> {WIDE_HOLD_HEADER}")
+
+
+def ap_default_batches():
+    return "1,2,3,4,5,6,7,8,9,10,11,12,13,14,15,16,20,24,32,48,64,96,128"
 
 
 def write_wino_header(rows, batches, copy_dir=None, four=False, hold=0):
