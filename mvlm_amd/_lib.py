@@ -98,6 +98,10 @@ SIGNATURES = {
     "mvlm_cnn_set_winograd4_wide": (C.c_int, [C.c_void_p, C.c_int]),
     "mvlm_conv_wino4_wide_serves": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "mvlm_conv_wino4_wide_launches": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    "mvlm_cnn_set_winograd4_padded": (C.c_int, [C.c_void_p, C.c_int]),
+    "mvlm_conv_wino4_padded_launches": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    "mvlm_conv_wino4_padded_stride": (C.c_int, [C.c_int]),
+    "mvlm_pack_winograd4_weights_padded": (C.c_int, [c_float_p, c_float_p, C.c_int, C.c_int, c_float_p, c_float_p]),
     "mvlm_cnn_execution_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                           C.POINTER(C.c_int64)]),
     "mvlm_pack_fast_weights": (C.c_size_t, [c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint16)]),

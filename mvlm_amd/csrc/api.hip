@@ -60,6 +60,7 @@ extern "C" void mvlm_ctx_destroy(mvlm_ctx* ctx) {
     if (ctx->cnn.fast16_blob) hipFree(ctx->cnn.fast16_blob);
     for (auto& ww : ctx->cnn.wino)
         if (ww.blob) hipFree(ww.blob);
+    if (ctx->cnn.wino4_pad_blob) hipFree(ctx->cnn.wino4_pad_blob);
     if (ctx->cnn.fast16_flag) hipFree(ctx->cnn.fast16_flag);
     if (ctx->switch_event) hipEventDestroy(ctx->switch_event);
     for (int i = 0; i < 2; ++i) {
@@ -692,6 +693,15 @@ extern "C" int mvlm_conv2d(mvlm_ctx* ctx, const float* x_dev, int batch, int cin
         form.transform(blob.data() + w_off, cin_pad, cout_pad, blob.data() + ww_off[f]);
     }
     const long b_off = vec(bias_host, cout, cout_pad);
+    // ... and the F(4,3) form at a cout stride of whole 32s, the bias alike, where the 80- or 84-row tile's launcher may hand the launch over
+    long wp_off = -1, bp_off = -1;
+    if (mvlm_conv_wino4_pad_serves_slot(ksize, cin_pad, cout_pad)) {
+        const int P = mvlm_conv_wino4_padded_cout(cout_pad);
+        wp_off = long(push(size_t(18) * cin_pad * P));
+        if (b_off >= 0) bp_off = long(push(size_t(P)));
+        mvlm_winograd4_pack_padded(blob.data() + w_off, b_off < 0 ? nullptr : blob.data() + b_off, cin_pad, cout_pad, blob.data() + wp_off,
+                                   bp_off < 0 ? nullptr : blob.data() + bp_off);
+    }
     const long ps_off = vec(pre_scale_host, cin, cin_pad), pt_off = vec(pre_shift_host, cin, cin_pad);
     const long qs_off = vec(post_scale_host, cout, cout_pad), qt_off = vec(post_shift_host, cout, cout_pad);
     auto* d = static_cast<float*>(ctx->get_scratch("conv2d.blob", blob.size() * 4));
@@ -720,6 +730,8 @@ extern "C" int mvlm_conv2d(mvlm_ctx* ctx, const float* x_dev, int batch, int cin
     a.res1_ctot = cout;
     a.out = y_dev;
     a.out_ctot = cout;
+    ctx->conv_wino4_pads[0] = {wp_off < 0 ? nullptr : d + wp_off, bp_off < 0 ? nullptr : d + bp_off};  // (this call's layer; null: none)
+    a.wino4_pad = wp_off < 0 ? 0 : 1;
     if (mvlm_launch_conv(ctx, a, nullptr)) return 1;
     MVLM_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
@@ -739,7 +751,8 @@ extern "C" int mvlm_conv_bench(mvlm_ctx* ctx, int batch, int cin, int cout, int 
     const bool plain = (flags & 4) && !(flags & (1 | 2 | 8));
     const int cout_pad = (plain && (cout + 15) / 16 * 16 == 80) ? 80 : (plain && ksize == 3 && cout == 84) ? 84 : (cout + 31) / 32 * 32;
     const size_t px = size_t(batch) * size * size;
-    const size_t n_w = size_t(ksize == 3 ? 18 : taps) * cin_pad * cout_pad, n_vec = size_t(cin_pad) * 2 + size_t(cout_pad) * 3;
+    // (zero data serves every form of the weights: 18 slices at the F(4,3) tile's padded cout stride cover them all)
+    const size_t n_w = size_t(ksize == 3 ? 18 : taps) * cin_pad * mvlm_conv_wino4_padded_cout(cout_pad), n_vec = size_t(cin_pad) * 2 + size_t(cout_pad) * 3;
     const size_t n_x = px * cin, n_y = px * cout;
     const size_t total = n_w + n_vec + n_x + 3 * n_y + 64;
     auto* base = static_cast<float*>(ctx->get_scratch("conv_bench", total * sizeof(float)));
@@ -761,6 +774,9 @@ extern "C" int mvlm_conv_bench(mvlm_ctx* ctx, int batch, int cin, int cout, int 
     a.w = w;
     for (int f = 0; f < MVLM_WINO_FORMS_N; ++f)  // (zero data: the transformed weights are zeros too)
         if (mvlm_wino_form(f).serves_slot(ksize, cin_pad, cout_pad)) a.*mvlm_wino_form(f).weights = w;
+    const bool padded = mvlm_conv_wino4_pad_serves_slot(ksize, cin_pad, cout_pad);
+    ctx->conv_wino4_pads[0] = padded ? ConvWino4Pad{w, vec + 2 * cin_pad} : ConvWino4Pad{};  // (this call's layer: the zero weights, the zero bias)
+    a.wino4_pad = padded ? 1 : 0;
     a.cout = cout;
     a.cout_pad = cout_pad;
     a.ksize = ksize;

@@ -17,6 +17,7 @@
 //
 // All views of a batch go through each layer together (pixels of all views form the GEMM's
 // N dimension), so even the 4x4 hourglass level fills MFMA tiles.
+#include <array>
 #include <cstdlib>
 
 #include "common.h"
@@ -175,6 +176,7 @@ struct Exec {
             const CnnState::WinoWeights& ww = st.wino[f];
             a.*mvlm_wino_form(f).weights = (size_t(slot) < ww.off.size() && ww.off[size_t(slot)] >= 0) ? ww.blob + ww.off[size_t(slot)] : nullptr;
         }
+        a.wino4_pad = size_t(slot) < st.wino4_pad_id.size() ? st.wino4_pad_id[size_t(slot)] : 0;
         a.bias = blob(r[7]);
         a.pre_scale = blob(r[8]);
         a.pre_shift = blob(r[9]);
@@ -884,6 +886,12 @@ extern "C" int mvlm_cnn_load(mvlm_ctx* ctx, const float* blob_host, size_t n_flo
             ww.blob = nullptr;
         }
     }
+    st.wino4_pad_id.clear();
+    ctx->conv_wino4_pads.resize(1);  // ([0]: the single-layer entry points')
+    if (st.wino4_pad_blob) {
+        (void)hipFree(st.wino4_pad_blob);
+        st.wino4_pad_blob = nullptr;
+    }
     st.drop_graphs();  // captured launches point into the old weight blob
     st.desc.assign(desc_host, desc_host + size_t(n_slots) * MVLM_CONV_DESC_INTS);
     // validate every offset before anything is launched with it
@@ -924,6 +932,31 @@ extern "C" int mvlm_cnn_load(mvlm_ctx* ctx, const float* blob_host, size_t n_flo
         if (!host.empty()) {
             MVLM_CHECK_HIP(ctx, hipMalloc(&ww.blob, host.size() * sizeof(float)));
             MVLM_CHECK_HIP(ctx, hipMemcpy(ww.blob, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+        }
+    }
+    // ... and the F(4,3) form at a cout stride of whole 32s, with the bias padded alike, of every 3x3 slot that tile would serve but
+    // for its cout_pad (conv6 / conv10 on 84 or 80 rows): what the 80- and 84-row tiles' launchers hand over (conv_inst_q0.hip)
+    {
+        std::vector<float> host;
+        std::vector<std::array<long long, 3>> made;  // slot, weights' offset, bias's offset or -1
+        for (int s = 0; s < n_slots; ++s) {
+            const int32_t* r = &st.desc[size_t(s) * MVLM_CONV_DESC_INTS];
+            if (!r[0] || !mvlm_conv_wino4_pad_serves_slot(r[3], r[4], r[5])) continue;
+            const int P = mvlm_conv_wino4_padded_cout(r[5]);
+            const size_t w_off = host.size(), b_off = w_off + size_t(18) * r[4] * P;
+            host.resize(b_off + (r[7] >= 0 ? P : 0));
+            mvlm_winograd4_pack_padded(blob_host + r[6], r[7] >= 0 ? blob_host + r[7] : nullptr, r[4], r[5], host.data() + w_off,
+                                       r[7] >= 0 ? host.data() + b_off : nullptr);
+            made.push_back({s, (long long)w_off, r[7] >= 0 ? (long long)b_off : -1});
+        }
+        if (!host.empty()) {
+            MVLM_CHECK_HIP(ctx, hipMalloc(&st.wino4_pad_blob, host.size() * sizeof(float)));
+            MVLM_CHECK_HIP(ctx, hipMemcpy(st.wino4_pad_blob, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+            st.wino4_pad_id.assign(size_t(n_slots), 0);
+            for (const auto& m : made) {
+                ctx->conv_wino4_pads.push_back({st.wino4_pad_blob + m[1], m[2] < 0 ? nullptr : st.wino4_pad_blob + m[2]});
+                st.wino4_pad_id[size_t(m[0])] = int(ctx->conv_wino4_pads.size());
+            }
         }
     }
     st.n_landmarks = n_landmarks;
@@ -1014,6 +1047,20 @@ extern "C" int mvlm_cnn_set_winograd4_wide(mvlm_ctx* ctx, int on) {
     MVLM_REQUIRE(ctx, on == 0 || on == 1, "cnn_set_winograd4_wide: 0 the 32 x 16 shape on every launch, 1 the wide shape where the output channels come in 64s (default)");
     if (on != ctx->conv_winograd4_wide) ctx->cnn.drop_graphs();
     ctx->conv_winograd4_wide = on;
+    return 0;
+}
+
+// whether the 80- and 84-row tiles' launchers hand eligible launches to the F(4,3) tile (captured graphs encode the kernels)
+extern "C" int mvlm_cnn_set_winograd4_padded(mvlm_ctx* ctx, int mode) {
+    return set_winograd_mode(ctx, &mvlm_ctx::conv_winograd4_padded, mode,
+                             "cnn_set_winograd4_padded: 0 never, 1 the measured table (default), 2 every eligible launch of the 80- and 84-row tiles");
+}
+
+// launches handed over that way since the context was made or the count was last reset (a host counter, as the one below)
+extern "C" int mvlm_conv_wino4_padded_launches(mvlm_ctx* ctx, int64_t* count, int reset) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (count) *count = ctx->conv_wino4_padded_launches;
+    if (reset) ctx->conv_wino4_padded_launches = 0;
     return 0;
 }
 

@@ -77,6 +77,10 @@ struct ConvArgs {
     // weights [taps][cin_pad][cout_pad]
     const float* w = nullptr;
     int cout = 0, cout_pad = 0, ksize = 3;
+    // 1 + the index in mvlm_ctx::conv_wino4_pads of this layer's F(4,3) weights and bias at a cout stride of whole 32s
+    // (mvlm_conv_wino4_padded_cout), where its cout_pad is none and the tile could serve it otherwise; 0: none.  Host only: it sits in
+    // the four bytes of padding between ksize and bias, so every field a kernel reads keeps its offset (the static_assert below).
+    int wino4_pad = 0;
     const float* bias = nullptr;        // [cout_pad] or null
     const float* post_scale = nullptr;  // [cout_pad] relu(v*s+t) or null
     const float* post_shift = nullptr;
@@ -135,8 +139,16 @@ struct ConvArgs {
     // mvlm_launch_conv puts it in `w` when it routes the launch to such a tile
     const float* w_wino = nullptr;
 };
-static_assert(sizeof(ConvArgs) == 360 && offsetof(ConvArgs, fast_ovf) == 328 && offsetof(ConvArgs, timing) == 344,
+static_assert(sizeof(ConvArgs) == 360 && offsetof(ConvArgs, wino4_pad) == 84 && offsetof(ConvArgs, bias) == 88 && offsetof(ConvArgs, fast_ovf) == 328 &&
+                  offsetof(ConvArgs, timing) == 344,
               "ConvArgs is passed to the kernels by value: moving a field changes the device code of every convolution kernel");
+
+// A layer's F(4,3) weights [18][cin_pad][P] and bias [P] at the cout stride P = mvlm_conv_wino4_padded_cout(cout_pad), zeros beyond
+// cout_pad (device pointers; bias null: the layer has none).  ConvArgs::wino4_pad names an entry of mvlm_ctx::conv_wino4_pads.
+struct ConvWino4Pad {
+    const float* w = nullptr;
+    const float* bias = nullptr;
+};
 
 struct ConvProfileRec {
     int slot, variant;
@@ -215,6 +227,10 @@ struct CnnState {
         float* blob = nullptr;
         std::vector<long long> off;
     } wino[MVLM_WINO_FORMS_N];
+    // the F(4,3) form at a cout stride of whole 32s, and the bias alike, of the slots whose cout_pad is no multiple of 32 (conv6 /
+    // conv10 on 80 or 84 rows), and per slot the ConvArgs::wino4_pad that names its entry of mvlm_ctx::conv_wino4_pads (0: none)
+    float* wino4_pad_blob = nullptr;
+    std::vector<int> wino4_pad_id;
     std::vector<CnnGraphEntry> graphs;
     long graph_replays = 0, graph_captures = 0, eager_runs = 0, graph_failures = 0;
     // forget the captured passes: they encode the kernels, their order and pointers into the weight blobs
@@ -296,6 +312,17 @@ struct mvlm_ctx {
     // x 8 rows on one staged input tile, where cout_pad is a multiple of 64; 0 the 32 x 16 shape on every launch; MVLM_WINOGRAD4_WIDE (default 1)
     int conv_winograd4_wide = [] { const char* e = getenv("MVLM_WINOGRAD4_WIDE"); return (e && e[0] >= '0' && e[0] <= '1' && !e[1]) ? e[0] - '0' : 1; }();
     long long conv_wino4_wide_launches = 0;  // launches issued on the wide shape (mvlm_conv_wino4_wide_launches)
+    // The 80- and 84-row direct tiles' launchers (variants 16 and 26) hand an eligible launch to the F(4,3) tile on weights padded to
+    // whole 32-channel columns (conv_inst_q0.hip: mvlm_conv_launch_wino4_padded): 0 never, 1 where the measured table
+    // conv_tuned_wino4_pad.h has a row, 2 every eligible launch (tests); MVLM_WINOGRAD4_PADDED (default 1)
+    int conv_winograd4_padded = [] { const char* e = getenv("MVLM_WINOGRAD4_PADDED"); return (e && e[0] >= '0' && e[0] <= '2' && !e[1]) ? e[0] - '0' : 1; }();
+    long long conv_wino4_padded_launches = 0;  // launches handed over that way (mvlm_conv_wino4_padded_launches)
+    // the padded weights such launches read: [0] the layer of the mvlm_conv2d / mvlm_conv_bench call in flight, then the loaded
+    // network's slots (mvlm_cnn_load); ConvArgs::wino4_pad is 1 + the index
+    std::vector<ConvWino4Pad> conv_wino4_pads = std::vector<ConvWino4Pad>(1);
+    // the variant code a launcher ran the launch on where that is not the code it was called for (-1: it is); mvlm_launch_conv
+    // clears it before the launch and reports it afterwards
+    int conv_launch_ran_as = -1;
     std::vector<ConvOverride> conv_overrides;  // tools/tune_in_network.py: kernel variant per (shape, kind), before any table
     // Conv kernels whose launch attributes are set on this ctx's device.  The 64 bits: a base variant's bit is its id (all below
     // MVLM_CONV_FAST_ATTR_BIT0, none MVLM_CONV_WINO4_ATTR_BIT or MVLM_CONV_WINO4_WIDE_ATTR_BIT: conv_mfma.hip asserts it), the F(4,3)
@@ -447,6 +474,15 @@ constexpr int MVLM_CONV_WINO4_ATTR_BIT = 41, MVLM_CONV_WINO4_WIDE_ATTR_BIT = 42,
 // its own: code 2048's launcher takes it where the context's switch is on and the layer's output channels come in 64s.  Everything
 // else about the layer is what the 32 x 16 shape asks, so this is asked of launches already routed to code 2048.
 inline bool mvlm_conv_wino4_wide_shape_ok(int cout_pad, int H) { return cout_pad > 0 && cout_pad % 64 == 0 && H % 16 == 0; }
+// The cout stride of the padded F(4,3) weights (ConvWino4Pad): whole 32-channel columns of the tile.  84 -> 96, 80 -> 96.
+inline int mvlm_conv_wino4_padded_cout(int cout_pad) { return (cout_pad + 31) / 32 * 32; }
+// Does a 3x3 slot of these channels get padded F(4,3) weights: the tile would serve it but for cout_pad % 32 != 0?
+inline bool mvlm_conv_wino4_pad_serves_slot(int ksize, int cin_pad, int cout_pad) {
+    return cout_pad > 0 && cout_pad % 32 != 0 && mvlm_conv_wino4_serves_slot(ksize, cin_pad, mvlm_conv_wino4_padded_cout(cout_pad));
+}
+// host: packed [9][cin_pad][cout_pad] -> [18][cin_pad][P], columns below cout_pad as mvlm_winograd4_transform, zeros beyond;
+// bias [cout_pad] or null -> [P] likewise (bias_pad may be null then)
+void mvlm_winograd4_pack_padded(const float* w9, const float* bias, int cin_pad, int cout_pad, float* w18_pad, float* bias_pad);
 constexpr int MVLM_CONV_VARIANT_FAST = 62;    // id reported for launches of the bf16x3 kernel
 constexpr int MVLM_CONV_VARIANT_FAST16 = 61;  // ... of the f16x2 kernel
 

@@ -465,7 +465,13 @@ int mvlm_launch_conv(mvlm_ctx* ctx, const ConvArgs& a, int* variant_out) {
     ConvArgs b = a;
     b.kparts = d.kparts;
     if (form) b.w = a.*form->weights;
-    return d.row ? d.row->launch(ctx, b) : ctx->fail("conv: unreachable variant");  // (check_variant<> refuses what the tile cannot serve)
+    if (!d.row) return ctx->fail("conv: unreachable variant");
+    ctx->conv_launch_ran_as = -1;
+    const int rc = d.row->launch(ctx, b);  // (check_variant<> refuses what the tile cannot serve)
+    // a launcher that ran the launch on another tile's kernel (variants 16 and 26 on the F(4,3) tile: conv_inst_q0.hip) noted its
+    // code: a profile record counts the FLOPs of the kernel that ran
+    if (variant_out && ctx->conv_launch_ran_as >= 0) *variant_out = ctx->conv_launch_ran_as;
+    return rc;
 }
 
 
@@ -551,5 +557,31 @@ void mvlm_winograd4_transform(const float* w9, int cin_pad, int cout_pad, float*
 extern "C" int mvlm_pack_winograd4_weights(const float* w9_host, int cin_pad, int cout_pad, float* w18_host) {
     if (!w9_host || !w18_host || cin_pad <= 0 || cout_pad <= 0) return 1;
     mvlm_winograd4_transform(w9_host, cin_pad, cout_pad, w18_host);
+    return 0;
+}
+
+// The same values at the cout stride P = mvlm_conv_wino4_padded_cout(cout_pad): the transform at its own stride, then every row of
+// cout_pad columns moved to the front of a row of P, zeros behind; the bias likewise.
+void mvlm_winograd4_pack_padded(const float* w9, const float* bias, int cin_pad, int cout_pad, float* w18_pad, float* bias_pad) {
+    const int P = mvlm_conv_wino4_padded_cout(cout_pad);
+    const size_t rows = size_t(18) * cin_pad;
+    std::vector<float> w18(rows * cout_pad);
+    mvlm_winograd4_transform(w9, cin_pad, cout_pad, w18.data());
+    for (size_t r = 0; r < rows; ++r) {
+        std::copy(w18.begin() + r * cout_pad, w18.begin() + (r + 1) * cout_pad, w18_pad + r * P);
+        std::fill(w18_pad + r * P + cout_pad, w18_pad + (r + 1) * P, 0.f);
+    }
+    if (bias && bias_pad) {
+        std::copy(bias, bias + cout_pad, bias_pad);
+        std::fill(bias_pad + cout_pad, bias_pad + P, 0.f);
+    }
+}
+
+extern "C" int mvlm_conv_wino4_padded_stride(int cout_pad) { return cout_pad > 0 ? mvlm_conv_wino4_padded_cout(cout_pad) : 0; }
+
+extern "C" int mvlm_pack_winograd4_weights_padded(const float* w9_host, const float* bias_host, int cin_pad, int cout_pad, float* w18_pad_host,
+                                                  float* bias_pad_host) {
+    if (!w9_host || !w18_pad_host || cin_pad <= 0 || cout_pad <= 0 || (bias_host && !bias_pad_host)) return 1;
+    mvlm_winograd4_pack_padded(w9_host, bias_host, cin_pad, cout_pad, w18_pad_host, bias_pad_host);
     return 0;
 }

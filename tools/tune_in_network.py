@@ -31,6 +31,12 @@ the keys marked at the largest batch in conv_wino4_wide_hold.h, which the tile's
 header already holds runs on that shape under either setting here and cannot be marked again, so its row is carried over: to
 measure it afresh, take it out of the header and build first.  --f43-mode 2 (default) puts every key the tile serves on it, 1
 leaves the pass to the measured table (no launch of the tile below 96 views).
+
+--winograd4-padded: the table of the 80- and 84-row direct tiles' launches that run on the F(4,3) tile over padded weights
+(conv_tuned_wino4_pad.h).  At 96 views (or --batches) the default pass is timed with mvlm_cnn_set_winograd4_padded at 0 and at 2,
+alternating, --passes times each, the quietest timing per launch; every (shape, kind) whose launches the switch moves to code 2048
+is listed with its time per pass under either setting, then the sum of the convolution kernels of a pass.  A key gets a row where
+the tile is faster by more than --min-gain in every net that has it; --write-header writes the rows, each held at 96 views.
 """
 from __future__ import annotations
 
@@ -50,6 +56,7 @@ HEADER = REPO / "mvlm_amd" / "csrc" / "conv_tuned_net.h"
 WINO_HEADER = REPO / "mvlm_amd" / "csrc" / "conv_tuned_wino.h"
 WINO4_HEADER = REPO / "mvlm_amd" / "csrc" / "conv_tuned_wino4.h"
 WIDE_HOLD_HEADER = REPO / "mvlm_amd" / "csrc" / "conv_wino4_wide_hold.h"
+WINO4_PAD_HEADER = REPO / "mvlm_amd" / "csrc" / "conv_tuned_wino4_pad.h"
 CAP = 1024
 
 
@@ -106,6 +113,7 @@ def main():
     ap.add_argument("--winograd", action="store_true", help="tune the Winograd tiles' table (conv_tuned_wino.h) instead")
     ap.add_argument("--winograd4", action="store_true", help="tune the F(4,3) Winograd tile's table (conv_tuned_wino4.h) instead")
     ap.add_argument("--winograd4-wide", action="store_true", help="time every key the F(4,3) tile's wide workgroup shape serves with the switch at 0 and 1")
+    ap.add_argument("--winograd4-padded", action="store_true", help="tune the table of the 80- / 84-row layers that run on the F(4,3) tile over padded weights (conv_tuned_wino4_pad.h)")
     ap.add_argument("--f43-mode", type=int, default=2, help="--winograd4-wide: the F(4,3) mode of the compared passes (2 every served key, 1 the table)")
     ap.add_argument("--hold-min-batch", type=int, default=0,
                     help="--winograd4: write no row below this many views, whatever won there (the header says so and why)")
@@ -118,6 +126,8 @@ def main():
         return tune_winograd(args, four=args.winograd4)
     if args.winograd4_wide:
         return compare_wide(args)
+    if args.winograd4_padded:
+        return tune_padded(args)
 
     import torch
 
@@ -356,6 +366,88 @@ def compare_wide(args):
     Path(args.out).write_text(json.dumps(rows, indent=0))
     if args.write_header:
         write_wide_hold_header(rows, max(batches))
+
+
+def tune_padded(args):
+    import torch
+
+    from mvlm_amd.prediction import BU3DFEPredictor, DTU3DPredictor
+
+    rows = []
+    batches = [96] if args.batches == ap_default_batches() else [int(b) for b in args.batches.split(",")]
+    for net in args.nets.split(","):
+        name, mode = net.split(":")
+        pred = (DTU3DPredictor if name == "dtu3d" else BU3DFEPredictor)(image_mode=mode, weights="synthetic:0", verbose=False)
+        ctx, lib = pred.ctx, pred.ctx.lib
+        nl = pred.get_lm_count()
+        for batch in batches:
+            rs = np.random.RandomState(batch)
+            images = torch.from_numpy(rs.rand(batch, 256, 256, 4).astype(np.float32)).cuda()
+            out = torch.empty((nl, batch, 3), dtype=torch.float32, device="cuda")
+            pred.set_execution(graphs=False)
+            runs = {0: [], 2: []}
+            for sw in (0, 2):  # first use of either kernel: launch attributes
+                ctx.check(lib.mvlm_cnn_set_winograd4_padded(ctx.handle, sw))
+                pred.predict_device(images, out=out)
+            ctx.check(lib.mvlm_cnn_set_profiling(ctx.handle, 1))
+            for _ in range(args.passes):
+                for sw in (0, 2):
+                    ctx.check(lib.mvlm_cnn_set_winograd4_padded(ctx.handle, sw))
+                    runs[sw] += profile_pass(pred, images, out, 1)
+            ctx.check(lib.mvlm_cnn_set_profiling(ctx.handle, 0))
+            ctx.check(lib.mvlm_cnn_set_winograd4_padded(ctx.handle, 1))
+            rec = {sw: min_records(runs[sw]) for sw in (0, 2)}
+            assert [(s, sh) for s, _, _, sh in rec[0]] == [(s, sh) for s, _, _, sh in rec[2]]  # the switch moves kernels, not launches
+            keys = {sw: defaultdict(float) for sw in (0, 2)}
+            count, direct = defaultdict(int), {}
+            for (s, v0, t0, sh), (_, v2, t2, _) in zip(rec[0], rec[2]):
+                if v0 != v2:
+                    assert v2 == WINO4_CODE, (s, v0, v2)
+                    keys[0][sh[:5]] += t0
+                    keys[2][sh[:5]] += t2
+                    count[sh[:5]] += 1
+                    direct[sh[:5]] = v0
+            for key in sorted(keys[0], key=lambda k: -keys[0][k]):
+                us0, us2 = keys[0][key], keys[2][key]
+                faster = us2 * (1.0 + args.min_gain) < us0
+                rows.append(dict(net=net, batch=batch, key=list(key), launches=count[key], direct_variant=direct[key], direct_us=round(us0, 1),
+                                 padded_us=round(us2, 1), faster=bool(faster)))
+                print(f"{net} B{batch:3d} {key[1]:3d}->{key[2]:3d} @{key[3]:3d} kind {key[4]}  {count[key]:2d} launches  variant {direct[key]:2d} {us0:9.1f} us  "
+                      f"F(4,3) padded {us2:9.1f} us  {us0 / us2:5.2f}x{'  <-- row' if faster else ''}", flush=True)
+            tot = {sw: sum(t for _, _, t, _ in rec[sw]) for sw in (0, 2)}
+            print(f"== {net} batch {batch}: conv kernels of a pass {tot[0] / 1e3:.3f} ms -> {tot[2] / 1e3:.3f} ms with the switch at 2 "
+                  f"(the moved launches: {sum(keys[0].values()) / 1e3:.3f} -> {sum(keys[2].values()) / 1e3:.3f} ms)", flush=True)
+            rows.append(dict(net=net, batch=batch, summary=True, before_us=round(tot[0], 1), after_us=round(tot[2], 1)))
+            del images, out
+        del pred
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(args.out).write_text(json.dumps(rows, indent=0))
+    if args.write_header:
+        write_padded_header(rows, max(batches))
+
+
+def write_padded_header(rows, batch, hold=96):
+    """a row per key (cin_pad, cout_pad, size, kind) that was faster on the tile at `batch` views in every net that has it"""
+    won = defaultdict(list)
+    for r in rows:
+        if not r.get("summary") and r["batch"] == batch:
+            won[tuple(r["key"][1:5])].append(r)
+    keep = {k: rs for k, rs in won.items() if all(r["faster"] for r in rs)}
+    lines = ["// GENERATED by tools/tune_in_network.py --winograd4-padded --write-header on an MI355X: the (shape, kind) keys of the 80- and 84-row",
+             "// direct tiles (variants 16 and 26) whose launches ran faster, by more than 2 %, on the F(4,3) Winograd tile over weights padded to",
+             "// whole 32-channel columns, timed INSIDE a forward pass.  The two tiles' launchers (conv_inst_g3.hip, conv_inst_g12.hip) hand such a",
+             "// launch to mvlm_conv_launch_wino4_padded (conv_inst_q0.hip).  {cin_pad, cout_pad, size, kind, min_batch}: from min_batch views on.",
+             f"// HELD: every row at {hold} views, the correctness gate of conv_tuned_wino4.h (DESIGN 4.1), not a timing result.",
+             "#ifndef MVLM_CONV_TUNED_WINO4_PAD_H", "#define MVLM_CONV_TUNED_WINO4_PAD_H",
+             "struct ConvTunedWino4Pad {", "    short cin_pad, cout_pad, size, kind, min_batch;", "};",
+             "static const ConvTunedWino4Pad MVLM_CONV_TUNED_WINO4_PAD[] = {"]
+    for k, rs in sorted(keep.items()):
+        note = "; ".join(f"B{batch} {r['launches']} launches: variant {r['direct_variant']} {r['direct_us']} us, padded {r['padded_us']} us [{r['net']}]" for r in rs)
+        lines.append(f"    {{{k[0]}, {k[1]}, {k[2]}, {k[3]}, {max(hold, 0)}}},  // {note}")
+    lines += ["    {0, 0, 0, 0, 0},  // (end: no layer has zero channels)", "};",
+              f"static const int MVLM_CONV_TUNED_WINO4_PAD_N = {len(keep)};", "#endif", ""]
+    WINO4_PAD_HEADER.write_text("\n".join(lines))
+    print(f"{len(keep)} keys -> {WINO4_PAD_HEADER}")
 
 
 def write_wide_hold_header(rows, batch):
