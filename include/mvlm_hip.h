@@ -380,14 +380,14 @@ int mvlm_cnn_set_winograd4_wide(mvlm_ctx* ctx, int on);
 int mvlm_conv_wino4_wide_serves(int ksize, int cin_pad, int cout_pad, int size);
 int mvlm_conv_wino4_wide_launches(mvlm_ctx* ctx, int64_t* count, int reset);
 /* The 3x3 layers whose padded output channels are no multiple of 32 - conv6 / conv10 of an 84-landmark network on the 84-row direct
- * tile (variant 26), of a 73-landmark one on the 80-row tile (variant 16) - on that F(4,3) tile.  The dispatcher's choice does not
- * move: below it, the two tiles' launchers hand an eligible launch (plain 3x3 + bias into a plain tensor, size a multiple of 16, up
- * to 256 input channels, no variant forced, Winograd mode and F(4,3) mode not 0) to the F(4,3) kernel on weights [18][cin_pad][P]
+ * tile (variant 26), of a 73-landmark one on the 80-row tile (variant 16) - on that F(4,3) tile.  The dispatcher's choice of variant does
+ * not move: once it is made, the dispatcher runs an eligible launch (plain 3x3 + bias into a plain tensor, size a multiple of 16, up
+ * to 256 input channels, no variant forced, Winograd mode and F(4,3) mode not 0) on the F(4,3) kernel over weights [18][cin_pad][P]
  * and a bias [P], P = cout_pad rounded up to whole 32s, zeros beyond cout_pad; both are made once, where the weights are packed.
  * A profile record of such a launch carries code 2048 and the FLOPs of that tile.
  *   mvlm_cnn_set_winograd4_padded: 0 never (the direct tiles' launches and bits), 1 where the measured table
  *     csrc/conv_tuned_wino4_pad.h has a row (default), 2 every eligible launch (tests); MVLM_WINOGRAD4_PADDED likewise for a new context.
- *   mvlm_conv_wino4_padded_launches: *count = launches handed over by this context so far (host counter; a graph replay issues
+ *   mvlm_conv_wino4_padded_launches: *count = launches run that way by this context so far (host counter; a graph replay issues
  *     none); reset != 0 sets it to zero afterwards.
  *   mvlm_conv_wino4_padded_stride: P for this cout_pad.
  *   mvlm_pack_winograd4_weights_padded: host, w9 [9][cin_pad][cout_pad] -> w18_pad [18][cin_pad][P], columns below cout_pad as

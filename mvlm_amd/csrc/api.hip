@@ -693,7 +693,7 @@ extern "C" int mvlm_conv2d(mvlm_ctx* ctx, const float* x_dev, int batch, int cin
         form.transform(blob.data() + w_off, cin_pad, cout_pad, blob.data() + ww_off[f]);
     }
     const long b_off = vec(bias_host, cout, cout_pad);
-    // ... and the F(4,3) form at a cout stride of whole 32s, the bias alike, where the 80- or 84-row tile's launcher may hand the launch over
+    // ... and the F(4,3) form at a cout stride of whole 32s, the bias alike, where the dispatcher may run the 80- or 84-row tile's launch on that tile
     long wp_off = -1, bp_off = -1;
     if (mvlm_conv_wino4_pad_serves_slot(ksize, cin_pad, cout_pad)) {
         const int P = mvlm_conv_wino4_padded_cout(cout_pad);

@@ -935,7 +935,7 @@ extern "C" int mvlm_cnn_load(mvlm_ctx* ctx, const float* blob_host, size_t n_flo
         }
     }
     // ... and the F(4,3) form at a cout stride of whole 32s, with the bias padded alike, of every 3x3 slot that tile would serve but
-    // for its cout_pad (conv6 / conv10 on 84 or 80 rows): what the 80- and 84-row tiles' launchers hand over (conv_inst_q0.hip)
+    // for its cout_pad (conv6 / conv10 on 84 or 80 rows): what the dispatcher swaps in for the 80- and 84-row tiles' launches (conv_mfma.hip)
     {
         std::vector<float> host;
         std::vector<std::array<long long, 3>> made;  // slot, weights' offset, bias's offset or -1
@@ -1050,13 +1050,13 @@ extern "C" int mvlm_cnn_set_winograd4_wide(mvlm_ctx* ctx, int on) {
     return 0;
 }
 
-// whether the 80- and 84-row tiles' launchers hand eligible launches to the F(4,3) tile (captured graphs encode the kernels)
+// whether the dispatcher runs eligible launches of the 80- and 84-row tiles on the F(4,3) tile (captured graphs encode the kernels)
 extern "C" int mvlm_cnn_set_winograd4_padded(mvlm_ctx* ctx, int mode) {
     return set_winograd_mode(ctx, &mvlm_ctx::conv_winograd4_padded, mode,
                              "cnn_set_winograd4_padded: 0 never, 1 the measured table (default), 2 every eligible launch of the 80- and 84-row tiles");
 }
 
-// launches handed over that way since the context was made or the count was last reset (a host counter, as the one below)
+// launches run that way since the context was made or the count was last reset (a host counter, as the one below)
 extern "C" int mvlm_conv_wino4_padded_launches(mvlm_ctx* ctx, int64_t* count, int reset) {
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (count) *count = ctx->conv_wino4_padded_launches;

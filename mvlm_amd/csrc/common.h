@@ -308,21 +308,18 @@ struct mvlm_ctx {
     // the F(4,3) Winograd tile, where Winograd mode is not 0 and the launch carries ConvArgs::w_wino4: 0 never, 1 where the measured
     // table (conv_tuned_wino4.h) has an entry and Winograd mode is 1, 2 every layer the tile can serve (tests); MVLM_WINOGRAD4 (default 1)
     int conv_winograd4 = [] { const char* e = getenv("MVLM_WINOGRAD4"); return (e && e[0] >= '0' && e[0] <= '2' && !e[1]) ? e[0] - '0' : 1; }();
-    // the workgroup shape of the F(4,3) tile's launches (conv_inst_q0.hip: mvlm_conv_launch_wino4): 1 the wide shape, 64 output channels
+    // the workgroup shape of the F(4,3) tile's launches (the dispatcher decides, conv_mfma.hip: f43_plan): 1 the wide shape, 64 output channels
     // x 8 rows on one staged input tile, where cout_pad is a multiple of 64; 0 the 32 x 16 shape on every launch; MVLM_WINOGRAD4_WIDE (default 1)
     int conv_winograd4_wide = [] { const char* e = getenv("MVLM_WINOGRAD4_WIDE"); return (e && e[0] >= '0' && e[0] <= '1' && !e[1]) ? e[0] - '0' : 1; }();
     long long conv_wino4_wide_launches = 0;  // launches issued on the wide shape (mvlm_conv_wino4_wide_launches)
-    // The 80- and 84-row direct tiles' launchers (variants 16 and 26) hand an eligible launch to the F(4,3) tile on weights padded to
-    // whole 32-channel columns (conv_inst_q0.hip: mvlm_conv_launch_wino4_padded): 0 never, 1 where the measured table
+    // The dispatcher runs an eligible launch of the 80- and 84-row direct tiles (variants 16 and 26) on the F(4,3) tile over weights
+    // padded to whole 32-channel columns (conv_mfma.hip: f43_plan): 0 never, 1 where the measured table
     // conv_tuned_wino4_pad.h has a row, 2 every eligible launch (tests); MVLM_WINOGRAD4_PADDED (default 1)
     int conv_winograd4_padded = [] { const char* e = getenv("MVLM_WINOGRAD4_PADDED"); return (e && e[0] >= '0' && e[0] <= '2' && !e[1]) ? e[0] - '0' : 1; }();
-    long long conv_wino4_padded_launches = 0;  // launches handed over that way (mvlm_conv_wino4_padded_launches)
+    long long conv_wino4_padded_launches = 0;  // launches run that way (mvlm_conv_wino4_padded_launches)
     // the padded weights such launches read: [0] the layer of the mvlm_conv2d / mvlm_conv_bench call in flight, then the loaded
     // network's slots (mvlm_cnn_load); ConvArgs::wino4_pad is 1 + the index
     std::vector<ConvWino4Pad> conv_wino4_pads = std::vector<ConvWino4Pad>(1);
-    // the variant code a launcher ran the launch on where that is not the code it was called for (-1: it is); mvlm_launch_conv
-    // clears it before the launch and reports it afterwards
-    int conv_launch_ran_as = -1;
     std::vector<ConvOverride> conv_overrides;  // tools/tune_in_network.py: kernel variant per (shape, kind), before any table
     // Conv kernels whose launch attributes are set on this ctx's device.  The 64 bits: a base variant's bit is its id (all below
     // MVLM_CONV_FAST_ATTR_BIT0, none MVLM_CONV_WINO4_ATTR_BIT or MVLM_CONV_WINO4_WIDE_ATTR_BIT: conv_mfma.hip asserts it), the F(4,3)
@@ -471,7 +468,7 @@ int mvlm_launch_conv_fast(mvlm_ctx* ctx, const ConvArgs& a, const unsigned short
 constexpr int MVLM_CONV_VARIANT_WINO4 = 2048;
 constexpr int MVLM_CONV_WINO4_ATTR_BIT = 41, MVLM_CONV_WINO4_WIDE_ATTR_BIT = 42, MVLM_CONV_FAST_ATTR_BIT0 = 54;
 // The wide shape of that tile (conv_inst_q1.hip: 64 output channels x 8 rows x 32 pixels on one staged input tile) is no variant of
-// its own: code 2048's launcher takes it where the context's switch is on and the layer's output channels come in 64s.  Everything
+// its own: the dispatcher takes it for code 2048 where the context's switch is on and the layer's output channels come in 64s.  Everything
 // else about the layer is what the 32 x 16 shape asks, so this is asked of launches already routed to code 2048.
 inline bool mvlm_conv_wino4_wide_shape_ok(int cout_pad, int H) { return cout_pad > 0 && cout_pad % 64 == 0 && H % 16 == 0; }
 // The cout stride of the padded F(4,3) weights (ConvWino4Pad): whole 32-channel columns of the tile.  84 -> 96, 80 -> 96.

@@ -48,8 +48,12 @@
 //   3. the in-network table conv_tuned_net.h, 4. the single-layer table conv_tuned.h - both by the entry of the smallest
 //      tuned batch >= the launch's, 5. the rules (pick_variant_rules).
 // Launches with a fused argmax, an upsampled input or a parity output and the 2x2 layers go straight to the rules: one
-// kernel can serve them.  Every decision is pinned by tests/golden/conv_routing.txt and, for launches that carry the F(4,3)
-// weights, tests/golden/conv_routing_wino4.txt (tests/test_conv_routing_cpu.py).
+// kernel can serve them.
+//   6. With the variant code in hand, however it was chosen, f43_plan() decides how the launch runs on the F(4,3) tile: code 2048 on
+//      the tile's wide workgroup shape (conv_inst_q1.hip) or its 32 x 16 shape (conv_inst_q0.hip), and a launch of the 80- or 84-row
+//      direct tile on the 32 x 16 shape over weights padded to whole 32-channel columns.  The launchers only launch.
+// Every decision is pinned by tests/golden/conv_routing.txt and, for launches that carry the F(4,3) weights,
+// tests/golden/conv_routing_wino4.txt; step 6 by tests/golden/conv_routing_f43.txt (tests/test_conv_routing_cpu.py).
 #include <algorithm>
 #include <array>
 #include <cstdlib>
@@ -67,6 +71,8 @@
 #include "conv_pair_tuned.h"
 #include "conv_tuned_wino.h"
 #include "conv_tuned_wino4.h"
+#include "conv_wino4_wide_hold.h"
+#include "conv_tuned_wino4_pad.h"
 
 // one launcher per variant, defined in conv_inst_g*.hip
 #define X(id, name, ...)                                         \
@@ -74,7 +80,9 @@
     int mvlm_conv_pair_launch_##id(mvlm_ctx* ctx, const ConvArgs& a0, const ConvArgs& a1);
 MVLM_CONV_VARIANTS(X)
 #undef X
-int mvlm_conv_launch_wino4(mvlm_ctx* ctx, const ConvArgs& a);  // the F(4,3) tile's, defined in conv_inst_q0.hip
+// the F(4,3) tile's two workgroup shapes: 32 x 16 (conv_inst_q0.hip) and wide (conv_inst_q1.hip)
+int mvlm_conv_launch_wino4_narrow(mvlm_ctx* ctx, const ConvArgs& a);
+int mvlm_conv_launch_wino4_wide(mvlm_ctx* ctx, const ConvArgs& a);
 
 // ---- the two Winograd forms (common.h: WinoForm) ----------------------------------------------------------------------------
 const WinoForm& mvlm_wino_form(int form) {
@@ -114,7 +122,7 @@ constexpr ConvVariantInfo VARIANTS[] = {
 #define X(id, name, ...) variant_info<id, __VA_ARGS__>(name, mvlm_conv_launch_##id, mvlm_conv_pair_launch_##id),
     MVLM_CONV_VARIANTS(X)
 #undef X
-    variant_info<MVLM_CONV_VARIANT_WINO4, MVLM_CONV_WINO4_CFG>(MVLM_CONV_WINO4_NAME, mvlm_conv_launch_wino4, nullptr),  // (the last row)
+    variant_info<MVLM_CONV_VARIANT_WINO4, MVLM_CONV_WINO4_CFG>(MVLM_CONV_WINO4_NAME, mvlm_conv_launch_wino4_narrow, nullptr),  // (the last row; f43_plan chooses the shape)
 };
 
 // the row of this base id or of the F(4,3) tile's code, or null
@@ -239,14 +247,53 @@ bool form_serves_slot(int form, int ksize, int cin_pad, int cout_pad, bool bn_bo
     return false;
 }
 
-// the variant a measured Winograd table ({cin_pad, cout_pad, size, kind, min_batch, variant}) sends this key to, or -1
+// The row of a measured F(4,3) / Winograd table for this (shape, kind), or null: every such table begins {cin_pad, cout_pad, size,
+// kind} and has one row per key.  What else a row says (min_batch, variant) is the caller's to apply.
+template <class E>
+const E* shape_kind_row(const E* table, int n, int cin_pad, int cout_pad, int size, int kind) {
+    for (int i = 0; i < n; ++i)
+        if (table[i].cin_pad == cin_pad && table[i].cout_pad == cout_pad && table[i].size == size && table[i].kind == kind) return &table[i];
+    return nullptr;
+}
+
+// the variant a measured Winograd table ({..., min_batch, variant}) sends this key to, or -1
 template <class E>
 int wino_table_variant(const E* table, int n, const ConvKey& k) {
-    for (int i = 0; i < n; ++i) {
-        const E& e = table[i];
-        if (e.cin_pad == k.cin_pad && e.cout_pad == k.cout_pad && e.size == k.size && e.kind == k.kind && k.batch >= e.min_batch) return e.variant;
+    const E* e = shape_kind_row(table, n, k.cin_pad, k.cout_pad, k.size, k.kind);
+    return e && k.batch >= e->min_batch ? e->variant : -1;
+}
+
+// ---- how a launch runs on the F(4,3) tile -------------------------------------------------------------------------------------
+// A pure function of the context's settings, the launch, its variant row and its K parts.
+//   wide / narrow: the row is the F(4,3) tile's (code 2048: routed, overridden or forced).  Wide where the context's switch is on,
+//     the output channels come in 64s and the (shape, kind) did not run slower that way inside the network (conv_wino4_wide_hold.h).
+//   padded: the row is a 3x3 direct tile with a 16-row strip (the 80- and 84-row tiles: their cout_pad is no multiple of 32, so
+//     tile_fits never sends such a layer to the F(4,3) tile) and the launch carries weights and bias padded to whole 32-channel
+//     columns (ConvArgs::wino4_pad).  A plain 3x3 layer writing a plain tensor, not forced, no mode at 0, and padded mode 2 or a row
+//     of conv_tuned_wino4_pad.h from its min_batch on: the kernel guards every store by cout, and the columns beyond cout_pad
+//     multiply zeros.
+enum class F43Plan { none, narrow, wide, padded };
+
+F43Plan f43_plan(const mvlm_ctx* ctx, const ConvArgs& a, const ConvVariantInfo& t, int kparts) {
+    const int kind = mvlm_conv_kind(a);
+    if (t.form == MVLM_WINO_F43) {
+        const bool wide = ctx->conv_winograd4_wide && mvlm_conv_wino4_wide_shape_ok(a.cout_pad, a.H) &&
+                          !shape_kind_row(MVLM_CONV_WINO4_WIDE_HOLD, MVLM_CONV_WINO4_WIDE_HOLD_N, a.cin_pad, a.cout_pad, a.H, kind);
+        return wide ? F43Plan::wide : F43Plan::narrow;
     }
-    return -1;
+    if (t.form >= 0 || !t.TAIL16 || t.KS != 3) return F43Plan::none;
+    if (a.wino4_pad <= 0 || size_t(a.wino4_pad) > ctx->conv_wino4_pads.size()) return F43Plan::none;
+    const ConvWino4Pad& pad = ctx->conv_wino4_pads[size_t(a.wino4_pad) - 1];
+    if (!pad.w || (a.bias && !pad.bias)) return F43Plan::none;
+    // a plain 3x3 layer writing a plain tensor, as the two direct tiles serve it
+    if (a.ksize != 3 || a.up_in || a.in2 || a.amax_val || a.res1 || a.res2 || a.post_scale || a.out_raw || a.pool_out || a.up_out || !a.out || a.n_par != 1 ||
+        kparts > 1 || a.H != a.W || a.H % 16 != 0 || a.cin_pad > 256)
+        return F43Plan::none;
+    if (ctx->conv_force_variant >= 0) return F43Plan::none;  // tools and tests force 16 / 26 to get the direct tile
+    if (ctx->conv_winograd == 0 || ctx->conv_winograd4 == 0 || ctx->conv_winograd4_padded == 0) return F43Plan::none;
+    if (ctx->conv_winograd4_padded == 2) return F43Plan::padded;
+    const ConvTunedWino4Pad* e = shape_kind_row(MVLM_CONV_TUNED_WINO4_PAD, MVLM_CONV_TUNED_WINO4_PAD_N, a.cin_pad, a.cout_pad, a.H, kind);
+    return e && a.B >= e->min_batch ? F43Plan::padded : F43Plan::none;
 }
 
 }  // namespace
@@ -466,14 +513,25 @@ int mvlm_launch_conv(mvlm_ctx* ctx, const ConvArgs& a, int* variant_out) {
     b.kparts = d.kparts;
     if (form) b.w = a.*form->weights;
     if (!d.row) return ctx->fail("conv: unreachable variant");
-    ctx->conv_launch_ran_as = -1;
-    const int rc = d.row->launch(ctx, b);  // (check_variant<> refuses what the tile cannot serve)
-    // a launcher that ran the launch on another tile's kernel (variants 16 and 26 on the F(4,3) tile: conv_inst_q0.hip) noted its
-    // code: a profile record counts the FLOPs of the kernel that ran
-    if (variant_out && ctx->conv_launch_ran_as >= 0) *variant_out = ctx->conv_launch_ran_as;
-    return rc;
+    // (check_variant<> at the launch refuses what the tile cannot serve)
+    switch (f43_plan(ctx, a, *d.row, d.kparts)) {
+    case F43Plan::wide:
+        if (mvlm_conv_launch_wino4_wide(ctx, b)) return 1;
+        ++ctx->conv_wino4_wide_launches;
+        return 0;
+    case F43Plan::padded: {
+        const ConvWino4Pad& pad = ctx->conv_wino4_pads[size_t(a.wino4_pad) - 1];
+        b.w = pad.w;
+        b.bias = a.bias ? pad.bias : nullptr;
+        b.cout_pad = mvlm_conv_wino4_padded_cout(a.cout_pad);  // (cout stays: the epilogue stores no channel beyond it)
+        if (mvlm_conv_launch_wino4_narrow(ctx, b)) return 1;
+        ++ctx->conv_wino4_padded_launches;
+        if (variant_out) *variant_out = MVLM_CONV_VARIANT_WINO4;  // a profile record counts the FLOPs of the kernel that ran
+        return 0;
+    }
+    default: return d.row->launch(ctx, b);  // (narrow: the F(4,3) row's own launcher)
+    }
 }
-
 
 // ---- tuning hooks (tools/tune_in_network.py) --------------------------------------------------------------------------------
 // can kernel variant `variant` (>= 256: a split-K variant with its input channels over 2 / 4 workgroups) run a 3x3 layer of

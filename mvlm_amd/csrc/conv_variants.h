@@ -72,14 +72,14 @@
 // (kx, cin) on the tile geometry of conv3x3_c32_t16x32, host-transformed weights [18][cin_pad][cout_pad].  Instantiated in
 // conv_inst_q0.hip, built into build/wino4/ (occupancy table tests/golden/kernel_occupancy_wino4.json).  It has no base id: what
 // every id in 0..1023 is called and serves is pinned by tests/golden/conv_routing.txt, so the tile has a code of its own beyond
-// that range (common.h: MVLM_CONV_VARIANT_WINO4), one launcher, mvlm_conv_launch_wino4, and no pair form.  In the dispatcher it is
+// that range (common.h: MVLM_CONV_VARIANT_WINO4), one launcher, mvlm_conv_launch_wino4_narrow, and no pair form.  In the dispatcher it is
 // a row of the variant table like every variant below (conv_mfma.hip: VARIANTS, decode_variant).
 #define MVLM_CONV_WINO4_NAME "conv3x3q_c32_t16x32"
 #define MVLM_CONV_WINO4_CFG Cfg<32, 32, 16, 1, 34, 4>
 // The same tile's wide workgroup shape: 64 cout x 8 rows x 32 pixels, wave w = (cout half w >> 1, row quad w & 1).  A staged
 // input tile then serves 64 output channels instead of 32: half the staging jobs (loads, BatchNorm, transform, LDS writes) per
 // MFMA, the same six accumulators per wave, the same workgroup count per layer and every output bit the same.  No variant code
-// of its own: mvlm_conv_launch_wino4 takes it where cout_pad % 64 == 0 and mvlm_cnn_set_winograd4_wide is on.  Instantiated in
+// of its own: the dispatcher (f43_plan) takes it where cout_pad % 64 == 0 and mvlm_cnn_set_winograd4_wide is on.  Instantiated in
 // conv_inst_q1.hip, built into build/wino4w/ (occupancy table tests/golden/kernel_occupancy_wino4w.json).
 #define MVLM_CONV_WINO4_WIDE_CFG Cfg<64, 32, 8, 1, 34, 4>
 #define MVLM_CONV_VARIANTS(X) \

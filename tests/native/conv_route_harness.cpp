@@ -11,6 +11,10 @@
 // features with and without w_wino4, code 2048 as override and as forced variant, and the per-variant queries for the codes
 // 1024..4200 (tests/golden/conv_routing_wino4.txt).  There a refused launch prints a bare E: which launches are refused, which
 // succeed and where they land is pinned, not the wording.
+// Run with the argument "f43", it prints only how launches run on the F(4,3) tile once they have their variant code (conv_mfma.hip:
+// f43_plan), driven through mvlm_launch_conv: the tile's wide or 32 x 16 workgroup shape for code 2048, and the 80- / 84-row direct
+// tiles' launches on that tile over padded weights (tests/golden/conv_routing_f43.txt; the format is in its first lines).  The tile
+// has a stub per workgroup shape; in the first two passes both report as code 2048, so those goldens do not see the shape.
 #include <cstdio>
 #include <cstring>
 #include <functional>
@@ -27,6 +31,8 @@
 #include "../../mvlm_amd/csrc/conv_pair_tuned.h"
 #include "../../mvlm_amd/csrc/conv_tuned_wino.h"
 #include "../../mvlm_amd/csrc/conv_tuned_wino4.h"
+#include "../../mvlm_amd/csrc/conv_wino4_wide_hold.h"
+#include "../../mvlm_amd/csrc/conv_tuned_wino4_pad.h"
 
 // ---- stubs ------------------------------------------------------------------------------------------------------------------
 hipError_t hipSetDevice(int) { return hipSuccess; }
@@ -41,12 +47,15 @@ namespace {
 struct Reached {
     int id = -1, kparts0 = 0, kparts1 = 0;
     const float* w = nullptr;
+    char f43_shape = 0;  // 'n' / 'w': the F(4,3) tile's 32 x 16 / wide stub
+    const float* bias = nullptr;
+    int cout_pad = 0;
 } g_reached;
 }  // namespace
 
 #define X(id, name, ...)                                                                    \
     int mvlm_conv_launch_##id(mvlm_ctx*, const ConvArgs& a) {                               \
-        g_reached = {id, a.kparts, 0, a.w};                                                 \
+        g_reached = {id, a.kparts, 0, a.w, 0, a.bias, a.cout_pad};                          \
         return 0;                                                                           \
     }                                                                                       \
     int mvlm_conv_pair_launch_##id(mvlm_ctx*, const ConvArgs& a0, const ConvArgs& a1) {     \
@@ -55,8 +64,12 @@ struct Reached {
     }
 MVLM_CONV_VARIANTS(X)
 #undef X
-int mvlm_conv_launch_wino4(mvlm_ctx*, const ConvArgs& a) {
-    g_reached = {MVLM_CONV_VARIANT_WINO4, a.kparts, 0, a.w};
+int mvlm_conv_launch_wino4_narrow(mvlm_ctx*, const ConvArgs& a) {
+    g_reached = {MVLM_CONV_VARIANT_WINO4, a.kparts, 0, a.w, 'n', a.bias, a.cout_pad};
+    return 0;
+}
+int mvlm_conv_launch_wino4_wide(mvlm_ctx*, const ConvArgs& a) {
+    g_reached = {MVLM_CONV_VARIANT_WINO4, a.kparts, 0, a.w, 'w', a.bias, a.cout_pad};
     return 0;
 }
 
@@ -258,9 +271,192 @@ ConvArgs feature_args(const Shape& s, int feature, int batch) {
     return a;
 }
 
+// ---- the third pass: how a launch runs on the F(4,3) tile (conv_mfma.hip: f43_plan) ----------------------------------------------
+float g_pad_w, g_pad_bias, g_bias;
+std::set<std::string> g_f43_failed;  // the statements of the golden's first lines that did not hold
+void expect(bool ok, const std::string& statement) {
+    if (!ok) g_f43_failed.insert(statement);
+}
+
+// One launch through mvlm_launch_conv.  The token: "<variant_out>" or "E[@<variant_out>]"; where it ran - n / w the F(4,3) tile's
+// 32 x 16 / wide stub, p<cout_pad> the 32 x 16 stub with the pad entry's weights, d another tile's stub, - none; "!" if the stub's
+// weights, bias or cout_pad are not what that way of running gives it; then the deltas of the two counters, wide/padded.
+struct F43Run {
+    std::string token;
+    char where;
+    int variant_out;
+    int cout_pad;
+    long long wide, padded;
+};
+F43Run f43_run(mvlm_ctx& ctx, ConvArgs a) {
+    if (a.pool_hint && !a.pool_out && mvlm_conv_can_pool(&ctx, a)) a.pool_out = &g_dummy;  // as the network does
+    const long long wide0 = ctx.conv_wino4_wide_launches, padded0 = ctx.conv_wino4_padded_launches;
+    g_reached = Reached();
+    ctx.err.clear();
+    int v = -9;
+    const int rc = mvlm_launch_conv(&ctx, a, &v);
+    F43Run r;
+    r.where = g_reached.id == -1 ? '-' : !g_reached.f43_shape ? 'd' : g_reached.w == &g_pad_w ? 'p' : g_reached.f43_shape;
+    r.variant_out = v;
+    r.cout_pad = g_reached.cout_pad;
+    r.wide = ctx.conv_wino4_wide_launches - wide0;
+    r.padded = ctx.conv_wino4_padded_launches - padded0;
+    r.token = rc ? "E" + (v != -9 ? "@" + std::to_string(v) : std::string()) : std::to_string(v);
+    r.token += r.where;
+    bool as_given = true;
+    if (r.where == 'p') {
+        r.token += std::to_string(r.cout_pad);
+        as_given = g_reached.f43_shape == 'n' && g_reached.bias == (a.bias ? &g_pad_bias : nullptr);
+    } else if (r.where == 'n' || r.where == 'w') {
+        as_given = g_reached.w == a.w_wino4 && g_reached.bias == a.bias && r.cout_pad == a.cout_pad;
+    } else if (r.where == 'd') {
+        as_given = (g_reached.w == a.w || g_reached.w == a.w_wino) && g_reached.bias == a.bias && r.cout_pad == a.cout_pad;
+    }
+    if (!as_given || (rc != 0) != (r.where == '-')) r.token += "!";
+    r.token += " " + std::to_string(r.wide) + "/" + std::to_string(r.padded);
+    return r;
+}
+
+int f43_pass() {
+    mvlm_ctx ctx;
+    Grouped g;
+    const auto reset = [&] {
+        set_state(ctx, DEFAULT_STATE);
+        ctx.conv_winograd4_wide = 1;
+        ctx.conv_winograd4_padded = 1;
+    };
+    reset();
+    std::printf("# How a launch runs on the F(4,3) tile once it has its variant code, through mvlm_launch_conv.  A result, run-length encoded over\n"
+                "# the batches: <variant_out> or E[@<variant_out>], then n = the tile's 32 x 16 stub, w = its wide stub, p<cout_pad> = the 32 x 16\n"
+                "# stub with the pad entry's weights, its bias where the launch has one, and this cout_pad, d = another tile's stub, - = no stub\n"
+                "# (refused); ! = the stub did not get what that way of running gives it; then <wide launches>/<padded launches> counted.\n"
+                "# This file is written by the code it pins.  What can be read off the parent's launchers by eye, and is checked by the harness:\n"
+                "#  a. the keys of conv_wino4_wide_hold.h reach n at every batch with the switch on, and w in their other kinds;\n"
+                "#  b. k3 256>84 @128 and k3 256>80 @128 (kind 0) reach p96 from batch 96 on and d below in padded mode 1 (p1w1q1f-1), p96 at every\n"
+                "#     batch in mode 2 (p2w1q1f-1), and never with padded mode 0, Winograd or F(4,3) mode 0, or the variant forced;\n"
+                "#  c. a launch with one more feature, one that lacks the pad entry, its weights or its bias, 260 input channels or a size that\n"
+                "#     is no multiple of 16 never reaches the F(4,3) tile, and both counters stay 0 (no_bias is the exception: it reaches p);\n"
+                "#  d. variant_out is 2048 exactly where p is printed; a wide launch counts 1/0, a padded one 0/1, any other 0/0.\n"
+                "# (A launch refused before any stub, as at batch 40000 for its tensors' size, is outside a. to c.)\n");
+
+    // -- the wide shape
+    std::printf("# -- code 2048: <shape> <kind> {<how>:s<wide switch>}, how = q2 routed by F(4,3) mode 2, f forced; the shapes of conv_tuned_wino4.h\n"
+                "# and conv_wino4_wide_hold.h, output channels not in 64s (32, 96), and @40, a size the tile does not divide (routed elsewhere; forced\n"
+                "# and refused only at the real launch)\n");
+    g_wino4 = true;
+    std::set<Shape> wide_set = {Shape{3, 64, 32, 64}, Shape{3, 64, 96, 64}, Shape{3, 64, 64, 40}};
+    for (int i = 0; i < MVLM_CONV_TUNED_WINO4_N; ++i) wide_set.insert({3, MVLM_CONV_TUNED_WINO4[i].cin_pad, MVLM_CONV_TUNED_WINO4[i].cout_pad, MVLM_CONV_TUNED_WINO4[i].size});
+    for (int i = 0; i < MVLM_CONV_WINO4_WIDE_HOLD_N; ++i) wide_set.insert({3, MVLM_CONV_WINO4_WIDE_HOLD[i].cin_pad, MVLM_CONV_WINO4_WIDE_HOLD[i].cout_pad, MVLM_CONV_WINO4_WIDE_HOLD[i].size});
+    for (const Shape& s : wide_set)
+        for (int kind = 0; kind < 3; ++kind) {
+            int held = 0, held_other_kind = 0;
+            for (int i = 0; i < MVLM_CONV_WINO4_WIDE_HOLD_N; ++i) {
+                const ConvWino4WideHold& e = MVLM_CONV_WINO4_WIDE_HOLD[i];
+                if (Shape{3, e.cin_pad, e.cout_pad, e.size} == s) (e.kind == kind ? held : held_other_kind) = 1;
+            }
+            for (int forced = 0; forced < 2; ++forced)
+                for (int sw = 0; sw < 2; ++sw) {
+                    ctx.conv_winograd4 = forced ? 1 : 2;
+                    ctx.conv_force_variant = forced ? MVLM_CONV_VARIANT_WINO4 : -1;
+                    ctx.conv_winograd4_wide = sw;
+                    g.add("wide " + shape_label(s) + " kind" + std::to_string(kind), std::string(forced ? "f" : "q2") + ":s" + std::to_string(sw), runs([&](int b) {
+                        const F43Run r = f43_run(ctx, make_args(s, kind, b));
+                        if (sw && held && r.where != '-') expect(r.where == 'n', "a");
+                        if (sw && !held && held_other_kind && r.where != '-') expect(r.where == 'w', "a");
+                        if (!sw) expect(r.where != 'w', "a");
+                        expect(r.padded == 0 && r.wide == (r.where == 'w'), "d");
+                        return r.token;
+                    }));
+                }
+        }
+    g.print();
+    reset();
+    g_wino4 = false;  // (a layer on 80 or 84 rows has no F(4,3) weights of its own: the tile does not divide it)
+
+    // -- the padded launches
+    ctx.conv_wino4_pads = {ConvWino4Pad{}, ConvWino4Pad{&g_pad_w, &g_pad_bias}, ConvWino4Pad{nullptr, &g_pad_bias}, ConvWino4Pad{&g_pad_w, nullptr}};
+    const int PAD_FULL = 2, PAD_NO_W = 3, PAD_NO_BIAS = 4;  // (ConvArgs::wino4_pad is 1 + the index)
+    const auto padded_args = [&](const Shape& s, int b) {
+        ConvArgs a = make_args(s, 0, b);
+        a.bias = &g_bias;
+        a.wino4_pad = PAD_FULL;
+        return a;
+    };
+    const auto check_d = [](const F43Run& r) {
+        expect((r.where == 'p') == (r.variant_out == MVLM_CONV_VARIANT_WINO4), "d");
+        expect(r.wide == 0 && r.padded == (r.where == 'p'), "d");
+    };
+    const Shape pad_shapes[] = {Shape{3, 256, 84, 128}, Shape{3, 256, 80, 128}, Shape{3, 8, 84, 32}, Shape{3, 64, 80, 32}};
+    std::printf("# -- the 84- / 80-row tiles' launches with a pad entry: <shape> {p<padded mode>w<Winograd mode>q<F(4,3) mode>f<conv_force_variant>}\n");
+    for (const Shape& s : pad_shapes) {
+        const bool in_table = std::get<1>(s) == 256;
+        const int direct = std::get<2>(s) == 84 ? 26 : 16;
+        for (int pm = 0; pm < 3; ++pm)
+            for (int wm = 0; wm < 2; ++wm)
+                for (int qm = 0; qm < 2; ++qm)
+                    for (int force : {-1, -2, direct}) {
+                        set_state(ctx, State{"", wm, force, qm});
+                        ctx.conv_winograd4_padded = pm;
+                        const std::string name = "p" + std::to_string(pm) + "w" + std::to_string(wm) + "q" + std::to_string(qm) + "f" + std::to_string(force);
+                        g.add("padded " + shape_label(s), name, runs([&](int b) {
+                            const F43Run r = f43_run(ctx, padded_args(s, b));
+                            check_d(r);
+                            if (r.where == 'p') expect(r.cout_pad == 96, "b");
+                            if (r.where == '-') return r.token;
+                            if (pm == 0 || wm == 0 || qm == 0 || force >= 0) expect(r.where == 'd' && r.variant_out == direct, "b");
+                            else if (force == -1 && in_table) expect(pm == 2 || b >= 96 ? r.where == 'p' : r.where == 'd' && r.variant_out == direct, "b");
+                            return r.token;
+                        }));
+                    }
+    }
+    g.print();
+    reset();
+
+    std::printf("# -- the same in padded mode 2, one thing changed: <shape> {<what>}\n");
+    ctx.conv_winograd4_padded = 2;
+    using Change = std::function<void(ConvArgs&)>;
+    const std::pair<const char*, Change> changes[] = {
+        {"none", [](ConvArgs&) {}},
+        {"res1", [](ConvArgs& a) { a.res1 = &g_dummy, a.res1_ctot = a.cout_pad; }},
+        {"res2", [](ConvArgs& a) { a.res2 = &g_dummy, a.res2_ctot = a.cout_pad; }},
+        {"post_scale", [](ConvArgs& a) { a.post_scale = a.post_shift = &g_dummy; }},
+        {"out_raw", [](ConvArgs& a) { a.out_raw = &g_dummy, a.raw_ctot = a.cout_pad; }},
+        {"up_out1", [](ConvArgs& a) { a.up_out = 1, a.skip = &g_dummy, a.skip_ctot = a.cout_pad; }},
+        {"amax_val", [](ConvArgs& a) { a.amax_val = &g_dummy, a.amax_idx = &g_dummy_int; }},
+        {"in2", [](ConvArgs& a) { a.in2 = &g_dummy, a.in2_ctot = a.cin_pad; }},
+        {"pool_out", [](ConvArgs& a) { a.pool_hint = 1, a.pool_out = &g_dummy, a.pool_ctot = a.cout_pad; }},
+        {"wino4_pad0", [](ConvArgs& a) { a.wino4_pad = 0; }},
+        {"wino4_pad_beyond", [](ConvArgs& a) { a.wino4_pad = 5; }},
+        {"pad_without_w", [&](ConvArgs& a) { a.wino4_pad = PAD_NO_W; }},
+        {"pad_without_bias", [&](ConvArgs& a) { a.wino4_pad = PAD_NO_BIAS; }},
+        {"no_bias", [](ConvArgs& a) { a.bias = nullptr; }},
+        {"no_bias_pad_without_bias", [&](ConvArgs& a) { a.bias = nullptr, a.wino4_pad = PAD_NO_BIAS; }},
+        {"cin_pad260", [](ConvArgs& a) { a.cin = a.cin_pad = a.in_ctot = 260; }},
+        {"@40", [](ConvArgs& a) { a.H = a.W = 40; }},
+    };
+    for (const Shape& s : pad_shapes)
+        for (const auto& c : changes) {
+            const std::string what = c.first;
+            g.add("padded " + shape_label(s), what, runs([&](int b) {
+                ConvArgs a = padded_args(s, b);
+                c.second(a);
+                const F43Run r = f43_run(ctx, a);
+                check_d(r);
+                if (what == "none" || what.rfind("no_bias", 0) == 0) expect(r.where == 'p' || r.where == '-', "c");
+                else expect((r.where == 'd' || r.where == '-') && r.wide == 0 && r.padded == 0, "c");
+                return r.token;
+            }));
+        }
+    g.print();
+
+    for (const std::string& f : g_f43_failed) std::fprintf(stderr, "statement %s of the first lines does not hold\n", f.c_str());
+    return g_f43_failed.empty() ? 0 : 1;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
+    if (argc > 1 && !std::strcmp(argv[1], "f43")) return f43_pass();
     g_wino4 = argc > 1 && !std::strcmp(argv[1], "wino4");
     const int n_features = g_wino4 ? 10 : 9;  // (no_w_wino4 says something in the second pass only)
     mvlm_ctx ctx;

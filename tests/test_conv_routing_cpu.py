@@ -12,6 +12,13 @@ features with and without those weights, code 2048 as tuning override and as for
 the codes 1024..4200.  That output must equal tests/golden/conv_routing_wino4.txt byte for byte.  It prints a refused launch
 without its message, so it pins which launches are refused, which succeed and on which kernel they land, not the wording.
 
+Run with the argument "f43", the harness prints only what the dispatcher decides once a launch has its variant code (f43_plan): which
+workgroup shape of the F(4,3) tile a launch of code 2048 takes (the wide switch, the shape, conv_wino4_wide_hold.h), and which
+launches of the 80- and 84-row direct tiles run on that tile over padded weights (the three modes, a forced variant, every feature
+that rules it out, conv_tuned_wino4_pad.h), with variant_out and the two launch counters.  That output must equal
+tests/golden/conv_routing_f43.txt byte for byte.  Its first lines list what a reader can check against the launchers this
+decision was moved out of; the harness checks those statements itself and exits non-zero where one does not hold.
+
 The goldens are a function of the committed tuned tables and of the variant list: a retune or a new variant regenerates them
 (run the harness built as below and keep its output) - a change of the dispatcher's code alone must not move them."""
 import shutil
@@ -28,7 +35,7 @@ HOST = ["--offload-host-only", "-std=c++17", "-O1", "-Wall", "-Wno-unused-value"
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    """The harness binary, built once for both tests."""
+    """The harness binary, built once for the three tests."""
     if HIPCC is None:
         pytest.skip("needs hipcc")
     tmp_path = tmp_path_factory.mktemp("conv_route")
@@ -63,3 +70,7 @@ def test_dispatcher_decisions_equal_the_golden(harness):
 
 def test_dispatcher_decisions_with_f43_weights_equal_the_golden(harness):
     _equals_golden(harness, ["wino4"], "conv_routing_wino4.txt")
+
+
+def test_f43_plan_decisions_equal_the_golden(harness):
+    _equals_golden(harness, ["f43"], "conv_routing_f43.txt")

@@ -1,7 +1,7 @@
 """-m gpu: the 84- and 80-row layers (conv6 / conv10: 3x3 + bias, cout_pad no multiple of 32) on the F(4,3) Winograd tile over weights
-padded to whole 32-channel columns (conv_inst_q0.hip: mvlm_conv_launch_wino4_padded, mvlm_cnn_set_winograd4_padded).
+padded to whole 32-channel columns (conv_mfma.hip: f43_plan, mvlm_cnn_set_winograd4_padded).
 
-The dispatcher still names variant 26 / 16 for them; the hand-over happens in those variants' launchers.  Single layers against torch
+The dispatcher still names variant 26 / 16 for them and then runs the launch on the tile (f43_plan).  Single layers against torch
 float64 with the switch at 2 (the bound of test_gpu_winograd4.py for the tile), the gates that leave the direct tile's launches and
 bits alone, the 84-landmark network at 2 views with its profile records and a replayed graph, and the benchmark's size once with
 the default switch against switch 0."""
@@ -68,7 +68,7 @@ def _layer_data(cin, cout, size, batch, with_bias):
 # (8, 84, 32, 1): two chunks (no steady loop), every border in one workgroup, the last column of workgroups holds 20 live channels
 # of 32; (73, 84, 64, 3): a padded last chunk, interior tile edges, several images - a store past channel 83 of an image lands in
 # the next image (or in the sentinel image behind the last) and shows in the compare; (256, 84, 32, 1): the LDS BatchNorm table's
-# limit; (64, 73, 32, 2): cout_pad 80, the 80-row tile's launcher (variant 16), 9 live channels in the last column.
+# limit; (64, 73, 32, 2): cout_pad 80, the 80-row tile (variant 16), 9 live channels in the last column.
 # Without a bias mvlm_conv2d packs 84 channels as cout_pad 96 (the 84-row tile is a conv + bias tile), and the dispatcher itself
 # sends the layer to the tile under F(4,3) mode 2: the same kernel, cout 84 of cout_pad 96, no bias vector; no padded launch.
 LAYER_CASES = [

@@ -27,7 +27,7 @@ beats the F(2,3) tile, the pair launch or the direct tile that serves it otherwi
 shape switch (mvlm_cnn_set_winograd4_wide) at 0 and at 1, alternating, and every (shape, kind) whose launches on code 2048 the
 wide shape takes (mvlm_conv_wino4_wide_serves) is listed with its time per pass under either setting, then the sum of the
 convolution kernels of a pass.  A key that the wide shape makes slower by more than --min-gain is marked; --write-header lists
-the keys marked at the largest batch in conv_wino4_wide_hold.h, which the tile's launcher keeps on the 32 x 16 shape.  A key the
+the keys marked at the largest batch in conv_wino4_wide_hold.h, which the dispatcher keeps on the 32 x 16 shape.  A key the
 header already holds runs on that shape under either setting here and cannot be marked again, so its row is carried over: to
 measure it afresh, take it out of the header and build first.  --f43-mode 2 (default) puts every key the tile serves on it, 1
 leaves the pass to the measured table (no launch of the tile below 96 views).
@@ -435,8 +435,8 @@ def write_padded_header(rows, batch, hold=96):
     keep = {k: rs for k, rs in won.items() if all(r["faster"] for r in rs)}
     lines = ["// GENERATED by tools/tune_in_network.py --winograd4-padded --write-header on an MI355X: the (shape, kind) keys of the 80- and 84-row",
              "// direct tiles (variants 16 and 26) whose launches ran faster, by more than 2 %, on the F(4,3) Winograd tile over weights padded to",
-             "// whole 32-channel columns, timed INSIDE a forward pass.  The two tiles' launchers (conv_inst_g3.hip, conv_inst_g12.hip) hand such a",
-             "// launch to mvlm_conv_launch_wino4_padded (conv_inst_q0.hip).  {cin_pad, cout_pad, size, kind, min_batch}: from min_batch views on.",
+             "// whole 32-channel columns, timed INSIDE a forward pass.  The dispatcher (conv_mfma.hip: f43_plan) runs such a launch on that tile's",
+             "// 32 x 16 workgroup shape over the padded weights.  {cin_pad, cout_pad, size, kind, min_batch}: from min_batch views on.",
              f"// HELD: every row at {hold} views, the correctness gate of conv_tuned_wino4.h (DESIGN 4.1), not a timing result.",
              "#ifndef MVLM_CONV_TUNED_WINO4_PAD_H", "#define MVLM_CONV_TUNED_WINO4_PAD_H",
              "struct ConvTunedWino4Pad {", "    short cin_pad, cout_pad, size, kind, min_batch;", "};",
@@ -463,8 +463,8 @@ def write_wide_hold_header(rows, batch):
         if not r.get("summary") and r["batch"] == batch and r["slower"]:
             held[tuple(r["key"][1:5])] = f"B{batch} {r['launches']} launches: narrow {r['narrow_us']} us, wide {r['wide_us']} us [{r['net']}]"
     lines = ["// GENERATED by tools/tune_in_network.py --winograd4-wide --write-header on an MI355X: the (shape, kind) keys whose launches on the",
-             "// F(4,3) tile ran slower on its wide workgroup shape than on the 32 x 16 shape INSIDE a forward pass, by more than 2 %.  The tile's",
-             "// launcher (conv_inst_q0.hip) keeps them on the 32 x 16 shape; every other launch with output channels in 64s takes the wide one.",
+             "// F(4,3) tile ran slower on its wide workgroup shape than on the 32 x 16 shape INSIDE a forward pass, by more than 2 %.  The",
+             "// dispatcher (conv_mfma.hip: f43_plan) keeps them on the 32 x 16 shape; every other launch with output channels in 64s takes the wide one.",
              "// {cin_pad, cout_pad, size, kind}",
              "#ifndef MVLM_CONV_WINO4_WIDE_HOLD_H", "#define MVLM_CONV_WINO4_WIDE_HOLD_H",
              "struct ConvWino4WideHold {", "    short cin_pad, cout_pad, size, kind;", "};",
