@@ -283,6 +283,40 @@ int mvlm_render_view_sheet(mvlm_ctx* ctx, const float* images_dev, int n_views, 
                            const double* rot_host, const double* landmarks_host, const uint8_t* lm_rgb_host, const uint8_t* used_host,
                            int background, int cols_in, int scale, int gap, double marker_radius, uint8_t* out_dev);
 
+/* ---- heat sheet (the view sheet's cells with the network's heatmaps laid over them; DESIGN.md 5.1, "Heat sheet") ---- */
+/* The peak of each of n_planes heatmap planes of 256 x 256 floats: its largest finite value, -inf when it has none (NaN and +-inf
+ * are not counted, so the value does not depend on the order of the reduction; +0 counts as larger than -0).
+ *   heat_dev  f32[n_planes,256,256]  on the device, 16-byte aligned
+ *   peaks_dev f32[n_planes]          on the device
+ * n_planes 1..32768.  A value out of range, a NULL or misaligned pointer set an error that starts with "heat sheet:" and launch
+ * nothing.  Only enqueues work on the launch stream. */
+int mvlm_heat_plane_peaks(mvlm_ctx* ctx, const float* heat_dev, int n_planes, float* peaks_dev);
+/* The sheet of mvlm_render_view_sheet(..., maxima_dev = NULL, ...) - the views alone, by the same code: cells, gaps, background
+ * bytes - and over it, per view pixel (v, y, x) - heat pixel [row, col] lies over image pixel [row, col] - the heatmaps:
+ *   images_dev f32[n_views,256,256,4]    mvlm_render's stack, on the device
+ *   heat_dev   f32[n_views,n_lm,256,256] as mvlm_cnn_heatmaps leaves them, on the device, 16-byte aligned
+ *   sel_host    u8[n_lm]                 0: the landmark is left out; NULL = all
+ *   lm_rgb_host u8[n_lm,3]               a colour per landmark; NULL = red (255, 0, 0)
+ *   floor, opacity                       finite, floor in [0, 1), opacity in (0, 1]
+ *   out_dev u8[height,width,4]           RGBA, alpha 255, top row first (mvlm_view_sheet_layout gives the extents)
+ * With m = the peak of plane (v, l) as mvlm_heat_plane_peaks gives it and h = heat[v, l, y, x]: among the selected landmarks in
+ * ascending order, those with m finite and > 0 and h finite are candidates with t = (double)h / (double)m; the largest t wins, the
+ * lowest index on equal t.  Without a candidate, or with the winner's t <= floor, the pixel stays as the background left it.
+ * Otherwise a = opacity * (t - floor) / (1.0 - floor) and per channel out = (int)(bg + a * ((double)col - bg) + 0.5), bg the
+ * background's byte and col the winner's colour byte as doubles; all scale x scale sheet pixels of the view pixel get the result.
+ * All of it in float64, in the operation order of csrc/heat_sheet_math.h.  No markers are drawn (the view sheet places its
+ * markers at X = b, Y = a + 1 in ray coordinates, another rule than this overlay's; the two never meet in one picture).
+ * n_lm 1..65536 and n_views * n_lm <= 32768 planes (8 GiB of heatmaps) per call; the layout is checked as
+ * mvlm_view_sheet_layout checks it and refused in its words.  A bad layout, background, floor, opacity, n_lm, plane count, a
+ * NULL images_dev / heat_dev / out_dev or a misaligned heat_dev set an error that starts with "heat sheet:" and launch nothing.
+ * Only enqueues work on the launch stream. */
+int mvlm_render_heat_sheet(mvlm_ctx* ctx, const float* images_dev, const float* heat_dev, int n_views, int n_lm,
+                           const uint8_t* sel_host /* u8[n_lm], NULL = all */, const uint8_t* lm_rgb_host /* u8[n_lm,3], NULL = (255,0,0) */,
+                           int background, int cols_in, int scale, int gap, double floor, double opacity, uint8_t* out_dev);
+/* With mvlm_render_set_profiling on, the last heat sheet's stages in milliseconds (HIP events), f32[3]: background (the views
+ * alone, with the copies of the two small tables), peak, compose.  Waits for the stream. */
+int mvlm_heat_sheet_stage_ms(mvlm_ctx* ctx, float* ms3);
+
 /* ---- PNG on the device (the views' files without the picture crossing to the host) ---- */
 /* Bytes that hold any file mvlm_png_encode writes for a picture of height x width (each 1..4096): the filtered stream
  * height * (1 + 3 * width), 10 bytes per 32 768-byte segment of it (5 of a stored block's header, 5 of the flush), and 63 of

@@ -23,6 +23,11 @@ def shard_files(files, rank: int, world: int):
     return [f for i, f in enumerate(files) if i % world == rank]
 
 
+def _index_list(text: str) -> list:
+    """"3,17,40" -> [3, 17, 40] (argparse reports what is no such list)."""
+    return [int(k) for k in text.split(",")]
+
+
 def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(prog="python -m mvlm_amd")
     parser.add_argument("-p", "--path", type=str, required=True)
@@ -70,7 +75,16 @@ def build_parser() -> argparse.ArgumentParser:
                              "to where the final landmark projects in that view (with --report a view the score filter dropped gets a "
                              "ring, and the markers carry the RANSAC branch colours)")
     parser.add_argument("--sheet-scale", type=int, default=1, choices=(1, 2, 3, 4),
-                        help="sheet pixels per view pixel of --visualize-sheet (the sheet may not exceed 4096 pixels a side)")
+                        help="sheet pixels per view pixel of --visualize-sheet and --visualize-heat (the sheet may not exceed 4096 pixels "
+                             "a side)")
+    parser.add_argument("--visualize-heat", action="store_true",
+                        help="write visualization/<stem>_<pipeline>_heat.png under the working directory for every scan: all rendered "
+                             "views in one picture with the network's heatmaps laid over them, per pixel the landmark whose value is the "
+                             "largest share of its heatmap's peak, in that landmark's colour (costs about one network pass more per scan)")
+    parser.add_argument("--heat-landmarks", type=_index_list, default=None, metavar="L,L,...",
+                        help="the landmarks --visualize-heat shows, e.g. 3,17,40 (default: all)")
+    parser.add_argument("--heat-floor", type=float, default=0.25, metavar="F",
+                        help="--visualize-heat draws a heatmap only where it exceeds this share of its peak (0 <= F < 1)")
     parser.add_argument("--point-radius", type=float, default=None, metavar="MM",
                         help="splat radius, in model units, of scans that have points but no faces (point clouds): 0.88 to 9.375, "
                              "i.e. 0.75 to 8 pixels of a view; default: automatic, from the spacing of the points (DESIGN.md 5.1)")
@@ -127,6 +141,11 @@ def main(argv=None) -> int:
     if args.visualize_sheet:
         extra["visualize_sheet"] = True
         extra["sheet_scale"] = args.sheet_scale
+    if args.visualize_heat:
+        extra["visualize_heat"] = True
+        extra["sheet_scale"] = args.sheet_scale
+        extra["heat_landmarks"] = args.heat_landmarks
+        extra["heat_floor"] = args.heat_floor
     if args.point_radius is not None:
         extra["point_radius"] = args.point_radius
     if args.png_encoder != "host":

@@ -69,6 +69,10 @@ SIGNATURES = {
                                          C.POINTER(C.c_int), C.c_char_p, C.c_int]),
     "mvlm_render_view_sheet": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, c_double_p, c_double_p, c_uint8_p,
                                          c_uint8_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p]),
+    "mvlm_heat_plane_peaks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "mvlm_render_heat_sheet": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, c_uint8_p, c_uint8_p, C.c_int, C.c_int,
+                                         C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]),
+    "mvlm_heat_sheet_stage_ms": (C.c_int, [C.c_void_p, c_float_p]),
     "mvlm_png_bound": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "mvlm_png_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                   C.POINTER(C.c_size_t)]),

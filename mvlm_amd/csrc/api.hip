@@ -88,6 +88,8 @@ extern "C" void mvlm_ctx_destroy(mvlm_ctx* ctx) {
         if (e) hipEventDestroy(e);
     for (auto e : ctx->png_events)
         if (e) hipEventDestroy(e);
+    for (auto e : ctx->heat_events)
+        if (e) hipEventDestroy(e);
     for (auto e : ctx->points_events)
         if (e) hipEventDestroy(e);
     for (auto e : ctx->cnn.sync_events)

@@ -353,6 +353,10 @@ struct mvlm_ctx {
     // PNG encoder (png_encode.hip): the five events around its four stages while render_profiling is on (mvlm_png_stage_ms)
     std::vector<hipEvent_t> png_events;
     bool png_events_valid = false;
+    // heat sheet (heat_sheet.hip): the four events around background, peak and compose while render_profiling is on
+    // (mvlm_heat_sheet_stage_ms)
+    std::vector<hipEvent_t> heat_events;
+    bool heat_events_valid = false;
     // device buffers of freed meshes, reused by the next upload: a folder of scans would otherwise pay
     // four hipMalloc + four (device-synchronising) hipFree per scan
     struct PoolEntry {
@@ -425,6 +429,11 @@ inline int mvlm_mesh_wait_ready(mvlm_ctx* ctx, const mvlm_mesh* m, hipStream_t s
 // jpeg.hip (the host parser and its declarations: jpeg_plan.h / jpeg_plan.cpp)
 int mvlm_jpeg_run(mvlm_ctx* ctx, MvlmJpegPlan& plan, const uint8_t* stage_pinned, uint8_t* rgb_dev, hipStream_t stream,
                   std::string& why, int* rounds_out);
+
+// view_sheet.hip: mvlm_render_view_sheet behind its MVLM_ENTER, for an entry point that has entered the context itself
+int mvlm_view_sheet_draw(mvlm_ctx* ctx, const float* images_dev, int n_views, const float* maxima_dev, int n_lm, const double* rot_host,
+                         const double* landmarks_host, const uint8_t* lm_rgb_host, const uint8_t* used_host, int background, int cols_in,
+                         int scale, int gap, double marker_radius, uint8_t* out_dev);
 
 // conv_mfma.hip
 constexpr long MVLM_KPARTS_MAX_TILES = 2048;  // output tiles of a launch that divides K over workgroups

@@ -161,12 +161,11 @@ extern "C" int mvlm_view_sheet_layout(int n_views, int cols_in, int scale, int g
     return 0;
 }
 
-// Checks the arguments - a bad one returns an error and launches nothing - then copies the small host tables and launches.
-extern "C" int mvlm_render_view_sheet(mvlm_ctx* ctx, const float* images_dev, int n_views, const float* maxima_dev, int n_lm,
-                                      const double* rot_host, const double* landmarks_host, const uint8_t* lm_rgb_host,
-                                      const uint8_t* used_host, int background, int cols_in, int scale, int gap, double marker_radius,
-                                      uint8_t* out_dev) {
-    MVLM_ENTER(ctx);
+// Checks the arguments - a bad one returns an error and launches nothing - then copies the small host tables and launches.  The
+// caller has entered the context: mvlm_render_view_sheet, and mvlm_render_heat_sheet (heat_sheet.hip) for its background.
+int mvlm_view_sheet_draw(mvlm_ctx* ctx, const float* images_dev, int n_views, const float* maxima_dev, int n_lm, const double* rot_host,
+                         const double* landmarks_host, const uint8_t* lm_rgb_host, const uint8_t* used_host, int background, int cols_in,
+                         int scale, int gap, double marker_radius, uint8_t* out_dev) {
     MVLM_REQUIRE(ctx, images_dev && out_dev, "view sheet: bad arguments");
     int cols = 0, rows = 0, width = 0, height = 0;
     const int code = vs_layout(n_views, cols_in, scale, gap, &cols, &rows, &width, &height);
@@ -223,4 +222,13 @@ extern "C" int mvlm_render_view_sheet(mvlm_ctx* ctx, const float* images_dev, in
                        height, reinterpret_cast<uint32_t*>(out_dev));
     MVLM_CHECK_HIP(ctx, hipGetLastError());
     return 0;
+}
+
+extern "C" int mvlm_render_view_sheet(mvlm_ctx* ctx, const float* images_dev, int n_views, const float* maxima_dev, int n_lm,
+                                      const double* rot_host, const double* landmarks_host, const uint8_t* lm_rgb_host,
+                                      const uint8_t* used_host, int background, int cols_in, int scale, int gap, double marker_radius,
+                                      uint8_t* out_dev) {
+    MVLM_ENTER(ctx);
+    return mvlm_view_sheet_draw(ctx, images_dev, n_views, maxima_dev, n_lm, rot_host, landmarks_host, lm_rgb_host, used_host, background,
+                                cols_in, scale, gap, marker_radius, out_dev);
 }

@@ -87,6 +87,9 @@ class _Stage:
 
 
 class Pipeline(abc.ABC):
+    visualize_heat = False  # (also for an object that never went through __init__: the checks below read it)
+    heat_landmarks = None
+
     def __init__(self, render_image_stack: bool = False, offscreen: bool = True, n_views: int = 8,
                  render_image_folder: Path | None = None, visualize_rays: bool = False,
                  screenshot_folder: Path | None = None, device: int = 0, shard_views: bool = False,
@@ -94,7 +97,7 @@ class Pipeline(abc.ABC):
                  visualize_img: bool = False, visualize_size: int = 1024, visualize_name: str | None = None,
                  visualize_rays_img: bool = False, visualize_rays_poses=((0, 0, 0), (0, 60, 0), (0, -60, 0)),
                  view_png_encoder: str = "host", point_radius: float | None = None, visualize_sheet: bool = False,
-                 sheet_scale: int = 1):
+                 sheet_scale: int = 1, visualize_heat: bool = False, heat_landmarks=None, heat_floor: float = 0.25):
         self.render_image_stack = render_image_stack
         self.render_image_folder = render_image_folder
         self.n_views = n_views
@@ -149,12 +152,37 @@ class Pipeline(abc.ABC):
         self.visualize_sheet = bool(visualize_sheet)
         self.sheet_scale = sheet_scale
         self.last_sheet_path = None
-        if self.visualize_sheet:
+        self.visualize_heat = bool(visualize_heat)  # (below; sheet_scale is shared)
+        if self.visualize_sheet or self.visualize_heat:
             if isinstance(sheet_scale, bool) or not isinstance(sheet_scale, (int, np.integer)) or not 1 <= sheet_scale <= 4:
                 raise ValueError(f"sheet_scale must be an integer in 1..4, not {sheet_scale!r}")
             self.sheet_scale = int(sheet_scale)
+        if self.visualize_sheet and n_views is not None:  # (a sheet beyond 4096 pixels a side: said here, with the scale that fits)
+            HipRenderer3D.view_sheet_layout(int(n_views), None, self.sheet_scale)
+        # visualize_heat: after every successful prediction the views the network saw are drawn side by side - the view sheet's
+        # cells, no markers - with the network's heatmaps laid over them: per pixel the landmark (of heat_landmarks; None: all) whose
+        # value is the largest share of its plane's peak, in its colour of utils/viewer.py's palette, shares up to heat_floor not
+        # drawn (HipRenderer3D.render_heat_sheet), into visualization/<stem>_<visualize_name>_heat.png; sheet_scale and
+        # view_png_encoder apply as for the view sheet.  The heatmaps are not kept by the prediction: the predictor's
+        # heatmaps_device runs once more on this pass's image stack, which costs about one network pass more per scan, and its
+        # tensor ([N,NL,256,256] float32: 2 GB at 96 views x 84 landmarks) lives until the picture is drawn.  Off (the default):
+        # nothing of it is launched, allocated or copied.
+        self.heat_landmarks = None
+        self.heat_floor = heat_floor
+        self.last_heat_path = None
+        if self.visualize_heat:
+            if isinstance(heat_floor, bool) or not isinstance(heat_floor, (int, float, np.integer, np.floating)) \
+                    or not (np.isfinite(heat_floor) and 0.0 <= heat_floor < 1.0):
+                raise ValueError(f"heat_floor must be a finite number in [0, 1), not {heat_floor!r}")
+            self.heat_floor = float(heat_floor)
+            if heat_landmarks is not None:
+                picked = list(heat_landmarks) if isinstance(heat_landmarks, (list, tuple, range, np.ndarray)) else None
+                if picked is None or any(isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 0 for k in picked) \
+                        or len(set(int(k) for k in picked)) != len(picked):
+                    raise ValueError(f"heat_landmarks must be None or a sequence of distinct landmark indices, not {heat_landmarks!r}")
+                self.heat_landmarks = [int(k) for k in picked]  # (the upper end: _check_visualize, once the predictor is there)
             if n_views is not None:  # (a sheet beyond 4096 pixels a side: said here, with the scale that fits)
-                HipRenderer3D.view_sheet_layout(int(n_views), None, self.sheet_scale)
+                HipRenderer3D._sheet_layout("heat sheet", int(n_views), None, self.sheet_scale, 2)
         if (self.visualize_img or self.visualize_rays_img) and (self.visualize_size < 64 or self.visualize_size > 2048 or self.visualize_size % 16):
             raise ValueError(f"visualize_size must be a multiple of 16 in 64..2048, not {visualize_size}")
         name = type(self).__name__.lower()
@@ -415,7 +443,7 @@ class Pipeline(abc.ABC):
 
         r3, p2, e3 = self.renderer_3d, self.predictor_2d, self.estimator_3d
         self._check_cloud(mesh)
-        if self.visualize_sheet:
+        if self.visualize_sheet or self.visualize_heat:
             self._check_visualize()
         n_total = int(transform_stack.shape[0])
         sharded = self.shard_views and parallel.is_distributed()
@@ -492,7 +520,8 @@ class Pipeline(abc.ABC):
             else:
                 maxima = torch.empty((p2.get_lm_count(), 0, 3), dtype=torch.float32,
                                      device=torch.device("cuda", self.device))
-            sheet_images = images if self.visualize_sheet else None  # (the stack stays where it is until the sheet is drawn)
+            # (the stack stays where it is until the sheets are drawn)
+            sheet_images = images if self.visualize_sheet or self.visualize_heat else None
             del images
             if sharded:
                 maxima = parallel.all_gather_views(maxima, n_total)
@@ -579,13 +608,31 @@ class Pipeline(abc.ABC):
             self._draw_view_sheet(mesh, sheet_images if keep is None else sheet_images.index_select(0, keep), maxima,
                                   rot if kept_views is None else rot[kept_views], landmarks,
                                   self.last_report if layout is not None else None)
+        if self.visualize_heat and sheet_images is not None:
+            keep = None if kept_views is None else torch.from_numpy(np.asarray(kept_views)).to(sheet_images.device)
+            self._draw_heat_sheet(mesh, sheet_images if keep is None else sheet_images.index_select(0, keep), landmarks)
         if self._keep_ray_view and (not sharded or rank == 0):  # drawn by _after_prediction, which knows the file and the selection
             self._ray_view = (mesh, starts, ends, landmarks, self.last_report if layout is not None else None)
         return landmarks, error
 
     def _check_visualize(self):
         """``visualize_img`` and ``visualize_rays_img`` need the renderer that holds the mesh on the device, ``visualize_sheet`` the
-        one that draws it - and all the views in one process: said before the prediction, not after it."""
+        one that draws it - and all the views in one process; ``visualize_heat`` as ``visualize_sheet``, and a predictor that hands
+        out its heatmaps: said before the prediction, not after it."""
+        if self.visualize_heat:
+            if not callable(getattr(self.predictor_2d, "heatmaps_device", None)):
+                raise ValueError("visualize_heat needs a predictor with heatmaps_device (HipPaulsenModel): "
+                                 f"{type(self.predictor_2d).__name__} has no heatmaps to show")
+            if not isinstance(self.renderer_3d, HipRenderer3D):
+                raise ValueError("visualize_heat needs a HipRenderer3D in the renderer slot (it draws the sheet), "
+                                 f"not {type(self.renderer_3d).__name__}")
+            if self.shard_views and parallel.is_distributed():
+                raise ValueError("visualize_heat is not supported with shard_views in a distributed run: a rank holds only its "
+                                 "slice of the views")
+            if self.heat_landmarks is not None:
+                nl = int(self.predictor_2d.get_lm_count())
+                if any(k >= nl for k in self.heat_landmarks):
+                    raise ValueError(f"heat_landmarks must lie in 0..{nl - 1}, not {self.heat_landmarks!r}")
         if self.visualize_sheet and not isinstance(self.renderer_3d, HipRenderer3D):
             raise ValueError("visualize_sheet needs a HipRenderer3D in the renderer slot (it draws the sheet), "
                              f"not {type(self.renderer_3d).__name__}")
@@ -657,6 +704,34 @@ class Pipeline(abc.ABC):
         self._say(f"[Pipeline] view sheet written to {self.last_sheet_path}")
         return self.last_sheet_path
 
+    def _draw_heat_sheet(self, mesh, images, landmarks):
+        """``visualize_heat``: the views of THIS pass (a device stack [N,256,256,4] or the slot protocol's numpy one) with the heatmaps
+        the predictor makes of them - a second forward pass, about one network pass more - drawn by
+        ``HipRenderer3D.render_heat_sheet``; the background is the planes the predictor read.  Nothing is drawn for a prediction that
+        failed (``landmarks`` None)."""
+        import torch
+
+        from ..utils.viewer import heat_colours, heat_sheet_path, write_view_png
+
+        if landmarks is None:
+            return None
+        self._check_visualize()
+        with self._timer.stage("visualize_heat"):
+            if not hasattr(images, "data_ptr"):
+                images = torch.from_numpy(np.ascontiguousarray(images, dtype=np.float32)).to(torch.device("cuda", self.renderer_3d.ctx.device))
+            heat = self.predictor_2d.heatmaps_device(images)
+            out_path = heat_sheet_path(getattr(mesh, "path", None) or "mesh.obj", self.visualize_name)
+            args = dict(landmarks=self.heat_landmarks, colors=heat_colours(int(heat.shape[1])), background="auto", scale=self.sheet_scale,
+                        floor=self.heat_floor, chan_sel=getattr(self.predictor_2d, "chan_sel", None))
+            if self.view_png_encoder == "device":  # the picture stays on the device
+                image = self.renderer_3d.render_heat_sheet_device(images, heat, **args)
+                self.last_heat_path = write_view_png(image, out_path, encoder="device", renderer=self.renderer_3d)
+                self.renderer_3d.check()
+            else:
+                self.last_heat_path = write_view_png(self.renderer_3d.render_heat_sheet(images, heat, **args), out_path)
+        self._say(f"[Pipeline] heat sheet written to {self.last_heat_path}")
+        return self.last_heat_path
+
     def _groupable(self, n_scans: int) -> bool:
         """Can ``n_scans`` scans share one network pass (predict_meshes_device)?"""
         p2, e3 = self.predictor_2d, self.estimator_3d
@@ -668,7 +743,7 @@ class Pipeline(abc.ABC):
             return False
         if self.landmark_report:
             return False  # one report per scan, made by the scan's own pass
-        if self.visualize_img or self.visualize_rays_img or self.visualize_sheet:
+        if self.visualize_img or self.visualize_rays_img or self.visualize_sheet or self.visualize_heat:
             return False  # one picture per scan, drawn by the scan's own pass while its mesh (its views) are resident
         n = int(self.renderer_3d.n_views)
         return e3.expected_counts(p2.get_lm_count(), n) is not None and n_scans * n <= (p2.device_batch or 128)
@@ -954,6 +1029,8 @@ class Pipeline(abc.ABC):
             self._draw_view_sheet(pd, np.asarray(image_stack, dtype=np.float32),
                                   np.asarray(landmark_stack, dtype=np.float32), view_rotations(np.asarray(transform_stack)), drawn,
                                   self.last_report if arrays is not None else None)
+        if self.visualize_heat:
+            self._draw_heat_sheet(pd, np.asarray(image_stack, dtype=np.float32), drawn)
         if self._keep_ray_view:
             self._ray_view = (pd, np.asarray(lines_s), np.asarray(lines_e), drawn, self.last_report if arrays is not None else None)
         return landmarks

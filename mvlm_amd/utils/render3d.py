@@ -9,6 +9,7 @@ batched HIP launch set (mvlm_amd/csrc/raster.hip) through ``mvlm_render``.
 from __future__ import annotations
 
 import ctypes as C
+import operator
 import time
 from pathlib import Path
 
@@ -484,38 +485,43 @@ class HipRenderer3D:
         """(cols, rows, width, height) of a sheet of ``n_views`` views (mvlm_view_sheet_layout; no GPU): ``cols`` columns, default
         ceil(sqrt(n_views)), cells of 256 * scale pixels, ``gap`` pixels between them and around the sheet.  ValueError with the
         library's reason for what does not fit (a side above 4096: the message names the largest scale that does)."""
+        return HipRenderer3D._sheet_layout("view sheet", n_views, cols, scale, gap)
+
+    @staticmethod
+    def _sheet_layout(label: str, n_views, cols, scale, gap) -> tuple:
+        """``view_sheet_layout`` for the picture ``label`` names in its refusals (the view sheet, the heat sheet)."""
         for name, value in (("n_views", n_views), ("scale", scale), ("gap", gap)) + ((("cols", cols),) if cols is not None else ()):
             if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
-                raise ValueError(f"view sheet: {name} must be an integer, not {value!r}")
+                raise ValueError(f"{label}: {name} must be an integer, not {value!r}")
         if cols is not None and cols < 1:
-            raise ValueError(f"view sheet: cols must be at least 1 ({cols} given)")
+            raise ValueError(f"{label}: cols must be at least 1 ({cols} given)")
         out = [C.c_int() for _ in range(4)]
         why = C.create_string_buffer(512)
         rc = _lib.load().mvlm_view_sheet_layout(int(n_views), 0 if cols is None else int(cols), int(scale), int(gap),
                                                 *[C.byref(o) for o in out], why, len(why))
         if rc != 0:
-            raise ValueError(f"view sheet: {why.value.decode()}")
+            raise ValueError(f"{label}: {why.value.decode()}")
         return tuple(int(o.value) for o in out)
 
-    def _sheet_tensor(self, x, what, dtype, dev, shape_ok, shape_words):
-        """A view-sheet input on the renderer's device: a tensor is taken where it lies (dtype, device and shape checked), anything
-        else is made a numpy array of that dtype and uploaded."""
+    def _sheet_tensor(self, x, what, dtype, dev, shape_ok, shape_words, label="view sheet"):
+        """A view-sheet (or, with its ``label``, heat-sheet) input on the renderer's device: a tensor is taken where it lies (dtype,
+        device and shape checked), anything else is made a numpy array of that dtype and uploaded."""
         import torch
 
         if hasattr(x, "data_ptr"):
             if x.dtype != dtype:
-                raise ValueError(f"view sheet: {what} must be {dtype}, not {x.dtype}")
+                raise ValueError(f"{label}: {what} must be {dtype}, not {x.dtype}")
             if x.device != dev:
-                raise ValueError(f"view sheet: {what} lives on {x.device}, the renderer on {dev}")
+                raise ValueError(f"{label}: {what} lives on {x.device}, the renderer on {dev}")
             t = x
         else:
             try:
                 a = np.ascontiguousarray(x, dtype={torch.float32: np.float32}[dtype])
             except (TypeError, ValueError) as e:
-                raise ValueError(f"view sheet: {what} is not a numeric array ({e})") from None
+                raise ValueError(f"{label}: {what} is not a numeric array ({e})") from None
             t = None if not shape_ok(a.shape) else torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
         if t is None or not shape_ok(tuple(t.shape)):
-            raise ValueError(f"view sheet: {what} must be {shape_words}, not {tuple(np.shape(x) if t is None else t.shape)}")
+            raise ValueError(f"{label}: {what} must be {shape_words}, not {tuple(np.shape(x) if t is None else t.shape)}")
         return t.contiguous()
 
     def render_view_sheet_device(self, images, maxima=None, rot=None, landmarks=None, colors=None, used=None, background="rgb",
@@ -594,6 +600,101 @@ class HipRenderer3D:
         image = out.cpu().numpy()[..., :3].copy()
         self.check()
         return image
+
+    # ---- heat sheet (the view sheet's cells with the network's heatmaps laid over them) ---------------------------
+    def render_heat_sheet_device(self, images, heat, landmarks=None, colors=None, background="rgb", cols=None, scale: int = 1,
+                                 gap: int = 2, floor: float = 0.25, opacity: float = 0.75, chan_sel=None):
+        """``render_heat_sheet`` with the picture left on the device: uint8 [H,W,4] RGBA, the layout ``encode_png`` takes.  Only
+        enqueues work; every bad argument is a ValueError that starts with "heat sheet:", raised before any launch."""
+        import torch
+
+        label = "heat sheet"
+        # what needs no tensor first: a bad scalar is refused before anything is uploaded
+        picked = None
+        if landmarks is not None:
+            try:
+                picked = [operator.index(k) for k in landmarks]
+            except TypeError:
+                raise ValueError(f"{label}: landmarks must be None or a sequence of integers, not {landmarks!r}") from None
+            if any(isinstance(k, (bool, np.bool_)) for k in landmarks):
+                raise ValueError(f"{label}: landmarks must be None or a sequence of integers, not {landmarks!r}")
+            if len(set(picked)) != len(picked):
+                raise ValueError(f"{label}: landmarks must be distinct, not {picked!r}")
+        if background == "auto":  # the planes the predictor read (Pipeline passes its chan_sel); unknown: the RGB planes
+            background = "rgb" if chan_sel is None or any(int(c) < 3 for c in chan_sel) else "depth"
+        if background not in ("rgb", "depth"):
+            raise ValueError(f'{label}: background must be "rgb", "depth" or "auto", not {background!r}')
+        try:
+            floor, opacity = float(floor), float(opacity)
+        except (TypeError, ValueError):
+            raise ValueError(f"{label}: floor and opacity must be numbers, not {floor!r} and {opacity!r}") from None
+        if not (np.isfinite(floor) and 0.0 <= floor < 1.0):
+            raise ValueError(f"{label}: floor must be finite and in [0, 1), not {floor}")
+        if not (np.isfinite(opacity) and 0.0 < opacity <= 1.0):
+            raise ValueError(f"{label}: opacity must be finite and in (0, 1], not {opacity}")
+        try:
+            shape = tuple(np.shape(images))
+        except ValueError:
+            shape = ()
+        if len(shape) == 4 and shape[0] >= 1:  # (any other shape: refused below, in _sheet_tensor's words)
+            _, _, width, height = self._sheet_layout(label, int(shape[0]), cols, scale, gap)
+        dev = torch.device("cuda", self.ctx.device)
+        images = self._sheet_tensor(images, "images", torch.float32, dev, lambda s: len(s) == 4 and s[0] >= 1 and tuple(s[1:]) == (256, 256, 4),
+                                    "float32 [N,256,256,4]", label)
+        n = int(images.shape[0])
+        heat = self._sheet_tensor(heat, "heat", torch.float32, dev,
+                                  lambda s: len(s) == 4 and s[0] == n and s[1] >= 1 and tuple(s[2:]) == (256, 256),
+                                  f"float32 [{n},NL,256,256]", label)
+        nl = int(heat.shape[1])
+        if nl > 65536 or n * nl > 32768:
+            raise ValueError(f"{label}: at most 65536 landmarks and 32768 planes (views x landmarks) per call, not {n} x {nl}")
+        if heat.data_ptr() % 16:
+            raise ValueError(f"{label}: heat must be 16-byte aligned on the device")
+        sel = None
+        if picked is not None:
+            if any(not 0 <= k < nl for k in picked):
+                raise ValueError(f"{label}: landmarks must lie in 0..{nl - 1}, not {picked!r}")
+            sel = np.zeros(nl, np.uint8)
+            sel[picked] = 1
+        if colors is not None:
+            if hasattr(colors, "data_ptr"):
+                colors = colors.detach().cpu().numpy()
+            try:
+                colors = np.ascontiguousarray(colors, dtype=np.uint8)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"{label}: colors is not a numeric array ({e})") from None
+            if colors.shape != (nl, 3):
+                raise ValueError(f"{label}: colors must be uint8 [{nl},3], not {colors.shape}")
+        out = torch.empty((height, width, 4), dtype=torch.uint8, device=dev)
+        self.ctx.bind_current_stream(torch, dev)
+        self.ctx.check(self.ctx.lib.mvlm_render_heat_sheet(
+            self.ctx.handle, C.c_void_p(images.data_ptr()), C.c_void_p(heat.data_ptr()), n, nl,
+            _lib.as_ptr(sel, C.c_uint8) if sel is not None else None, _lib.as_ptr(colors, C.c_uint8) if colors is not None else None,
+            1 if background == "depth" else 0, 0 if cols is None else int(cols), int(scale), int(gap), C.c_double(floor),
+            C.c_double(opacity), C.c_void_p(out.data_ptr())), ValueError)
+        self._sheet_keepalive = (images, heat)  # (read by the enqueued kernels)
+        return out
+
+    def render_heat_sheet(self, images, heat, landmarks=None, colors=None, background="rgb", cols=None, scale: int = 1, gap: int = 2,
+                          floor: float = 0.25, opacity: float = 0.75, chan_sel=None):
+        """Every rendered view in one picture - the cells of ``render_view_sheet(images)`` - with the network's heatmaps laid over
+        it: uint8 [H,W,3].  ``images`` float32 [N,256,256,4] (``render_device``'s stack), ``heat`` float32 [N,NL,256,256]
+        (``HipPaulsenModel.heatmaps_device``'s) - tensors on the renderer's device, or numpy arrays, which are uploaded.  Per view
+        pixel the landmark of ``landmarks`` (None: all; else distinct ints in 0..NL-1) whose value is the largest share t of its
+        plane's largest finite value wins, the lowest index on a tie, and is laid over the background in its colour of ``colors`` uint8
+        [NL,3] (default red) with opacity ``opacity`` * (t - ``floor``) / (1 - ``floor``); t <= ``floor`` draws nothing.  Heat pixel
+        [row, col] lies over image pixel [row, col]; no markers are drawn.  ``background``, ``cols``, ``scale``, ``gap``:
+        ``render_view_sheet`` ("Heat sheet")."""
+        out = self.render_heat_sheet_device(images, heat, landmarks, colors, background, cols, scale, gap, floor, opacity, chan_sel)
+        image = out.cpu().numpy()[..., :3].copy()
+        self.check()
+        return image
+
+    def heat_sheet_stage_ms(self) -> np.ndarray:
+        """Milliseconds of the last heat sheet's stages under render profiling: background, peak, compose."""
+        ms = np.zeros(3, np.float32)
+        self.ctx.check(self.ctx.lib.mvlm_heat_sheet_stage_ms(self.ctx.handle, _lib.as_ptr(ms, C.c_float)))
+        return ms
 
     # ---- PNG on the device -------------------------------------------------------------------
     @staticmethod

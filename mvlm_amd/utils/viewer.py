@@ -12,7 +12,8 @@ from pathlib import Path
 
 import numpy as np
 
-__all__ = ["LandmarkViewer", "RayVisualizer", "RayVisualizerConfig", "view_path", "view_sheet_path", "write_view_png"]
+__all__ = ["LandmarkViewer", "RayVisualizer", "RayVisualizerConfig", "view_path", "view_sheet_path", "heat_sheet_path", "HEAT_PALETTE",
+           "heat_colours", "write_view_png"]
 
 
 def view_path(filename, pname: str | None = None) -> Path:
@@ -25,6 +26,22 @@ def view_sheet_path(filename, pname: str | None = None) -> Path:
     """``visualization/<stem>[_<pname>]_views.png`` relative to the working directory: the view sheet beside the landmark view."""
     suffix = f"_{pname}" if pname else ""
     return Path("visualization") / f"{Path(filename).stem}{suffix}_views.png"
+
+
+def heat_sheet_path(filename, pname: str | None = None) -> Path:
+    """``visualization/<stem>[_<pname>]_heat.png`` relative to the working directory: the heat sheet beside the view sheet."""
+    suffix = f"_{pname}" if pname else ""
+    return Path("visualization") / f"{Path(filename).stem}{suffix}_heat.png"
+
+
+# The heat sheet's default colours, cycled over the landmark index: neighbouring landmarks, whose blobs lie side by side, differ.
+HEAT_PALETTE = ((255, 0, 0), (0, 200, 0), (0, 90, 255), (255, 200, 0), (255, 0, 255), (0, 220, 220), (255, 120, 0), (150, 60, 255))
+
+
+def heat_colours(n_landmarks: int) -> np.ndarray:
+    """uint8 [n_landmarks,3]: ``HEAT_PALETTE[l % len(HEAT_PALETTE)]`` for landmark l."""
+    palette = np.asarray(HEAT_PALETTE, dtype=np.uint8)
+    return palette[np.arange(int(n_landmarks)) % len(palette)].copy()
 
 
 PNG_ENCODERS = ("host", "device")
