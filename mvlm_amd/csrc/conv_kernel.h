@@ -674,10 +674,10 @@ struct Wino4Stage {
     unsigned off[N][6];  // BYTE offset of row 4q - 1 + r at the job's x from the chunk's first channel in this image (0: masked row)
     unsigned msk[N][3];  // all ones: the column and row 4q - 1 (0), rows 4q .. 4q + 3 (1), row 4q + 4 (2) lie inside the image; 0: padding
     int lds4[N], lds2[N];  // stage offsets of the job's v0 and v4
-    int bn[N];             // the job's channel within the chunk
+    int bn[N];             // the job's channel in the chunk that is staged next
     unsigned woff[NW];     // BYTE offset of the lane's float4 i of the weight slice from the chunk's first channel row ...
     int wlds[NW];          // ... and its float4 index in the staged slice (a lane without a float4 i repeats its float4 i - 1)
-    float xw[N][6];
+    float xw[N][6];  // the job's six rows as loaded, then (in place) after BatchNorm + ReLU and the padding mask
     float bn_s[N], bn_t[N];
     f32x4 wv[NW];
     float floor;  // ReLU of the pre-activation: 0; no pre-activation: -inf
@@ -685,13 +685,63 @@ struct Wino4Stage {
     int bbase4[2][C::CK / 2], bbase2[2][C::CK / 2];  // ... and its pixel's v0 / v4 in stage s, channel pair cp
 };
 
-template <class C, int T>
-__device__ __forceinline__ void issue_item_wino4(const char* in_cb, const char* w_cb, Wino4Stage<C>& ws) {
+// Where the slices of a chunk's staging sit among its MFMAs.  A chunk is 6 * KSTEPS MFMAs; gap g is what a wave issues between
+// MFMA g and MFMA g + 1 (the first gap of a k-step also holds the next k-step's operand reads, its last gap the next k-step's
+// wait, the chunk's last gap the barrier).  A staging item is cut into slices of at most eight instructions, and a gap takes one
+// slice of the loads and one of the writes at most, so a 64-cycle MFMA covers what is issued behind it.  An x-item (six loads,
+// BatchNorm + ReLU + mask, the input transform, two LDS writes) is four issue slices (three load pairs, the BatchNorm pair's LDS
+// read) and six write slices (rows 0-1 behind the item's ONE counted vmcnt, rows 2-3, rows 4-5, v0 v1, v2 v3 + the 16-byte write,
+// v4 v5 + the 8-byte write); a weight float4 is one slice of either kind.  Both kinds run in the order x-item 0, its share of the
+// weight float4s, x-item 1, ...: the loads from gap 0 on, one per gap outside the k-steps' last gaps, the writes one per gap so
+// that the last one sits in the gap before the chunk's last MFMA.
+template <class C>
+struct Wino4Plan {
+    static constexpr int NX = C::WINO4 ? C::X_ITERS : 1, NW = C::WINO4 ? C::W_ITERS : 1;
+    static constexpr int GAPS = 6 * C::KSTEPS;
+    static constexpr int XI = 4, XW = 6;  // issue / write slices of an x-item
+    static constexpr int NI = XI * NX + NW, NWR = XW * NX + NW;
+    static constexpr int ADVANCE = 6 * (C::KSTEPS / 2) - 1;  // the gap that steps the chunk's bases on, behind the last issue slice
+    static constexpr int wfirst(int i) { return i * NW / NX; }  // the weight float4s [wfirst(i), wfirst(i + 1)) follow x-item i
+    static constexpr int slices(int t, int per) { return t < NX ? per : 1; }
+    static constexpr int seq(int t, int p, int per) {  // position of slice p of item t in its kind's order
+        if (t < NX) return t * per + wfirst(t) + p;
+        int i = 0;
+        while (wfirst(i + 1) <= t - NX) ++i;
+        return (i + 1) * per + (t - NX);
+    }
+    static constexpr int issue_gap(int t, int p) { return (seq(t, p, XI) / 5) * 6 + seq(t, p, XI) % 5; }
+    static constexpr int write_gap(int t, int p) { return GAPS - 1 - NWR + seq(t, p, XW); }
+    static constexpr int loads(int t, int p) { return t >= NX ? 1 : p < 3 ? 2 : 0; }
+    // global loads that may still be in flight when item t's first write slice runs: those requested behind the item's own and
+    // before that gap's write slice (loads return in order; a gap's issue slice precedes its write slice)
+    static constexpr int later(int t) {
+        int n = 0;
+        for (int u = 0; u < NX + NW; ++u)
+            for (int q = 0; q < slices(u, XI); ++q)
+                if (seq(u, q, XI) > seq(t, slices(t, XI) - 1, XI) && issue_gap(u, q) <= write_gap(t, 0)) n += loads(u, q);
+        return n;
+    }
+    static constexpr bool ordered() {  // every load is requested before its item's first write slice, and before the bases move
+        for (int t = 0; t < NX + NW; ++t)
+            if (issue_gap(t, slices(t, XI) - 1) >= write_gap(t, 0) || issue_gap(t, slices(t, XI) - 1) > ADVANCE || later(t) >= 16) return false;
+        return true;
+    }
+};
+
+// Issue slice P of staging item T: an x-item's rows 2P, 2P + 1 (P < 3) or its BatchNorm pair (P == 3); a weight float4
+template <class C, int T, int P>
+__device__ __forceinline__ void issue_slice_wino4(const char* in_cb, const char* w_cb, const float* sbn, Wino4Stage<C>& ws) {
     if constexpr (T < C::X_ITERS) {
+        if constexpr (P < 3) {
 #pragma unroll
-        for (int r = 0; r < 6; ++r) {
-            wino_opaque(ws.off[T][r]);
-            ws.xw[T][r] = *reinterpret_cast<const float*>(in_cb + ws.off[T][r]);
+            for (int r = 2 * P; r < 2 * P + 2; ++r) {
+                wino_opaque(ws.off[T][r]);
+                ws.xw[T][r] = *reinterpret_cast<const float*>(in_cb + ws.off[T][r]);
+            }
+        } else {
+            const float2 st = *reinterpret_cast<const float2*>(sbn + 2 * ws.bn[T]);
+            ws.bn_s[T] = st.x;
+            ws.bn_t[T] = st.y;
         }
     } else {
         constexpr int I = T - C::X_ITERS;
@@ -701,51 +751,106 @@ __device__ __forceinline__ void issue_item_wino4(const char* in_cb, const char* 
 }
 
 template <class C, int T>
-__device__ __forceinline__ void bn_item_wino4(const float* sbn, int cb, Wino4Stage<C>& ws) {
+__device__ __forceinline__ void issue_item_wino4(const char* in_cb, const char* w_cb, Wino4Stage<C>& ws) {
     if constexpr (T < C::X_ITERS) {
-        const float2 st = *reinterpret_cast<const float2*>(sbn + 2 * (cb + ws.bn[T]));
-        ws.bn_s[T] = st.x;
-        ws.bn_t[T] = st.y;
+        static_for<0, 3>([&](auto pc) { issue_slice_wino4<C, T, decltype(pc)::value>(in_cb, w_cb, nullptr, ws); });
+    } else {
+        issue_slice_wino4<C, T, 0>(in_cb, w_cb, nullptr, ws);
     }
 }
 
-// BatchNorm + ReLU, zero padding AFTER the activation, the input transform, a 16-byte and an 8-byte LDS write into stage NEXT
-template <class C, int T, int NEXT>
-__device__ __forceinline__ void write_item_wino4(float* smem, const Wino4Stage<C>& ws) {
+template <class C, int T>
+__device__ __forceinline__ void bn_item_wino4(const float* sbn, Wino4Stage<C>& ws) {
+    if constexpr (T < C::X_ITERS) issue_slice_wino4<C, T, 3>(nullptr, nullptr, sbn, ws);
+}
+
+// Write slice P of staging item T into stage NEXT (v01: the item's v0, v1 from slice 3 to slice 4).  An x-item: BatchNorm + ReLU
+// and the zero padding AFTER the activation of rows 2P, 2P + 1 (P < 3, in place), then the input transform: v0 v1 (P == 3), v2 v3
+// and the 16-byte LDS write (4), v4 v5 and the 8-byte write (5).  A weight float4: its LDS write.
+template <class C, int T, int P, int NEXT>
+__device__ __forceinline__ void write_slice_wino4(float* smem, Wino4Stage<C>& ws, float (&v01)[2]) {
     if constexpr (T < C::X_ITERS) {
-        float d[6];
+        float(&d)[6] = ws.xw[T];
+        if constexpr (P < 3) {
 #pragma unroll
-        for (int r = 0; r < 6; ++r) {
-            const float v = fmaxf(fmaf(ws.xw[T][r], ws.bn_s[T], ws.bn_t[T]), ws.floor);
-            d[r] = __uint_as_float(__float_as_uint(v) & ws.msk[T][r == 0 ? 0 : r == 5 ? 2 : 1]);
+            for (int r = 2 * P; r < 2 * P + 2; ++r) {
+                const float v = fmaxf(fmaf(d[r], ws.bn_s[T], ws.bn_t[T]), ws.floor);
+                d[r] = __uint_as_float(__float_as_uint(v) & ws.msk[T][r == 0 ? 0 : r == 5 ? 2 : 1]);
+            }
+        } else if constexpr (P == 3) {
+            v01[0] = fmaf(-1.5f, d[3], fmaf(-2.f, d[2], fmaf(1.5f, d[1], d[0]))) + d[4];
+            v01[1] = fmaf(-0.5f, d[3], fmaf(-2.5f, d[2], -d[1])) + d[4];
+        } else if constexpr (P == 4) {
+            const float v2 = fmaf(-2.5f, d[3], fmaf(0.5f, d[2], d[1])) + d[4];
+            const float v3 = fmaf(0.5f, d[3], fmaf(-0.5f, d[1], -d[2])) + d[4];
+            *reinterpret_cast<f32x4*>(smem + NEXT * C::STAGE + ws.lds4[T]) = f32x4{v01[0], v01[1], v2, v3};
+        } else {
+            const float v4 = fmaf(-2.f, d[3], fmaf(2.f, d[1], -d[2])) + d[4];
+            const float v5 = fmaf(-1.5f, d[4], fmaf(-2.f, d[3], fmaf(1.5f, d[2], d[1]))) + d[5];
+            *reinterpret_cast<float2*>(smem + NEXT * C::STAGE + ws.lds2[T]) = make_float2(v4, v5);
         }
-        const float v0 = fmaf(-1.5f, d[3], fmaf(-2.f, d[2], fmaf(1.5f, d[1], d[0]))) + d[4];
-        const float v1 = fmaf(-0.5f, d[3], fmaf(-2.5f, d[2], -d[1])) + d[4];
-        const float v2 = fmaf(-2.5f, d[3], fmaf(0.5f, d[2], d[1])) + d[4];
-        const float v3 = fmaf(0.5f, d[3], fmaf(-0.5f, d[1], -d[2])) + d[4];
-        const float v4 = fmaf(-2.f, d[3], fmaf(2.f, d[1], -d[2])) + d[4];
-        const float v5 = fmaf(-1.5f, d[4], fmaf(-2.f, d[3], fmaf(1.5f, d[2], d[1]))) + d[5];
-        *reinterpret_cast<f32x4*>(smem + NEXT * C::STAGE + ws.lds4[T]) = f32x4{v0, v1, v2, v3};
-        *reinterpret_cast<float2*>(smem + NEXT * C::STAGE + ws.lds2[T]) = make_float2(v4, v5);
     } else {
         constexpr int I = T - C::X_ITERS;
         reinterpret_cast<f32x4*>(smem + NEXT * C::STAGE + C::XT_PAD)[ws.wlds[I]] = ws.wv[I];
     }
 }
 
+template <class C, int T, int NEXT>
+__device__ __forceinline__ void write_item_wino4(float* smem, Wino4Stage<C>& ws) {
+    float v01[2];
+    static_for<0, Wino4Plan<C>::slices(T, Wino4Plan<C>::XW)>([&](auto pc) { write_slice_wino4<C, T, decltype(pc)::value, NEXT>(smem, ws, v01); });
+}
+
+// The bases of the chunk after the one being staged: stepped inside the chunk, not in the gap that holds its barrier
+template <class C>
+__device__ __forceinline__ void wino4_advance(const char*& in_cb, const char*& w_cb, size_t in_step, size_t w_step, Wino4Stage<C>& ws) {
+    in_cb += in_step, w_cb += w_step;
+#pragma unroll
+    for (int i = 0; i < C::X_ITERS; ++i) ws.bn[i] += C::CK;
+}
+
+// The slices of gap G while stage NEXT is being filled: the issue slice first, then the write slice, whose item waits ONCE, at
+// its first slice, for its own loads (Wino4Plan::later)
+template <class C, int G, int NEXT>
+__device__ __forceinline__ void gap_wino4(float* smem, const float* sbn, const char*& in_cb, const char*& w_cb, size_t in_step, size_t w_step,
+                                          Wino4Stage<C>& ws, float (&v01)[2]) {
+    using P = Wino4Plan<C>;
+    static_for<0, P::NX + P::NW>([&](auto tc) {
+        constexpr int t = decltype(tc)::value;
+        static_for<0, P::slices(t, P::XI)>([&](auto pc) {
+            constexpr int p = decltype(pc)::value;
+            if constexpr (P::issue_gap(t, p) == G) issue_slice_wino4<C, t, p>(in_cb, w_cb, sbn, ws);
+        });
+    });
+    static_for<0, P::NX + P::NW>([&](auto tc) {
+        constexpr int t = decltype(tc)::value;
+        static_for<0, P::slices(t, P::XW)>([&](auto pc) {
+            constexpr int p = decltype(pc)::value;
+            if constexpr (P::write_gap(t, p) == G) {
+                if constexpr (p == 0) {
+                    __builtin_amdgcn_s_waitcnt(0x0F70 | P::later(t));  // vmcnt(later)
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                write_slice_wino4<C, t, p, NEXT>(smem, ws, v01);
+            }
+        });
+    });
+    if constexpr (G == P::ADVANCE) wino4_advance<C>(in_cb, w_cb, in_step, w_step, ws);
+}
+
 // The MFMAs of one K-chunk out of LDS stage CUR, as compute_chunk_wino: k-steps (kx, channel pair) in a fixed order, per step
-// the six GEMMs t = 0..5 of the wave's row quad; with STAGE_NEXT the next chunk is staged in the MFMAs' shadow.
+// the six GEMMs t = 0..5 of the wave's row quad; with STAGE_NEXT the chunk at in_cb / w_cb is staged in the MFMAs' shadow, slice by
+// slice in the gaps between single MFMAs (Wino4Plan), and the bases are stepped on to the chunk after it.
 template <class C, int CUR, bool STAGE_NEXT>
-__device__ __forceinline__ void compute_chunk_wino4(float* smem, const float* sbn, const char* in_cb, const char* w_cb, int cb_next,
-                                                    Wino4Stage<C>& ws, f32x16 (&acc)[6]) {
-    constexpr int T_TOT = C::X_ITERS + C::W_ITERS;
-    constexpr int ISSUE_SPAN = C::KSTEPS / 2 > 0 ? C::KSTEPS / 2 : 1;
-    constexpr int WRITE_SPAN = ISSUE_SPAN;
-    constexpr int WRITE_START = C::KSTEPS - WRITE_SPAN;
+__device__ __forceinline__ void compute_chunk_wino4(float* smem, const float* sbn, const char*& in_cb, const char*& w_cb, size_t in_step,
+                                                    size_t w_step, Wino4Stage<C>& ws, f32x16 (&acc)[6]) {
+    using P = Wino4Plan<C>;
+    static_assert(P::NI <= 5 * (C::KSTEPS / 2) && P::NWR <= P::GAPS - 1 && P::ordered(), "loads in the first half of the k-steps, every write behind its loads");
     const float* const st = smem + CUR * C::STAGE;
     float av[2][6];
     f32x4 bv4[2];  // v0..v3 of the lane's pixel column: one 16-byte read
     float2 bv2[2];  // v4, v5: one 8-byte read
+    float v01[2];   // (one x-item at a time is between its write slices 3 and 4)
 #pragma unroll
     for (int t = 0; t < 6; ++t) av[0][t] = st[ws.abase + t * 3 * C::CK * C::COUT_T];
     bv4[0] = *reinterpret_cast<const f32x4*>(smem + ws.bbase4[CUR][0]);
@@ -753,7 +858,7 @@ __device__ __forceinline__ void compute_chunk_wino4(float* smem, const float* sb
     static_for<0, C::KSTEPS>([&](auto ksc) {
         constexpr int ks = decltype(ksc)::value;
         constexpr int nx = ks + 1;
-        // ONE wait per k-step (see compute_chunk_wino)
+        // ONE wait per k-step (see compute_chunk_wino): this step's operands, and the LDS traffic of the slices behind them
         __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (nx < C::KSTEPS) {
@@ -769,40 +874,15 @@ __device__ __forceinline__ void compute_chunk_wino4(float* smem, const float* sb
             else if constexpr (t == 4) return bv2[ks & 1].x;
             else return bv2[ks & 1].y;
         };
-        constexpr int LEAD = 2;
         static_for<0, 6>([&](auto tc) {
             constexpr int t = decltype(tc)::value;
-            if constexpr (t < LEAD) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[ks & 1][t], bval(tc), acc[t], 0, 0, 0);
-        });
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (STAGE_NEXT) {
-            // ONE wait for the global loads a k-step writes to LDS: what may stay in flight is what was requested after the
-            // last item written here (a job is six loads, a weight float4 one)
-            if constexpr (ks >= WRITE_START) {
-                constexpr int t_last = ((ks - WRITE_START + 1) * T_TOT + WRITE_SPAN - 1) / WRITE_SPAN - 1;
-                static_assert(WRITE_START + (t_last * WRITE_SPAN) / T_TOT == ks && (t_last + 1 == T_TOT || WRITE_START + ((t_last + 1) * WRITE_SPAN) / T_TOT > ks));
-                constexpr int later = (t_last + 1 < C::X_ITERS ? 6 * (C::X_ITERS - t_last - 1) + C::W_ITERS : T_TOT - t_last - 1);
-                static_assert(later < 16);
-                __builtin_amdgcn_s_waitcnt(0x0F70 | later);  // vmcnt(later)
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[ks & 1][t], bval(tc), acc[t], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (STAGE_NEXT) {
+                gap_wino4<C, 6 * ks + t, CUR ^ 1>(smem, sbn, in_cb, w_cb, in_step, w_step, ws, v01);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            static_for<0, T_TOT>([&](auto tc) {
-                constexpr int t = decltype(tc)::value;
-                if constexpr ((t * ISSUE_SPAN) / T_TOT == ks) {
-                    issue_item_wino4<C, t>(in_cb, w_cb, ws);
-                    bn_item_wino4<C, t>(sbn, cb_next, ws);
-                }
-                if constexpr (WRITE_START + (t * WRITE_SPAN) / T_TOT == ks) write_item_wino4<C, t, CUR ^ 1>(smem, ws);
-            });
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        __builtin_amdgcn_s_setprio(1);
-        static_for<0, 6>([&](auto tc) {
-            constexpr int t = decltype(tc)::value;
-            if constexpr (t >= LEAD) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[ks & 1][t], bval(tc), acc[t], 0, 0, 0);
         });
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
     });
 }
 
@@ -916,7 +996,7 @@ __device__ __forceinline__ void wino4_main(const ConvArgs& a, float* smem, const
         sbn[2 * i + 1] = a.pre_scale != nullptr ? a.pre_shift[i] : -0.f;
     }
     __syncthreads();
-    static_for<0, T_TOT>([&](auto tc) { bn_item_wino4<C, decltype(tc)::value>(sbn, 0, ws); });
+    static_for<0, T_TOT>([&](auto tc) { bn_item_wino4<C, decltype(tc)::value>(sbn, ws); });
     if (odd) {
         static_for<0, T_TOT>([&](auto tc) { write_item_wino4<C, decltype(tc)::value, 1>(smem, ws); });
     } else {
@@ -932,28 +1012,28 @@ __device__ __forceinline__ void wino4_main(const ConvArgs& a, float* smem, const
     if (last > 0) {
         int cb = 0;  // the chunk to multiply next
         const size_t in_step = size_t(C::CK) * HWin * 4, w_cstep = size_t(C::CK) * a.cout_pad * 4;
-        const char* in_nx = in0 + in_step;
-        const char* w_nx = w0 + w_cstep;
+        const char* in_nx = in0;  // the chunk to stage next: chunk 1 (compute_chunk_wino4 steps the bases on)
+        const char* w_nx = w0;
+        wino4_advance<C>(in_nx, w_nx, in_step, w_cstep, ws);
         if (odd) {  // (three chunks or more: chunk 1 is not the last)
-            compute_chunk_wino4<C, 1, true>(smem, sbn, in_nx, w_nx, C::CK, ws, wacc);
+            compute_chunk_wino4<C, 1, true>(smem, sbn, in_nx, w_nx, in_step, w_cstep, ws, wacc);
             __syncthreads();  // next stage complete; everybody is done reading this one
-            cb = C::CK, in_nx += in_step, w_nx += w_cstep;
+            cb = C::CK;
         }
         wino4_forget_bases<C>(ws);
         for (; cb + C::CK < last; cb += 2 * C::CK) {
-            compute_chunk_wino4<C, 0, true>(smem, sbn, in_nx, w_nx, cb + C::CK, ws, wacc);
+            compute_chunk_wino4<C, 0, true>(smem, sbn, in_nx, w_nx, in_step, w_cstep, ws, wacc);
             __syncthreads();
-            in_nx += in_step, w_nx += w_cstep;
-            compute_chunk_wino4<C, 1, true>(smem, sbn, in_nx, w_nx, cb + 2 * C::CK, ws, wacc);
+            compute_chunk_wino4<C, 1, true>(smem, sbn, in_nx, w_nx, in_step, w_cstep, ws, wacc);
             __syncthreads();
-            in_nx += in_step, w_nx += w_cstep;
         }
         wino4_forget_bases<C>(ws);
         wino4_mask_tail<C>(a, last, tid, ws);
-        compute_chunk_wino4<C, 0, true>(smem, sbn, in_nx, w_nx, last, ws, wacc);
+        compute_chunk_wino4<C, 0, true>(smem, sbn, in_nx, w_nx, in_step, w_cstep, ws, wacc);
         __syncthreads();
     }
-    compute_chunk_wino4<C, 1, false>(smem, sbn, nullptr, nullptr, 0, ws, wacc);
+    const char* none = nullptr;
+    compute_chunk_wino4<C, 1, false>(smem, sbn, none, none, 0, 0, ws, wacc);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const float m0 = wacc[0][r], m1 = wacc[1][r], m2 = wacc[2][r], m3 = wacc[3][r], m4 = wacc[4][r], m5 = wacc[5][r];
@@ -2046,6 +2126,23 @@ int launch_variant(mvlm_ctx* ctx, const ConvArgs& a_in, int attr_bit) {
         if (mvlm_conv_kparts_workspace(ctx, &a.kws, &a.kcnt)) return 1;
     }
     if (set_variant_attributes<C>(ctx, attr_bit)) return 1;
+#if defined(MVLM_CONV_TIMING)  // diagnostic build: MVLM_CONV_TIMING_WINO4_LDS = dynamic LDS bytes an F(4,3) launch asks for at least.
+    // More than half of a CU's 160 KiB leaves one workgroup per CU: the K loop's rate without a partner on the matrix pipe.
+    if constexpr (C::WINO4) {
+        if (const char* e = getenv("MVLM_CONV_TIMING_WINO4_LDS")) {
+            const size_t lds = strtoull(e, nullptr, 0);
+            if (lds > size_t(C::LDS_BYTES) && !a.amax_val && !a.in2) {
+                MVLM_REQUIRE(ctx, lds <= 160 * 1024, "conv: MVLM_CONV_TIMING_WINO4_LDS beyond a CU's LDS");
+                MVLM_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_mfma_kernel<C, false>),
+                                                        hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
+                hipLaunchKernelGGL((conv_mfma_kernel<C, false>), dim3((unsigned)g.nblk), dim3(256), lds, ctx->cur_stream(), a,
+                                   g.tiles_x, g.tiles_y, g.cout_tiles);
+                MVLM_CHECK_HIP(ctx, hipGetLastError());
+                return 0;
+            }
+        }
+    }
+#endif
     if (a.amax_val) {
         if constexpr (C::HAS_AMAX) {
             hipLaunchKernelGGL((conv_mfma_kernel<C, true>), dim3((unsigned)g.nblk), dim3(256), C::LDS_BYTES, ctx->cur_stream(),

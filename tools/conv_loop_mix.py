@@ -4,6 +4,7 @@
     tools/conv_loop_mix.py            print the table
     tools/conv_loop_mix.py --write    rewrite tests/golden/conv_loop_mix_wino.json, conv_loop_mix_wino4.json and
                                       conv_loop_mix_wino4w.json (the Winograd kernels' rows) from the build
+    tools/conv_loop_mix.py --write-gaps    rewrite tests/golden/conv_gap_mix_wino4.json (the F(4,3) kernels' largest MFMA gap)
 
 A convolution tile is compute-bound by construction: what it loses against the matrix peak is time its waves spend issuing
 anything but MFMAs inside the K loop (addresses, staging arithmetic, LDS traffic, waits, branches).  The ratio of those to the
@@ -11,7 +12,11 @@ MFMAs can be read off the object file, before any GPU time is spent.  The steady
 backward branch whose body holds MFMAs and a barrier (the loop over K-chunks); where a kernel has several, the one with the most
 MFMAs.  Instructions are classed by the prefix of their mnemonic.  tests/test_winograd_loop_mix.py holds the Winograd kernel
 to the committed row, tests/test_winograd4_loop_mix.py the F(4,3) kernel (build/wino4/) to its own,
-tests/test_winograd4_wide_loop_mix.py that kernel's wide workgroup shape (build/wino4w/) to its own."""
+tests/test_winograd4_wide_loop_mix.py that kernel's wide workgroup shape (build/wino4w/) to its own.
+
+A wave issues in order, so an MFMA covers only what stands directly behind it: the `gap` column is the longest run of other
+instructions between two consecutive MFMAs of the loop (waits and the barrier count).  tests/test_winograd4_gap_mix.py holds both
+F(4,3) shapes to tests/golden/conv_gap_mix_wino4.json."""
 import json
 import re
 import subprocess
@@ -25,6 +30,8 @@ BUILD = REPO / "mvlm_amd" / "csrc" / "build"
 WINO_TABLE = REPO / "tests" / "golden" / "conv_loop_mix_wino.json"
 WINO4_TABLE = REPO / "tests" / "golden" / "conv_loop_mix_wino4.json"
 WINO4W_TABLE = REPO / "tests" / "golden" / "conv_loop_mix_wino4w.json"
+WINO4_GAP_TABLE = REPO / "tests" / "golden" / "conv_gap_mix_wino4.json"  # object directory -> kernel -> largest MFMA gap
+WINO4_GAP_DIRS = ("wino4", "wino4w")
 CLASSES = ("valu", "lds_read", "lds_write", "global_load", "scalar", "wait", "other")
 MFMAS_PER_CHUNK_WINO = 48  # a 4-channel group of the 64 x (8 x 32) Winograd tile: 6 k-steps x 2 cout tiles x 4 GEMMs
 MFMAS_PER_CHUNK_WINO4 = 36  # a 4-channel group of the 32 x (16 x 32) F(4,3) tile, and of its 64 x (8 x 32) shape: 6 k-steps x 6 GEMMs
@@ -108,7 +115,21 @@ def loop_mix(insns) -> dict | None:
     row.update({c: kinds.count(c) for c in CLASSES})
     row["non_mfma"] = sum(row[c] for c in CLASSES) + row["barriers"]
     row["non_mfma_per_mfma"] = round(row["non_mfma"] / row["mfma"], 3)
+    row["max_gap"] = max(mfma_gaps(kinds))
     return row
+
+
+def mfma_gaps(kinds) -> list:
+    """The non-MFMA instructions (waits and barriers included) between each two consecutive MFMAs of a loop body, the body
+    taken as a cycle: the run behind the last MFMA continues with the run in front of the first."""
+    at = [i for i, k in enumerate(kinds) if k == "mfma"]
+    gaps = [b - a - 1 for a, b in zip(at, at[1:])]
+    return gaps + [len(kinds) - 1 - at[-1] + at[0]]
+
+
+def gap_table(objdir: Path) -> dict:
+    """kernel -> the largest MFMA gap of its steady loop (tests/golden/conv_gap_mix_wino4.json)"""
+    return {k: v["max_gap"] for k, v in build_table(objdir).items()}
 
 
 def build_table(objdir: Path = BUILD) -> dict:
@@ -126,15 +147,19 @@ def build_table(objdir: Path = BUILD) -> dict:
 
 
 if __name__ == "__main__":
-    if "--write" in sys.argv:
+    if "--write-gaps" in sys.argv:
+        rows = {d: gap_table(BUILD / d) for d in WINO4_GAP_DIRS}
+        WINO4_GAP_TABLE.write_text(json.dumps(rows, indent=1) + "\n")
+        print(f"{sum(len(v) for v in rows.values())} kernels -> {WINO4_GAP_TABLE}")
+    elif "--write" in sys.argv:
         for path, objdir in ((WINO_TABLE, BUILD / "wino"), (WINO4_TABLE, BUILD / "wino4"), (WINO4W_TABLE, BUILD / "wino4w")):
-            rows = build_table(objdir)
+            rows = {k: {c: n for c, n in v.items() if c != "max_gap"} for k, v in build_table(objdir).items()}
             path.write_text(json.dumps(rows, indent=1) + "\n")
             print(f"{len(rows)} kernels -> {path}")
     else:
-        hdr = f"{'mfma':>5s} {'other':>6s} {'/mfma':>6s} {'barr':>5s} " + " ".join(f"{c:>11s}" for c in CLASSES)
+        hdr = f"{'mfma':>5s} {'other':>6s} {'/mfma':>6s} {'barr':>5s} {'gap':>4s} " + " ".join(f"{c:>11s}" for c in CLASSES)
         print(hdr + "  kernel")
         for objdir in (BUILD, BUILD / "wino", BUILD / "wino4", BUILD / "wino4w"):
             for k, v in build_table(objdir).items():
-                print(f"{v['mfma']:5d} {v['non_mfma']:6d} {v['non_mfma_per_mfma']:6.2f} {v['barriers']:5d} " +
+                print(f"{v['mfma']:5d} {v['non_mfma']:6d} {v['non_mfma_per_mfma']:6.2f} {v['barriers']:5d} {v['max_gap']:4d} " +
                       " ".join(f"{v[c]:11d}" for c in CLASSES) + f"  {k}")

@@ -5,6 +5,11 @@ mvlm_amd/csrc/conv_kernel.h).  Run on the GPU box:
 
   make -C mvlm_amd/csrc timing        # builds mvlm_amd/lib/libmvlm_hip_timing.so
   MVLM_HIP_LIB=mvlm_amd/lib/libmvlm_hip_timing.so python tools/conv_phase_timing.py
+
+MVLM_PHASE_WINO4_ALONE=1 runs every forced F(4,3) case a second time with one workgroup per CU (the timing build pads the launch's
+dynamic LDS, MVLM_CONV_TIMING_WINO4_LDS), and both runs print their K loop in cycles per 4-channel chunk: with a partner the two
+workgroups share the matrix pipe (2 x 36 MFMAs of 64 cycles = 4 608 per chunk), alone the pipe needs 2 304 and whatever else a chunk
+costs is cycles in which the wave had no MFMA of its own to issue.
 """
 import ctypes as C
 import os
@@ -73,7 +78,14 @@ def main():
         CASES = [c for c in CASES if len(c) > 9]
     if os.environ.get("MVLM_PHASE_CASES") == "winograd4":
         CASES = [c for c in CASES if len(c) > 9 and c[9] == 2048]
-    for name, cin, cout, size, k, batch, pre, res, post, *forced in CASES:
+    alone = os.environ.get("MVLM_PHASE_WINO4_ALONE") == "1"
+    runs = [(c, wgs) for c in CASES for wgs in ((2, 1) if alone and len(c) > 9 and c[9] == 2048 else (2,))]
+    for (name, cin, cout, size, k, batch, pre, res, post, *forced), wgs in runs:
+        if wgs == 1:  # more than half of a CU's 160 KiB of LDS: one workgroup per CU
+            os.environ["MVLM_CONV_TIMING_WINO4_LDS"] = str(96 * 1024)
+            name += " alone"
+        else:
+            os.environ.pop("MVLM_CONV_TIMING_WINO4_LDS", None)
         batch = int(os.environ.get("MVLM_PHASE_BATCH", batch))
         x = torch.randn(batch, cin, size, size, device="cuda")
         y = torch.empty(batch, cout, size, size, device="cuda")
@@ -111,7 +123,8 @@ def main():
         ms = min(times)  # includes the hook's host-side packing only before the launch; event pair brackets the kernel + H2D
         flops = 2.0 * cin * cout * k * k * size * size * batch
         print(f"{name:40s} {ms:7.3f} {flops / ms / 1e9:8.1f} | {t[0] / n:9.0f} {t[1] / n:9.0f} {t[2] / n:9.0f}   "
-              f"{100 * t[0] / tot:4.1f}% {100 * t[1] / tot:4.1f}% {100 * t[2] / tot:4.1f}%   ({int(n)} workgroups)")
+              f"{100 * t[0] / tot:4.1f}% {100 * t[1] / tot:4.1f}% {100 * t[2] / tot:4.1f}%   ({int(n)} workgroups)"
+              + (f"   K loop {t[1] / n / (cin / 4):6.0f} cycles per chunk, {wgs} workgroup{'s' if wgs > 1 else ''} per CU" if forced and forced[0] == 2048 else ""))
         del x, y, r
 
 
