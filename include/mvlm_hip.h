@@ -378,7 +378,7 @@ int mvlm_cnn_heatmaps(mvlm_ctx* ctx, const float* images_dev, int n_views, const
  * captures failed (those passes ran eagerly instead). */
 int mvlm_cnn_set_execution(mvlm_ctx* ctx, int graph_mode, int concurrency);
 int mvlm_cnn_set_pairing(mvlm_ctx* ctx, int mode);
-/* F(2,3) Winograd tiles on the exact path (csrc/conv_kernel.h: Cfg::WINO): the large stride-1 3x3 layers computed as four
+/* F(2,3) Winograd tiles on the exact path (csrc/conv_wino.h; conv_cfg.h: Cfg::WINO): the large stride-1 3x3 layers computed as four
  * GEMMs over row-transformed inputs and load-time-transformed weights - fp32 in, fp32 accumulation on the same MFMA, 4
  * multiplies per output pair where the direct form spends 6.  mode 0: never (the direct tiles only), 1 (default): where the
  * measured table csrc/conv_tuned_wino.h lists the layer (shape, kind, device batch), 2: every layer a Winograd variant can
@@ -390,7 +390,7 @@ int mvlm_cnn_set_pairing(mvlm_ctx* ctx, int mode);
  * float64 arithmetic, one rounding). */
 int mvlm_cnn_set_winograd(mvlm_ctx* ctx, int mode);
 int mvlm_pack_winograd_weights(const float* w9_host, int cin_pad, int cout_pad, float* w12_host);
-/* The F(4,3) Winograd tile (csrc/conv_kernel.h: Cfg::WINO4, variant conv3x3q_c32_t16x32): four output rows from six transformed
+/* The F(4,3) Winograd tile (csrc/conv_wino4.h; conv_cfg.h: Cfg::WINO4, variant conv3x3q_c32_t16x32): four output rows from six transformed
  * input rows and six GEMMs on the points 0, 1, -1, 2, -1/2, inf - 6 multiplies per four outputs where F(2,3) spends 8 and the
  * direct form 12, fp32 in and fp32 accumulation on the same MFMA.  It is consulted ahead of the F(2,3) table while the Winograd
  * mode is not 0.  mode 0: never, 1 (default): where the measured table csrc/conv_tuned_wino4.h lists the layer and the Winograd

@@ -455,7 +455,7 @@ void mvlm_winograd_transform(const float* w9, int cin_pad, int cout_pad, float* 
 bool mvlm_conv_wino4_serves_slot(int ksize, int cin_pad, int cout_pad);  // the F(4,3) tile can serve these channels
 // host: packed [9][cin_pad][cout_pad] -> [18][cin_pad][cout_pad] (u_t per kx: t * 3 + kx), float64 arithmetic, one rounding
 void mvlm_winograd4_transform(const float* w9, int cin_pad, int cout_pad, float* w18);
-// two independent convolutions in one grid (conv_kernel.h: conv_pair_kernel)
+// two independent convolutions in one grid (conv_tile.h: conv_pair_kernel)
 constexpr int MVLM_CONV_PAIR_FLAG = 0x1000;  // variant code of a paired launch: flag | base id | lg(kparts0) << 8 | lg(kparts1) << 10
 int mvlm_conv_pair_variant(const ConvArgs& a0, const ConvArgs& a1, int mode);
 int mvlm_launch_conv_pair(mvlm_ctx* ctx, const ConvArgs& a0, const ConvArgs& a1, int pair_variant);

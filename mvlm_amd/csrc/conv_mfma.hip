@@ -30,7 +30,7 @@
 //   scatter, and for the last layer the per-(view, landmark) argmax
 //   (paulsenpredictor.py:123) so the [N,NL,256,256] heatmaps never reach HBM.
 //
-//   The large stride-1 3x3 layers also exist as F(2,3) Winograd along y (conv_kernel.h: Cfg::WINO, variants conv3x3w_*):
+//   The large stride-1 3x3 layers also exist as F(2,3) Winograd along y (conv_cfg.h: Cfg::WINO, variants conv3x3w_*):
 //   row pairs of transformed inputs x load-time-transformed weights, four GEMMs over K = (kx, cin), 4 MFMAs per output pair
 //   where the direct form spends 6 - same instruction, fp32 in and out.  mvlm_conv_wino_variant() routes a launch there where
 //   the measured table conv_tuned_wino.h says it is faster (mvlm_cnn_set_winograd / MVLM_WINOGRAD: 0 never, 1 table, 2 always).
@@ -64,7 +64,7 @@
 #include <vector>
 
 #include "common.h"
-#include "conv_kernel.h"   // Cfg<> (tile geometry) for the variant table below; kernels are not instantiated here
+#include "conv_cfg.h"      // Cfg<> (tile geometry) for the variant table below; kernels are not instantiated here
 #include "conv_variants.h"
 #include "conv_tuned.h"
 #include "conv_tuned_net.h"
@@ -152,7 +152,7 @@ VariantCode decode_variant(int v) {
 const ConvVariantInfo* variant_row(int v) { return conv_variant(v == MVLM_CONV_VARIANT_WINO4 ? v : v & 255); }
 
 // Does the tile divide this layer?  Every "can this variant serve ..." question is this plus the caller's own conditions.
-// (check_variant<C> in conv_kernel.h states the same once more at the launch, as the last line of defence.)
+// (check_variant<C> in conv_launch.h states the same once more at the launch, as the last line of defence.)
 bool tile_fits(const ConvVariantInfo& t, int ksize, int cin_pad, int cout_pad, int H, int W) {
     return ksize == t.KS && W % t.TW == 0 && H % t.TRI == 0 && cout_pad % t.COUT_T == 0 && cin_pad % t.CK == 0 &&
            (!t.SPLITK || cin_pad % 32 == 0);

@@ -63,12 +63,12 @@
     X(30, "conv3x3_sk16_t8x8", Cfg<32, 8, 8, 1, 3, 16, true>) \
     X(31, "conv3x3_sk8_t8x8", Cfg<32, 8, 8, 1, 3, 8, true>) \
     X(32, "conv3x3_sk16_t4x16", Cfg<32, 16, 4, 1, 3, 16, true>)
-// F(2,3) Winograd along y (KS parameter 32 = "3x3 as F(2,3)", conv_kernel.h: Cfg::WINO): 4 MFMAs per output pair and
+// F(2,3) Winograd along y (KS parameter 32 = "3x3 as F(2,3)", conv_cfg.h: Cfg::WINO): 4 MFMAs per output pair and
 // (kx, cin) instead of 6 on transformed rows and host-transformed weights ([12][cin_pad][cout_pad]).  Instantiated in
 // conv_inst_w0.hip, built into build/wino/ (occupancy table tests/golden/kernel_occupancy_wino.json).
 #define MVLM_CONV_VARIANTS_W0(X) \
     X(40, "conv3x3w_c64_t8x32", Cfg<64, 32, 8, 1, 32, 4>)
-// F(4,3) Winograd along y (KS parameter 34 = "3x3 as F(4,3)", conv_kernel.h: Cfg::WINO4): 6 MFMAs per four output rows and
+// F(4,3) Winograd along y (KS parameter 34 = "3x3 as F(4,3)", conv_cfg.h: Cfg::WINO4): 6 MFMAs per four output rows and
 // (kx, cin) on the tile geometry of conv3x3_c32_t16x32, host-transformed weights [18][cin_pad][cout_pad].  Instantiated in
 // conv_inst_q0.hip, built into build/wino4/ (occupancy table tests/golden/kernel_occupancy_wino4.json).  It has no base id: what
 // every id in 0..1023 is called and serves is pinned by tests/golden/conv_routing.txt, so the tile has a code of its own beyond

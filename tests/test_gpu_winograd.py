@@ -1,4 +1,4 @@
-"""-m gpu: the F(2,3) Winograd tiles of the large 3x3 layers (conv_kernel.h: Cfg::WINO, mvlm_cnn_set_winograd).
+"""-m gpu: the F(2,3) Winograd tiles of the large 3x3 layers (conv_wino.h; conv_cfg.h: Cfg::WINO, mvlm_cnn_set_winograd).
 
 Single layers with the variant forced against torch float64 (the bound of test_conv2d_matches_torch), the network with every
 servable layer on a Winograd tile (mode 2) against the direct path (mode 0) and against the reference's own vectors, mode 0 as

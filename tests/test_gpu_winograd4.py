@@ -1,4 +1,4 @@
-"""-m gpu: the F(4,3) Winograd tile of the 3x3 layers (conv_kernel.h: Cfg::WINO4, variant conv3x3q_c32_t16x32, mvlm_cnn_set_winograd4).
+"""-m gpu: the F(4,3) Winograd tile of the 3x3 layers (conv_wino4.h; conv_cfg.h: Cfg::WINO4, variant conv3x3q_c32_t16x32, mvlm_cnn_set_winograd4).
 
 Single layers with the variant forced against torch float64 (the bound of test_conv2d_matches_torch), the network with every
 servable layer on the tile (F(4,3) mode 2) against the direct path (Winograd mode 0) and against the reference's own vectors,

@@ -1,4 +1,4 @@
-"""-m gpu: the K loop of the F(2,3) Winograd tile (conv_kernel.h: wino_main) at the smallest shapes where it can go wrong.
+"""-m gpu: the K loop of the F(2,3) Winograd tile (conv_wino.h: wino_main) at the smallest shapes where it can go wrong.
 
 The loop runs two channel groups per iteration with compile-time LDS stages, stages the last group of a layer apart from the
 steady loop (the only one that can hold padded channels), lets lanes without a staging job repeat another lane's and folds the

@@ -1,4 +1,4 @@
-"""The F(4,3)-along-y form of the 3x3 layers (mvlm_amd/csrc/conv_kernel.h: Cfg::WINO4, points 0, 1, -1, 2, -1/2, inf) on the CPU:
+"""The F(4,3)-along-y form of the 3x3 layers (mvlm_amd/csrc/conv_wino4.h; conv_cfg.h: Cfg::WINO4, points 0, 1, -1, 2, -1/2, inf) on the CPU:
 a float64 numpy model of the tile's arithmetic - six transformed rows v_t per row quad, six transformed weight columns u_t, six
 GEMMs over (kx, cin), the output transform - against the direct convolution, and the library's host weight transform against
 the model's."""

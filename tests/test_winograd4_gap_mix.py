@@ -3,7 +3,7 @@ built objects (tools/conv_loop_mix.py: max_gap; build/wino4/ and build/wino4w/),
 
 A wave issues in order: behind an MFMA, only what that one MFMA covers is free.  A v_mfma_f32_32x32x2_f32 holds the matrix pipe
 for 64 cycles and a vector instruction takes 4 to issue, so 16 instructions is what a gap can hold.  The chunk schedule places
-the staging slice by slice in the gaps (conv_kernel.h: Wino4Plan); tests/golden/conv_gap_mix_wino4.json records the largest gap per
+the staging slice by slice in the gaps (conv_wino4.h: Wino4Plan); tests/golden/conv_gap_mix_wino4.json records the largest gap per
 kernel, nothing may exceed its record, and no record may exceed 16.
 
 The commit before the slices placed a k-step's whole staging between its 2nd and 3rd MFMA: its largest gaps, read from its

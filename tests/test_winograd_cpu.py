@@ -1,4 +1,4 @@
-"""The F(2,3)-along-y form of the large 3x3 layers (mvlm_amd/csrc/conv_kernel.h: Cfg::WINO) on the CPU: a float64 numpy model of
+"""The F(2,3)-along-y form of the large 3x3 layers (mvlm_amd/csrc/conv_wino.h; conv_cfg.h: Cfg::WINO) on the CPU: a float64 numpy model of
 the tile's arithmetic - transformed rows v_t, transformed weight columns u_t, four GEMMs over (kx, cin), the output transform -
 against the direct convolution, and the library's host weight transform against the model's."""
 import ctypes as C

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Where a convolution workgroup spends its cycles: prologue / K loop / epilogue of wave 0, summed over
 the workgroups of one launch (diagnostic build of the library with -DMVLM_CONV_TIMING, see
-mvlm_amd/csrc/conv_kernel.h).  Run on the GPU box:
+mvlm_amd/csrc/conv_tile.h; the launch's side in conv_launch.h).  Run on the GPU box:
 
   make -C mvlm_amd/csrc timing        # builds mvlm_amd/lib/libmvlm_hip_timing.so
   MVLM_HIP_LIB=mvlm_amd/lib/libmvlm_hip_timing.so python tools/conv_phase_timing.py

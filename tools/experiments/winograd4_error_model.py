@@ -1,4 +1,4 @@
-"""CPU model of the rounding error of a 3x3 layer as the direct tile, as F(2,3) along y (conv_kernel.h: Cfg::WINO) and as F(4,3) along
+"""CPU model of the rounding error of a 3x3 layer as the direct tile, as F(2,3) along y (conv_wino.h; conv_cfg.h: Cfg::WINO) and as F(4,3) along
 y (Cfg::WINO4) on two point sets, each against float64.
 
 The model is the tiles' arithmetic: BatchNorm + ReLU in fp32, the input transform in fp32 summed left to right (all coefficients

@@ -1,4 +1,4 @@
-"""CPU estimate of the rounding error of the F(2,3)-along-y form of a 3x3 layer (conv_kernel.h: Cfg::WINO) against a direct fp32
+"""CPU estimate of the rounding error of the F(2,3)-along-y form of a 3x3 layer (conv_wino.h; conv_cfg.h: Cfg::WINO) against a direct fp32
 convolution, both measured against float64: inputs, weights, pre-BN and residual drawn as tests/test_gpu_parity.py draws them, the
 four GEMMs as 1x3 fp32 convolutions over the transformed rows.  torch's CPU kernels do not sum in the GPU tile's k order, so these
 are estimates of size; the measured figures are tests/test_gpu_winograd.py's (profiles/r08_winograd_error.txt)."""
