@@ -1,5 +1,4 @@
-// Context, mesh upload and the single-convolution test hook of the C ABI
-// (include/mvlm_hip.h).
+// Context and mesh upload of the C ABI (include/mvlm_hip.h); the single-convolution hooks are conv_hooks.hip.
 #include <atomic>
 #include <cstring>
 
@@ -640,334 +639,6 @@ extern "C" void mvlm_mesh_free(mvlm_ctx* ctx, mvlm_mesh* m) {
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     delete m;
-}
-
-// test / tuning hook: the next mvlm_conv2d calls on this ctx use exactly this kernel variant (-1: the dispatcher's choice)
-extern "C" int mvlm_conv_force_variant(mvlm_ctx* ctx, int variant) {
-    MVLM_ENTER(ctx);
-    ctx->conv_force_variant = variant < 0 ? -1 : variant;
-    return 0;
-}
-
-// ---- single convolution (test hook): packs the weights like mvlm_amd/weights.py does -------
-extern "C" int mvlm_conv2d(mvlm_ctx* ctx, const float* x_dev, int batch, int cin, int h, int w, const float* w_host,
-                           int cout, int ksize, const float* bias_host, const float* pre_scale_host,
-                           const float* pre_shift_host, const float* post_scale_host, const float* post_shift_host,
-                           const float* r_dev, int upsample_in, float* y_dev) {
-    MVLM_ENTER(ctx);
-    MVLM_REQUIRE(ctx, x_dev && w_host && y_dev, "conv2d: null pointer");
-    MVLM_REQUIRE(ctx, ksize == 1 || ksize == 3, "conv2d: kernel size must be 1 or 3");
-    MVLM_REQUIRE(ctx, (pre_scale_host == nullptr) == (pre_shift_host == nullptr), "conv2d: pre scale/shift come in pairs");
-    MVLM_REQUIRE(ctx, (post_scale_host == nullptr) == (post_shift_host == nullptr), "conv2d: post scale/shift come in pairs");
-    // same padding rules as mvlm_amd/weights.py: a plain conv + bias layer on the 32-pixel-row tiles may
-    // end in one 16-row strip
-    const bool tail16 = ksize == 3 && (cout + 15) / 16 * 16 == 80 && !pre_scale_host && !post_scale_host && !r_dev &&
-                        w >= 32 && h % 8 == 0;
-    const int cin_pad = (ksize == 1 ? (cin + 7) / 8 * 8 : (cin + 3) / 4 * 4), taps = ksize * ksize;
-    // ... or, with exactly 84 output channels, in a 16-row and a 4-row strip (conv6 / conv10 of the 84-landmark network)
-    const bool tail4 = ksize == 3 && cout == 84 && bias_host && !pre_scale_host && !post_scale_host && !r_dev && !upsample_in &&
-                       w >= 32 && h % 8 == 0;
-    const int cout_pad = tail16 ? (cout + 15) / 16 * 16 : tail4 ? 84 : (cout + 31) / 32 * 32;
-    std::vector<float> blob;
-    auto push = [&](size_t n) {
-        const size_t off = blob.size();
-        blob.resize(off + (n + 3) / 4 * 4, 0.f);
-        return off;
-    };
-    const size_t w_off = push(size_t(taps) * cin_pad * cout_pad);
-    for (int co = 0; co < cout; ++co)
-        for (int ci = 0; ci < cin; ++ci)
-            for (int t = 0; t < taps; ++t)
-                blob[w_off + (size_t(t) * cin_pad + ci) * cout_pad + co] = w_host[(size_t(co) * cin + ci) * taps + t];
-    auto vec = [&](const float* src, int n, int n_pad) -> long {
-        if (!src) return -1;
-        const size_t off = push(n_pad);
-        for (int i = 0; i < n; ++i) blob[off + i] = src[i];
-        return long(off);
-    };
-    // the Winograd forms beside it where such a tile could be chosen or forced
-    long ww_off[MVLM_WINO_FORMS_N];
-    for (int f = 0; f < MVLM_WINO_FORMS_N; ++f) {
-        const WinoForm& form = mvlm_wino_form(f);
-        ww_off[f] = -1;
-        if (!form.serves_slot(ksize, cin_pad, cout_pad)) continue;
-        ww_off[f] = long(push(size_t(form.slices) * cin_pad * cout_pad));
-        form.transform(blob.data() + w_off, cin_pad, cout_pad, blob.data() + ww_off[f]);
-    }
-    const long b_off = vec(bias_host, cout, cout_pad);
-    // ... and the F(4,3) form at a cout stride of whole 32s, the bias alike, where the dispatcher may run the 80- or 84-row tile's launch on that tile
-    long wp_off = -1, bp_off = -1;
-    if (mvlm_conv_wino4_pad_serves_slot(ksize, cin_pad, cout_pad)) {
-        const int P = mvlm_conv_wino4_padded_cout(cout_pad);
-        wp_off = long(push(size_t(18) * cin_pad * P));
-        if (b_off >= 0) bp_off = long(push(size_t(P)));
-        mvlm_winograd4_pack_padded(blob.data() + w_off, b_off < 0 ? nullptr : blob.data() + b_off, cin_pad, cout_pad, blob.data() + wp_off,
-                                   bp_off < 0 ? nullptr : blob.data() + bp_off);
-    }
-    const long ps_off = vec(pre_scale_host, cin, cin_pad), pt_off = vec(pre_shift_host, cin, cin_pad);
-    const long qs_off = vec(post_scale_host, cout, cout_pad), qt_off = vec(post_shift_host, cout, cout_pad);
-    auto* d = static_cast<float*>(ctx->get_scratch("conv2d.blob", blob.size() * 4));
-    MVLM_REQUIRE(ctx, d, "conv2d: scratch allocation failed");
-    MVLM_CHECK_HIP(ctx, hipMemcpy(d, blob.data(), blob.size() * 4, hipMemcpyHostToDevice));
-    ConvArgs a;
-    a.in = x_dev;
-    a.in_ctot = cin;
-    a.cin = cin;
-    a.cin_pad = cin_pad;
-    a.up_in = upsample_in;
-    a.B = batch;
-    a.H = h;
-    a.W = w;
-    a.w = d + w_off;
-    for (int f = 0; f < MVLM_WINO_FORMS_N; ++f) a.*mvlm_wino_form(f).weights = ww_off[f] < 0 ? nullptr : d + ww_off[f];
-    a.cout = cout;
-    a.cout_pad = cout_pad;
-    a.ksize = ksize;
-    a.bias = b_off < 0 ? nullptr : d + b_off;
-    a.pre_scale = ps_off < 0 ? nullptr : d + ps_off;
-    a.pre_shift = pt_off < 0 ? nullptr : d + pt_off;
-    a.post_scale = qs_off < 0 ? nullptr : d + qs_off;
-    a.post_shift = qt_off < 0 ? nullptr : d + qt_off;
-    a.res1 = r_dev;
-    a.res1_ctot = cout;
-    a.out = y_dev;
-    a.out_ctot = cout;
-    ctx->conv_wino4_pads[0] = {wp_off < 0 ? nullptr : d + wp_off, bp_off < 0 ? nullptr : d + bp_off};  // (this call's layer; null: none)
-    a.wino4_pad = wp_off < 0 ? 0 : 1;
-    if (mvlm_launch_conv(ctx, a, nullptr)) return 1;
-    MVLM_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-
-// ---- kernel-variant timing (tools/tune_conv.py): one layer shape, dummy data, a forced variant ----------
-// Times `iters` launches of one convolution with HIP events on the ctx stream.  flags: 1 = pre-BN+ReLU on the
-// input, 2 = residual add + raw copy (a residual block's conv1 / conv2), 4 = bias, 8 = post-BN+ReLU.
-// variant -1: the dispatcher's own choice, -2: its rules without the tuned table (returned in *variant_used).
-// Shapes a variant cannot serve fail.
-extern "C" int mvlm_conv_bench(mvlm_ctx* ctx, int batch, int cin, int cout, int ksize, int size, int flags, int variant,
-                               int iters, float* ms_per_launch, int* variant_used) {
-    MVLM_ENTER(ctx);
-    MVLM_REQUIRE(ctx, batch > 0 && cin > 0 && cout > 0 && size > 0 && iters > 0 && ms_per_launch, "conv_bench: bad arguments");
-    MVLM_REQUIRE(ctx, ksize == 1 || ksize == 3, "conv_bench: kernel size must be 1 or 3");
-    const int cin_pad = (ksize == 1 ? (cin + 7) / 8 * 8 : (cin + 3) / 4 * 4), taps = ksize * ksize;
-    const bool plain = (flags & 4) && !(flags & (1 | 2 | 8));
-    const int cout_pad = (plain && (cout + 15) / 16 * 16 == 80) ? 80 : (plain && ksize == 3 && cout == 84) ? 84 : (cout + 31) / 32 * 32;
-    const size_t px = size_t(batch) * size * size;
-    // (zero data serves every form of the weights: 18 slices at the F(4,3) tile's padded cout stride cover them all)
-    const size_t n_w = size_t(ksize == 3 ? 18 : taps) * cin_pad * mvlm_conv_wino4_padded_cout(cout_pad), n_vec = size_t(cin_pad) * 2 + size_t(cout_pad) * 3;
-    const size_t n_x = px * cin, n_y = px * cout;
-    const size_t total = n_w + n_vec + n_x + 3 * n_y + 64;
-    auto* base = static_cast<float*>(ctx->get_scratch("conv_bench", total * sizeof(float)));
-    MVLM_REQUIRE(ctx, base, "conv_bench: scratch allocation failed");
-    MVLM_CHECK_HIP(ctx, hipMemsetAsync(base, 0, total * sizeof(float), ctx->stream));
-    float* w = base;
-    float* vec = w + n_w;
-    float* x = vec + (n_vec + 3) / 4 * 4;
-    float* y = x + (n_x + 3) / 4 * 4;
-    float* raw = y + (n_y + 3) / 4 * 4;
-    float* res = raw + (n_y + 3) / 4 * 4;
-    ConvArgs a;
-    a.in = x;
-    a.in_ctot = cin;
-    a.cin = cin;
-    a.cin_pad = cin_pad;
-    a.B = batch;
-    a.H = a.W = size;
-    a.w = w;
-    for (int f = 0; f < MVLM_WINO_FORMS_N; ++f)  // (zero data: the transformed weights are zeros too)
-        if (mvlm_wino_form(f).serves_slot(ksize, cin_pad, cout_pad)) a.*mvlm_wino_form(f).weights = w;
-    const bool padded = mvlm_conv_wino4_pad_serves_slot(ksize, cin_pad, cout_pad);
-    ctx->conv_wino4_pads[0] = padded ? ConvWino4Pad{w, vec + 2 * cin_pad} : ConvWino4Pad{};  // (this call's layer: the zero weights, the zero bias)
-    a.wino4_pad = padded ? 1 : 0;
-    a.cout = cout;
-    a.cout_pad = cout_pad;
-    a.ksize = ksize;
-    if (flags & 1) {
-        a.pre_scale = vec;
-        a.pre_shift = vec + cin_pad;
-    }
-    if (flags & 4) a.bias = vec + 2 * cin_pad;
-    if (flags & 8) {
-        a.post_scale = vec + 2 * cin_pad + cout_pad;
-        a.post_shift = vec + 2 * cin_pad + 2 * cout_pad;
-    }
-    if (flags & 2) {
-        a.res1 = res;
-        a.res1_ctot = cout;
-        a.out_raw = raw;
-        a.raw_ctot = cout;
-    }
-    a.out = y;
-    a.out_ctot = cout;
-    const int saved = ctx->conv_force_variant;
-    ctx->conv_force_variant = variant >= 0 ? variant : (variant == -2 ? -2 : -1);
-    int used = -1;
-    unsigned short* wq = nullptr;
-    // the opt-in split kernels on zero weights: 62 bf16x3, 61 f16x2
-    const int splits = variant == MVLM_CONV_VARIANT_FAST ? 3 : (variant == MVLM_CONV_VARIANT_FAST16 ? 2 : 0);
-    if (splits) {
-        a.cin_pad = (cin + 15) / 16 * 16;
-        a.cout_pad = mvlm_fast_cout_pad(cout);
-        const size_t n16 = size_t(a.cin_pad / 16) * 9 * 2 * splits * a.cout_pad * 8;
-        wq = static_cast<unsigned short*>(ctx->get_scratch("conv_bench.wq", n16 * 2));
-        if (!wq || !mvlm_conv_fast_ok(a, splits)) {
-            ctx->conv_force_variant = saved;
-            return ctx->fail("conv_bench: shape not eligible for the fast kernel");
-        }
-        (void)hipMemsetAsync(wq, 0, n16 * 2, ctx->stream);
-    }
-    auto launch = [&](int* v) { return wq ? mvlm_launch_conv_fast(ctx, a, wq, splits, 1.f) : mvlm_launch_conv(ctx, a, v); };
-    int rc = launch(&used);  // warm-up (also sets the launch attributes)
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (!rc && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) rc = ctx->fail("conv_bench: hipEventCreate failed");
-    if (!rc) {
-        hipEventRecord(e0, ctx->stream);
-        for (int i = 0; i < iters && !rc; ++i) rc = launch(nullptr);
-        hipEventRecord(e1, ctx->stream);
-        if (!rc && hipEventSynchronize(e1) != hipSuccess) rc = ctx->fail("conv_bench: kernel failed");
-        float ms = 0.f;
-        if (!rc) hipEventElapsedTime(&ms, e0, e1);
-        *ms_per_launch = ms / iters;
-    }
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    ctx->conv_force_variant = saved;
-    if (variant_used) *variant_used = used;
-    return rc;
-}
-
-// ---- two independent 3x3 convolutions in one launch (test hook for conv_pair_kernel) -----------------------------------
-// Problem i: x_i f32[B,cin,size_i,size_i] * w_i f32[cout,cin,3,3] (+ shared pre-BN+ReLU, + residual r_i, raw copy raw_i)
-// -> y_i; `variant` as in mvlm_conv_pair_bench.  The results must equal mvlm_conv2d's with the same kernel variant forced.
-extern "C" int mvlm_conv2d_pair(mvlm_ctx* ctx, int batch, int cin, int cout, const float* x0_dev, int size0, const float* w0_host,
-                                const float* r0_dev, float* raw0_dev, float* y0_dev, const float* x1_dev, int size1,
-                                const float* w1_host, const float* r1_dev, float* raw1_dev, float* y1_dev,
-                                const float* pre_scale_host, const float* pre_shift_host, int variant) {
-    MVLM_ENTER(ctx);
-    MVLM_REQUIRE(ctx, x0_dev && x1_dev && w0_host && w1_host && y0_dev && y1_dev && variant >= 0, "conv2d_pair: bad arguments");
-    MVLM_REQUIRE(ctx, (pre_scale_host == nullptr) == (pre_shift_host == nullptr), "conv2d_pair: pre scale/shift come in pairs");
-    const int cin_pad = (cin + 3) / 4 * 4, cout_pad = (cout + 31) / 32 * 32;
-    const size_t n_w = (size_t(9) * cin_pad * cout_pad + 3) / 4 * 4;
-    std::vector<float> blob(2 * n_w + 2 * size_t(cin_pad), 0.f);
-    const float* ws[2] = {w0_host, w1_host};
-    for (int i = 0; i < 2; ++i)
-        for (int co = 0; co < cout; ++co)
-            for (int ci = 0; ci < cin; ++ci)
-                for (int t = 0; t < 9; ++t) blob[i * n_w + (size_t(t) * cin_pad + ci) * cout_pad + co] = ws[i][(size_t(co) * cin + ci) * 9 + t];
-    if (pre_scale_host)
-        for (int i = 0; i < cin; ++i) {
-            blob[2 * n_w + i] = pre_scale_host[i];
-            blob[2 * n_w + cin_pad + i] = pre_shift_host[i];
-        }
-    auto* d = static_cast<float*>(ctx->get_scratch("conv2d.blob", blob.size() * 4));
-    MVLM_REQUIRE(ctx, d, "conv2d_pair: scratch allocation failed");
-    MVLM_CHECK_HIP(ctx, hipMemcpy(d, blob.data(), blob.size() * 4, hipMemcpyHostToDevice));
-    ConvArgs a[2];
-    const float* xs[2] = {x0_dev, x1_dev};
-    const float* rs[2] = {r0_dev, r1_dev};
-    float* raws[2] = {raw0_dev, raw1_dev};
-    float* ys[2] = {y0_dev, y1_dev};
-    const int sizes[2] = {size0, size1};
-    for (int i = 0; i < 2; ++i) {
-        ConvArgs& c = a[i];
-        c.in = xs[i];
-        c.in_ctot = cin;
-        c.cin = cin;
-        c.cin_pad = cin_pad;
-        c.B = batch;
-        c.H = c.W = sizes[i];
-        c.w = d + i * n_w;
-        c.cout = cout;
-        c.cout_pad = cout_pad;
-        c.ksize = 3;
-        if (pre_scale_host) {
-            c.pre_scale = d + 2 * n_w;
-            c.pre_shift = d + 2 * n_w + cin_pad;
-        }
-        c.res1 = rs[i];
-        c.res1_ctot = cout;
-        c.out_raw = raws[i];
-        c.raw_ctot = cout;
-        c.out = ys[i];
-        c.out_ctot = cout;
-    }
-    if (mvlm_launch_conv_pair(ctx, a[0], a[1], (variant & 0xfff) | MVLM_CONV_PAIR_FLAG)) return 1;
-    MVLM_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-
-// Tuning hook for tools/tune_conv_pairs.py: conv j of a hourglass level's skip block at `size` and of the next level's first
-// block at size / 2 (same channels, pre-BN + residual + raw copy as in the network) on zero data.  variant < 0: the two
-// tuned single launches back to back; variant >= 0: ONE two-problem launch of kernel variant (variant & 255) with
-// 1 << ((variant >> 8) & 3) / 1 << ((variant >> 10) & 3) K parts for the size / size / 2 problem.
-extern "C" int mvlm_conv_pair_bench(mvlm_ctx* ctx, int batch, int cin, int cout, int size, int flags, int variant, int iters,
-                                    float* ms_per_launch) {
-    MVLM_ENTER(ctx);
-    MVLM_REQUIRE(ctx, batch > 0 && cin > 0 && cout > 0 && size >= 8 && size % 2 == 0 && iters > 0 && ms_per_launch, "conv_pair_bench: bad arguments");
-    const int cin_pad = (cin + 3) / 4 * 4, cout_pad = (cout + 31) / 32 * 32;
-    const size_t n_w = size_t(9) * cin_pad * cout_pad, n_vec = (size_t(cin_pad) * 2 + size_t(cout_pad) * 3 + 3) / 4 * 4;
-    size_t px[2] = {size_t(batch) * size * size, size_t(batch) * (size / 2) * (size / 2)};
-    size_t total = n_w + n_vec + 64;
-    for (int i = 0; i < 2; ++i) total += (px[i] * cin + 3) / 4 * 4 + 3 * ((px[i] * cout + 3) / 4 * 4);
-    auto* base = static_cast<float*>(ctx->get_scratch("conv_bench", total * sizeof(float)));
-    MVLM_REQUIRE(ctx, base, "conv_pair_bench: scratch allocation failed");
-    MVLM_CHECK_HIP(ctx, hipMemsetAsync(base, 0, total * sizeof(float), ctx->stream));
-    float* w = base;
-    float* vec = w + n_w;
-    float* cur = vec + n_vec;
-    ConvArgs a[2];
-    for (int i = 0; i < 2; ++i) {
-        ConvArgs& c = a[i];
-        const size_t n_x = (px[i] * cin + 3) / 4 * 4, n_y = (px[i] * cout + 3) / 4 * 4;
-        c.in = cur;
-        float* y = cur + n_x;
-        float* raw = y + n_y;
-        float* res = raw + n_y;
-        cur = res + n_y;
-        c.in_ctot = cin;
-        c.cin = cin;
-        c.cin_pad = cin_pad;
-        c.B = batch;
-        c.H = c.W = i ? size / 2 : size;
-        c.w = w;
-        c.cout = cout;
-        c.cout_pad = cout_pad;
-        c.ksize = 3;
-        if (flags & 1) {
-            c.pre_scale = vec;
-            c.pre_shift = vec + cin_pad;
-        }
-        if (flags & 2) {
-            c.res1 = res;
-            c.res1_ctot = cout;
-            c.out_raw = raw;
-            c.raw_ctot = cout;
-        }
-        c.out = y;
-        c.out_ctot = cout;
-    }
-    const int saved = ctx->conv_force_variant;
-    ctx->conv_force_variant = -1;
-    auto launch = [&]() -> int {
-        if (variant < 0) return mvlm_launch_conv(ctx, a[0], nullptr) || mvlm_launch_conv(ctx, a[1], nullptr);
-        return mvlm_launch_conv_pair(ctx, a[0], a[1], (variant & 0xfff) | MVLM_CONV_PAIR_FLAG);
-    };
-    int rc = launch();  // warm-up (also sets the launch attributes)
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (!rc && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) rc = ctx->fail("conv_pair_bench: hipEventCreate failed");
-    if (!rc) {
-        hipEventRecord(e0, ctx->stream);
-        for (int i = 0; i < iters && !rc; ++i) rc = launch();
-        hipEventRecord(e1, ctx->stream);
-        if (!rc && hipEventSynchronize(e1) != hipSuccess) rc = ctx->fail("conv_pair_bench: kernel failed");
-        float ms = 0.f;
-        if (!rc) hipEventElapsedTime(&ms, e0, e1);
-        *ms_per_launch = ms / iters;
-    }
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    ctx->conv_force_variant = saved;
-    return rc;
 }
 
 // ---- landmark view (raster_view.hip; DESIGN.md 5.1, "Landmark view") and ray view (raster_rays.hip; "Ray view") -----------

@@ -17,8 +17,8 @@
 //
 // All views of a batch go through each layer together (pixels of all views form the GEMM's
 // N dimension), so even the 4x4 hourglass level fills MFMA tiles.
-#include <array>
 #include <cstdlib>
+#include <cstring>
 
 #include "common.h"
 
@@ -40,6 +40,9 @@ struct Block {
     int arena;      // 0: main stream, 1: side stream - a block is only ever reused by kernels of its own arena's stream
     bool deferred;  // released while the streams ran apart: becomes free at the join
 };
+
+// conv11's parity slots are in the packed weights, on a cout_pad one of the 2x2 tiles serves
+bool parity_slots_usable(const ConvSlotDesc& r) { return r.present != 0 && (r.cout_pad == 96 || r.cout_pad == 80 || r.cout_pad == 84); }
 
 struct Exec {
     mvlm_ctx* ctx;
@@ -155,35 +158,40 @@ struct Exec {
             rc = ctx->fail("cnn: join of the side stream failed");
     }
 
-    const int32_t* d(int slot) const { return &st.desc[size_t(slot) * MVLM_CONV_DESC_INTS]; }
+    const ConvSlotDesc& d(int slot) const { return st.desc[size_t(slot)]; }
     const float* blob(int off) const { return off < 0 ? nullptr : st.blob + off; }
 
+    // the shape of `slot` at size S into `a`: what the dispatcher chooses a kernel variant by
+    void fill_shape(int slot, ConvArgs& a, int S) const {
+        const ConvSlotDesc& r = d(slot);
+        a.cin = r.cin;
+        a.cout = r.cout;
+        a.ksize = r.ksize;
+        a.cin_pad = r.cin_pad;
+        a.cout_pad = r.cout_pad;
+        a.B = B;
+        a.H = a.W = S;
+    }
     // weights / BN / bias / shape of `slot` into `a`
     int fill(int slot, const Tensor& x, ConvArgs& a, int S) {
         if (rc) return rc;
-        const int32_t* r = d(slot);
-        if (!r[0]) return rc = ctx->fail("cnn: conv slot not present in the packed weights");
+        const ConvSlotDesc& r = d(slot);
+        if (!r.present) return rc = ctx->fail("cnn: conv slot not present in the packed weights");
         a.in = x.p;
         a.in_ctot = x.C;
         a.in_coff = 0;
-        a.cin = r[1];
-        a.cout = r[2];
-        a.ksize = r[3];
-        a.cin_pad = r[4];
-        a.cout_pad = r[5];
-        a.w = blob(r[6]);
+        fill_shape(slot, a, S);
+        a.w = blob(r.w_off);
         for (int f = 0; f < MVLM_WINO_FORMS_N; ++f) {
             const CnnState::WinoWeights& ww = st.wino[f];
             a.*mvlm_wino_form(f).weights = (size_t(slot) < ww.off.size() && ww.off[size_t(slot)] >= 0) ? ww.blob + ww.off[size_t(slot)] : nullptr;
         }
         a.wino4_pad = size_t(slot) < st.wino4_pad_id.size() ? st.wino4_pad_id[size_t(slot)] : 0;
-        a.bias = blob(r[7]);
-        a.pre_scale = blob(r[8]);
-        a.pre_shift = blob(r[9]);
-        a.post_scale = blob(r[10]);
-        a.post_shift = blob(r[11]);
-        a.B = B;
-        a.H = a.W = S;
+        a.bias = blob(r.bias_off);
+        a.pre_scale = blob(r.pre_scale_off);
+        a.pre_shift = blob(r.pre_shift_off);
+        a.post_scale = blob(r.post_scale_off);
+        a.post_shift = blob(r.post_shift_off);
         if (x.C != a.cin) return rc = ctx->fail("cnn: channel mismatch between graph and packed weights");
         return 0;
     }
@@ -292,9 +300,9 @@ struct Exec {
         P.base = 1 + 4 * rb_index;
         P.S = x.S;
         P.x = x;
-        P.cout = d(P.base + 1)[2] * 2;
+        P.cout = d(P.base + 1).cout * 2;
         const int cout = P.cout, h = cout / 2, q = cout / 4;
-        P.resample = d(P.base)[0] != 0;
+        P.resample = d(P.base).present != 0;
         if (!hi) P.y = alloc(cout, P.S);
         if (P.resample && hi) {
             rc = ctx->fail("cnn: resampling block cannot scatter");
@@ -412,12 +420,14 @@ struct Exec {
 
     // the four parity slots of conv11 differ in their weights only (same shapes, one bias): they can share a launch
     bool parity_weights_uniform(int slot0) const {
-        const int32_t* r0 = d(slot0);
+        auto plain = [](const ConvSlotDesc& r) { return r.pre_scale_off < 0 && r.pre_shift_off < 0 && r.post_scale_off < 0 && r.post_shift_off < 0; };
+        const ConvSlotDesc& r0 = d(slot0);
         for (int q = 1; q < 4; ++q) {
-            const int32_t* r = d(slot0 + q);
-            if (!r[0] || r[1] != r0[1] || r[2] != r0[2] || r[3] != r0[3] || r[4] != r0[4] || r[5] != r0[5] || (r[7] < 0) != (r0[7] < 0)) return false;
-            for (int k = 8; k <= 11; ++k)
-                if (r[k] >= 0 || r0[k] >= 0) return false;  // plain conv + bias layers
+            const ConvSlotDesc& r = d(slot0 + q);
+            if (!r.present || r.cin != r0.cin || r.cout != r0.cout || r.ksize != r0.ksize || r.cin_pad != r0.cin_pad || r.cout_pad != r0.cout_pad ||
+                (r.bias_off < 0) != (r0.bias_off < 0))
+                return false;
+            if (!plain(r) || !plain(r0)) return false;  // plain conv + bias layers
         }
         return true;
     }
@@ -425,14 +435,7 @@ struct Exec {
     // would conv `slot` on this input run a kernel variant that can also emit the pooled tensor?
     bool pool_fusable(int slot, const Tensor& x, ConvArgs a, int S) {
         if (no_pool_fusion) return false;
-        const int32_t* r = d(slot);
-        a.cin = r[1];
-        a.cout = r[2];
-        a.ksize = r[3];
-        a.cin_pad = r[4];
-        a.cout_pad = r[5];
-        a.B = B;
-        a.H = a.W = S;
+        fill_shape(slot, a, S);
         (void)x;
         if (runs_fast(slot, a)) return !(S & 1);  // the split-operand kernels pool in their epilogues too (round 5)
         return mvlm_conv_can_pool(ctx, a);
@@ -448,7 +451,7 @@ struct Exec {
         if (st.fast || scatter_only || B > consumer_add_max_batch) return false;
         ConvArgs a;
         Tensor x;
-        x.C = d(slot)[1];
+        x.C = d(slot).cin;
         x.S = 128;
         const int saved = rc;
         if (fill(slot, x, a, 128)) {
@@ -551,7 +554,6 @@ struct Exec {
     // images: [B,256,256,4]; either maxima (+view0/n_total) or heat ([B,NL,256,256]) is set
     int forward(const float* images, const int* sel4, float* maxima, int view0, int n_total, float* heat) {
         const int NL = st.n_landmarks, C = st.in_channels;
-        const int SLOT_CONV5 = 1 + 4 * 43;
         Tensor x0 = alloc(C, 256);
         if (!dry && mvlm_launch_pack_input(ctx, images, B, sel4, C, x0.p)) return 1;
         Tensor a0 = alloc(64, 256);
@@ -572,7 +574,7 @@ struct Exec {
         Tensor r3 = rb(2, a2, nullptr, &r3p);  // conv4 (+ its pooled copy for the hourglass)
         release(a2);
         Tensor h1_low;
-        const bool cs1 = consumer_side_add(SLOT_CONV5);
+        const bool cs1 = consumer_side_add(MVLM_SLOT_CONV5);
         Tensor h1 = hourglass(3, r3, r3p, cs1 ? &h1_low : nullptr);
         release(r3p);
         Tensor ll1 = alloc(256, 128);
@@ -584,7 +586,7 @@ struct Exec {
                 a.in2 = h1_low.p;
                 a.in2_ctot = h1_low.C;
             }
-            conv(SLOT_CONV5, h1, a, 128);  // conv5 + bn2 + relu (on up1 + upsample(low3) when the add is the consumer's)
+            conv(MVLM_SLOT_CONV5, h1, a, 128);  // conv5 + bn2 + relu (on up1 + upsample(low3) when the add is the consumer's)
         }
         release(h1);
         if (cs1) release(h1_low);
@@ -593,7 +595,7 @@ struct Exec {
             ConvArgs a;
             a.out = x6.p;
             a.out_ctot = NL;
-            conv(SLOT_CONV5 + 1, ll1, a, 128);  // conv6
+            conv(MVLM_SLOT_CONV6, ll1, a, 128);  // conv6
         }
         Tensor sum = alloc(256, 128), sump;
         {
@@ -606,19 +608,19 @@ struct Exec {
             a.out_ctot = 256;
             sump = alloc(256, 64);
             a.pool_hint = 1;
-            const bool fused = pool_fusable(SLOT_CONV5 + 2, x6, a, 128);
+            const bool fused = pool_fusable(MVLM_SLOT_CONV7, x6, a, 128);
             if (fused) {
                 a.pool_out = sump.p;
                 a.pool_ctot = 256;
             }
-            conv(SLOT_CONV5 + 2, x6, a, 128);
+            conv(MVLM_SLOT_CONV7, x6, a, 128);
             if (!fused && !dry && !rc) pool_kernel(sum.p, 256, 128, sump.p);
         }
         release(x6);
         release(r3);
         release(ll1);
         Tensor h2_low;
-        const bool cs2 = consumer_side_add(SLOT_CONV5 + 3);
+        const bool cs2 = consumer_side_add(MVLM_SLOT_CONV9);
         Tensor h2 = hourglass(23, sum, sump, cs2 ? &h2_low : nullptr);
         release(sump);
         release(sum);
@@ -631,7 +633,7 @@ struct Exec {
                 a.in2 = h2_low.p;
                 a.in2_ctot = h2_low.C;
             }
-            conv(SLOT_CONV5 + 3, h2, a, 128);  // conv9 + bn3 + relu
+            conv(MVLM_SLOT_CONV9, h2, a, 128);  // conv9 + bn3 + relu
         }
         release(h2);
         if (cs2) release(h2_low);
@@ -640,15 +642,15 @@ struct Exec {
             ConvArgs a;
             a.out = x10.p;
             a.out_ctot = NL;
-            conv(SLOT_CONV5 + 4, x9, a, 128);  // conv10
+            conv(MVLM_SLOT_CONV10, x9, a, 128);  // conv10
         }
         release(x9);
         {
             // conv11 over the nearest-upsampled conv10 output (:428-429).  When the packed weights
             // carry the four parity slots (2x2 kernels with pre-summed taps) each output parity is
             // one launch over the 128x128 tensor: 16 instead of 36 tap evaluations per low-res pixel.
-            const int SLOT_PARITY = SLOT_CONV5 + 6;
-            const bool parity = d(SLOT_PARITY)[0] != 0 && (d(SLOT_PARITY)[5] == 96 || d(SLOT_PARITY)[5] == 80 || d(SLOT_PARITY)[5] == 84);
+            const int SLOT_PARITY = MVLM_SLOT_PARITY0;
+            const bool parity = parity_slots_usable(d(SLOT_PARITY));
             const int parts1 = parity ? mvlm_conv_amax_parts(128, 128) : mvlm_conv_amax_parts(256, 256);
             const int parts = parity ? 4 * parts1 : parts1;
             Tensor av, ai, abest;
@@ -672,7 +674,7 @@ struct Exec {
                     a.up_out = 2;
                     if (one_launch) {
                         a.n_par = 4;
-                        for (int q = 0; q < 4; ++q) a.w_par[q] = blob(d(SLOT_PARITY + q)[6]);
+                        for (int q = 0; q < 4; ++q) a.w_par[q] = blob(d(SLOT_PARITY + q).w_off);
                         a.amax_par_stride = parts1;
                     }
                 } else {
@@ -688,7 +690,7 @@ struct Exec {
                     a.amax_parts = parts;
                     a.amax_part0 = pl * parts1;
                 }
-                conv(parity ? SLOT_PARITY + pl : SLOT_CONV5 + 5, xin, a, parity ? 128 : 256);
+                conv(parity ? SLOT_PARITY + pl : MVLM_SLOT_CONV11, xin, a, parity ? 128 : 256);
             }
             if (!heat) {
                 if (!dry && !rc &&
@@ -698,10 +700,10 @@ struct Exec {
                 if (moment && !dry && !rc) {
                     // paulsenpredictor.py:129-156 on the planes whose peak lies more than 15 pixels inside: the 31x31 window is
                     // recomputed from x10 with the parity kernels' own arithmetic - no [N,NL,256,256] tensor
-                    const int32_t* r0 = d(SLOT_PARITY);
+                    const ConvSlotDesc& r0 = d(SLOT_PARITY);
                     const float* wq[4];
-                    for (int q = 0; q < 4; ++q) wq[q] = blob(d(SLOT_PARITY + q)[6]);
-                    if (mvlm_launch_moment_refine(ctx, x10.p, B, NL, r0[4], r0[5], wq, blob(r0[7]), reinterpret_cast<int*>(abest.p), view0,
+                    for (int q = 0; q < 4; ++q) wq[q] = blob(d(SLOT_PARITY + q).w_off);
+                    if (mvlm_launch_moment_refine(ctx, x10.p, B, NL, r0.cin_pad, r0.cout_pad, wq, blob(r0.bias_off), reinterpret_cast<int*>(abest.p), view0,
                                                   n_total, maxima))
                         rc = 1;
                 }
@@ -858,7 +860,7 @@ extern "C" int mvlm_cnn_load(mvlm_ctx* ctx, const float* blob_host, size_t n_flo
                              int n_slots, int n_landmarks, int in_channels) {
     MVLM_ENTER(ctx);
     MVLM_REQUIRE(ctx, blob_host && desc_host && n_floats > 0, "cnn_load: null weights");
-    MVLM_REQUIRE(ctx, n_slots == 1 + 4 * 43 + 6 + 4, "cnn_load: descriptor table must have 183 conv slots");
+    MVLM_REQUIRE(ctx, n_slots == MVLM_N_SLOTS, "cnn_load: descriptor table must have 183 conv slots");
     MVLM_REQUIRE(ctx, n_landmarks > 0 && in_channels >= 1 && in_channels <= 4, "cnn_load: bad landmark / channel count");
     CnnState& st = ctx->cnn;
     MVLM_CHECK_HIP(ctx, hipSetDevice(ctx->device));
@@ -879,85 +881,78 @@ extern "C" int mvlm_cnn_load(mvlm_ctx* ctx, const float* blob_host, size_t n_flo
         (void)hipFree(st.fast16_blob);
         st.fast16_blob = nullptr;
     }
-    for (CnnState::WinoWeights& ww : st.wino) {
-        ww.off.clear();
-        if (ww.blob) {
-            (void)hipFree(ww.blob);
-            ww.blob = nullptr;
+    float** const form_blobs[MVLM_WINO_FORMS_N + 1] = {&st.wino[MVLM_WINO_F23].blob, &st.wino[MVLM_WINO_F43].blob, &st.wino4_pad_blob};
+    for (float** b : form_blobs)
+        if (*b) {
+            (void)hipFree(*b);
+            *b = nullptr;
         }
-    }
+    for (CnnState::WinoWeights& ww : st.wino) ww.off.clear();
     st.wino4_pad_id.clear();
     ctx->conv_wino4_pads.resize(1);  // ([0]: the single-layer entry points')
-    if (st.wino4_pad_blob) {
-        (void)hipFree(st.wino4_pad_blob);
-        st.wino4_pad_blob = nullptr;
-    }
     st.drop_graphs();  // captured launches point into the old weight blob
-    st.desc.assign(desc_host, desc_host + size_t(n_slots) * MVLM_CONV_DESC_INTS);
+    st.desc.resize(size_t(n_slots));
+    memcpy(st.desc.data(), desc_host, size_t(n_slots) * sizeof(ConvSlotDesc));
     // validate every offset before anything is launched with it
-    for (int s = 0; s < n_slots; ++s) {
-        const int32_t* r = &st.desc[size_t(s) * MVLM_CONV_DESC_INTS];
-        if (!r[0]) continue;
-        MVLM_REQUIRE(ctx, r[1] > 0 && r[2] > 0 && r[3] >= 1 && r[3] <= 3, "cnn_load: bad conv shape");
+    for (const ConvSlotDesc& r : st.desc) {
+        if (!r.present) continue;
+        MVLM_REQUIRE(ctx, r.cin > 0 && r.cout > 0 && r.ksize >= 1 && r.ksize <= 3, "cnn_load: bad conv shape");
         // output channels: multiples of 16 (32-row tiles, 64 + 16-row strip), or exactly 84 = 64 + 16 + 4 rows
-        MVLM_REQUIRE(ctx, r[4] % 4 == 0 && r[4] >= r[1] && (r[5] % 16 == 0 || (r[5] == 84 && r[2] == 84 && (r[3] == 3 || r[3] == 2))) && r[5] >= r[2],
+        MVLM_REQUIRE(ctx, r.cin_pad % 4 == 0 && r.cin_pad >= r.cin &&
+                              (r.cout_pad % 16 == 0 || (r.cout_pad == 84 && r.cout == 84 && (r.ksize == 3 || r.ksize == 2))) && r.cout_pad >= r.cout,
                      "cnn_load: bad padding");
-        const size_t wsz = size_t(r[3]) * r[3] * r[4] * r[5];
-        MVLM_REQUIRE(ctx, r[6] >= 0 && size_t(r[6]) + wsz <= n_floats, "cnn_load: weight offset out of range");
-        const int offs[5] = {r[7], r[8], r[9], r[10], r[11]};
-        const int lens[5] = {r[5], r[4], r[4], r[5], r[5]};
+        const size_t wsz = size_t(r.ksize) * r.ksize * r.cin_pad * r.cout_pad;
+        MVLM_REQUIRE(ctx, r.w_off >= 0 && size_t(r.w_off) + wsz <= n_floats, "cnn_load: weight offset out of range");
+        const int offs[5] = {r.bias_off, r.pre_scale_off, r.pre_shift_off, r.post_scale_off, r.post_shift_off};
+        const int lens[5] = {r.cout_pad, r.cin_pad, r.cin_pad, r.cout_pad, r.cout_pad};
         for (int k = 0; k < 5; ++k)
             MVLM_REQUIRE(ctx, offs[k] < 0 || size_t(offs[k]) + lens[k] <= n_floats, "cnn_load: vector offset out of range");
     }
-    MVLM_REQUIRE(ctx, st.desc[1] == in_channels, "cnn_load: conv1 input channels != in_channels");
-    MVLM_REQUIRE(ctx, st.desc[size_t(1 + 4 * 43 + 5) * MVLM_CONV_DESC_INTS + 2] == n_landmarks,
-                 "cnn_load: conv11 output channels != n_landmarks");
+    MVLM_REQUIRE(ctx, st.desc[0].cin == in_channels, "cnn_load: conv1 input channels != in_channels");
+    MVLM_REQUIRE(ctx, st.desc[MVLM_SLOT_CONV11].cout == n_landmarks, "cnn_load: conv11 output channels != n_landmarks");
     MVLM_CHECK_HIP(ctx, hipMalloc(&st.blob, n_floats * sizeof(float)));
     MVLM_CHECK_HIP(ctx, hipMemcpy(st.blob, blob_host, n_floats * sizeof(float), hipMemcpyHostToDevice));
-    // The weights are fixed for the life of the model: each Winograd form of every 3x3 slot a tile of that form can serve is
-    // made here, once, in a buffer of its own (4/3 of those slots' weight bytes for F(2,3), twice for F(4,3)).
-    for (int f = 0; f < MVLM_WINO_FORMS_N; ++f) {
-        const WinoForm& form = mvlm_wino_form(f);
-        CnnState::WinoWeights& ww = st.wino[f];
-        std::vector<float> host;
-        ww.off.assign(size_t(n_slots), -1);
-        for (int s = 0; s < n_slots; ++s) {
-            const int32_t* r = &st.desc[size_t(s) * MVLM_CONV_DESC_INTS];
-            if (!r[0] || !form.serves_slot(r[3], r[4], r[5])) continue;
-            const size_t off = host.size();
-            host.resize(off + size_t(form.slices) * r[4] * r[5]);
-            form.transform(blob_host + r[6], r[4], r[5], host.data() + off);
-            ww.off[size_t(s)] = (long long)off;
-        }
-        if (!host.empty()) {
-            MVLM_CHECK_HIP(ctx, hipMalloc(&ww.blob, host.size() * sizeof(float)));
-            MVLM_CHECK_HIP(ctx, hipMemcpy(ww.blob, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+    // The weights are fixed for the life of the model: every other form of a slot's weights is made here, once, by the one packer
+    // (conv_pack.cpp), in a buffer per form beside the packed ones.  Each Winograd form of every 3x3 slot a tile of that form can
+    // serve (4/3 of those slots' weight bytes for F(2,3), twice for F(4,3)); and the F(4,3) form at a cout stride of whole 32s, with
+    // the bias padded alike, of every 3x3 slot that tile would serve but for its cout_pad (conv6 / conv10 on 84 or 80 rows): what the
+    // dispatcher swaps in for the 80- and 84-row tiles' launches (conv_mfma.hip: f43_plan).
+    std::vector<float> host[MVLM_WINO_FORMS_N + 1];  // (as form_blobs above)
+    std::vector<ConvPackTargets> to(st.desc.size());
+    size_t total[MVLM_WINO_FORMS_N + 1] = {0, 0, 0};
+    for (int s = 0; s < n_slots; ++s) {
+        const ConvSlotDesc& r = st.desc[size_t(s)];
+        if (!r.present) continue;
+        const ConvPackSizes sizes = mvlm_conv_pack_sizes(r.ksize, r.cin_pad, r.cout_pad);
+        for (int f = 0; f < MVLM_WINO_FORMS_N; ++f)
+            if (mvlm_wino_form(f).serves_slot(r.ksize, r.cin_pad, r.cout_pad)) {
+                to[size_t(s)].wino[f] = &host[f];
+                total[f] += sizes.wino[f];
+            }
+        if (mvlm_conv_wino4_pad_serves_slot(r.ksize, r.cin_pad, r.cout_pad)) {
+            to[size_t(s)].wino4_pad = &host[MVLM_WINO_FORMS_N];
+            total[MVLM_WINO_FORMS_N] += sizes.wino4_pad + sizes.wino4_pad_bias;
         }
     }
-    // ... and the F(4,3) form at a cout stride of whole 32s, with the bias padded alike, of every 3x3 slot that tile would serve but
-    // for its cout_pad (conv6 / conv10 on 84 or 80 rows): what the dispatcher swaps in for the 80- and 84-row tiles' launches (conv_mfma.hip)
-    {
-        std::vector<float> host;
-        std::vector<std::array<long long, 3>> made;  // slot, weights' offset, bias's offset or -1
-        for (int s = 0; s < n_slots; ++s) {
-            const int32_t* r = &st.desc[size_t(s) * MVLM_CONV_DESC_INTS];
-            if (!r[0] || !mvlm_conv_wino4_pad_serves_slot(r[3], r[4], r[5])) continue;
-            const int P = mvlm_conv_wino4_padded_cout(r[5]);
-            const size_t w_off = host.size(), b_off = w_off + size_t(18) * r[4] * P;
-            host.resize(b_off + (r[7] >= 0 ? P : 0));
-            mvlm_winograd4_pack_padded(blob_host + r[6], r[7] >= 0 ? blob_host + r[7] : nullptr, r[4], r[5], host.data() + w_off,
-                                       r[7] >= 0 ? host.data() + b_off : nullptr);
-            made.push_back({s, (long long)w_off, r[7] >= 0 ? (long long)b_off : -1});
+    for (int k = 0; k <= MVLM_WINO_FORMS_N; ++k) host[k].reserve(total[k]);  // (no copy while a blob grows to its size)
+    for (CnnState::WinoWeights& ww : st.wino) ww.off.assign(size_t(n_slots), -1);
+    st.wino4_pad_id.assign(size_t(n_slots), 0);
+    std::vector<ConvPackOffsets> made(st.desc.size());
+    for (int s = 0; s < n_slots; ++s) {
+        const ConvSlotDesc& r = st.desc[size_t(s)];
+        if (r.present) made[size_t(s)] = mvlm_conv_pack_forms(to[size_t(s)], blob_host + r.w_off, r.bias_off >= 0 ? blob_host + r.bias_off : nullptr, r.cin_pad, r.cout_pad);
+    }
+    for (int k = 0; k <= MVLM_WINO_FORMS_N; ++k)
+        if (!host[k].empty()) {
+            MVLM_CHECK_HIP(ctx, hipMalloc(form_blobs[k], host[k].size() * sizeof(float)));
+            MVLM_CHECK_HIP(ctx, hipMemcpy(*form_blobs[k], host[k].data(), host[k].size() * sizeof(float), hipMemcpyHostToDevice));
         }
-        if (!host.empty()) {
-            MVLM_CHECK_HIP(ctx, hipMalloc(&st.wino4_pad_blob, host.size() * sizeof(float)));
-            MVLM_CHECK_HIP(ctx, hipMemcpy(st.wino4_pad_blob, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
-            st.wino4_pad_id.assign(size_t(n_slots), 0);
-            for (const auto& m : made) {
-                ctx->conv_wino4_pads.push_back({st.wino4_pad_blob + m[1], m[2] < 0 ? nullptr : st.wino4_pad_blob + m[2]});
-                st.wino4_pad_id[size_t(m[0])] = int(ctx->conv_wino4_pads.size());
-            }
-        }
+    for (int s = 0; s < n_slots; ++s) {
+        const ConvPackOffsets& m = made[size_t(s)];
+        for (int f = 0; f < MVLM_WINO_FORMS_N; ++f) st.wino[f].off[size_t(s)] = m.wino[f];
+        if (m.wino4_pad < 0) continue;
+        ctx->conv_wino4_pads.push_back({st.wino4_pad_blob + m.wino4_pad, m.wino4_pad_bias < 0 ? nullptr : st.wino4_pad_blob + m.wino4_pad_bias});
+        st.wino4_pad_id[size_t(s)] = int(ctx->conv_wino4_pads.size());
     }
     st.n_landmarks = n_landmarks;
     st.in_channels = in_channels;
@@ -1005,9 +1000,8 @@ extern "C" int mvlm_cnn_set_selection(mvlm_ctx* ctx, int method) {
     CnnState& st = ctx->cnn;
     MVLM_REQUIRE(ctx, st.loaded, "cnn_set_selection: mvlm_cnn_load comes first");
     if (method == MVLM_MAXIMA_MOMENT) {
-        const int slot = 1 + 4 * 43 + 6;
-        const int32_t* r = &st.desc[size_t(slot) * MVLM_CONV_DESC_INTS];
-        MVLM_REQUIRE(ctx, r[0] != 0 && (r[5] == 96 || r[5] == 80 || r[5] == 84) && r[3] == 2,
+        const ConvSlotDesc& r = st.desc[MVLM_SLOT_PARITY0];
+        MVLM_REQUIRE(ctx, parity_slots_usable(r) && r.ksize == 2,
                      "cnn_set_selection: the fused moment selection needs conv11's parity slots in the packed weights");
     }
     if (method != st.selection) st.drop_graphs();  // captured graphs encode the launches
@@ -1085,62 +1079,51 @@ extern "C" int mvlm_cnn_execution_stats(mvlm_ctx* ctx, int64_t* eager_runs, int6
 }
 
 // ---- opt-in "fast" precision ------------------------------------------------------------------------------------------------
-extern "C" int mvlm_cnn_load_fast(mvlm_ctx* ctx, const uint16_t* blob_host, size_t n_u16, const int64_t* slot_offsets, int n_slots) {
-    MVLM_ENTER(ctx);
+// One loader behind the two split forms' entry points: `splits` operand parts per weight (3 bf16, 2 f16), per conv slot the u16
+// offset in the blob (-1: the layer stays exact), and for the f16x2 form the inverse of the scale each slot's weights carry
+// (slot_unscale null: the bf16x3 form, which has none).  `who` begins every message.
+static int load_fast_weights(mvlm_ctx* ctx, const std::string& who, int splits, const uint16_t* blob_host, size_t n_u16, const int64_t* slot_offsets,
+                             const float* slot_unscale, int n_slots) {
     CnnState& st = ctx->cnn;
-    MVLM_REQUIRE(ctx, st.loaded, "cnn_load_fast: mvlm_cnn_load comes first");
-    MVLM_REQUIRE(ctx, blob_host && slot_offsets && n_u16 > 0 && size_t(n_slots) * MVLM_CONV_DESC_INTS == st.desc.size(),
-                 "cnn_load_fast: bad arguments");
+    const bool f16 = splits == 2;
+    MVLM_REQUIRE(ctx, st.loaded, who + ": mvlm_cnn_load comes first");
+    MVLM_REQUIRE(ctx, blob_host && slot_offsets && (slot_unscale || !f16) && n_u16 > 0 && size_t(n_slots) == st.desc.size(), who + ": bad arguments");
     for (int s = 0; s < n_slots; ++s) {
         if (slot_offsets[s] < 0) continue;
-        const int32_t* r = &st.desc[size_t(s) * MVLM_CONV_DESC_INTS];
-        MVLM_REQUIRE(ctx, r[0] && r[3] == 3 && mvlm_fast_channels_ok(r[1], r[2]), "cnn_load_fast: slot is not a fast-eligible 3x3 layer");
-        const size_t need = size_t(mvlm_fast_cin_pad(r[1]) / 16) * 9 * 2 * 3 * size_t(mvlm_fast_cout_pad(r[2])) * 8;
-        MVLM_REQUIRE(ctx, slot_offsets[s] % 8 == 0 && size_t(slot_offsets[s]) + need <= n_u16, "cnn_load_fast: offset out of range");
+        const ConvSlotDesc& r = st.desc[size_t(s)];
+        MVLM_REQUIRE(ctx, r.present && r.ksize == 3 && mvlm_fast_channels_ok(r.cin, r.cout), who + ": slot is not a fast-eligible 3x3 layer");
+        const size_t need = size_t(mvlm_fast_cin_pad(r.cin) / 16) * 9 * 2 * splits * size_t(mvlm_fast_cout_pad(r.cout)) * 8;
+        MVLM_REQUIRE(ctx, slot_offsets[s] % 8 == 0 && size_t(slot_offsets[s]) + need <= n_u16, who + ": offset out of range");
+        MVLM_REQUIRE(ctx, !f16 || (slot_unscale[s] > 0.f && slot_unscale[s] < 3.0e38f), who + ": bad inverse scale");
     }
     st.drop_graphs();
-    if (st.fast == 1) st.fast = 0;
-    if (st.fast_blob) {
-        MVLM_CHECK_HIP(ctx, hipFree(st.fast_blob));
-        st.fast_blob = nullptr;
+    if (st.fast == (f16 ? 2 : 1)) st.fast = 0;
+    unsigned short*& blob = f16 ? st.fast16_blob : st.fast_blob;
+    if (blob) {
+        MVLM_CHECK_HIP(ctx, hipFree(blob));
+        blob = nullptr;
     }
-    MVLM_CHECK_HIP(ctx, hipMalloc(&st.fast_blob, n_u16 * sizeof(uint16_t)));
-    MVLM_CHECK_HIP(ctx, hipMemcpy(st.fast_blob, blob_host, n_u16 * sizeof(uint16_t), hipMemcpyHostToDevice));
-    st.fast_off.assign(slot_offsets, slot_offsets + n_slots);
+    if (f16 && !st.fast16_flag) {
+        MVLM_CHECK_HIP(ctx, hipMalloc(&st.fast16_flag, sizeof(unsigned)));
+        MVLM_CHECK_HIP(ctx, hipMemset(st.fast16_flag, 0, sizeof(unsigned)));
+    }
+    MVLM_CHECK_HIP(ctx, hipMalloc(&blob, n_u16 * sizeof(uint16_t)));
+    MVLM_CHECK_HIP(ctx, hipMemcpy(blob, blob_host, n_u16 * sizeof(uint16_t), hipMemcpyHostToDevice));
+    (f16 ? st.fast16_off : st.fast_off).assign(slot_offsets, slot_offsets + n_slots);
+    if (f16) st.fast16_unscale.assign(slot_unscale, slot_unscale + n_slots);
     return 0;
+}
+
+extern "C" int mvlm_cnn_load_fast(mvlm_ctx* ctx, const uint16_t* blob_host, size_t n_u16, const int64_t* slot_offsets, int n_slots) {
+    MVLM_ENTER(ctx);
+    return load_fast_weights(ctx, "cnn_load_fast", 3, blob_host, n_u16, slot_offsets, nullptr, n_slots);
 }
 
 // the f16x2 form's weights (mvlm_pack_fast_weights16): one blob, per conv slot the u16 offset (-1: stays exact) and the inverse scale
 extern "C" int mvlm_cnn_load_fast16(mvlm_ctx* ctx, const uint16_t* blob_host, size_t n_u16, const int64_t* slot_offsets,
                                     const float* slot_unscale, int n_slots) {
     MVLM_ENTER(ctx);
-    CnnState& st = ctx->cnn;
-    MVLM_REQUIRE(ctx, st.loaded, "cnn_load_fast16: mvlm_cnn_load comes first");
-    MVLM_REQUIRE(ctx, blob_host && slot_offsets && slot_unscale && n_u16 > 0 && size_t(n_slots) * MVLM_CONV_DESC_INTS == st.desc.size(),
-                 "cnn_load_fast16: bad arguments");
-    for (int s = 0; s < n_slots; ++s) {
-        if (slot_offsets[s] < 0) continue;
-        const int32_t* r = &st.desc[size_t(s) * MVLM_CONV_DESC_INTS];
-        MVLM_REQUIRE(ctx, r[0] && r[3] == 3 && mvlm_fast_channels_ok(r[1], r[2]), "cnn_load_fast16: slot is not a fast-eligible 3x3 layer");
-        const size_t need = size_t(mvlm_fast_cin_pad(r[1]) / 16) * 9 * 2 * 2 * size_t(mvlm_fast_cout_pad(r[2])) * 8;
-        MVLM_REQUIRE(ctx, slot_offsets[s] % 8 == 0 && size_t(slot_offsets[s]) + need <= n_u16, "cnn_load_fast16: offset out of range");
-        MVLM_REQUIRE(ctx, slot_unscale[s] > 0.f && slot_unscale[s] < 3.0e38f, "cnn_load_fast16: bad inverse scale");
-    }
-    st.drop_graphs();
-    if (st.fast == 2) st.fast = 0;
-    if (st.fast16_blob) {
-        MVLM_CHECK_HIP(ctx, hipFree(st.fast16_blob));
-        st.fast16_blob = nullptr;
-    }
-    if (!st.fast16_flag) {
-        MVLM_CHECK_HIP(ctx, hipMalloc(&st.fast16_flag, sizeof(unsigned)));
-        MVLM_CHECK_HIP(ctx, hipMemset(st.fast16_flag, 0, sizeof(unsigned)));
-    }
-    MVLM_CHECK_HIP(ctx, hipMalloc(&st.fast16_blob, n_u16 * sizeof(uint16_t)));
-    MVLM_CHECK_HIP(ctx, hipMemcpy(st.fast16_blob, blob_host, n_u16 * sizeof(uint16_t), hipMemcpyHostToDevice));
-    st.fast16_off.assign(slot_offsets, slot_offsets + n_slots);
-    st.fast16_unscale.assign(slot_unscale, slot_unscale + n_slots);
-    return 0;
+    return load_fast_weights(ctx, "cnn_load_fast16", 2, blob_host, n_u16, slot_offsets, slot_unscale, n_slots);
 }
 
 // did an f16x2 launch of the last mvlm_cnn_maxima / mvlm_cnn_heatmaps call meet an activation outside fp16's range?  Waits for

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/mvlm_hip.h"
+#include "conv_pack.h"
 #include "jpeg_plan.h"
 
 #define MVLM_CHECK_HIP(ctx, expr)                                                            \
@@ -181,12 +182,10 @@ struct CnnGraphEntry {
     hipGraphExec_t exec = nullptr;
 };
 
-// The two Winograd forms of a 3x3 layer's weights, described once (conv_mfma.hip: mvlm_wino_form): what loading, packing, the
-// executor and the dispatcher need to know about a form.  A variant's row names its form (ConvVariantInfo::form).
-enum { MVLM_WINO_F23 = 0, MVLM_WINO_F43 = 1, MVLM_WINO_FORMS_N = 2 };
+// The two Winograd forms of a 3x3 layer's weights (conv_pack.h: MVLM_WINO_F23, MVLM_WINO_F43), described once (conv_mfma.hip:
+// mvlm_wino_form): what loading, the executor and the dispatcher need to know about a form; conv_pack.cpp makes the weights.  A
+// variant's row names its form (ConvVariantInfo::form).
 struct WinoForm {
-    int slices;                                                                  // the weights are [slices][cin_pad][cout_pad]: 4 or 6 per kx
-    void (*transform)(const float* w9, int cin_pad, int cout_pad, float* out);   // host: packed [9][cin_pad][cout_pad] -> that
     bool (*serves_slot)(int ksize, int cin_pad, int cout_pad);                   // a tile of this form exists for these channels
     const float* ConvArgs::*weights;                                             // the launch's member that carries them
     double macs;                                                                 // multiply-adds per output and input channel (direct: 9)
@@ -194,11 +193,31 @@ struct WinoForm {
 };
 const WinoForm& mvlm_wino_form(int form);
 
+// One row of the network's descriptor table by name (mvlm_amd/weights.py: pack_for_device): the *_off fields are float offsets
+// into the packed weights, -1 absent.
+struct ConvSlotDesc {
+    int32_t present, cin, cout, ksize, cin_pad, cout_pad, w_off, bias_off, pre_scale_off, pre_shift_off, post_scale_off, post_shift_off;
+};
+static_assert(sizeof(ConvSlotDesc) == MVLM_CONV_DESC_INTS * sizeof(int32_t), "a row is the 12 ints of include/mvlm_hip.h");
+// The table's slots (mvlm_amd/arch.py: conv_slots): conv1, four per residual block (the 1x1 resample, conv1..conv3) of the 43
+// blocks, conv5..conv11 (conv8 is dead at inference and has no slot), conv11's four output parities as 2x2 layers.
+enum {
+    MVLM_SLOT_CONV5 = 1 + 4 * 43,
+    MVLM_SLOT_CONV6,
+    MVLM_SLOT_CONV7,
+    MVLM_SLOT_CONV9,
+    MVLM_SLOT_CONV10,
+    MVLM_SLOT_CONV11,
+    MVLM_SLOT_PARITY0,
+    MVLM_N_SLOTS = MVLM_SLOT_PARITY0 + 4,
+};
+static_assert(MVLM_N_SLOTS == 183, "the descriptor table has 183 conv slots");
+
 struct CnnState {
     bool loaded = false;
     int n_landmarks = 0, in_channels = 0;
     float* blob = nullptr;  // device copy of the packed weights
-    std::vector<int32_t> desc;  // host copy of the descriptor table
+    std::vector<ConvSlotDesc> desc;  // host copy of the descriptor table
     bool profiling = false;
     std::vector<ConvProfileRec> prof;
     std::vector<hipEvent_t> event_pool;
@@ -450,11 +469,7 @@ bool mvlm_conv_variant_is_wino4(int variant);  // the F(4,3) Winograd tile (read
 // the Winograd variant this launch is routed to (overrides, mode and table of the context), or -1: the direct tiles
 int mvlm_conv_wino_variant(const mvlm_ctx* ctx, const ConvArgs& a);
 bool mvlm_conv_wino_serves_slot(int ksize, int cin_pad, int cout_pad);  // a Winograd variant exists for these channels
-// host: packed [9][cin_pad][cout_pad] -> [12][cin_pad][cout_pad] (u_t per kx: t * 3 + kx), float64 arithmetic, one rounding
-void mvlm_winograd_transform(const float* w9, int cin_pad, int cout_pad, float* w12);
 bool mvlm_conv_wino4_serves_slot(int ksize, int cin_pad, int cout_pad);  // the F(4,3) tile can serve these channels
-// host: packed [9][cin_pad][cout_pad] -> [18][cin_pad][cout_pad] (u_t per kx: t * 3 + kx), float64 arithmetic, one rounding
-void mvlm_winograd4_transform(const float* w9, int cin_pad, int cout_pad, float* w18);
 // two independent convolutions in one grid (conv_tile.h: conv_pair_kernel)
 constexpr int MVLM_CONV_PAIR_FLAG = 0x1000;  // variant code of a paired launch: flag | base id | lg(kparts0) << 8 | lg(kparts1) << 10
 int mvlm_conv_pair_variant(const ConvArgs& a0, const ConvArgs& a1, int mode);
@@ -480,15 +495,10 @@ constexpr int MVLM_CONV_WINO4_ATTR_BIT = 41, MVLM_CONV_WINO4_WIDE_ATTR_BIT = 42,
 // its own: the dispatcher takes it for code 2048 where the context's switch is on and the layer's output channels come in 64s.  Everything
 // else about the layer is what the 32 x 16 shape asks, so this is asked of launches already routed to code 2048.
 inline bool mvlm_conv_wino4_wide_shape_ok(int cout_pad, int H) { return cout_pad > 0 && cout_pad % 64 == 0 && H % 16 == 0; }
-// The cout stride of the padded F(4,3) weights (ConvWino4Pad): whole 32-channel columns of the tile.  84 -> 96, 80 -> 96.
-inline int mvlm_conv_wino4_padded_cout(int cout_pad) { return (cout_pad + 31) / 32 * 32; }
 // Does a 3x3 slot of these channels get padded F(4,3) weights: the tile would serve it but for cout_pad % 32 != 0?
 inline bool mvlm_conv_wino4_pad_serves_slot(int ksize, int cin_pad, int cout_pad) {
     return cout_pad > 0 && cout_pad % 32 != 0 && mvlm_conv_wino4_serves_slot(ksize, cin_pad, mvlm_conv_wino4_padded_cout(cout_pad));
 }
-// host: packed [9][cin_pad][cout_pad] -> [18][cin_pad][P], columns below cout_pad as mvlm_winograd4_transform, zeros beyond;
-// bias [cout_pad] or null -> [P] likewise (bias_pad may be null then)
-void mvlm_winograd4_pack_padded(const float* w9, const float* bias, int cin_pad, int cout_pad, float* w18_pad, float* bias_pad);
 constexpr int MVLM_CONV_VARIANT_FAST = 62;    // id reported for launches of the bf16x3 kernel
 constexpr int MVLM_CONV_VARIANT_FAST16 = 61;  // ... of the f16x2 kernel
 

@@ -36,7 +36,8 @@
 //   the measured table conv_tuned_wino.h says it is faster (mvlm_cnn_set_winograd / MVLM_WINOGRAD: 0 never, 1 table, 2 always).
 //   A profile record of such a launch counts the FLOPs its MFMAs execute (12 Cin Cout H W B, not 18).
 //   The F(4,3) form along y (Cfg::WINO4, conv3x3q_c32_t16x32) likewise: six GEMMs per four output rows, 9 Cin Cout H W B.  What the
-//   two forms differ in on the host (slices, transform, which ConvArgs member carries the weights) is mvlm_wino_form() below.
+//   two forms differ in for the dispatcher (which channels a tile serves, which ConvArgs member carries the weights) is
+//   mvlm_wino_form() below; the weights themselves are made by conv_pack.cpp.
 //
 // How a launch finds its kernel.  Every variant of conv_variants.h, the F(4,3) tile included, has one row in VARIANTS below
 // (tile geometry, features, Winograd form, launchers); tile_fits() is the one statement of "this tile divides this layer", and
@@ -87,8 +88,8 @@ int mvlm_conv_launch_wino4_wide(mvlm_ctx* ctx, const ConvArgs& a);
 // ---- the two Winograd forms (common.h: WinoForm) ----------------------------------------------------------------------------
 const WinoForm& mvlm_wino_form(int form) {
     static const WinoForm forms[MVLM_WINO_FORMS_N] = {
-        {12, mvlm_winograd_transform, mvlm_conv_wino_serves_slot, &ConvArgs::w_wino, 6.0, "mvlm_pack_winograd_weights"},
-        {18, mvlm_winograd4_transform, mvlm_conv_wino4_serves_slot, &ConvArgs::w_wino4, 4.5, "mvlm_pack_winograd4_weights"},
+        {mvlm_conv_wino_serves_slot, &ConvArgs::w_wino, 6.0, "mvlm_pack_winograd_weights"},
+        {mvlm_conv_wino4_serves_slot, &ConvArgs::w_wino4, 4.5, "mvlm_pack_winograd4_weights"},
     };
     return forms[form];
 }
@@ -572,74 +573,5 @@ extern "C" int mvlm_conv_set_override(mvlm_ctx* ctx, int ksize, int cin_pad, int
         }
     }
     ctx->cnn.drop_graphs();
-    return 0;
-}
-
-// ---- Winograd weights -----------------------------------------------------------------------------------------------------
-// Filter column g0, g1, g2 (ky = 0, 1, 2) of every (kx, cin, cout) -> u0 = g0, u1 = (g0 + g1 + g2) / 2, u2 = (g0 - g1 + g2) / 2,
-// u3 = g2, in float64 from the fp32 weights, rounded once.  Slice t * 3 + kx of the result is u_t at kx; padded channels stay zero.
-void mvlm_winograd_transform(const float* w9, int cin_pad, int cout_pad, float* w12) {
-    const size_t n = size_t(cin_pad) * cout_pad;
-    for (int kx = 0; kx < 3; ++kx)
-        for (size_t i = 0; i < n; ++i) {
-            const double g0 = w9[size_t(kx) * n + i], g1 = w9[size_t(3 + kx) * n + i], g2 = w9[size_t(6 + kx) * n + i];
-            w12[size_t(kx) * n + i] = float(g0);
-            w12[size_t(3 + kx) * n + i] = float((g0 + g1 + g2) * 0.5);
-            w12[size_t(6 + kx) * n + i] = float((g0 - g1 + g2) * 0.5);
-            w12[size_t(9 + kx) * n + i] = float(g2);
-        }
-}
-
-extern "C" int mvlm_pack_winograd_weights(const float* w9_host, int cin_pad, int cout_pad, float* w12_host) {
-    if (!w9_host || !w12_host || cin_pad <= 0 || cout_pad <= 0) return 1;
-    mvlm_winograd_transform(w9_host, cin_pad, cout_pad, w12_host);
-    return 0;
-}
-
-// The F(4,3) form on the points 0, 1, -1, 2, -1/2, inf: u0 = g0, u1 = -(g0 + g1 + g2) / 3, u2 = (g0 - g1 + g2) / 3,
-// u3 = (g0 + 2 g1 + 4 g2) / 15, u4 = (-16 g0 + 8 g1 - 4 g2) / 15, u5 = g2, likewise in float64 and rounded once; slice t * 3 + kx.
-void mvlm_winograd4_transform(const float* w9, int cin_pad, int cout_pad, float* w18) {
-    const size_t n = size_t(cin_pad) * cout_pad;
-    for (int kx = 0; kx < 3; ++kx)
-        for (size_t i = 0; i < n; ++i) {
-            const double g0 = w9[size_t(kx) * n + i], g1 = w9[size_t(3 + kx) * n + i], g2 = w9[size_t(6 + kx) * n + i];
-            w18[size_t(kx) * n + i] = float(g0);
-            w18[size_t(3 + kx) * n + i] = float(0.0 - (g0 + g1 + g2) / 3.0);  // (0 - x: a padded channel stays +0)
-            w18[size_t(6 + kx) * n + i] = float((g0 - g1 + g2) / 3.0);
-            w18[size_t(9 + kx) * n + i] = float((g0 + 2.0 * g1 + 4.0 * g2) / 15.0);
-            w18[size_t(12 + kx) * n + i] = float((-16.0 * g0 + 8.0 * g1 - 4.0 * g2) / 15.0);
-            w18[size_t(15 + kx) * n + i] = float(g2);
-        }
-}
-
-extern "C" int mvlm_pack_winograd4_weights(const float* w9_host, int cin_pad, int cout_pad, float* w18_host) {
-    if (!w9_host || !w18_host || cin_pad <= 0 || cout_pad <= 0) return 1;
-    mvlm_winograd4_transform(w9_host, cin_pad, cout_pad, w18_host);
-    return 0;
-}
-
-// The same values at the cout stride P = mvlm_conv_wino4_padded_cout(cout_pad): the transform at its own stride, then every row of
-// cout_pad columns moved to the front of a row of P, zeros behind; the bias likewise.
-void mvlm_winograd4_pack_padded(const float* w9, const float* bias, int cin_pad, int cout_pad, float* w18_pad, float* bias_pad) {
-    const int P = mvlm_conv_wino4_padded_cout(cout_pad);
-    const size_t rows = size_t(18) * cin_pad;
-    std::vector<float> w18(rows * cout_pad);
-    mvlm_winograd4_transform(w9, cin_pad, cout_pad, w18.data());
-    for (size_t r = 0; r < rows; ++r) {
-        std::copy(w18.begin() + r * cout_pad, w18.begin() + (r + 1) * cout_pad, w18_pad + r * P);
-        std::fill(w18_pad + r * P + cout_pad, w18_pad + (r + 1) * P, 0.f);
-    }
-    if (bias && bias_pad) {
-        std::copy(bias, bias + cout_pad, bias_pad);
-        std::fill(bias_pad + cout_pad, bias_pad + P, 0.f);
-    }
-}
-
-extern "C" int mvlm_conv_wino4_padded_stride(int cout_pad) { return cout_pad > 0 ? mvlm_conv_wino4_padded_cout(cout_pad) : 0; }
-
-extern "C" int mvlm_pack_winograd4_weights_padded(const float* w9_host, const float* bias_host, int cin_pad, int cout_pad, float* w18_pad_host,
-                                                  float* bias_pad_host) {
-    if (!w9_host || !w18_pad_host || cin_pad <= 0 || cout_pad <= 0 || (bias_host && !bias_pad_host)) return 1;
-    mvlm_winograd4_pack_padded(w9_host, bias_host, cin_pad, cout_pad, w18_pad_host, bias_pad_host);
     return 0;
 }

@@ -3,7 +3,8 @@
 
     tools/device_code_diff.py OBJDIR_A OBJDIR_B      (e.g. <parent worktree>/mvlm_amd/csrc/build mvlm_amd/csrc/build)
 
-One line per object file of the two directories (sub-directories included): identical, or how many of its kernels differ;
+One line per object file of the two directories (sub-directories included): identical, or how many of its kernels differ (an
+object only one side has counts as differing when it holds a kernel);
 one line per kernel whose instruction stream (mnemonics and operands) differs or that only one side has, with instruction
 count, MFMA count, VGPRs, SGPRs and scratch bytes of both sides.  What a refactoring that should not change the machine code
 is checked with before any GPU time is spent (done by hand for profiles/r09_wino_loop_disasm_diff.txt).  It only diffs."""
@@ -69,8 +70,9 @@ def main(dir_a: Path, dir_b: Path) -> int:
     for n in names:
         pa, pb = dir_a / n, dir_b / n
         if not (pa.is_file() and pb.is_file()):
-            print(f"{n}: only in {dir_a if pa.is_file() else dir_b}")
-            n_differ += 1
+            only = object_kernels(pa if pa.is_file() else pb)  # (a unit without kernels adds or removes no device code)
+            print(f"{n}: only in {dir_a if pa.is_file() else dir_b}, {len(only)} kernels")
+            n_differ += bool(only)
             continue
         ka, kb = object_kernels(pa), object_kernels(pb)
         differ = [k for k in sorted(set(ka) | set(kb)) if k not in ka or k not in kb or ka[k]["text"] != kb[k]["text"]
