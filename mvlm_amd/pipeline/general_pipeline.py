@@ -28,7 +28,9 @@ from ..prediction.paulsenpredictor import HipPaulsenModel
 from ..utils.estimator3d import HipEstimator3D
 from ..utils.hostmem import retain_freed_host_memory
 from ..utils.render3d import HipRenderer3D
-from ..utils.report import LandmarkReport, ReportLayout
+from ..utils.report import LandmarkReport, ResultPack
+from ..utils.viewer import check_png_encoder, select_rays
+from . import pictures
 
 __all__ = ["Pipeline"]
 
@@ -87,7 +89,8 @@ class _Stage:
 
 
 class Pipeline(abc.ABC):
-    visualize_heat = False  # (also for an object that never went through __init__: the checks below read it)
+    # (also for an object that never went through __init__: the picture rules and predict_mesh_device read them)
+    visualize_heat = _keep_ray_view = False
     heat_landmarks = None
 
     def __init__(self, render_image_stack: bool = False, offscreen: bool = True, n_views: int = 8,
@@ -115,79 +118,24 @@ class Pipeline(abc.ABC):
         # coordinates.  Off (the default): nothing of it is launched, allocated or copied.
         self.landmark_report = bool(landmark_report)
         self.last_report = None
-        # visualize_img: after every successful prediction the RESIDENT device mesh is drawn with a sphere at every landmark
-        # (the reference's --visualize-img, main.py:66-67; HipRenderer3D.render_landmark_view) into
-        # visualization/<stem>_<visualize_name>.png under the working directory, visualize_size pixels a side.  With
-        # landmark_report the spheres carry the report's branch colours (utils/report.py: BRANCH_COLOURS).  Off (the
-        # default): nothing of it is launched or allocated.
+        # the pictures a prediction can leave behind: pictures.py documents every option and checks them
         self.visualize_img = bool(visualize_img)
         self.visualize_size = int(visualize_size)
-        # visualize_rays_img: after every successful prediction the resident mesh is drawn with every selected view ray (the device
-        # tensors the consensus just used, clipped on the device when clip_rays_to_mesh is set) and the landmarks, one picture
-        # per pose of visualize_rays_poses in ONE call (the reference's visualize_rays=True, visualization/ray_visualizer.py;
-        # HipRenderer3D.render_ray_view), into <screenshot_folder or visualization/ray_screenshots>/
-        # <stem>_<visualize_name>_rays_<i>.png.  With landmark_report the rays carry LandmarkReport.ray_colours().  A flag of
-        # its own: visualize_rays keeps writing its .npz and nothing else.
         self.visualize_rays_img = bool(visualize_rays_img)
         self.visualize_rays_poses = np.asarray(visualize_rays_poses, dtype=np.float64).reshape(-1, 3)
-        self.last_ray_view_paths: list = []
-        # view_png_encoder: who makes the PNG files of visualize_img and visualize_rays_img.  "host" (the default): the picture
-        # is copied to the host and Pillow encodes it.  "device": the picture stays where render_*_view_device left it and
-        # HipRenderer3D.encode_png filters and compresses it there (mvlm_png_encode; the ray view's pictures in one call) - the
-        # same pixels in a file of other bytes, and only the compressed bytes cross to the host.
-        from ..utils.viewer import check_png_encoder
-
         self.view_png_encoder = check_png_encoder(view_png_encoder)
-        # (mesh, starts, ends, landmarks in the uploaded space, report) of the current call, kept only between a prediction made by
-        # predict_one_file / predict_files (_keep_ray_view) and the _after_prediction that draws it: predict_mesh_device called on
-        # its own has no file name, draws nothing and leaves nothing behind
+        self.visualize_sheet = bool(visualize_sheet)
+        self.visualize_heat = bool(visualize_heat)
+        self.sheet_scale, self.heat_floor, self.heat_landmarks = sheet_scale, heat_floor, None  # (sheet_scale: of both sheets)
+        pictures.check_options(self, n_views, heat_landmarks, visualize_size)
+        self.last_view_path = self.last_sheet_path = self.last_heat_path = None
+        self.last_ray_view_paths: list = []
+        # the pictures.Pass of the current call, kept only between a prediction made by predict_one_file / predict_files
+        # (_keep_ray_view) and the _after_prediction that draws its ray view
         self._ray_view = None
         self._keep_ray_view = False
-        # visualize_sheet: after every successful prediction the views the network saw are drawn side by side, with a marker where
-        # it put each landmark in each view and a red residual to where the final landmark projects there (the reference's
-        # Predictor2D.draw_image_with_landmarks for all views; HipRenderer3D.render_view_sheet), from this pass's own device
-        # buffers, into visualization/<stem>_<visualize_name>_views.png; sheet_scale 1..4 sheet pixels per view pixel.  With
-        # landmark_report a view the score filter dropped gets a ring and the markers carry the report's branch colours.  Off (the
-        # default): nothing of it is launched, allocated or copied.
-        self.visualize_sheet = bool(visualize_sheet)
-        self.sheet_scale = sheet_scale
-        self.last_sheet_path = None
-        self.visualize_heat = bool(visualize_heat)  # (below; sheet_scale is shared)
-        if self.visualize_sheet or self.visualize_heat:
-            if isinstance(sheet_scale, bool) or not isinstance(sheet_scale, (int, np.integer)) or not 1 <= sheet_scale <= 4:
-                raise ValueError(f"sheet_scale must be an integer in 1..4, not {sheet_scale!r}")
-            self.sheet_scale = int(sheet_scale)
-        if self.visualize_sheet and n_views is not None:  # (a sheet beyond 4096 pixels a side: said here, with the scale that fits)
-            HipRenderer3D.view_sheet_layout(int(n_views), None, self.sheet_scale)
-        # visualize_heat: after every successful prediction the views the network saw are drawn side by side - the view sheet's
-        # cells, no markers - with the network's heatmaps laid over them: per pixel the landmark (of heat_landmarks; None: all) whose
-        # value is the largest share of its plane's peak, in its colour of utils/viewer.py's palette, shares up to heat_floor not
-        # drawn (HipRenderer3D.render_heat_sheet), into visualization/<stem>_<visualize_name>_heat.png; sheet_scale and
-        # view_png_encoder apply as for the view sheet.  The heatmaps are not kept by the prediction: the predictor's
-        # heatmaps_device runs once more on this pass's image stack, which costs about one network pass more per scan, and its
-        # tensor ([N,NL,256,256] float32: 2 GB at 96 views x 84 landmarks) lives until the picture is drawn.  Off (the default):
-        # nothing of it is launched, allocated or copied.
-        self.heat_landmarks = None
-        self.heat_floor = heat_floor
-        self.last_heat_path = None
-        if self.visualize_heat:
-            if isinstance(heat_floor, bool) or not isinstance(heat_floor, (int, float, np.integer, np.floating)) \
-                    or not (np.isfinite(heat_floor) and 0.0 <= heat_floor < 1.0):
-                raise ValueError(f"heat_floor must be a finite number in [0, 1), not {heat_floor!r}")
-            self.heat_floor = float(heat_floor)
-            if heat_landmarks is not None:
-                picked = list(heat_landmarks) if isinstance(heat_landmarks, (list, tuple, range, np.ndarray)) else None
-                if picked is None or any(isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 0 for k in picked) \
-                        or len(set(int(k) for k in picked)) != len(picked):
-                    raise ValueError(f"heat_landmarks must be None or a sequence of distinct landmark indices, not {heat_landmarks!r}")
-                self.heat_landmarks = [int(k) for k in picked]  # (the upper end: _check_visualize, once the predictor is there)
-            if n_views is not None:  # (a sheet beyond 4096 pixels a side: said here, with the scale that fits)
-                HipRenderer3D._sheet_layout("heat sheet", int(n_views), None, self.sheet_scale, 2)
-        if (self.visualize_img or self.visualize_rays_img) and (self.visualize_size < 64 or self.visualize_size > 2048 or self.visualize_size % 16):
-            raise ValueError(f"visualize_size must be a multiple of 16 in 64..2048, not {visualize_size}")
         name = type(self).__name__.lower()
         self.visualize_name = visualize_name if visualize_name is not None else name[:-len("pipeline")] if name.endswith("pipeline") else name
-        self.last_view_path = None
         self._rays = None  # (mesh, starts, ends) of the current call when visualize_rays is set
         self._buffers: dict = {}
         self._lock = threading.RLock()  # see _serialised
@@ -325,21 +273,31 @@ class Pipeline(abc.ABC):
         # and only the GPU section - RNG draws, device buffers, launch graphs, timings - is one caller at a time.
         mesh, load_seconds = None, 0.0
         if self._fusable():
-            from ..utils.render3d import upload_mesh
-
             t0 = time.perf_counter()
-            mesh = self.renderer_3d.load_mesh(self.renderer_3d._check_file(file_name), load_texture=self._texture_needed())
-            self._check_cloud(mesh)
-            upload_mesh(self.renderer_3d.ctx, mesh)  # (thread-safe beside a launching thread: include/mvlm_hip.h)
+            mesh = self._ingest(file_name, self._texture_needed())
             load_seconds = time.perf_counter() - t0
+        return self._predict_scan(file_name, mesh, load_seconds, landmark_indices, view_indices, clip_rays_to_mesh)
+
+    def _ingest(self, file_name: Path, load_texture: bool):
+        """File -> pre-aligned mesh, checked and uploaded once.  The device copy goes through pinned staging and a copy stream of
+        the library's own (mvlm_mesh_upload; the renderer waits for its event), so a reader thread's transfer runs beside the
+        current scan's kernels (thread-safe beside a launching thread: include/mvlm_hip.h)."""
+        from ..utils.render3d import upload_mesh
+
+        mesh = self.renderer_3d.load_mesh(self.renderer_3d._check_file(file_name), load_texture=load_texture)
+        self._check_cloud(mesh)
+        upload_mesh(self.renderer_3d.ctx, mesh)
+        return mesh
+
+    def _predict_scan(self, file_name, mesh=None, load_seconds=0.0, landmark_indices=None, view_indices=None, clip_rays_to_mesh=True):
+        """One scan's GPU section, under the pipeline lock: the per-call ray state, the prediction (fused for a ``mesh`` that is
+        ingested and uploaded already, else the slot protocol) under the ``total`` stage, and what follows every prediction.
+        ``load_seconds``: what the caller spent on ingest and upload, outside the lock."""
         with self._lock:
             self._rays = None
             self._ray_view, self._keep_ray_view = None, self.visualize_rays_img
             with self._timer.stage("total"):
-                if mesh is not None:
-                    landmarks = self._predict_fused(file_name, mesh=mesh)
-                else:
-                    landmarks = self._predict_slots(file_name)
+                landmarks = self._predict_fused(file_name, mesh=mesh) if mesh is not None else self._predict_slots(file_name)
             if mesh is not None:
                 self.timings["load"] = self.timings.get("load", 0.0) + load_seconds
                 self.timings["total"] += load_seconds
@@ -363,52 +321,9 @@ class Pipeline(abc.ABC):
         self._ray_view, self._keep_ray_view = None, False
 
     def draw_ray_view(self, file_name: Path, landmark_indices=None, view_indices=None, clip_to_mesh: bool = True):
-        """``visualize_rays_img``: the pictures the reference's ``RayVisualizer`` shows (ray_visualizer.py:150-338), drawn by
-        ``HipRenderer3D.render_ray_view_device`` - the mesh as it lies on the device, the rays of the selected landmarks and
-        views (subset exactly as ``dump_rays`` subsets them) from the tensors the consensus used, clipped on the device, the
-        landmarks in the uploaded space; all poses in one call.  Returns the paths (also ``last_ray_view_paths``)."""
-        import torch
-
-        from ..utils.viewer import write_view_png
-
+        """``visualize_rays_img``: the ray view of the pass kept in ``_ray_view`` (pictures.draw_ray_view)."""
         self._check_visualize()
-        mesh, starts, ends, landmarks, report = self._ray_view
-        with self._timer.stage("visualize_rays"):
-            dev = torch.device("cuda", self.renderer_3d.ctx.device)
-            starts = starts if hasattr(starts, "data_ptr") else torch.from_numpy(np.ascontiguousarray(starts, dtype=np.float64)).to(dev)
-            ends = ends if hasattr(ends, "data_ptr") else torch.from_numpy(np.ascontiguousarray(ends, dtype=np.float64)).to(dev)
-            nl, nv = int(starts.shape[0]), int(starts.shape[1])
-            lm_idx = list(range(nl)) if landmark_indices is None else [int(i) % nl for i in landmark_indices]
-            v_idx = list(range(nv)) if view_indices is None else [int(i) % nv for i in view_indices]
-            li = torch.as_tensor(lm_idx, dtype=torch.long, device=dev)
-            vi = torch.as_tensor(v_idx, dtype=torch.long, device=dev)
-            fs = starts.index_select(0, li).index_select(1, vi).contiguous()
-            fe = ends.index_select(0, li).index_select(1, vi).contiguous()
-            if clip_to_mesh and fs.numel():
-                fe, _ = self.estimator_3d.clip_rays_device(mesh, fs, fe)
-            landmarks = np.asarray(landmarks, dtype=np.float64).reshape(-1, 3)
-            colours = report.branch_colours() if report is not None else None
-            ray_colours = None
-            if report is not None:
-                ray_colours = report.ray_colours(np.asarray(report.view_indices)[v_idx])[lm_idx].reshape(-1, 3)
-            finite = np.isfinite(landmarks).all(axis=1)
-            if not finite.all():
-                landmarks = landmarks[finite]
-                colours = None if colours is None else colours[finite]
-            device = self.view_png_encoder == "device"
-            draw = self.renderer_3d.render_ray_view_device if device else self.renderer_3d.render_ray_view
-            images = draw(mesh, landmarks, fs, fe, poses=self.visualize_rays_poses, size=self.visualize_size, colors=colours,
-                          ray_colors=ray_colours)
-            folder = Path(self.screenshot_folder) if self.screenshot_folder else Path.cwd() / "visualization" / "ray_screenshots"
-            stem = Path(file_name).stem
-            paths = [folder / f"{stem}_{self.visualize_name}_rays_{i}.png" for i in range(len(images))]
-            if device:  # the pictures stay on the device: one encode call for all poses
-                self.last_ray_view_paths = write_view_png(images, paths, encoder="device", renderer=self.renderer_3d)
-                self.renderer_3d.check()
-            else:
-                self.last_ray_view_paths = [write_view_png(image, q) for image, q in zip(images, paths)]
-        self._say(f"[Pipeline] ray view written to {[str(q) for q in self.last_ray_view_paths]}")
-        return self.last_ray_view_paths
+        return pictures.draw_ray_view(self, self._ray_view, file_name, landmark_indices, view_indices, clip_to_mesh)
 
     def dump_rays(self, file_name: Path, landmarks, landmark_indices=None, view_indices=None, clip_to_mesh: bool = True):
         """What the reference hands to its VTK ``RayVisualizer`` (general_pipeline.py:111-128), written
@@ -416,8 +331,7 @@ class Pipeline(abc.ABC):
         clipped to their first hit with the mesh when ``clip_to_mesh`` (ray_visualizer.py:172-192,
         here on the GPU: mvlm_clip_rays_to_mesh), ``hit`` [L,V], the indices and the landmarks."""
         mesh, starts, ends = self._rays
-        lm_idx = list(range(starts.shape[0])) if landmark_indices is None else [int(i) % starts.shape[0] for i in landmark_indices]
-        v_idx = list(range(starts.shape[1])) if view_indices is None else [int(i) % starts.shape[1] for i in view_indices]
+        lm_idx, v_idx = select_rays(starts.shape[0], starts.shape[1], landmark_indices, view_indices)
         fs = np.ascontiguousarray(starts[np.ix_(lm_idx, v_idx)])
         fe = np.ascontiguousarray(ends[np.ix_(lm_idx, v_idx)])
         hit = np.zeros(fs.shape[:2], bool)
@@ -443,7 +357,8 @@ class Pipeline(abc.ABC):
 
         r3, p2, e3 = self.renderer_3d, self.predictor_2d, self.estimator_3d
         self._check_cloud(mesh)
-        if self.visualize_sheet or self.visualize_heat:
+        drawing = pictures.wanted(self)  # (the one question the hot path asks about the pictures)
+        if drawing:
             self._check_visualize()
         n_total = int(transform_stack.shape[0])
         sharded = self.shard_views and parallel.is_distributed()
@@ -457,280 +372,154 @@ class Pipeline(abc.ABC):
         dev_t = torch.device("cuda", self.device)
         # this call owns the renderer's / estimator's context until it returns: the launch stream is bound once
         with r3.ctx.hold_stream(torch, dev_t), e3.ctx.hold_stream(torch, dev_t):
-            return self._predict_mesh_device_held(mesh, transform_stack, rot, r3, p2, e3, tm, dev_t, n_total, sharded, rank, lo, hi)
-
-    def _predict_mesh_device_held(self, mesh, transform_stack, rot, r3, p2, e3, tm, dev_t, n_total, sharded, rank, lo, hi):
-        import torch
-
-        # What the GPU waits for first is the render: single-process, it is enqueued before anything else the host has to
-        # prepare (the rotations' second upload, the result buffers, the RANSAC draws: all of that then happens while the
-        # rasteriser runs - at 0.5 ms per step, configs[4], the host's serial part is what the step time is made of).
-        # Sharded, the draws come out of a collective, which must not queue up behind this step's network: they go first.
-        draws_fn = None
-        if sharded:
-            # one RNG stream for the job: rank 0 draws (global numpy RNG, as the reference) and broadcasts the table
-            def draws_fn(counts, keep_on_device=False):
-                draws = e3.draw_ransac_indices(counts) if rank == 0 else None
-                return parallel.broadcast_int32(draws, (len(counts), 8), dev_t, keep_on_device=keep_on_device)
-
-            draws_fn.device_result = True  # plan_draws may ask for the collective's device tensor (RCCL)
-
-        nl_all = p2.get_lm_count()
-        plan = e3.plan_draws(nl_all, n_total, draws_fn) if sharded else None
-        with tm.stage("render"):
-            # one image stack / maxima buffer per view count, reused from call to call: stable addresses let the
-            # predictor replay its captured launch graph instead of re-enqueueing ~160 kernels per mesh
-            images = None
-            if hi > lo:
-                images = r3.render_device(mesh, transform_stack[lo:hi], rot=rot[lo:hi],
-                                          out=self._buffer("images", (hi - lo, 256, 256, 4)))
-            if self.verbose:
-                torch.cuda.synchronize()
-        if images is not None and hi - lo == n_total and r3.ctx is e3.ctx:
-            rot_dev = r3.rotations_device()   # all views rendered here: the rays read the rasteriser's own device copy
-        else:
-            # (enqueued behind the render on the same stream, through pinned staging: the host does not wait)
-            rot_dev = e3.upload_rotations_async(rot)
-        # landmarks f64[NL,3] | error f64[NL] | survivor counts i32[NL] in ONE buffer: one device-to-host copy per mesh,
-        # into pinned memory, enqueued right behind the last kernel
-        base_bytes, report_bytes = nl_all * (24 + 8 + 4), 0
-        layout = rviews = None
-        if self.landmark_report:
-            # the report rides behind the result in the same buffer (8-byte aligned): still one copy per mesh.  Room for all
-            # views: should a detector's ``valid`` mask drop some, the smaller layout made below fits
-            base_bytes = (base_bytes + 7) // 8 * 8
-            report_bytes = ReportLayout(nl_all, n_total).nbytes
-        pack = self._buffer_bytes("result", base_bytes + report_bytes)
-        pack_host, pack_np = self._pinned_bytes("result_host", int(pack.numel()))
-        snap_view = pack[: nl_all * 24].view(torch.float64).view(nl_all, 3)
-        err_view = pack[nl_all * 24: nl_all * 32].view(torch.float64)
-        count_view = pack[nl_all * 32: nl_all * 36].view(torch.int32)
-        if self.render_image_stack and images is not None:
-            self.visualize_image_stack(images.cpu().numpy(), mesh.path or Path("mesh.obj"), first_index=lo)
-
-        kept_views = None  # positions in the pose table of the views a detector's ``valid`` mask left (None: all)
-        valid = None  # host bool [views of this rank]: a detector's "nothing found in this view" (None: all valid)
-        with tm.stage("prediction"):
-            if images is not None and isinstance(p2, HipPaulsenModel):
-                maxima = p2.predict_device(images, out=self._buffer("maxima", (p2.get_lm_count(), hi - lo, 3)))
-            elif images is not None:
-                maxima = p2.predict_device(images)
-                if isinstance(maxima, tuple):
-                    maxima, valid = maxima
-            else:
-                maxima = torch.empty((p2.get_lm_count(), 0, 3), dtype=torch.float32,
-                                     device=torch.device("cuda", self.device))
-            # (the stack stays where it is until the sheets are drawn)
-            sheet_images = images if self.visualize_sheet or self.visualize_heat else None
-            del images
+            # What the GPU waits for first is the render: single-process, it is enqueued before anything else the host has to
+            # prepare (the rotations' second upload, the result buffers, the RANSAC draws: all of that then happens while the
+            # rasteriser runs - at 0.5 ms per step, configs[4], the host's serial part is what the step time is made of).
+            # Sharded, the draws come out of a collective, which must not queue up behind this step's network: they go first.
+            draws_fn = None
             if sharded:
-                maxima = parallel.all_gather_views(maxima, n_total)
-                if not isinstance(p2, HipPaulsenModel):  # (same predictor class on every rank: all join or none does)
-                    valid = parallel.all_gather_valid(valid, hi - lo, n_total, self.device)
-            if self.verbose:
-                torch.cuda.synchronize()
-        if valid is not None and not valid.all():
-            # views without a detection leave the call here, as in the reference (general_pipeline.py:93-95:
-            # landmark_stack[:, valid], transform_stack[valid]) - before rays, filter and the RANSAC draws, which
-            # address the remaining views by position
-            keep = np.nonzero(valid)[0]
-            maxima = maxima.index_select(1, torch.from_numpy(keep).to(maxima.device)).contiguous()
-            transform_stack = transform_stack[keep]
-            rot_dev = e3.upload_rotations_async(rot[keep])
-            n_total = int(len(keep))
-            kept_views = keep
-            if plan is not None:  # sharded: the draws planned for all views are void - plan again for the views that remain
-                np.random.set_state(plan["rng_state"])
-                plan = e3.plan_draws(nl_all, n_total, draws_fn)
+                # one RNG stream for the job: rank 0 draws (global numpy RNG, as the reference) and broadcasts the table
+                def draws_fn(counts, keep_on_device=False):
+                    draws = e3.draw_ransac_indices(counts) if rank == 0 else None
+                    return parallel.broadcast_int32(draws, (len(counts), 8), dev_t, keep_on_device=keep_on_device)
 
-        if plan is None:
-            # the RANSAC draws for the expected survivor counts (~0.3 ms of numpy calls) are made now, while the GPU
-            # works on the views; they travel through pinned memory on a copy stream of their own
-            plan = e3.plan_draws(nl_all, n_total, None)
+                draws_fn.device_result = True  # plan_draws may ask for the collective's device tensor (RCCL)
 
-        with tm.stage("lines"):
-            starts, ends = e3.lines_device(maxima, transform_stack, 256, rot_dev=rot_dev)
+            nl_all = p2.get_lm_count()
+            plan = e3.plan_draws(nl_all, n_total, draws_fn) if sharded else None
+            with tm.stage("render"):
+                # one image stack / maxima buffer per view count, reused from call to call: stable addresses let the
+                # predictor replay its captured launch graph instead of re-enqueueing ~160 kernels per mesh
+                images = None
+                if hi > lo:
+                    images = r3.render_device(mesh, transform_stack[lo:hi], rot=rot[lo:hi],
+                                              out=self._buffer("images", (hi - lo, 256, 256, 4)))
+                if self.verbose:
+                    torch.cuda.synchronize()
+            if images is not None and hi - lo == n_total and r3.ctx is e3.ctx:
+                rot_dev = r3.rotations_device()   # all views rendered here: the rays read the rasteriser's own device copy
+            else:
+                # (enqueued behind the render on the same stream, through pinned staging: the host does not wait)
+                rot_dev = e3.upload_rotations_async(rot)
+            # landmarks f64[NL,3] | error f64[NL] | survivor counts i32[NL] in ONE buffer: one device-to-host copy per mesh,
+            # into pinned memory, enqueued right behind the last kernel
+            # (ResultPack); with landmark_report the report rides behind the result in the same buffer: still one copy per mesh.
+            # Room for all views: should a detector's ``valid`` mask drop some, the smaller layout made below fits
+            rp = ResultPack(nl_all, n_total if self.landmark_report else None)
+            pack = self._buffer_bytes("result", rp.total)
+            pack_host, pack_np = self._pinned_bytes("result_host", int(pack.numel()))
+            dev_views, host, rviews, report = rp.device_views(pack), rp.host_views(pack_np), None, None
+            if self.render_image_stack and images is not None:
+                self.visualize_image_stack(images.cpu().numpy(), mesh.path or Path("mesh.obj"), first_index=lo)
 
-        with tm.stage("consensus"):
-            if self.visualize_rays:
-                self._rays = (mesh, starts.cpu().numpy(), ends.cpu().numpy())
-            if self.landmark_report:
-                layout = ReportLayout(nl_all, n_total)
-                rviews = layout.device_views(pack[base_bytes: base_bytes + layout.nbytes])
-                rviews["scores"].copy_(maxima[:, :, 2])
-            # (with a report, every solve - the one verify may repeat too - is followed by the report kernel)
-            out, err, verify = e3.consensus_device(maxima, starts, ends, deferred=True, plan=plan, err_out=err_view,
-                                                   count_out=count_view, report=rviews)
+            kept_views = None  # positions in the pose table of the views a detector's ``valid`` mask left (None: all)
+            valid = None  # host bool [views of this rank]: a detector's "nothing found in this view" (None: all valid)
+            with tm.stage("prediction"):
+                if images is not None and isinstance(p2, HipPaulsenModel):
+                    maxima = p2.predict_device(images, out=self._buffer("maxima", (p2.get_lm_count(), hi - lo, 3)))
+                elif images is not None:
+                    maxima = p2.predict_device(images)
+                    if isinstance(maxima, tuple):
+                        maxima, valid = maxima
+                else:
+                    maxima = torch.empty((p2.get_lm_count(), 0, 3), dtype=torch.float32,
+                                         device=torch.device("cuda", self.device))
+                # (the stack stays where it is until the sheets are drawn)
+                sheet_images = images if drawing and (self.visualize_sheet or self.visualize_heat) else None
+                del images
+                if sharded:
+                    maxima = parallel.all_gather_views(maxima, n_total)
+                    if not isinstance(p2, HipPaulsenModel):  # (same predictor class on every rank: all join or none does)
+                        valid = parallel.all_gather_valid(valid, hi - lo, n_total, self.device)
+                if self.verbose:
+                    torch.cuda.synchronize()
+            if valid is not None and not valid.all():
+                # views without a detection leave the call here, as in the reference (general_pipeline.py:93-95:
+                # landmark_stack[:, valid], transform_stack[valid]) - before rays, filter and the RANSAC draws, which
+                # address the remaining views by position
+                keep = np.nonzero(valid)[0]
+                maxima = maxima.index_select(1, torch.from_numpy(keep).to(maxima.device)).contiguous()
+                transform_stack = transform_stack[keep]
+                rot_dev = e3.upload_rotations_async(rot[keep])
+                n_total = int(len(keep))
+                kept_views = keep
+                if rp.report is not None:
+                    rp = ResultPack(nl_all, n_total)
+                if plan is not None:  # sharded: the draws planned for all views are void - plan again for the views that remain
+                    np.random.set_state(plan["rng_state"])
+                    plan = e3.plan_draws(nl_all, n_total, draws_fn)
 
-        def snap():
-            e3.project_device(mesh, out, out=snap_view)
-            if rviews is not None:  # behind the snap: the same search once more, leaving triangle, weights and uv
-                e3.attach_device(mesh, out, views=rviews)
+            if plan is None:
+                # the RANSAC draws for the expected survivor counts (~0.3 ms of numpy calls) are made now, while the GPU
+                # works on the views; they travel through pinned memory on a copy stream of their own
+                plan = e3.plan_draws(nl_all, n_total, None)
 
-        with tm.stage("project"):
-            # the snap is enqueued before anything is fetched: one wait and one copy per mesh, at the end
-            snap()
-            stream = torch.cuda.current_stream(dev_t)
-            pack_host.copy_(pack, non_blocking=True)
-            stream.synchronize()
-            host = pack_np
-            if verify(counts=host[nl_all * 32: nl_all * 36].view(np.int32)):
-                # the RANSAC draws had to be repeated for other survivor counts (tied / NaN scores, absolute mode)
+            with tm.stage("lines"):
+                starts, ends = e3.lines_device(maxima, transform_stack, 256, rot_dev=rot_dev)
+
+            with tm.stage("consensus"):
+                if self.visualize_rays:
+                    self._rays = (mesh, starts.cpu().numpy(), ends.cpu().numpy())
+                if rp.report is not None:
+                    rviews = rp.report.device_views(rp.report_bytes(pack))
+                    rviews["scores"].copy_(maxima[:, :, 2])
+                # (with a report, every solve - the one verify may repeat too - is followed by the report kernel)
+                out, err, verify = e3.consensus_device(maxima, starts, ends, deferred=True, plan=plan, err_out=dev_views["error"],
+                                                       count_out=dev_views["counts"], report=rviews)
+
+            def snap():
+                e3.project_device(mesh, out, out=dev_views["snapped"])
+                if rviews is not None:  # behind the snap: the same search once more, leaving triangle, weights and uv
+                    e3.attach_device(mesh, out, views=rviews)
+
+            with tm.stage("project"):
+                # the snap is enqueued before anything is fetched: one wait and one copy per mesh, at the end
                 snap()
+                stream = torch.cuda.current_stream(dev_t)
                 pack_host.copy_(pack, non_blocking=True)
                 stream.synchronize()
-            landmarks = host[: nl_all * 24].view(np.float64).reshape(nl_all, 3).copy()
-            error = e3.mean_error(host[nl_all * 24: nl_all * 32].view(np.float64))
-            r3.check()  # deferred renderer status (the stream has been waited for above)
-            if layout is not None:
-                # (model space; _predict_fused maps ``landmarks`` back to the file's coordinates.  Should the fp16 range guard
-                # below repeat the scan, the repeated pass leaves its own report here.)
-                self.last_report = LandmarkReport(layout.host_arrays(host[base_bytes: base_bytes + layout.nbytes]),
-                                                  landmarks=landmarks, view_indices=kept_views)
-        asked16 = getattr(p2, "configured_precision", getattr(p2, "precision", None)) == "fast16"
-        if asked16:
-            # an activation beyond fp16's range somewhere in the network (the kernel raised the context's flag; the maxima of
-            # the pass carry NaN scores, which survive no filter - the landmarks above are finite nonsense).  Same scan again
-            # on bf16x3; asked here, after the step's own wait for its results, the question costs one 4-byte copy.
-            # (the global RNG stands behind this call's draws: the repeat draws again, as a second call would.)
-            # Sharded: the decision is taken by all ranks together - a rank repeating alone would wait in collectives nobody
-            # else joins - and WHETHER to ask is decided from what the caller configured, which is the same on every rank:
-            # a rank that already fell back on its own (predict_landmarks_from_images) still joins the all-reduce.
-            mine = p2.precision == "fast16" and p2.fast16_overflowed()
-            if parallel.any_rank(mine, self.device) if sharded else mine:
-                return p2.repeat_without_fp16(lambda: self.predict_mesh_device(mesh, transform_stack))
-        self._say("Landmarks [Error]: ", f"{error:08.6f}", " mm")
-        self.last_error = error
-        if self.visualize_img and (not sharded or rank == 0):  # (sharded: every rank holds the result, one draws)
-            self._draw_landmark_view(mesh, landmarks, self.last_report if layout is not None else None)  # (THIS pass's report)
-        if self.visualize_sheet and sheet_images is not None:
-            keep = None if kept_views is None else torch.from_numpy(np.asarray(kept_views)).to(sheet_images.device)
-            self._draw_view_sheet(mesh, sheet_images if keep is None else sheet_images.index_select(0, keep), maxima,
-                                  rot if kept_views is None else rot[kept_views], landmarks,
-                                  self.last_report if layout is not None else None)
-        if self.visualize_heat and sheet_images is not None:
-            keep = None if kept_views is None else torch.from_numpy(np.asarray(kept_views)).to(sheet_images.device)
-            self._draw_heat_sheet(mesh, sheet_images if keep is None else sheet_images.index_select(0, keep), landmarks)
-        if self._keep_ray_view and (not sharded or rank == 0):  # drawn by _after_prediction, which knows the file and the selection
-            self._ray_view = (mesh, starts, ends, landmarks, self.last_report if layout is not None else None)
-        return landmarks, error
+                if verify(counts=host["counts"]):
+                    # the RANSAC draws had to be repeated for other survivor counts (tied / NaN scores, absolute mode)
+                    snap()
+                    pack_host.copy_(pack, non_blocking=True)
+                    stream.synchronize()
+                landmarks = host["snapped"].copy()  # (the pinned staging buffer is the next call's too)
+                error = e3.mean_error(host["error"])
+                r3.check()  # deferred renderer status (the stream has been waited for above)
+                if rp.report is not None:
+                    # (model space; _predict_fused maps ``landmarks`` back to the file's coordinates.  Should the fp16 range guard
+                    # below repeat the scan, the repeated pass leaves its own report here.)
+                    report = self.last_report = LandmarkReport(rp.report.host_arrays(rp.report_bytes(pack_np)), landmarks=landmarks,
+                                                               view_indices=kept_views)
+            asked16 = getattr(p2, "configured_precision", getattr(p2, "precision", None)) == "fast16"
+            if asked16:
+                # an activation beyond fp16's range somewhere in the network (the kernel raised the context's flag; the maxima of
+                # the pass carry NaN scores, which survive no filter - the landmarks above are finite nonsense).  Same scan again
+                # on bf16x3; asked here, after the step's own wait for its results, the question costs one 4-byte copy.
+                # (the global RNG stands behind this call's draws: the repeat draws again, as a second call would.)
+                # Sharded: the decision is taken by all ranks together - a rank repeating alone would wait in collectives nobody
+                # else joins - and WHETHER to ask is decided from what the caller configured, which is the same on every rank:
+                # a rank that already fell back on its own (predict_landmarks_from_images) still joins the all-reduce.
+                mine = p2.precision == "fast16" and p2.fast16_overflowed()
+                if parallel.any_rank(mine, self.device) if sharded else mine:
+                    return p2.repeat_without_fp16(lambda: self.predict_mesh_device(mesh, transform_stack))
+            self._say("Landmarks [Error]: ", f"{error:08.6f}", " mm")
+            self.last_error = error
+            if drawing:
+                if kept_views is not None and sheet_images is not None:  # the views a detector's ``valid`` mask left
+                    sheet_images = sheet_images.index_select(0, torch.from_numpy(np.asarray(kept_views)).to(sheet_images.device))
+                    rot = rot[kept_views]
+                # (sharded: every rank holds the result, one draws)
+                pictures.draw(self, pictures.Pass(mesh, sheet_images, maxima, rot, starts, ends, landmarks, report, not sharded or rank == 0))
+            return landmarks, error
 
     def _check_visualize(self):
-        """``visualize_img`` and ``visualize_rays_img`` need the renderer that holds the mesh on the device, ``visualize_sheet`` the
-        one that draws it - and all the views in one process; ``visualize_heat`` as ``visualize_sheet``, and a predictor that hands
-        out its heatmaps: said before the prediction, not after it."""
-        if self.visualize_heat:
-            if not callable(getattr(self.predictor_2d, "heatmaps_device", None)):
-                raise ValueError("visualize_heat needs a predictor with heatmaps_device (HipPaulsenModel): "
-                                 f"{type(self.predictor_2d).__name__} has no heatmaps to show")
-            if not isinstance(self.renderer_3d, HipRenderer3D):
-                raise ValueError("visualize_heat needs a HipRenderer3D in the renderer slot (it draws the sheet), "
-                                 f"not {type(self.renderer_3d).__name__}")
-            if self.shard_views and parallel.is_distributed():
-                raise ValueError("visualize_heat is not supported with shard_views in a distributed run: a rank holds only its "
-                                 "slice of the views")
-            if self.heat_landmarks is not None:
-                nl = int(self.predictor_2d.get_lm_count())
-                if any(k >= nl for k in self.heat_landmarks):
-                    raise ValueError(f"heat_landmarks must lie in 0..{nl - 1}, not {self.heat_landmarks!r}")
-        if self.visualize_sheet and not isinstance(self.renderer_3d, HipRenderer3D):
-            raise ValueError("visualize_sheet needs a HipRenderer3D in the renderer slot (it draws the sheet), "
-                             f"not {type(self.renderer_3d).__name__}")
-        if self.visualize_sheet and self.shard_views and parallel.is_distributed():
-            raise ValueError("visualize_sheet is not supported with shard_views in a distributed run: a rank holds only its slice "
-                             "of the views")
-        if self.visualize_rays_img and not isinstance(self.renderer_3d, HipRenderer3D):
-            raise ValueError("visualize_rays_img needs a HipRenderer3D in the renderer slot (it draws the mesh resident on the "
-                             f"device), not {type(self.renderer_3d).__name__}")
-        if self.visualize_img and not isinstance(self.renderer_3d, HipRenderer3D):
-            raise ValueError("visualize_img needs a HipRenderer3D in the renderer slot (it draws the mesh resident on the device), "
-                             f"not {type(self.renderer_3d).__name__}")
+        """What the picture flags need of the slots and the run (pictures.check): said before the prediction, not after it."""
+        pictures.check(self)
 
     def _draw_landmark_view(self, mesh, landmarks, report=None):
-        """``visualize_img``: the mesh as it lies on the device - no second ingest, no second upload - with the landmarks in the
-        space it was uploaded in (with a pre-align block: before the inverse mapping, so the points sit on the drawn surface),
-        front view, ``frame="fit"``; written as ``LandmarkViewer`` names it.  ``report``: the LandmarkReport of THIS prediction
-        (its branches colour the spheres) or None (blue).  A landmark that is not finite (a consensus without lines can leave one)
-        is left out of the picture: the flag does not fail a prediction that succeeded."""
-        from ..utils.viewer import view_path, write_view_png
-
-        if landmarks is None:
-            return None
-        self._check_visualize()
-        with self._timer.stage("visualize"):
-            landmarks = np.asarray(landmarks, dtype=np.float64).reshape(-1, 3)
-            colours = report.branch_colours() if report is not None else None
-            finite = np.isfinite(landmarks).all(axis=1)
-            if not finite.all():
-                landmarks = landmarks[finite]
-                colours = None if colours is None else colours[finite]
-            out_path = view_path(getattr(mesh, "path", None) or "mesh.obj", self.visualize_name)
-            if self.view_png_encoder == "device":  # the picture stays on the device
-                image = self.renderer_3d.render_landmark_view_device(mesh, landmarks, size=self.visualize_size, colors=colours)[0]
-                self.last_view_path = write_view_png(image, out_path, encoder="device", renderer=self.renderer_3d)
-                self.renderer_3d.check()
-            else:
-                image = self.renderer_3d.render_landmark_view(mesh, landmarks, size=self.visualize_size, colors=colours)[0]
-                self.last_view_path = write_view_png(image, out_path)
-        self._say(f"[Pipeline] landmark view written to {self.last_view_path}")
-        return self.last_view_path
-
-    def _draw_view_sheet(self, mesh, images, maxima, rot, landmarks, report=None):
-        """``visualize_sheet``: the views of THIS pass (a device stack [N,256,256,4] or the slot protocol's numpy one), their maxima
-        [NL,N,3], the views' rotations and the landmarks in the space the mesh was uploaded in, drawn by
-        ``HipRenderer3D.render_view_sheet``; the background is the planes the predictor read.  ``report``: the LandmarkReport of this
-        prediction (its survivor flags make rings, its branches colour the markers) or None."""
-        from ..utils.viewer import view_sheet_path, write_view_png
-
-        if landmarks is None:
-            return None
-        self._check_visualize()
-        with self._timer.stage("visualize_sheet"):
-            colours = used = None
-            if report is not None:
-                colours = report.branch_colours()
-                used = ((np.asarray(report.view_flags) & LandmarkReport.VIEW_KEPT) != 0).astype(np.uint8)
-            out_path = view_sheet_path(getattr(mesh, "path", None) or "mesh.obj", self.visualize_name)
-            if hasattr(maxima, "data_ptr"):
-                maxima = maxima.float()  # (a detector's device maxima may be float64; the network's are float32 already)
-            args = dict(maxima=maxima, rot=rot, landmarks=np.asarray(landmarks, dtype=np.float64).reshape(-1, 3), colors=colours,
-                        used=used, background="auto", scale=self.sheet_scale, chan_sel=getattr(self.predictor_2d, "chan_sel", None))
-            if self.view_png_encoder == "device":  # the picture stays on the device
-                image = self.renderer_3d.render_view_sheet_device(images, **args)
-                self.last_sheet_path = write_view_png(image, out_path, encoder="device", renderer=self.renderer_3d)
-                self.renderer_3d.check()
-            else:
-                self.last_sheet_path = write_view_png(self.renderer_3d.render_view_sheet(images, **args), out_path)
-        self._say(f"[Pipeline] view sheet written to {self.last_sheet_path}")
-        return self.last_sheet_path
-
-    def _draw_heat_sheet(self, mesh, images, landmarks):
-        """``visualize_heat``: the views of THIS pass (a device stack [N,256,256,4] or the slot protocol's numpy one) with the heatmaps
-        the predictor makes of them - a second forward pass, about one network pass more - drawn by
-        ``HipRenderer3D.render_heat_sheet``; the background is the planes the predictor read.  Nothing is drawn for a prediction that
-        failed (``landmarks`` None)."""
-        import torch
-
-        from ..utils.viewer import heat_colours, heat_sheet_path, write_view_png
-
-        if landmarks is None:
-            return None
-        self._check_visualize()
-        with self._timer.stage("visualize_heat"):
-            if not hasattr(images, "data_ptr"):
-                images = torch.from_numpy(np.ascontiguousarray(images, dtype=np.float32)).to(torch.device("cuda", self.renderer_3d.ctx.device))
-            heat = self.predictor_2d.heatmaps_device(images)
-            out_path = heat_sheet_path(getattr(mesh, "path", None) or "mesh.obj", self.visualize_name)
-            args = dict(landmarks=self.heat_landmarks, colors=heat_colours(int(heat.shape[1])), background="auto", scale=self.sheet_scale,
-                        floor=self.heat_floor, chan_sel=getattr(self.predictor_2d, "chan_sel", None))
-            if self.view_png_encoder == "device":  # the picture stays on the device
-                image = self.renderer_3d.render_heat_sheet_device(images, heat, **args)
-                self.last_heat_path = write_view_png(image, out_path, encoder="device", renderer=self.renderer_3d)
-                self.renderer_3d.check()
-            else:
-                self.last_heat_path = write_view_png(self.renderer_3d.render_heat_sheet(images, heat, **args), out_path)
-        self._say(f"[Pipeline] heat sheet written to {self.last_heat_path}")
-        return self.last_heat_path
+        """``visualize_img`` (pictures.draw_landmark_view); ``report``: the LandmarkReport of THIS prediction or None."""
+        return pictures.draw_landmark_view(self, mesh, landmarks, report)
 
     def _groupable(self, n_scans: int) -> bool:
         """Can ``n_scans`` scans share one network pass (predict_meshes_device)?"""
@@ -778,7 +567,8 @@ class Pipeline(abc.ABC):
                 out.append((self._report_landmarks(self._to_original(m, landmarks)), err))
             return out
         nl, n = p2.get_lm_count(), int(r3.n_views)
-        per = (nl * 36 + 7) // 8 * 8
+        rp = ResultPack(nl)
+        per = rp.nbytes  # a scan's stride in the shared buffer
         stacks, rots, rot_devs, plans = [], [], [], []
         for j in range(k):  # the host's RNG work first, in the loop's order; uploads while the stream is empty
             ts = pose_fn()
@@ -800,21 +590,18 @@ class Pipeline(abc.ABC):
         pending = []
         with tm.stage("consensus"):
             for j in range(k):
-                seg = pack[j * per:(j + 1) * per]
-                snap_view = seg[: nl * 24].view(torch.float64).view(nl, 3)
-                err_view = seg[nl * 24: nl * 32].view(torch.float64)
-                count_view = seg[nl * 32: nl * 36].view(torch.int32)
+                views = rp.device_views(pack[j * per:(j + 1) * per])
                 mj = maxima[:, j * n:(j + 1) * n].contiguous()
                 starts, ends = e3.lines_device(mj, stacks[j], 256, rot_dev=rot_devs[j])
-                out, _, verify = e3.consensus_device(mj, starts, ends, deferred=True, plan=plans[j], err_out=err_view,
-                                                     count_out=count_view)
-                e3.project_device(meshes[j], out, out=snap_view)
-                pending.append((out, verify, snap_view))
+                out, _, verify = e3.consensus_device(mj, starts, ends, deferred=True, plan=plans[j], err_out=views["error"],
+                                                     count_out=views["counts"])
+                e3.project_device(meshes[j], out, out=views["snapped"])
+                pending.append((out, verify, views["snapped"]))
         results = []
 
         def unpack(host_seg):
-            landmarks = host_seg[: nl * 24].view(np.float64).reshape(nl, 3).copy()
-            return landmarks, e3.mean_error(host_seg[nl * 24: nl * 32].view(np.float64))
+            fetched = rp.host_views(host_seg)
+            return fetched["snapped"].copy(), e3.mean_error(fetched["error"])
 
         def original(j, res):
             return self._to_original(meshes[j], res[0]), res[1]
@@ -824,7 +611,7 @@ class Pipeline(abc.ABC):
             for j in range(k):
                 out, verify, snap_view = pending[j]
                 seg = host[j * per:(j + 1) * per]
-                if verify(counts=seg[nl * 32: nl * 36].view(np.int32)):
+                if verify(counts=rp.host_views(seg)["counts"]):
                     # other survivor counts than planned: this scan's draws + solve were repeated from its saved RNG
                     # state; the RNG now stands where the loop would have it, so the remaining scans go one by one
                     e3.project_device(meshes[j], out, out=snap_view)
@@ -852,9 +639,6 @@ class Pipeline(abc.ABC):
         (``predict_meshes_device``; same results, higher throughput when a scan has few views)."""
         from concurrent.futures import ThreadPoolExecutor
 
-        from ..utils.mesh_io import load_obj
-        from ..utils.render3d import upload_mesh
-
         files = [Path(f) for f in files]
         if self.predictor_2d is None:
             raise ValueError("Predictor2D is not initialized.")
@@ -866,15 +650,8 @@ class Pipeline(abc.ABC):
 
         load_texture = self._texture_needed()
 
-        def ingest(f: Path):
-            if not f.exists():
-                return None
-            mesh = self.renderer_3d.load_mesh(self.renderer_3d._check_file(f), load_texture=load_texture)  # pre-aligned here, uploaded once
-            self._check_cloud(mesh)
-            # device copy from the reader thread too: pinned staging + a copy stream of the library's own, so the
-            # transfer runs beside the current scan's kernels (mvlm_mesh_upload); the renderer waits for its event
-            upload_mesh(self.renderer_3d.ctx, mesh)
-            return mesh
+        def ingest(f: Path):  # (on a reader thread)
+            return self._ingest(f, load_texture) if f.exists() else None
 
         if readers is None:
             readers = min(4, max(1, (os.cpu_count() or 4) // 4))
@@ -895,7 +672,6 @@ class Pipeline(abc.ABC):
                         results = self.predict_meshes_device([m for _, m in group])
                     for (gf, gm), (landmarks, _) in zip(group, results):
                         self._dump_pre_aligned(gm, gf)  # (ingest pre-aligned the scan)
-                        self._rays = None
                         self._after_prediction(gf, landmarks)
                 done = [(gf, landmarks) for (gf, _), (landmarks, _) in zip(group, results)]
                 pool.submit(_drop, [m for _, m in group])
@@ -923,12 +699,7 @@ class Pipeline(abc.ABC):
                     if len(group) == batch_scans or i + 1 == len(files):
                         yield from flush()
                     continue
-                with self._lock:
-                    self._rays = None
-                    self._ray_view, self._keep_ray_view = None, self.visualize_rays_img
-                    with self._timer.stage("total"):
-                        landmarks = self._predict_fused(f, mesh=mesh)
-                    self._after_prediction(f, landmarks)
+                landmarks = self._predict_scan(f, mesh)
                 # returning a scan's 10-25 MB of host arrays to the OS costs milliseconds (page
                 # unmapping under the GPU driver's MMU notifier): let the reader thread drop them
                 # while this thread goes on to the next scan
@@ -1017,22 +788,17 @@ class Pipeline(abc.ABC):
         # a mesh handle that went through the config's pre-align block carries its matrix: results go back to
         # the file's coordinates (the rays kept for visualisation stay in the aligned space, with the mesh handle)
         landmarks = self._to_original(pd, landmarks)
+        report = None
         if arrays is not None:
             kept = np.asarray(valid)
-            self.last_report = LandmarkReport(arrays, landmarks=landmarks,
+            report = self.last_report = LandmarkReport(arrays, landmarks=landmarks,
                                               view_indices=np.nonzero(kept)[0] if kept.dtype == bool else kept)
-        if self.visualize_img:  # behind the report: the spheres carry THIS scan's branches
-            self._draw_landmark_view(pd, drawn, self.last_report if arrays is not None else None)
-        if self.visualize_sheet:
+        if pictures.wanted(self):  # behind the report: the pictures carry THIS scan's branches
             from ..utils.render3d import view_rotations
 
-            self._draw_view_sheet(pd, np.asarray(image_stack, dtype=np.float32),
-                                  np.asarray(landmark_stack, dtype=np.float32), view_rotations(np.asarray(transform_stack)), drawn,
-                                  self.last_report if arrays is not None else None)
-        if self.visualize_heat:
-            self._draw_heat_sheet(pd, np.asarray(image_stack, dtype=np.float32), drawn)
-        if self._keep_ray_view:
-            self._ray_view = (pd, np.asarray(lines_s), np.asarray(lines_e), drawn, self.last_report if arrays is not None else None)
+            pictures.draw(self, pictures.Pass(pd, np.asarray(image_stack, dtype=np.float32), np.asarray(landmark_stack, dtype=np.float32),
+                                              view_rotations(np.asarray(transform_stack)), np.asarray(lines_s), np.asarray(lines_e),
+                                              drawn, report))
         return landmarks
 
     def visualize_image_stack(self, image_stack: np.ndarray, file_name: Path, first_index: int = 0):

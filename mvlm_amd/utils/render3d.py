@@ -272,6 +272,29 @@ class HipRenderer3D:
         return self.random_transform(size=self.n_views)
 
     # ---- rendering --------------------------------------------------------------------
+    def _push_render_mode(self) -> None:
+        """Shading, sub-pixel bits and samples of THIS renderer into the context, when they are not the ones it holds (renderers
+        of one GPU share the context)."""
+        mode = (1 if self.shading == "geometry" else 0, self.subpixel_bits, self.multisamples)
+        if getattr(self.ctx, "_render_mode", None) != mode:
+            self.ctx.check(self.ctx.lib.mvlm_set_render_shading(self.ctx.handle, mode[0]))
+            self.ctx.check(self.ctx.lib.mvlm_set_render_subpixel_bits(self.ctx.handle, mode[1]))
+            self.ctx.check(self.ctx.lib.mvlm_set_render_multisamples(self.ctx.handle, mode[2]))
+            self.ctx._render_mode = mode
+
+    @staticmethod
+    def _view_colours_and_size(colors, nl: int, size) -> tuple:
+        """The landmark and ray views' checks of ``colors`` (None or uint8 [NL,3]) and ``size`` -> (colour table or None, size)."""
+        rgb = None
+        if colors is not None:
+            rgb = np.ascontiguousarray(colors, dtype=np.uint8)
+            if rgb.shape != (nl, 3):
+                raise ValueError(f"colors must be uint8 [{nl},3], not {rgb.shape}")
+        size = int(size)
+        if size < 64 or size > 2048 or size % 16:
+            raise ValueError(f"size must be a multiple of 16 in 64..2048, not {size}")
+        return rgb, size
+
     def render_device(self, mesh: Mesh, transform_stack: np.ndarray, rot: np.ndarray | None = None, out=None):
         """Poses -> torch.float32 [N,256,256,4] on the device (RGB + depth, /255, flipped).
         Only enqueues work; ``check()`` reports a deferred failure after the caller's sync.
@@ -287,12 +310,7 @@ class HipRenderer3D:
         rot = np.ascontiguousarray(view_rotations(transform_stack) if rot is None else rot, dtype=np.float64)
         handle = upload_mesh(self.ctx, mesh)
         self.ctx.bind_current_stream(torch, dev)
-        mode = (1 if self.shading == "geometry" else 0, self.subpixel_bits, self.multisamples)
-        if getattr(self.ctx, "_render_mode", None) != mode:  # (renderers of one GPU share the context)
-            self.ctx.check(self.ctx.lib.mvlm_set_render_shading(self.ctx.handle, mode[0]))
-            self.ctx.check(self.ctx.lib.mvlm_set_render_subpixel_bits(self.ctx.handle, mode[1]))
-            self.ctx.check(self.ctx.lib.mvlm_set_render_multisamples(self.ctx.handle, mode[2]))
-            self.ctx._render_mode = mode
+        self._push_render_mode()
         # (a cloud's refusals - geometry shading, multisampling - are argument errors, said before anything is launched)
         self.ctx.check(self.ctx.lib.mvlm_render(self.ctx.handle, handle, _lib.as_ptr(rot, C.c_double), n,
                                                 C.c_void_p(out.data_ptr())), ValueError if mesh.n_tris == 0 else _lib.MvlmHipError)
@@ -343,26 +361,14 @@ class HipRenderer3D:
 
         poses, frames, lm, radius = self.landmark_view_arguments(mesh, landmarks, poses, frame, radius)
         n, nl = poses.shape[0], lm.shape[0]
-        rgb = None
-        if colors is not None:
-            rgb = np.ascontiguousarray(colors, dtype=np.uint8)
-            if rgb.shape != (nl, 3):
-                raise ValueError(f"colors must be uint8 [{nl},3], not {rgb.shape}")
-        size = int(size)
-        if size < 64 or size > 2048 or size % 16:
-            raise ValueError(f"size must be a multiple of 16 in 64..2048, not {size}")
+        rgb, size = self._view_colours_and_size(colors, nl, size)
         dev = torch.device("cuda", self.ctx.device)
         out = torch.empty((n, size, size, 4), dtype=torch.uint8, device=dev)
         pixels = torch.empty((n, nl), dtype=torch.int32, device=dev) if return_pixels else None
         rot = np.ascontiguousarray(view_rotations(poses), dtype=np.float64)
         handle = upload_mesh(self.ctx, mesh)
         self.ctx.bind_current_stream(torch, dev)
-        mode = (1 if self.shading == "geometry" else 0, self.subpixel_bits, self.multisamples)
-        if getattr(self.ctx, "_render_mode", None) != mode:  # (the view reads the shading and the sub-pixel bits)
-            self.ctx.check(self.ctx.lib.mvlm_set_render_shading(self.ctx.handle, mode[0]))
-            self.ctx.check(self.ctx.lib.mvlm_set_render_subpixel_bits(self.ctx.handle, mode[1]))
-            self.ctx.check(self.ctx.lib.mvlm_set_render_multisamples(self.ctx.handle, mode[2]))
-            self.ctx._render_mode = mode
+        self._push_render_mode()  # (the view reads the shading and the sub-pixel bits)
         self.ctx.check(self.ctx.lib.mvlm_render_landmark_view(
             self.ctx.handle, handle, _lib.as_ptr(rot, C.c_double), n, size, _lib.as_ptr(frames, C.c_float),
             _lib.as_ptr(lm, C.c_double) if nl else None, nl, C.c_float(radius), None if rgb is None or nl == 0 else _lib.as_ptr(rgb, C.c_uint8),
@@ -428,14 +434,7 @@ class HipRenderer3D:
         a, b, ray_radius, rrgb = self.ray_view_arguments(starts, ends, ray_radius, ray_colors)
         poses, frames, lm, radius = self.landmark_view_arguments(mesh, landmarks, poses, frame, radius)
         n, nl, nr = poses.shape[0], lm.shape[0], int(a.shape[0])
-        rgb = None
-        if colors is not None:
-            rgb = np.ascontiguousarray(colors, dtype=np.uint8)
-            if rgb.shape != (nl, 3):
-                raise ValueError(f"colors must be uint8 [{nl},3], not {rgb.shape}")
-        size = int(size)
-        if size < 64 or size > 2048 or size % 16:
-            raise ValueError(f"size must be a multiple of 16 in 64..2048, not {size}")
+        rgb, size = self._view_colours_and_size(colors, nl, size)
         dev = torch.device("cuda", self.ctx.device)
         a_dev = a.to(dev) if hasattr(a, "data_ptr") else torch.from_numpy(a).to(dev)
         b_dev = b.to(dev) if hasattr(b, "data_ptr") else torch.from_numpy(b).to(dev)
@@ -445,12 +444,7 @@ class HipRenderer3D:
         rot = np.ascontiguousarray(view_rotations(poses), dtype=np.float64)
         handle = upload_mesh(self.ctx, mesh)
         self.ctx.bind_current_stream(torch, dev)
-        mode = (1 if self.shading == "geometry" else 0, self.subpixel_bits, self.multisamples)
-        if getattr(self.ctx, "_render_mode", None) != mode:  # (the view reads the shading and the sub-pixel bits)
-            self.ctx.check(self.ctx.lib.mvlm_set_render_shading(self.ctx.handle, mode[0]))
-            self.ctx.check(self.ctx.lib.mvlm_set_render_subpixel_bits(self.ctx.handle, mode[1]))
-            self.ctx.check(self.ctx.lib.mvlm_set_render_multisamples(self.ctx.handle, mode[2]))
-            self.ctx._render_mode = mode
+        self._push_render_mode()  # (the view reads the shading and the sub-pixel bits)
         self.ctx.check(self.ctx.lib.mvlm_render_ray_view(
             self.ctx.handle, handle, _lib.as_ptr(rot, C.c_double), n, size, _lib.as_ptr(frames, C.c_float),
             _lib.as_ptr(lm, C.c_double) if nl else None, nl, C.c_float(radius), None if rgb is None or nl == 0 else _lib.as_ptr(rgb, C.c_uint8),

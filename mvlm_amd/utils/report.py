@@ -18,13 +18,25 @@ from pathlib import Path
 
 import numpy as np
 
-__all__ = ["LandmarkReport", "ReportLayout", "CSV_HEADER", "texel"]
+__all__ = ["LandmarkReport", "ReportLayout", "ResultPack", "CSV_HEADER", "texel"]
 
 N_STATS = 9  # MVLM_REPORT_STATS: rms, max_dist, sigma2, cov xx yy zz xy xz yz
 VIEW_KEPT, VIEW_DRAWN, VIEW_INLIER, VIEW_USED = 1, 2, 4, 8  # MVLM_VIEW_* (include/mvlm_hip.h)
 # the ray view's colours by what the consensus did with a view's ray (LandmarkReport.ray_colours)
 RAY_USED, RAY_KEPT, RAY_FILTERED = (26, 230, 26), (255, 165, 0), (160, 160, 160)
 CSV_HEADER = "index,x,y,z,n_kept,n_inliers,n_used,branch,error,rms,sigma,snap_dist,tri,b0,b1,b2,u,v"
+
+
+def _device_views(fields: dict, buf) -> dict:
+    """{name: (offset, bytes, dtype, shape)} over a uint8 device tensor -> {name: typed tensor view} (no copies)."""
+    import torch
+
+    kinds = {"f8": torch.float64, "i4": torch.int32, "f4": torch.float32, "u1": torch.uint8}
+    views = {}
+    for name, (off, nb, dt, shape) in fields.items():
+        flat = buf[off: off + nb].view(kinds[dt.str[1:]])
+        views[name] = flat if len(shape) == 1 else flat.view(shape)  # (on the hot path: no second view where [NL] is the shape)
+    return views
 
 
 class ReportLayout:
@@ -48,14 +60,44 @@ class ReportLayout:
 
     def device_views(self, buf) -> dict:
         """uint8 device tensor (8-byte aligned, at least ``nbytes`` long) -> {name: typed tensor view}."""
-        import torch
-
-        kinds = {"f8": torch.float64, "i4": torch.int32, "f4": torch.float32, "u1": torch.uint8}
-        return {name: buf[off: off + nb].view(kinds[dt.str[1:]]).view(shape) for name, (off, nb, dt, shape) in self.fields.items()}
+        return _device_views(self.fields, buf)
 
     def host_arrays(self, host: np.ndarray) -> dict:
         """The fetched bytes -> {name: array} (copies: the staging buffer is reused by the next call)."""
         return {name: host[off: off + nb].view(dt).reshape(shape).copy() for name, (off, nb, dt, shape) in self.fields.items()}
+
+
+class ResultPack:
+    """Byte offsets of a prediction's result buffer for NL landmarks: ``snapped`` f64 [NL,3] | ``error`` f64 [NL] | ``counts``
+    i32 [NL] (the survivors the RANSAC draws were made for), rounded up to 8 bytes: ``nbytes``, which is also a scan's stride
+    when several scans share one buffer.  With ``n_views`` a report for that many views rides behind it in the same buffer and
+    the same copy: ``report`` (a ``ReportLayout``) starts at ``nbytes``, and ``total`` covers both."""
+
+    FIELDS = (("snapped", np.dtype("f8"), 3), ("error", np.dtype("f8"), 1), ("counts", np.dtype("i4"), 1))
+
+    def __init__(self, n_landmarks: int, n_views: int | None = None):
+        self.nl = int(n_landmarks)
+        self.fields, off = {}, 0
+        for name, dt, width in self.FIELDS:
+            nbytes = self.nl * width * dt.itemsize
+            self.fields[name] = (off, nbytes, dt, (self.nl, width) if width > 1 else (self.nl,))
+            off += nbytes
+        self.nbytes = (off + 7) // 8 * 8
+        self.report = None if n_views is None else ReportLayout(self.nl, n_views)
+        self.total = self.nbytes + (0 if self.report is None else self.report.nbytes)
+
+    def device_views(self, buf) -> dict:
+        """uint8 device tensor (8-byte aligned, at least ``nbytes`` long) -> {name: typed tensor view}."""
+        return _device_views(self.fields, buf)
+
+    def host_views(self, host: np.ndarray) -> dict:
+        """The fetched bytes -> {name: array view}.  Views, not copies: the staging buffer is reused by the next call, so what a
+        caller keeps of them it copies."""
+        return {name: np.ndarray(shape, dt, host, off) for name, (off, nb, dt, shape) in self.fields.items()}
+
+    def report_bytes(self, buf):
+        """The byte range of ``buf`` (device tensor or fetched array) that holds the report."""
+        return buf[self.nbytes: self.total]
 
 
 def texel(u, v, tex_w: int, tex_h: int):

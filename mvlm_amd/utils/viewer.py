@@ -16,22 +16,32 @@ __all__ = ["LandmarkViewer", "RayVisualizer", "RayVisualizerConfig", "view_path"
            "heat_colours", "write_view_png"]
 
 
+def _picture_path(filename, pname: str | None, kind: str) -> Path:
+    suffix = f"_{pname}" if pname else ""
+    return Path("visualization") / f"{Path(filename).stem}{suffix}{kind}.png"
+
+
 def view_path(filename, pname: str | None = None) -> Path:
     """``visualization/<stem>[_<pname>].png`` relative to the working directory (viewer.py:89-92)."""
-    suffix = f"_{pname}" if pname else ""
-    return Path("visualization") / f"{Path(filename).stem}{suffix}.png"
+    return _picture_path(filename, pname, "")
 
 
 def view_sheet_path(filename, pname: str | None = None) -> Path:
     """``visualization/<stem>[_<pname>]_views.png`` relative to the working directory: the view sheet beside the landmark view."""
-    suffix = f"_{pname}" if pname else ""
-    return Path("visualization") / f"{Path(filename).stem}{suffix}_views.png"
+    return _picture_path(filename, pname, "_views")
 
 
 def heat_sheet_path(filename, pname: str | None = None) -> Path:
     """``visualization/<stem>[_<pname>]_heat.png`` relative to the working directory: the heat sheet beside the view sheet."""
-    suffix = f"_{pname}" if pname else ""
-    return Path("visualization") / f"{Path(filename).stem}{suffix}_heat.png"
+    return _picture_path(filename, pname, "_heat")
+
+
+def select_rays(n_landmarks: int, n_views: int, landmark_indices=None, view_indices=None) -> tuple:
+    """The rows (landmarks) and columns (views) of a ray table [NL,N,3] that a caller picked, as two lists: None means all,
+    otherwise every index wraps round (``int(i) % n``: -1 is the last), as the reference's ``RayVisualizer`` takes them."""
+    lm_idx = list(range(n_landmarks)) if landmark_indices is None else [int(i) % n_landmarks for i in landmark_indices]
+    v_idx = list(range(n_views)) if view_indices is None else [int(i) % n_views for i in view_indices]
+    return lm_idx, v_idx
 
 
 # The heat sheet's default colours, cycled over the landmark index: neighbouring landmarks, whose blobs lie side by side, differ.
@@ -84,6 +94,21 @@ def write_view_png(image, out_path, encoder: str = "host", renderer=None):
     return out_path
 
 
+def render_to_png(renderer, kind: str, encoder: str, out, *args, first: bool = False, **kw) -> tuple:
+    """``renderer.render_<kind>(*args, **kw)`` into the file ``out`` (a list: one file per picture) by the encoder asked for ->
+    (pictures, what ``write_view_png`` returned).  "device": ``render_<kind>_device`` leaves the pictures on the device and one
+    encode call makes all the files; ``first``: the call returns a stack of which the first picture is the one meant."""
+    device = check_png_encoder(encoder) == "device"
+    images = getattr(renderer, f"render_{kind}_device" if device else f"render_{kind}")(*args, **kw)
+    if first:
+        images = images[0]
+    if device:
+        written = write_view_png(images, out, encoder="device", renderer=renderer)
+        renderer.check()
+        return images, written
+    return images, [write_view_png(im, q) for im, q in zip(images, out)] if isinstance(out, list) else write_view_png(images, out)
+
+
 class LandmarkViewer:
     def __init__(self, filename, landmarks: np.ndarray | None = None, pname: str | None = None, save: bool = True,
                  size: int = 1024, device: int = 0, encoder: str = "host") -> None:
@@ -98,14 +123,12 @@ class LandmarkViewer:
         self.size = int(size)
         renderer = HipRenderer3D(n_views=1, device=device, verbose=False)
         mesh = load_mesh(self.filename)
-        if check_png_encoder(encoder) == "device":  # the picture stays on the device; ``image`` is read back on demand only
-            self.image_device = renderer.render_landmark_view_device(mesh, landmarks, size=self.size)[0]
-            self.out_path = write_view_png(self.image_device, view_path(self.filename, pname), encoder="device", renderer=renderer)
-            renderer.check()
-            self.image = None
+        image, self.out_path = render_to_png(renderer, "landmark_view", encoder, view_path(self.filename, pname), mesh, landmarks,
+                                             first=True, size=self.size)
+        if encoder == "device":  # the picture stays on the device; ``image`` is read back on demand only
+            self.image_device, self.image = image, None
         else:
-            self.image = renderer.render_landmark_view(mesh, landmarks, size=self.size)[0]
-            self.out_path = write_view_png(self.image, view_path(self.filename, pname))
+            self.image = image
 
 
 def colour_byte(c: float) -> int:
@@ -154,8 +177,7 @@ class RayVisualizer:
         starts, ends = np.asarray(line_starts, dtype=np.float64), np.asarray(line_ends, dtype=np.float64)
         if starts.ndim != 3 or starts.shape[-1] != 3 or starts.shape != ends.shape:
             raise ValueError(f"line_starts and line_ends must both be [NL,N,3], not {starts.shape} and {ends.shape}")
-        lm_idx = list(range(starts.shape[0])) if landmark_indices is None else [int(i) % starts.shape[0] for i in landmark_indices]
-        v_idx = list(range(starts.shape[1])) if view_indices is None else [int(i) % starts.shape[1] for i in view_indices]
+        lm_idx, v_idx = select_rays(starts.shape[0], starts.shape[1], landmark_indices, view_indices)
         fs = np.ascontiguousarray(starts[np.ix_(lm_idx, v_idx)])
         fe = np.ascontiguousarray(ends[np.ix_(lm_idx, v_idx)])
         if clip_to_mesh and fs.size:
@@ -163,17 +185,12 @@ class RayVisualizer:
         renderer = HipRenderer3D(n_views=1, device=self.device, verbose=False)
         nl = 0 if landmarks is None else len(np.asarray(landmarks).reshape(-1, 3))
         nr = fs.reshape(-1, 3).shape[0]
-        device = check_png_encoder(cfg.encoder) == "device"
-        draw = renderer.render_ray_view_device if device else renderer.render_ray_view
-        self.images = draw(
+        folder = Path(screenshot_dir) if screenshot_dir else Path("visualization") / "ray_screenshots"
+        stem = Path(obj_path or getattr(mesh, "path", None) or "mesh.obj").stem
+        # (``images`` stays the device tensor [n,S,S,4] under the "device" encoder)
+        self.images, paths = render_to_png(
+            renderer, "ray_view", cfg.encoder, [folder / f"{stem}_rays_{i}.png" for i in range(len(np.reshape(cfg.poses, (-1, 3))))],
             mesh, landmarks, fs, fe, poses=cfg.poses, size=cfg.size, radius=cfg.landmark_radius, ray_radius=cfg.ray_radius,
             colors=np.tile(np.array([colour_byte(c) for c in cfg.landmark_color], np.uint8), (nl, 1)) if nl else None,
             ray_colors=np.tile(np.array([colour_byte(c) for c in cfg.ray_color], np.uint8), (nr, 1)) if nr else None)
-        folder = Path(screenshot_dir) if screenshot_dir else Path("visualization") / "ray_screenshots"
-        stem = Path(obj_path or getattr(mesh, "path", None) or "mesh.obj").stem
-        if device:  # (``images`` stays the device tensor [n,S,S,4]; one encode call for all poses)
-            paths = write_view_png(self.images, [folder / f"{stem}_rays_{i}.png" for i in range(len(self.images))], encoder="device",
-                                   renderer=renderer)
-            renderer.check()
-            return paths
-        return [write_view_png(image, folder / f"{stem}_rays_{i}.png") for i, image in enumerate(self.images)]
+        return paths
