@@ -77,6 +77,11 @@ int mvlm_obj_copy(const mvlm_obj* obj, float* verts, float* uvs, int32_t* tris);
  * its colour).  mvlm_obj_copy_colors on a mesh without colours returns MVLM_OBJ_ERR_EMPTY. */
 int mvlm_obj_has_colors(const mvlm_obj* obj, int* has);
 int mvlm_obj_copy_colors(const mvlm_obj* obj, uint8_t* rgb);
+/* per-point normals, where the file carries them (.ply float / double nx ny nz, all three; legacy .vtk POINT_DATA NORMALS):
+ * *has = 1, and normals f32[V,3] receives them as written (not normalised).  A count other than the points' means none; OBJ
+ * "vn" lines are not read.  mvlm_obj_copy_normals on a mesh without normals returns MVLM_OBJ_ERR_EMPTY. */
+int mvlm_obj_has_normals(const mvlm_obj* obj, int* has);
+int mvlm_obj_copy_normals(const mvlm_obj* obj, float* normals);
 void mvlm_obj_free(mvlm_obj* obj);
 /* The reference's legacy multi-format reader (Utils3D.multi_read_surface, utils3d.py:389-423) by file extension:
  * .obj (as above), .ply (ASCII / binary), .stl (ASCII / binary, coincident points merged like vtkSTLReader),
@@ -133,6 +138,31 @@ int mvlm_points_get_stats(mvlm_ctx* ctx, unsigned long long* covered, unsigned l
 /* ms2[0], ms2[1]: milliseconds of the splat and of the tile kernel of the last cloud render made while
  * mvlm_render_set_profiling was on; synchronises the stream. */
 int mvlm_points_stage_ms(mvlm_ctx* ctx, float* ms2);
+/* ---- normals of a point cloud: geometry shading of its splats (csrc/cloud_normals_math.h, DESIGN.md 5.1 "Point clouds") ----
+ * A cloud that HAS normals renders under shading 1: the splat kernel runs unchanged, then a tile kernel of its own writes
+ * shade / 255 into planes 0..2, shade = (int)(|nz| / len * 255 + 0.5) in float64 with nz = (M[6] n.x + M[7] n.y) + M[8] n.z and
+ * len = sqrt((n.x n.x + n.y n.y) + n.z n.z) of the winner's float32 normal n - two-sided, so the sign of n does not matter; 0
+ * where len is zero or not finite; colours are ignored, the depth plane and the background are the texture mode's.  A cloud
+ * WITHOUT normals is still refused under shading 1, as are multisampled clouds.
+ *   mvlm_mesh_upload_normals  normals_host f32[V,3] (a file's nx ny nz; any length) become the cloud's normals; an error on a
+ *                             mesh with triangles or for another count.  Staging, copy stream and ready event of the mesh upload.
+ *   mvlm_mesh_estimate_normals  estimates them on the device and attaches them: per finite point the K = 16 finite points of
+ *                             least (d2, id), itself included, d2 = (dx dx + dy dy) + dz dz in float64; centroid and 3x3
+ *                             covariance in float64, summed in that order; the unit eigenvector of the least eigenvalue (cyclic
+ *                             Jacobi, float64), stored as float32, sign unspecified; (0,0,0) for a non-finite point, fewer than 3
+ *                             neighbours or a zero covariance.  neighbors_dev: NULL, or i32[V,16] on the device that receives
+ *                             each row in ascending (d2, id), unused slots -1, a non-finite point's row all -1.  The result does
+ *                             not depend on the order in which threads or atomics land.  Only enqueues work.
+ *   mvlm_mesh_copy_normals    the device copy's normals -> host f32[V,3]; waits for the stream; an error without normals.
+ *   mvlm_normals_stage_ms     ms3: grid build, search, solve of the last estimate made while mvlm_render_set_profiling was on.
+ *   mvlm_normals_get_stats    measuring hook: with mvlm_points_set_counting on, an estimate runs the search kernel's counting form;
+ *                             stats3 receives what the last such estimate summed over all points: shells walked, candidates
+ *                             tested, candidates that entered a list.  Waits for the stream. */
+int mvlm_mesh_upload_normals(mvlm_ctx* ctx, mvlm_mesh* mesh, const float* normals_host, int n_verts);
+int mvlm_mesh_estimate_normals(mvlm_ctx* ctx, mvlm_mesh* mesh, int32_t* neighbors_dev);
+int mvlm_mesh_copy_normals(mvlm_ctx* ctx, const mvlm_mesh* mesh, float* normals_host);
+int mvlm_normals_stage_ms(mvlm_ctx* ctx, float* ms3);
+int mvlm_normals_get_stats(mvlm_ctx* ctx, unsigned long long* stats3);
 void mvlm_mesh_free(mvlm_ctx* ctx, mvlm_mesh* mesh);
 
 /* ---- JPEG texture decoded on the device (replaces vtkJPEGReader in obj_to_actor, utils3d.py:28-34 / :42-48, and in

@@ -88,6 +88,10 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--point-radius", type=float, default=None, metavar="MM",
                         help="splat radius, in model units, of scans that have points but no faces (point clouds): 0.88 to 9.375, "
                              "i.e. 0.75 to 8 pixels of a view; default: automatic, from the spacing of the points (DESIGN.md 5.1)")
+    parser.add_argument("--point-normals", choices=("file", "estimate"), default="file",
+                        help="where a point cloud's normals come from under a geometry image mode: 'file' takes the scan's own (a "
+                             "cloud without is refused), 'estimate' has the GPU estimate them from each point's 16 nearest neighbours "
+                             "(DESIGN.md 5.1)")
     parser.add_argument("--png-encoder", choices=("host", "device"), default="host",
                         help="who makes the PNG files of --visualize-img and --visualize-rays: 'host' copies the picture to the host "
                              "and encodes it with Pillow; 'device' filters and compresses it on the GPU and copies only the file's "
@@ -148,6 +152,8 @@ def main(argv=None) -> int:
         extra["heat_floor"] = args.heat_floor
     if args.point_radius is not None:
         extra["point_radius"] = args.point_radius
+    if args.point_normals != "file":
+        extra["point_normals"] = args.point_normals
     if args.png_encoder != "host":
         extra["view_png_encoder"] = args.png_encoder
     if args.config is not None:

@@ -36,6 +36,8 @@ SIGNATURES = {
     "mvlm_obj_copy": (C.c_int, [C.c_void_p, c_float_p, c_float_p, c_int32_p]),
     "mvlm_obj_has_colors": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "mvlm_obj_copy_colors": (C.c_int, [C.c_void_p, c_uint8_p]),
+    "mvlm_obj_has_normals": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "mvlm_obj_copy_normals": (C.c_int, [C.c_void_p, c_float_p]),
     "mvlm_obj_free": (None, [C.c_void_p]),
     "mvlm_mesh_upload": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_int, c_int32_p, C.c_int, c_uint8_p,
                                    C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
@@ -46,6 +48,11 @@ SIGNATURES = {
     "mvlm_points_set_counting": (C.c_int, [C.c_void_p, C.c_int]),
     "mvlm_points_stage_ms": (C.c_int, [C.c_void_p, c_float_p]),
     "mvlm_points_get_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "mvlm_mesh_upload_normals": (C.c_int, [C.c_void_p, C.c_void_p, c_float_p, C.c_int]),
+    "mvlm_mesh_estimate_normals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mvlm_mesh_copy_normals": (C.c_int, [C.c_void_p, C.c_void_p, c_float_p]),
+    "mvlm_normals_stage_ms": (C.c_int, [C.c_void_p, c_float_p]),
+    "mvlm_normals_get_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mvlm_mesh_free": (None, [C.c_void_p, C.c_void_p]),
     "mvlm_jpeg_info": (C.c_int, [c_uint8_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_int]),
     "mvlm_mesh_upload_jpeg": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_int, c_int32_p, C.c_int, c_uint8_p, C.c_size_t,

@@ -91,6 +91,8 @@ extern "C" void mvlm_ctx_destroy(mvlm_ctx* ctx) {
         if (e) hipEventDestroy(e);
     for (auto e : ctx->points_events)
         if (e) hipEventDestroy(e);
+    for (auto e : ctx->normals_events)
+        if (e) hipEventDestroy(e);
     for (auto e : ctx->cnn.sync_events)
         if (e) hipEventDestroy(e);
     ctx->cnn.drop_graphs();
@@ -552,6 +554,80 @@ extern "C" int mvlm_mesh_upload_colors(mvlm_ctx* ctx, mvlm_mesh* m, const uint8_
     return 0;
 }
 
+// The buffer a cloud's normals go to (declared in common.h; the caller holds ctx->mu): the mesh's own when it has normals, else
+// one from the mesh pool, which stays the mesh's (normals_buf) and goes back with the others in mvlm_mesh_free.  The caller sets
+// m->normals once the normals are on their way.
+float* mvlm_mesh_normals_buffer(mvlm_ctx* ctx, mvlm_mesh* m) {
+    if (m->normals_buf) return m->normals_buf;
+    if (!ctx->upload_stream && hipStreamCreateWithFlags(&ctx->upload_stream, hipStreamNonBlocking) != hipSuccess) return nullptr;
+    const size_t bytes = size_t(m->n_verts) * 3 * sizeof(float);
+    void* dst = nullptr;
+    size_t cap = 0;
+    hipEvent_t waited = nullptr;
+    if (!take_upload_buffer(ctx, bytes, bytes, &dst, &cap, &waited)) {
+        if (dst) (void)hipFree(dst);  // (the pool's buffer could not be waited for: back to the allocator)
+        if (waited) ctx->event_free.push_back(waited);
+        return nullptr;
+    }
+    // a pooled buffer's previous owner was made to precede the upload stream; the launch stream writes an estimate's normals
+    if (waited && hipStreamWaitEvent(ctx->stream, waited, 0) != hipSuccess) {
+        (void)hipFree(dst);
+        ctx->event_free.push_back(waited);
+        return nullptr;
+    }
+    m->cap[5] = cap;
+    m->waited[5] = waited;
+    m->normals_buf = static_cast<float*>(dst);
+    return m->normals_buf;
+}
+
+// Per-point normals for a point mesh: normals_host f32[V,3] as a file gives them (any length; the shade divides by it) -> the
+// device, through the pinned staging and the upload stream like the colours; the mesh's ready event is recorded again behind the
+// copy.  May run on a reader thread.  A second call, or one after mvlm_mesh_estimate_normals, replaces the normals.
+extern "C" int mvlm_mesh_upload_normals(mvlm_ctx* ctx, mvlm_mesh* m, const float* normals_host, int n_verts) {
+    MVLM_REQUIRE(ctx, m && normals_host, "mesh_upload_normals: null pointer");
+    MVLM_REQUIRE(ctx, m->n_tris == 0, "mesh_upload_normals: the mesh has triangles (normals belong to a point cloud)");
+    MVLM_REQUIRE(ctx, n_verts == m->n_verts, "mesh_upload_normals: " + std::to_string(n_verts) + " normals for a mesh of " +
+                                                  std::to_string(m->n_verts) + " points");
+    const size_t bytes = size_t(n_verts) * 3 * sizeof(float);
+    std::lock_guard<std::mutex> upload_lock(ctx->upload_mu);
+    MVLM_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->upload_stream) MVLM_CHECK_HIP(ctx, hipStreamCreateWithFlags(&ctx->upload_stream, hipStreamNonBlocking));
+    const int slot = ctx->upload_stage_next;
+    ctx->upload_stage_next ^= 1;
+    if (ctx->upload_stage_done[slot]) MVLM_CHECK_HIP(ctx, hipEventSynchronize(ctx->upload_stage_done[slot]));
+    if (ctx->upload_stage_cap[slot] < bytes) {
+        if (ctx->upload_stage[slot]) (void)hipHostFree(ctx->upload_stage[slot]);
+        ctx->upload_stage[slot] = nullptr;
+        ctx->upload_stage_cap[slot] = 0;
+        const size_t cap = (bytes + (size_t(4) << 20)) / (size_t(4) << 20) * (size_t(4) << 20);
+        MVLM_CHECK_HIP(ctx, hipHostMalloc(&ctx->upload_stage[slot], cap, hipHostMallocDefault));
+        ctx->upload_stage_cap[slot] = cap;
+    }
+    std::memcpy(ctx->upload_stage[slot], normals_host, bytes);
+    std::lock_guard<std::mutex> lock(ctx->mu);  // pool, events, the mesh's fields: shared with the launch entry points
+    const bool replacing = m->normals_buf != nullptr;
+    float* const dst = mvlm_mesh_normals_buffer(ctx, m);
+    bool ok = dst != nullptr;
+    if (ok && replacing) {  // a render that was enqueued with the old normals reads them first
+        hipEvent_t e = ctx->take_event();
+        ok = e && hipEventRecord(e, ctx->stream) == hipSuccess && hipStreamWaitEvent(ctx->upload_stream, e, 0) == hipSuccess;
+        if (e) ctx->event_free.push_back(e);
+    }
+    ok = ok && hipMemcpyAsync(dst, ctx->upload_stage[slot], bytes, hipMemcpyHostToDevice, ctx->upload_stream) == hipSuccess;
+    if (ok) {
+        if (!ctx->upload_stage_done[slot]) ctx->upload_stage_done[slot] = ctx->take_event();
+        if (!m->ready) m->ready = ctx->take_event();
+        ok = ctx->upload_stage_done[slot] && m->ready &&
+             hipEventRecord(ctx->upload_stage_done[slot], ctx->upload_stream) == hipSuccess &&
+             hipEventRecord(m->ready, ctx->upload_stream) == hipSuccess;
+    }
+    if (!ok) (void)hipStreamSynchronize(ctx->upload_stream);  // (whatever was enqueued has left the staging slot)
+    if (ok) m->normals = dst;
+    MVLM_REQUIRE(ctx, ok, "mesh_upload_normals: device allocation / copy failed");
+    return 0;
+}
+
 // The splat radius of a point mesh, in model units (raster_points_math.h): admitted from 0.75 to 8 pixels of the 256-pixel window
 // that shows 300 units.  Renders enqueued before the call keep the radius they were launched with.
 extern "C" int mvlm_mesh_set_point_radius(mvlm_ctx* ctx, mvlm_mesh* m, double r_model_units) {
@@ -611,14 +687,14 @@ extern "C" int mvlm_points_stage_ms(mvlm_ctx* ctx, float* ms2) {
 // mesh before the free may still read them.  ctx == NULL (or a pool that is full): plain hipFree (which waits for the device).
 extern "C" void mvlm_mesh_free(mvlm_ctx* ctx, mvlm_mesh* m) {
     if (!m) return;
-    void* bufs[5] = {m->verts, m->uvs, m->tris, m->tex, m->colors};
+    void* bufs[6] = {m->verts, m->uvs, m->tris, m->tex, m->colors, m->normals_buf};
     constexpr size_t POOL_MAX_BYTES = size_t(1) << 30;
     constexpr size_t POOL_MAX_ENTRIES = 32;
-    hipEvent_t spare[6] = {m->ready, m->waited[0], m->waited[1], m->waited[2], m->waited[3], m->waited[4]};
+    hipEvent_t spare[7] = {m->ready, m->waited[0], m->waited[1], m->waited[2], m->waited[3], m->waited[4], m->waited[5]};
     if (ctx) {
         std::lock_guard<std::mutex> lock(ctx->mu);
         (void)hipSetDevice(ctx->device);
-        for (int i = 0; i < 5; ++i)
+        for (int i = 0; i < 6; ++i)
             if (bufs[i] && m->cap[i] && ctx->mesh_pool.size() < POOL_MAX_ENTRIES &&
                 ctx->mesh_pool_bytes + m->cap[i] <= POOL_MAX_BYTES) {
                 hipEvent_t ev = ctx->take_event();

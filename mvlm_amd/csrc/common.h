@@ -266,6 +266,8 @@ struct mvlm_mesh {
     int32_t* tris = nullptr;  // [T,3]
     uint8_t* tex = nullptr;   // [H,W,3] or null
     uint8_t* colors = nullptr;  // [V,4] per-vertex r g b 255 (one aligned 4-byte load per vertex) or null: mvlm_mesh_upload_colors
+    float* normals = nullptr;   // [V,3] per-point normals of a cloud or null: mvlm_mesh_upload_normals, mvlm_mesh_estimate_normals
+    float* normals_buf = nullptr;  // the buffer they live in, allocated on first use (api.hip: mvlm_mesh_normals_buffer); normals is it or null
     int n_verts = 0, n_tris = 0, tex_h = 0, tex_w = 0;
     // a point mesh (n_tris == 0, tris == null; raster_points_math.h): the splat radius in model units, the same in lattice
     // steps and the paraboloid's coefficient - the automatic radius at upload, mvlm_mesh_set_point_radius replaces it
@@ -273,11 +275,11 @@ struct mvlm_mesh {
     int32_t point_R = 0;
     float point_c = 0.f;
     unsigned long long uid = 0;  // unique per upload (an address can be recycled): key of per-mesh derived data a context keeps
-    size_t cap[5] = {0, 0, 0, 0, 0};  // allocation sizes of verts / uvs / tris / tex / colors (for the ctx's mesh pool)
+    size_t cap[6] = {0, 0, 0, 0, 0, 0};  // allocation sizes of verts / uvs / tris / tex / colors / normals (for the ctx's mesh pool)
     // recorded on the context's upload stream behind the host-to-device copies (again behind the colours' copy, when they
     // follow); every consumer's stream waits for it
     hipEvent_t ready = nullptr;
-    hipEvent_t waited[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // "previous owner is done" events of recycled buffers
+    hipEvent_t waited[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // "previous owner is done" events of recycled buffers
 };
 
 struct RenderProfileRec {
@@ -360,6 +362,9 @@ struct mvlm_ctx {
     // under render profiling, round the two kernels of a cloud's render: before the splats, between, behind the tile stage
     std::vector<hipEvent_t> points_events;
     bool points_events_valid = false;
+    // likewise round the three stages of a cloud's normal estimate (cloud_normals.hip: grid build, search, solve; mvlm_normals_stage_ms)
+    std::vector<hipEvent_t> normals_events;
+    bool normals_events_valid = false;
     bool render_profiling = false;        // mvlm_render_set_profiling: HIP events around each render's kernels
     std::vector<RenderProfileRec> render_prof;
     std::vector<hipEvent_t> render_events;
@@ -522,6 +527,10 @@ int mvlm_project_partials(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* pt
 int mvlm_points_nearest(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* pts_dev, int n_points, double* out_dev);
 // raster_points.hip: the automatic splat radius of a cloud (host only; exported, include/mvlm_hip.h)
 extern "C" int mvlm_points_auto_radius(const float* verts, int n, double* r_out);
+
+// api.hip: the buffer a cloud's normals go to, f32[V,3] - the mesh's own when it has normals already, else one from the mesh pool
+// (recorded in cap[5] / waited[5]; the caller sets mesh->normals once the normals are on their way).  The caller holds ctx->mu.
+float* mvlm_mesh_normals_buffer(mvlm_ctx* ctx, mvlm_mesh* mesh);
 
 // small kernels (misc.hip)
 int mvlm_launch_pack_input(mvlm_ctx* ctx, const float* images, int n, const int* sel4, int c, float* out);

@@ -10,6 +10,7 @@ struct mvlm_obj {
     std::vector<int32_t> tris;  // [T,3]
     int64_t n_positions = 0;
     std::vector<uint8_t> colors;  // [V,3] per-point r g b (PLY red green blue, VTK COLOR_SCALARS, OBJ "v x y z r g b") or empty
+    std::vector<float> normals;   // [V,3] per-point normals as written (PLY nx ny nz, VTK POINT_DATA NORMALS) or empty
 };
 
 // A colour channel written as a float in [0,1] (ASCII .vtk COLOR_SCALARS, OBJ "v x y z r g b") -> its byte: clamped, rounded

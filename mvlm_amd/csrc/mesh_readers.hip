@@ -7,12 +7,13 @@
 //
 //   .ply  ASCII and binary little/big endian; element vertex with x y z (+ s t | u v | texture_u texture_v, + uchar
 //         red green blue | diffuse_red diffuse_green diffuse_blue: per-point colours; another type: no colours; an alpha
-//         is skipped), element face with a list property (vertex_indices | vertex_index); other elements / properties skipped
+//         is skipped, + float | double nx ny nz: per-point normals; one missing or of an integer type: no normals), element face with a list property (vertex_indices | vertex_index); other elements / properties skipped
 //   .stl  ASCII and binary; vtkSTLReader merges coincident points (Merging is on by default): vertices with
 //         bit-identical coordinates share one point, numbered in order of first appearance
 //   .vtk  legacy POLYDATA, ASCII and BINARY (big endian): POINTS, POLYGONS, TRIANGLE_STRIPS,
 //         POINT_DATA TEXTURE_COORDINATES <name> 2 <type> and COLOR_SCALARS <name> 3|4 (per-point colours: bytes in a
-//         BINARY file, floats in [0,1] in an ASCII one); the 5.x OFFSETS / CONNECTIVITY form of POLYGONS too
+//         BINARY file, floats in [0,1] in an ASCII one) and NORMALS <name> <type> (per-point normals); the 5.x OFFSETS /
+//         CONNECTIVITY form of POLYGONS too
 //   .wrl  VRML 2.0 IndexedFaceSet: Coordinate point [], coordIndex [], TextureCoordinate point [],
 //         texCoordIndex [] (a point used with several texture coordinates is duplicated, like OBJ corners);
 //         the last IndexedFaceSet of the file wins (utils3d.py:401: GetActors().GetLastActor()); Color nodes are not read
@@ -253,11 +254,12 @@ int read_ply(const std::vector<char>& data, mvlm_obj* o, std::string* msg) {
     const bool swap = format != 0 && ((format == 1) != host_is_little_endian());
     std::vector<float> uv;
     std::vector<uint8_t> col;
+    std::vector<float> nrm;
     std::vector<long long> ids;
     for (const PlyElem& e : elems) {
         const bool is_vertex = e.name == "vertex", is_face = e.name == "face";
         int ix = -1, iy = -1, iz = -1, iu = -1, iv = -1, ilist = -1;
-        int irgb[3] = {-1, -1, -1}, idiffuse[3] = {-1, -1, -1};
+        int irgb[3] = {-1, -1, -1}, idiffuse[3] = {-1, -1, -1}, inrm[3] = {-1, -1, -1};
         for (int k = 0; k < int(e.props.size()); ++k) {
             const std::string& n = e.props[size_t(k)].name;
             if (is_vertex && !e.props[size_t(k)].is_list) {
@@ -272,6 +274,9 @@ int read_ply(const std::vector<char>& data, mvlm_obj* o, std::string* msg) {
                 else if (n == "diffuse_red") idiffuse[0] = k;
                 else if (n == "diffuse_green") idiffuse[1] = k;
                 else if (n == "diffuse_blue") idiffuse[2] = k;
+                else if (n == "nx") inrm[0] = k;
+                else if (n == "ny") inrm[1] = k;
+                else if (n == "nz") inrm[2] = k;
             }
             if (is_face && e.props[size_t(k)].is_list && (n == "vertex_indices" || n == "vertex_index")) ilist = k;
         }
@@ -283,16 +288,22 @@ int read_ply(const std::vector<char>& data, mvlm_obj* o, std::string* msg) {
             for (int k = 0; k < 3; ++k) irgb[k] = idiffuse[k];
         bool want_col = is_vertex;
         for (int k = 0; k < 3; ++k) want_col = want_col && irgb[k] >= 0 && e.props[size_t(irgb[k])].type == P_U8;
+        // per-point normals: nx ny nz, all three of a float type - an integer normal has no agreed scale and means "no normals"
+        bool want_nrm = is_vertex;
+        for (int k = 0; k < 3; ++k)
+            want_nrm = want_nrm && inrm[k] >= 0 && (e.props[size_t(inrm[k])].type == P_F32 || e.props[size_t(inrm[k])].type == P_F64);
         if (is_vertex) {
             // a count the file cannot possibly hold must not drive an allocation
             if (e.count > int64_t(data.size())) { *msg = "PLY vertex count exceeds the file size"; return MVLM_OBJ_ERR_SYNTAX; }
             o->verts.reserve(size_t(e.count) * 3);
             if (want_uv) uv.reserve(size_t(e.count) * 2);
             if (want_col) col.reserve(size_t(e.count) * 3);
+            if (want_nrm) nrm.reserve(size_t(e.count) * 3);
         }
         for (long long r = 0; r < e.count; ++r) {
             double vals[5] = {0, 0, 0, 0, 0};
             uint8_t rgb[3] = {0, 0, 0};
+            float nv[3] = {0.f, 0.f, 0.f};
             for (int k = 0; k < int(e.props.size()); ++k) {
                 const PlyProp& pr = e.props[size_t(k)];
                 long long n = 1;
@@ -328,6 +339,8 @@ int read_ply(const std::vector<char>& data, mvlm_obj* o, std::string* msg) {
                         else if (k == iv) vals[4] = v;
                         else if (want_col && (k == irgb[0] || k == irgb[1] || k == irgb[2]))  // (uchar: 0..255 in a binary file)
                             rgb[k == irgb[0] ? 0 : k == irgb[1] ? 1 : 2] = uint8_t(v >= 255.0 ? 255 : v > 0.0 ? int(v) : 0);
+                        else if (want_nrm && (k == inrm[0] || k == inrm[1] || k == inrm[2]))
+                            nv[k == inrm[0] ? 0 : k == inrm[1] ? 1 : 2] = float(v);
                     }
                 }
             }
@@ -340,6 +353,7 @@ int read_ply(const std::vector<char>& data, mvlm_obj* o, std::string* msg) {
                     uv.push_back(float(vals[4]));
                 }
                 if (want_col) col.insert(col.end(), rgb, rgb + 3);
+                if (want_nrm) nrm.insert(nrm.end(), nv, nv + 3);
             } else if (is_face && ilist >= 0 && ids.size() >= 3) {
                 for (long long id : ids)
                     if (id < 0 || id >= MAX_ELEMS) { *msg = "PLY face references a vertex that does not exist"; return MVLM_OBJ_ERR_INDEX; }
@@ -349,6 +363,7 @@ int read_ply(const std::vector<char>& data, mvlm_obj* o, std::string* msg) {
     }
     o->uvs.swap(uv);
     o->colors.swap(col);
+    o->normals.swap(nrm);
     return 0;
 }
 
@@ -598,7 +613,17 @@ int read_vtk(const std::vector<char>& data, mvlm_obj* o, std::string* msg) {
                     }
             }
         }
-        // every other keyword (VERTICES, LINES, SCALARS, NORMALS, ...): its values are skipped as tokens, which is
+        // per-point normals: "NORMALS <name> <type>", then three numbers per point
+        else if (kw == "normals" && point_data) {
+            std::string name, type;
+            if (!sc.word(&name) || !sc.word(&type) || n_points < 0 || !vtk_values(&sc, binary, type, n_points * 3, &vals)) {
+                *msg = "bad VTK NORMALS";
+                return MVLM_OBJ_ERR_SYNTAX;
+            }
+            o->normals.resize(vals.size());
+            for (size_t i = 0; i < vals.size(); ++i) o->normals[i] = float(vals[i]);
+        }
+        // every other keyword (VERTICES, LINES, SCALARS, cell NORMALS, ...): its values are skipped as tokens, which is
         // safe for ASCII; an unknown BINARY block would desynchronise the scan, so stop at the first one
         else if (binary && (kw == "vertices" || kw == "lines" || kw == "scalars" || kw == "normals" || kw == "vectors" ||
                             kw == "color_scalars" || kw == "field" || kw == "lookup_table" || kw == "tensors")) {
@@ -791,6 +816,7 @@ extern "C" int mvlm_mesh_read(const char* path, mvlm_obj** out, char* err, int e
     }
     if (!rc && !o->uvs.empty() && o->uvs.size() != size_t(n_points) * 2) o->uvs.clear();  // partial texture coordinates: none
     if (!rc && !o->colors.empty() && o->colors.size() != size_t(n_points) * 3) o->colors.clear();  // (likewise)
+    if (!rc && !o->normals.empty() && o->normals.size() != size_t(n_points) * 3) o->normals.clear();  // (likewise)
     if (rc) {
         delete o;
         set_err(err, err_len, std::string("File ") + path + ": " + msg);

@@ -532,4 +532,17 @@ extern "C" int mvlm_obj_copy_colors(const mvlm_obj* obj, uint8_t* rgb) {
     return 0;
 }
 
+extern "C" int mvlm_obj_has_normals(const mvlm_obj* obj, int* has) {
+    if (!obj || !has) return MVLM_OBJ_ERR_ARGS;
+    *has = !obj->normals.empty() && obj->normals.size() == obj->verts.size() ? 1 : 0;
+    return 0;
+}
+
+extern "C" int mvlm_obj_copy_normals(const mvlm_obj* obj, float* normals) {
+    if (!obj || !normals) return MVLM_OBJ_ERR_ARGS;
+    if (obj->normals.empty() || obj->normals.size() != obj->verts.size()) return MVLM_OBJ_ERR_EMPTY;
+    memcpy(normals, obj->normals.data(), obj->normals.size() * sizeof(float));
+    return 0;
+}
+
 extern "C" void mvlm_obj_free(mvlm_obj* obj) { delete obj; }

@@ -192,8 +192,10 @@ extern "C" int mvlm_render(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* r
     // A point mesh (n_tris == 0) is drawn as splats by the kernels of raster_points.hip; what it does not have is refused here,
     // before anything is enqueued.
     const bool cloud = mesh->n_tris == 0;
-    MVLM_REQUIRE(ctx, !cloud || ctx->render_shading == 0,
-                 "render: geometry shading of a point cloud is not supported (it needs normals, a cloud has none)");
+    // (with normals - a file's, or estimated: point_normals="estimate" / mvlm_mesh_estimate_normals - a cloud is geometry-shaded)
+    MVLM_REQUIRE(ctx, !cloud || ctx->render_shading == 0 || mesh->normals,
+                 "render: geometry shading of a point cloud is not supported without normals (this cloud has none: upload a file's, "
+                 "or have them estimated - point_normals=\"estimate\", mvlm_mesh_estimate_normals)");
     MVLM_REQUIRE(ctx, !cloud || ctx->render_multisamples == 0, "render: multisampled rendering of a point cloud is not supported");
     MVLM_REQUIRE(ctx, !cloud || n_views <= 65535, "render: at most 65535 views of a point cloud per call");
     if (mvlm_mesh_wait_ready(ctx, mesh, ctx->stream)) return 1;  // the upload runs on a stream of its own
@@ -255,8 +257,15 @@ extern "C" int mvlm_render(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* r
             MVLM_CHECK_HIP(ctx, hipEventRecord(pev[0], ctx->stream));
         }
         // per-point colours shade the RGB planes (white without them); a texture or uvs on a faceless mesh are ignored
-        raster_points_launch(ctx->stream, mesh->verts, mesh->colors, V, rot, n_views, ctx->render_subpixel_bits, mesh->point_R,
-                             mesh->point_c, keys, point_stats, overflow_host, out_dev, pev ? pev[1] : nullptr);
+        if (ctx->render_shading == 1) {  // the same splats, then the tile stage that shades with the normals (cloud_normals.hip)
+            raster_points_splat_launch(ctx->stream, mesh->verts, V, rot, n_views, ctx->render_subpixel_bits, mesh->point_R, mesh->point_c,
+                                       keys, point_stats);
+            if (pev) (void)hipEventRecord(pev[1], ctx->stream);
+            cloud_normals_tile_launch(ctx->stream, mesh->normals, rot, n_views, keys, overflow_host, out_dev);
+        } else {
+            raster_points_launch(ctx->stream, mesh->verts, mesh->colors, V, rot, n_views, ctx->render_subpixel_bits, mesh->point_R,
+                                 mesh->point_c, keys, point_stats, overflow_host, out_dev, pev ? pev[1] : nullptr);
+        }
         if (pev) {
             MVLM_CHECK_HIP(ctx, hipEventRecord(pev[2], ctx->stream));
             ctx->points_events_valid = true;

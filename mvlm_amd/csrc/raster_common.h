@@ -92,5 +92,12 @@ void raster_vc_tile(hipStream_t stream, int samples, const void* tv, const int32
 void raster_points_launch(hipStream_t stream, const float* verts, const uint8_t* colors, int n_points, const double* rot,
                           int n_views, int sub_bits, int R, float c, unsigned long long* keys, unsigned long long* stats,
                           int* overflow_host, float* out, hipEvent_t between);
+// The first of those two kernels alone, for a render whose tile stage is another one (cloud_normals.hip).
+void raster_points_splat_launch(hipStream_t stream, const float* verts, int n_points, const double* rot, int n_views, int sub_bits,
+                                int R, float c, unsigned long long* keys, unsigned long long* stats);
+// The tile stage of a cloud's geometry-shaded render (cloud_normals.hip): key, EMPTY hand-back, depth byte, flip and overflow word as
+// the points' tile kernel, planes 0..2 the two-sided shade of the winner's normal (cloud_normals_math.h); `normals` f32[n_points,3].
+void cloud_normals_tile_launch(hipStream_t stream, const float* normals, const double* rot, int n_views, unsigned long long* keys,
+                               int* overflow_host, float* out);
 
 #endif

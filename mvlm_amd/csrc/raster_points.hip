@@ -88,14 +88,19 @@ __global__ __launch_bounds__(256) void points_tile_kernel(const uchar4* __restri
 
 }  // namespace
 
-void raster_points_launch(hipStream_t stream, const float* verts, const uint8_t* colors, int n_points, const double* rot,
-                          int n_views, int sub_bits, int R, float c, unsigned long long* keys, unsigned long long* stats,
-                          int* overflow_host, float* out, hipEvent_t between) {
+void raster_points_splat_launch(hipStream_t stream, const float* verts, int n_points, const double* rot, int n_views, int sub_bits,
+                                int R, float c, unsigned long long* keys, unsigned long long* stats) {
     const dim3 grid(unsigned((n_points + 255) / 256), unsigned(n_views));
     if (stats)
         hipLaunchKernelGGL(points_splat_kernel<true>, grid, dim3(256), 0, stream, verts, n_points, rot, sub_bits, R, c, keys, stats);
     else
         hipLaunchKernelGGL(points_splat_kernel<false>, grid, dim3(256), 0, stream, verts, n_points, rot, sub_bits, R, c, keys, stats);
+}
+
+void raster_points_launch(hipStream_t stream, const float* verts, const uint8_t* colors, int n_points, const double* rot,
+                          int n_views, int sub_bits, int R, float c, unsigned long long* keys, unsigned long long* stats,
+                          int* overflow_host, float* out, hipEvent_t between) {
+    raster_points_splat_launch(stream, verts, n_points, rot, n_views, sub_bits, R, c, keys, stats);
     if (between) (void)hipEventRecord(between, stream);
     const size_t n_pixels = size_t(n_views) * RM_SIZE * RM_SIZE;
     hipLaunchKernelGGL(points_tile_kernel, dim3(unsigned((n_pixels + 255) / 256)), dim3(256), 0, stream,

@@ -100,7 +100,8 @@ class Pipeline(abc.ABC):
                  visualize_img: bool = False, visualize_size: int = 1024, visualize_name: str | None = None,
                  visualize_rays_img: bool = False, visualize_rays_poses=((0, 0, 0), (0, 60, 0), (0, -60, 0)),
                  view_png_encoder: str = "host", point_radius: float | None = None, visualize_sheet: bool = False,
-                 sheet_scale: int = 1, visualize_heat: bool = False, heat_landmarks=None, heat_floor: float = 0.25):
+                 sheet_scale: int = 1, visualize_heat: bool = False, heat_landmarks=None, heat_floor: float = 0.25,
+                 point_normals: str = "file"):
         self.render_image_stack = render_image_stack
         self.render_image_folder = render_image_folder
         self.n_views = n_views
@@ -151,8 +152,11 @@ class Pipeline(abc.ABC):
                 torch.cuda.set_device(device)
         # render_multisamples: samples per pixel of the renderer (HipRenderer3D.multisamples: 0 or 4)
         # point_radius: splat radius (model units) of scans without faces - point clouds -, None = automatic (HipRenderer3D)
+        # point_normals: where a point cloud's normals come from under a geometry image mode: "file" (its own, else refused) or
+        # "estimate" (a cloud without gets them estimated on the device) (HipRenderer3D)
         self.renderer_3d = HipRenderer3D(image_size=(256, 256), offscreen=offscreen, n_views=n_views, device=device,
-                                         verbose=verbose, multisamples=render_multisamples, point_radius=point_radius)
+                                         verbose=verbose, multisamples=render_multisamples, point_radius=point_radius,
+                                         point_normals=point_normals)
         self.estimator_3d = HipEstimator3D(device=device, verbose=verbose)
         self.predictor_2d = None  # will be assigned externally
 
@@ -199,8 +203,11 @@ class Pipeline(abc.ABC):
         r3 = self.renderer_3d
         if getattr(r3, "multisamples", 0):
             raise ValueError(f"{name} is a point cloud: multisampled rendering (render_multisamples=4) is not supported")
-        if getattr(r3, "shading", "texture") == "geometry":
-            raise ValueError(f"{name} is a point cloud: a geometry image mode is not supported (geometry shading needs normals)")
+        # geometry shading needs normals: the cloud's own (a .ply's nx ny nz, a .vtk's NORMALS), or the device's estimate
+        if (getattr(r3, "shading", "texture") == "geometry" and getattr(mesh, "normals", None) is None
+                and getattr(r3, "point_normals", "file") != "estimate"):
+            raise ValueError(f"{name} is a point cloud without normals: a geometry image mode needs them (geometry shading of a point "
+                             'cloud: point_normals="estimate" / --point-normals estimate has them estimated)')
 
     def _to_original(self, mesh, landmarks):
         """Landmarks found on a pre-aligned mesh -> the file's own coordinates (utils3d.py:505-527)."""

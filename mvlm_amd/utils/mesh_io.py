@@ -44,6 +44,11 @@ class Mesh:
     # 5.1, "Point clouds").  The splat radius in model units, 0.75 to 8 pixels of the 256-pixel window over 300 units
     # (0.879 .. 9.375); None = the automatic one, from the spacing of the uploaded points.  Ignored on a mesh with triangles.
     point_radius: float | None = None
+    # [V,3] float32, one normal per point, of any length (.ply nx ny nz, legacy .vtk POINT_DATA NORMALS; OBJ "vn" lines are not
+    # read).  A point cloud that has them is geometry-shaded with them (|n.z| / |n| in view space, two-sided); a cloud without can
+    # have them estimated on the device (HipRenderer3D(point_normals="estimate"), estimate_point_normals), which fills this
+    # field.  A mesh with triangles keeps them and renders as ever: its geometry plane comes from the triangles.
+    normals: np.ndarray | None = None
 
     @property
     def n_verts(self) -> int:
@@ -149,9 +154,10 @@ def _read_texture(jpg: Path):
         return None
 
 
-def _read_obj_native(path: Path, any_format: bool = False):
+def _read_obj_native(path: Path, any_format: bool = False, with_normals: bool = False):
     """Parse with the library's readers: mvlm_obj_read (mvlm_amd/csrc/obj_reader.hip) or, with ``any_format``,
-    mvlm_mesh_read (mesh_readers.hip: .obj .ply .stl .vtk .wrl by extension)."""
+    mvlm_mesh_read (mesh_readers.hip: .obj .ply .stl .vtk .wrl by extension).  -> (verts, tris, uvs, colors), and with
+    ``with_normals`` a fifth entry, the file's per-point normals float32 [V,3] or None."""
     import ctypes as C
 
     from .. import _lib
@@ -176,9 +182,16 @@ def _read_obj_native(path: Path, any_format: bool = False):
         colors = np.empty((nv.value, 3), np.uint8) if has_col.value else None
         if colors is not None and lib.mvlm_obj_copy_colors(handle, _lib.as_ptr(colors, C.c_uint8)) != 0:
             colors = None
+        normals = None
+        if with_normals:
+            has_nrm = C.c_int(0)
+            lib.mvlm_obj_has_normals(handle, C.byref(has_nrm))
+            normals = np.empty((nv.value, 3), np.float32) if has_nrm.value else None
+            if normals is not None and lib.mvlm_obj_copy_normals(handle, _lib.as_ptr(normals, C.c_float)) != 0:
+                normals = None
     finally:
         lib.mvlm_obj_free(handle)
-    return verts, tris, uvs, colors
+    return (verts, tris, uvs, colors, normals) if with_normals else (verts, tris, uvs, colors)
 
 
 def _read_obj_python(path: Path):
@@ -295,12 +308,12 @@ def load_mesh(path: Union[Path, str], load_texture: bool = True, texture_file_na
             tex_job = threading.Thread(target=lambda: box.__setitem__(0, _read_texture(tex_path)), daemon=True)
             tex_job.start()
     try:
-        verts, tris, uvs, colors = _read_obj_native(path, any_format=True)
+        verts, tris, uvs, colors, normals = _read_obj_native(path, any_format=True, with_normals=True)
     finally:
         if tex_job is not None:
             tex_job.join()
     texture = box[0] if uvs is not None else None
-    return Mesh(verts, tris, uvs, texture, path, texture_jpeg=jpeg_bytes if uvs is not None else None, colors=colors)
+    return Mesh(verts, tris, uvs, texture, path, texture_jpeg=jpeg_bytes if uvs is not None else None, colors=colors, normals=normals)
 
 
 def write_obj(path: Union[Path, str], verts: np.ndarray, tris: np.ndarray, uvs: np.ndarray | None = None,

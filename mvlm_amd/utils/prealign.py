@@ -50,6 +50,8 @@ def apply_prealign(mesh: Mesh, cfg: dict) -> tuple[Mesh, np.ndarray]:
     out = Mesh(v.astype(np.float32), mesh.tris, mesh.uvs, getattr(mesh, "_texture", None), mesh.path, to_original=m,
                texture_jpeg=mesh.texture_jpeg, colors=mesh.colors,
                point_radius=mesh.point_radius)  # (a cloud's automatic radius is computed on these points, at upload)
+    if mesh.normals is not None:  # normals turn with the points (the scale drops out of |n.z| / |n|)
+        out.normals = (np.asarray(mesh.normals, dtype=np.float64).reshape(-1, 3) @ m[:3, :3].T).astype(np.float32)
     if hasattr(mesh, "_colors_wanted"):
         out._colors_wanted = mesh._colors_wanted
     out._texture_ahead = getattr(mesh, "_texture_ahead", None)  # (a texture decoded ahead moves to the copy that is uploaded)

@@ -74,14 +74,22 @@ def _view_rotations_uncached(t: np.ndarray, n: int) -> np.ndarray:
     return out
 
 
-def upload_mesh(ctx: "_lib.Context", mesh: Mesh) -> C.c_void_p:
-    """Copy a host mesh to the context's device once; cached on the Mesh object."""
+POINT_NORMALS = ("file", "estimate")
+
+
+def upload_mesh(ctx: "_lib.Context", mesh: Mesh, normals: str | None = None) -> C.c_void_p:
+    """Copy a host mesh to the context's device once; cached on the Mesh object.  ``normals``: what a renderer that shades
+    geometry asks for a point cloud's device copy - "file": ``mesh.normals`` follow the points where the mesh has them;
+    "estimate": likewise, and a cloud without gets them estimated on the device (mvlm_mesh_estimate_normals, on the context's
+    launch stream); None (every other caller): normals are left alone.  Done once per device copy."""
     key = id(ctx)
     ent = mesh._device.get(key)
     if ent is not None:
         if mesh.n_tris == 0 and ent[3] != mesh.point_radius:  # the cloud's radius was changed after the upload
             _set_point_radius(ctx, ent[0], mesh)
-            mesh._device[key] = ent[:3] + (mesh.point_radius,)
+            ent = mesh._device[key] = ent[:3] + (mesh.point_radius,) + ent[4:]
+        if normals is not None and mesh.n_tris == 0 and ent[4] is None:
+            mesh._device[key] = ent[:4] + (_send_point_normals(ctx, ent[0], mesh, normals),)
         return ent[0]
     cloud = mesh.n_tris == 0  # a point cloud: the points (and their colours) alone; uvs and texture are ignored
     verts = np.ascontiguousarray(mesh.verts, dtype=np.float32)
@@ -146,9 +154,29 @@ def upload_mesh(ctx: "_lib.Context", mesh: Mesh) -> C.c_void_p:
         ctx.check(ctx.lib.mvlm_mesh_upload_colors(ctx.handle, handle, _lib.as_ptr(colors, C.c_uint8), mesh.n_verts), ValueError)
     if cloud and mesh.point_radius is not None:
         _set_point_radius(ctx, handle, mesh)
-    # (the third entry: were colours uploaded with it?  the fourth: the point radius the device copy has, None = automatic)
-    mesh._device[key] = (handle, owner, send_colors, mesh.point_radius if cloud else None)
+    # (the third entry: were colours uploaded with it?  the fourth: the point radius the device copy has, None = automatic; the
+    # fifth: the normals the device copy has - None, "file" or "estimated")
+    mesh._device[key] = (handle, owner, send_colors, mesh.point_radius if cloud else None, None)
+    if cloud and normals is not None:
+        mesh._device[key] = mesh._device[key][:4] + (_send_point_normals(ctx, handle, mesh, normals),)
     return handle
+
+
+def _send_point_normals(ctx: "_lib.Context", handle, mesh: Mesh, mode: str):
+    """Normals for a cloud's device copy: the mesh's own where it has them, else - under "estimate" - the device's estimate.
+    -> what the copy has now: "file", "estimated" or None."""
+    if mode not in POINT_NORMALS:
+        raise ValueError(f"point_normals must be 'file' or 'estimate', not {mode!r}")
+    if mesh.normals is not None:
+        nrm = np.ascontiguousarray(mesh.normals, dtype=np.float32)
+        if nrm.shape != (mesh.n_verts, 3):
+            raise ValueError(f"mesh normals must be float32 [V,3] with V = {mesh.n_verts}, not {nrm.shape}")
+        ctx.check(ctx.lib.mvlm_mesh_upload_normals(ctx.handle, handle, _lib.as_ptr(nrm, C.c_float), mesh.n_verts), ValueError)
+        return "file"
+    if mode == "estimate":
+        ctx.check(ctx.lib.mvlm_mesh_estimate_normals(ctx.handle, handle, None), ValueError)
+        return "estimated"
+    return None
 
 
 def _set_point_radius(ctx: "_lib.Context", handle, mesh: Mesh) -> None:
@@ -206,7 +234,7 @@ class HipRenderer3D:
                  min_z_angle: int = -20, max_z_angle: int = 20, min_scale: float = 1.4, max_scale: float = 1.9,
                  min_tx: int = -20, max_tx: int = 20, min_ty: int = -20, max_ty: int = 20, device: int = 0,
                  verbose: bool = True, shading: str = "texture", subpixel_bits: int = 8, multisamples: int = 0,
-                 point_radius: float | None = None):
+                 point_radius: float | None = None, point_normals: str = "file"):
         if tuple(image_size) != (256, 256):
             raise ValueError("the HIP renderer is built for 256x256 views (general_pipeline.py:57)")
         self.n_views = n_views
@@ -236,6 +264,12 @@ class HipRenderer3D:
         # splat radius (model units) of the point clouds - scans without faces - that load_mesh reads: None = automatic, from
         # the spacing of the points (Mesh.point_radius, which a Mesh handed to render_device carries itself)
         self.point_radius = None if point_radius is None else float(point_radius)
+        # where a point cloud's normals come from when this renderer shades geometry: "file" - the cloud's own (Mesh.normals: a
+        # .ply's nx ny nz, a .vtk's NORMALS), a cloud without is refused; "estimate" - a cloud without gets them estimated on the
+        # device, once per device copy (a file's normals still win).  DESIGN.md 5.1, "Point clouds".
+        if point_normals not in POINT_NORMALS:
+            raise ValueError(f"point_normals must be 'file' or 'estimate', not {point_normals!r}")
+        self.point_normals = point_normals
         # "pre-align" block of a Deep-MVLM config (utils/prealign.py; utils3d.py:465-503): applied to every mesh this
         # renderer loads, the mesh handle it returns carries the matrix (Mesh.to_original)
         self.pre_align: dict | None = None
@@ -308,10 +342,10 @@ class HipRenderer3D:
         elif tuple(out.shape) != (n, 256, 256, 4) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
             raise ValueError("render_device: out must be a contiguous float32 [N,256,256,4] tensor on the renderer's GPU")
         rot = np.ascontiguousarray(view_rotations(transform_stack) if rot is None else rot, dtype=np.float64)
-        handle = upload_mesh(self.ctx, mesh)
-        self.ctx.bind_current_stream(torch, dev)
+        self.ctx.bind_current_stream(torch, dev)  # (before the upload: a cloud's normals may be estimated on this stream)
+        handle = upload_mesh(self.ctx, mesh, normals=self.point_normals if self.shading == "geometry" else None)
         self._push_render_mode()
-        # (a cloud's refusals - geometry shading, multisampling - are argument errors, said before anything is launched)
+        # (a cloud's refusals - geometry shading without normals, multisampling - are argument errors, said before anything is launched)
         self.ctx.check(self.ctx.lib.mvlm_render(self.ctx.handle, handle, _lib.as_ptr(rot, C.c_double), n,
                                                 C.c_void_p(out.data_ptr())), ValueError if mesh.n_tris == 0 else _lib.MvlmHipError)
         return out
@@ -730,6 +764,34 @@ class HipRenderer3D:
         """Milliseconds of the last ``encode_png``'s stages under render profiling: filter, deflate, gather, copy to host."""
         ms = np.zeros(4, dtype=np.float32)
         self.ctx.check(self.ctx.lib.mvlm_png_stage_ms(self.ctx.handle, _lib.as_ptr(ms, C.c_float)))
+        return ms
+
+    # ---- normals of a point cloud ---------------------------------------------------------------
+    def estimate_point_normals(self, mesh: Mesh, return_neighbors: bool = False):
+        """Normals of a point cloud estimated on the device (mvlm_mesh_estimate_normals; DESIGN.md 5.1, "Point clouds"): per point
+        the least-variance direction of its 16 nearest neighbours, itself included - float32 [V,3], unit length, the sign
+        unspecified, (0,0,0) for a non-finite point, fewer than 3 neighbours or coincident ones.  They become ``mesh.normals`` and
+        the device copy's normals.  With ``return_neighbors`` also int32 [V,16]: per point the ids of those neighbours in ascending
+        (squared distance, id), unused slots -1.  ValueError for a mesh with triangles."""
+        import torch
+
+        dev = torch.device("cuda", self.ctx.device)
+        handle = upload_mesh(self.ctx, mesh)
+        self.ctx.bind_current_stream(torch, dev)
+        table = torch.empty((mesh.n_verts, 16), dtype=torch.int32, device=dev) if return_neighbors else None
+        self.ctx.check(self.ctx.lib.mvlm_mesh_estimate_normals(self.ctx.handle, handle, None if table is None else C.c_void_p(table.data_ptr())),
+                       ValueError)
+        normals = np.empty((mesh.n_verts, 3), np.float32)
+        self.ctx.check(self.ctx.lib.mvlm_mesh_copy_normals(self.ctx.handle, handle, _lib.as_ptr(normals, C.c_float)))
+        mesh.normals = normals
+        key = id(self.ctx)
+        mesh._device[key] = mesh._device[key][:4] + ("estimated",)
+        return (normals, table.cpu().numpy()) if return_neighbors else normals
+
+    def normals_stage_ms(self) -> np.ndarray:
+        """Milliseconds of the last normal estimate's stages under render profiling: grid build, search, solve."""
+        ms = np.zeros(3, np.float32)
+        self.ctx.check(self.ctx.lib.mvlm_normals_stage_ms(self.ctx.handle, _lib.as_ptr(ms, C.c_float)))
         return ms
 
     def rotations_device(self):

@@ -8,7 +8,8 @@
                                          kernel_occupancy_report.json,
                                          kernel_occupancy_view.json, kernel_occupancy_rays.json,
                                          kernel_occupancy_png.json, kernel_occupancy_points.json,
-                                         kernel_occupancy_sheet.json, kernel_occupancy_heat.json) from the build
+                                         kernel_occupancy_sheet.json, kernel_occupancy_heat.json,
+                                         kernel_occupancy_normals.json) from the build
 
 A convolution tile's rate depends on how many workgroups a CU holds, i.e. on which side of 168 / 128 / 102 ... registers the
 compiler lands - and every epilogue kind compiled into a tile moves that number (round 4: two new kinds took the 80-row tile
@@ -28,7 +29,9 @@ tests/golden/kernel_occupancy_rays.json, tests/test_rays_occupancy.py) and the f
 tests/golden/kernel_occupancy_png.json, tests/test_png_occupancy.py) and the point-cloud kernels - splat renderer and
 nearest-point snap - (build/points/, tests/golden/kernel_occupancy_points.json, tests/test_points_occupancy.py) and the three
 kernels of the view sheet (build/sheet/, tests/golden/kernel_occupancy_sheet.json, tests/test_sheet_occupancy.py) and the two
-kernels of the heat sheet (build/heat/, tests/golden/kernel_occupancy_heat.json, tests/test_heat_occupancy.py)."""
+kernels of the heat sheet (build/heat/, tests/golden/kernel_occupancy_heat.json, tests/test_heat_occupancy.py) and the kernels of a
+cloud's normals - the estimate and the tile stage that shades with them - (build/normals/,
+tests/golden/kernel_occupancy_normals.json, tests/test_normals_occupancy.py)."""
 import json
 import re
 import subprocess
@@ -51,6 +54,7 @@ PNG_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_png.json"
 POINTS_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_points.json"
 SHEET_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_sheet.json"
 HEAT_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_heat.json"
+NORMALS_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_normals.json"
 BUILD = REPO / "mvlm_amd" / "csrc" / "build"
 
 
@@ -98,10 +102,11 @@ if __name__ == "__main__":
     for table_path, objdir in ((TABLE, BUILD), (MSAA_TABLE, BUILD / "msaa"), (VCOLOR_TABLE, BUILD / "vcolor"),
                                 (WINO_TABLE, BUILD / "wino"), (WINO4_TABLE, BUILD / "wino4"), (WINO4W_TABLE, BUILD / "wino4w"), (REPORT_TABLE, BUILD / "report"),
                                 (VIEW_TABLE, BUILD / "view"), (RAYS_TABLE, BUILD / "rays"), (PNG_TABLE, BUILD / "png"),
-                                (POINTS_TABLE, BUILD / "points"), (SHEET_TABLE, BUILD / "sheet"), (HEAT_TABLE, BUILD / "heat")):
+                                (POINTS_TABLE, BUILD / "points"), (SHEET_TABLE, BUILD / "sheet"), (HEAT_TABLE, BUILD / "heat"),
+                                (NORMALS_TABLE, BUILD / "normals")):
         t = build_table(objdir)
         if "--write" in sys.argv:
-            fields = ("waves_per_simd", "spilled", "scratch") if table_path in (VIEW_TABLE, RAYS_TABLE, PNG_TABLE, POINTS_TABLE, SHEET_TABLE, HEAT_TABLE) else ("waves_per_simd", "spilled")
+            fields = ("waves_per_simd", "spilled", "scratch") if table_path in (VIEW_TABLE, RAYS_TABLE, PNG_TABLE, POINTS_TABLE, SHEET_TABLE, HEAT_TABLE, NORMALS_TABLE) else ("waves_per_simd", "spilled")
             table_path.write_text(json.dumps({k: {f: v[f] for f in fields} for k, v in t.items()}, indent=1) + "\n")
             print(f"{len(t)} kernels -> {table_path}")
         else:
