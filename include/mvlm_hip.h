@@ -254,6 +254,15 @@ int mvlm_render_landmark_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double
  * front of the kernels (the key plane, 8 bytes per pixel, is filled in every call), transform, classify, scan, bin fill, landmark
  * projection, tile.  Waits for the stream. */
 int mvlm_landmark_view_stage_ms(mvlm_ctx* ctx, float* ms7);
+/* mvlm_render_landmark_view with a colour per vertex given by the caller: vert_rgba_dev u8[n_verts,4] on the device, 4-byte aligned,
+ * r g b and a fourth byte that is not read (mvlm_surface_heat writes this layout).  The same checks and the same launch set; the
+ * tile kernel shades with those colours, no texture and shading 0.  Contract: byte for byte mvlm_render_landmark_view of the same
+ * geometry uploaded with those colours as its vertex colours and no texture, under shading 0.  A NULL or misaligned vert_rgba_dev
+ * returns an error and launches nothing. */
+int mvlm_render_landmark_view_colored(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot_host, int n_views, int size,
+                                      const float* frame_host, const double* landmarks_host, int n_lm, float radius,
+                                      const uint8_t* lm_rgb_host, uint8_t* out_dev, int32_t* lm_pixels_dev,
+                                      const uint8_t* vert_rgba_dev /* [n_verts,4] */);
 
 /* ---- ray view (replaces visualization/ray_visualizer.py's RayVisualizer for the offscreen case) ---- */
 /* mvlm_render_landmark_view's picture with n_rays rays between the mesh and the spheres: each an opaque, head-lit capsule, the
@@ -346,6 +355,47 @@ int mvlm_render_heat_sheet(mvlm_ctx* ctx, const float* images_dev, const float* 
 /* With mvlm_render_set_profiling on, the last heat sheet's stages in milliseconds (HIP events), f32[3]: background (the views
  * alone, with the copies of the two small tables), peak, compose.  Waits for the stream. */
 int mvlm_heat_sheet_stage_ms(mvlm_ctx* ctx, float* ms3);
+
+/* ---- surface heat (all views' heatmaps laid on the scan; DESIGN.md 5.1, "Surface heat") ---- */
+/* Every vertex of the mesh is carried into every view with mvlm_render's own transform (the context's sub-pixel bits), tested
+ * against the depth plane the network saw, and where a view sees it the view's heatmap values at its pixel add up per landmark.
+ *   rot_dev     f64[n_views,9]             the rendered views' rotations on the device (mvlm_render_rotations_dev)
+ *   images_dev  f32[n_views,256,256,4]     mvlm_render's stack (plane 3, the depth, is read), 16-byte aligned
+ *   heat_dev    f32[n_views,n_lm,256,256]  as mvlm_cnn_heatmaps leaves them, 16-byte aligned
+ *   sel_host    u8[n_lm] or NULL           the landmarks that may win a vertex's colour; NULL = all
+ *   lm_rgb_host u8[n_lm,3] or NULL         a colour per landmark; NULL = (255, 0, 0)
+ *   floor in [0, 1): scores up to it are not drawn; opacity in (0, 1]: at score 1; depth_tol 0..255: the depth steps (1/255 of the
+ *   clip range, 5.9 model units) a vertex may lie behind the rendered surface and still count as seen
+ *   vert_rgba_dev    u8[n_verts,4]         r g b 255 per vertex: what mvlm_render_landmark_view_colored takes
+ *   score_dev        f32[n_verts,n_lm] or NULL (then the scores live in the context's scratch)
+ *   n_vis_dev        i32[n_verts] or NULL  the views that see each vertex
+ *   peak_vertex_dev  i32[n_lm]             per landmark the vertex of the largest score above 0, the lowest id on a tie; -1: none
+ *   peak_score_dev   f32[n_lm]             that score; 0 for -1
+ * Vertex v lies in view n at o = rm_transform(rot[n], v): pixel i = floor(o.X / 256), j = floor(o.Y / 256), inside iff v is finite,
+ * 0 <= i, j < 256 and o.z in [0, 1]; the heat / image pixel is [255 - j, i].  It is seen iff inside and
+ * trunc(255 o.z) <= ((256 - trunc(images[n,255-j,i,3] * 255 + 0.5)) & 255) + depth_tol.  With m the peak of plane (n, l) as
+ * mvlm_heat_plane_peaks gives it and h the plane's value at the pixel, a view that sees v adds max(h / m, 0) where m is finite and
+ * above 0 and h is finite, else 0; score[v,l] = (float)(the float64 sum over the views in ascending order / the views that see v),
+ * 0 where none does.  Colour: the selected landmark of the largest score, the lowest index on a tie; a score <= floor leaves the
+ * base - the vertex's own colour, else the nearest texel of its texture coordinates, else (200, 200, 200) -, otherwise the
+ * landmark's colour is laid over the base with opacity * (score - floor) / (1 - floor), as the heat sheet blends.  All of it in
+ * float64 or integers in the operation order of csrc/surface_backproject_math.h; no value depends on the scheduling.
+ * n_lm 1..65536, n_views * n_lm <= 32768 planes and n_verts * n_lm <= 268435456 scores per call.  A NULL or misaligned pointer, a
+ * value out of range or a point cloud ("point cloud" is in the message) set an error that starts with "surface heat:" and launch
+ * nothing.  Only enqueues work on the launch stream. */
+int mvlm_surface_heat(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot_dev, const float* images_dev, const float* heat_dev,
+                      int n_views, int n_lm, const uint8_t* sel_host, const uint8_t* lm_rgb_host, double floor, double opacity,
+                      int depth_tol, uint8_t* vert_rgba_dev, float* score_dev /* f32[V,n_lm] or NULL */,
+                      int32_t* n_vis_dev /* i32[V] or NULL */, int32_t* peak_vertex_dev /* i32[n_lm] */,
+                      float* peak_score_dev /* f32[n_lm] */);
+/* With mvlm_render_set_profiling on, the last surface heat's stages in milliseconds (HIP events), f32[3]: peak, back-projection
+ * (the scores), paint (colours and per-landmark peaks).  Waits for the stream. */
+int mvlm_surface_heat_stage_ms(mvlm_ctx* ctx, float* ms3);
+/* Frees the surface heat's grow-only scratch (peaks, keys, the two small tables; the scores - 4 bytes per vertex and landmark -
+ * where a call kept no score_dev).  Waits for the stream; the next mvlm_surface_heat allocates again. */
+int mvlm_surface_heat_release(mvlm_ctx* ctx);
+/* Bytes of the context's grow-only internal scratch whose names start with `prefix` ("backproject": the surface heat's; "": all). */
+int mvlm_scratch_bytes(mvlm_ctx* ctx, const char* prefix, size_t* bytes);
 
 /* ---- PNG on the device (the views' files without the picture crossing to the host) ---- */
 /* Bytes that hold any file mvlm_png_encode writes for a picture of height x width (each 1..4096): the filtered stream

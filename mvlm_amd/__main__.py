@@ -85,6 +85,17 @@ def build_parser() -> argparse.ArgumentParser:
                         help="the landmarks --visualize-heat shows, e.g. 3,17,40 (default: all)")
     parser.add_argument("--heat-floor", type=float, default=0.25, metavar="F",
                         help="--visualize-heat draws a heatmap only where it exceeds this share of its peak (0 <= F < 1)")
+    parser.add_argument("--visualize-surface", action="store_true",
+                        help="write visualization/<stem>_<pipeline>_surface.png under the working directory for every scan: the mesh "
+                             "with all views' heatmaps laid on it, per vertex the landmark with the largest mean share of its heatmaps' "
+                             "peaks over the views that see the vertex, and the final landmarks as spheres (--heat-landmarks and "
+                             "--heat-floor apply; costs about one network pass more per scan, shared with --visualize-heat)")
+    parser.add_argument("--surface-depth-tol", type=int, default=2, metavar="STEPS",
+                        help="--visualize-surface: depth steps (1/255 of the clip range, 5.9 model units) a vertex may lie behind a "
+                             "view's rendered surface and still count as seen there (0..255)")
+    parser.add_argument("--surface-mesh", action="store_true",
+                        help="with --visualize-surface (which it turns on): also write <stem>_<pipeline>_surface.obj beside the "
+                             "landmark file, the scan with those colours per vertex")
     parser.add_argument("--point-radius", type=float, default=None, metavar="MM",
                         help="splat radius, in model units, of scans that have points but no faces (point clouds): 0.88 to 9.375, "
                              "i.e. 0.75 to 8 pixels of a view; default: automatic, from the spacing of the points (DESIGN.md 5.1)")
@@ -150,6 +161,12 @@ def main(argv=None) -> int:
         extra["sheet_scale"] = args.sheet_scale
         extra["heat_landmarks"] = args.heat_landmarks
         extra["heat_floor"] = args.heat_floor
+    if args.visualize_surface or args.surface_mesh:
+        extra["visualize_surface"] = True
+        extra["visualize_size"] = args.visualize_size
+        extra["surface_depth_tol"] = args.surface_depth_tol
+        extra["heat_landmarks"] = args.heat_landmarks
+        extra["heat_floor"] = args.heat_floor
     if args.point_radius is not None:
         extra["point_radius"] = args.point_radius
     if args.point_normals != "file":
@@ -182,6 +199,8 @@ def main(argv=None) -> int:
             np.savetxt((path_to_out / f"{file.stem}_{pname}.txt").as_posix(), landmarks, delimiter=",")
             if args.report:
                 dm.last_report.to_csv(path_to_out / f"{file.stem}_{pname}_report.csv")
+            if args.surface_mesh:
+                dm.write_surface_mesh(path_to_out / f"{file.stem}_{pname}_surface.obj")
     return 0
 
 

@@ -763,6 +763,36 @@ extern "C" int mvlm_render_landmark_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, c
                                      out_dev, lm_pixels_dev);
 }
 
+// The landmark view with the caller's colour per vertex (the surface heat's, mvlm_surface_heat): the same checks and the same launch
+// set, the tile kernel given those colours, no texture and shading 0.
+extern "C" int mvlm_render_landmark_view_colored(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot_host, int n_views, int size,
+                                                 const float* frame_host, const double* landmarks_host, int n_lm, float radius,
+                                                 const uint8_t* lm_rgb_host, uint8_t* out_dev, int32_t* lm_pixels_dev,
+                                                 const uint8_t* vert_rgba_dev) {
+    MVLM_ENTER(ctx);
+    std::vector<float> frames;
+    if (view_check_arguments(ctx, "landmark view", mesh, rot_host, n_views, size, frame_host, landmarks_host, n_lm, radius, out_dev,
+                             frames))
+        return 1;
+    MVLM_REQUIRE(ctx, vert_rgba_dev && reinterpret_cast<uintptr_t>(vert_rgba_dev) % 4 == 0,
+                 "landmark view: the vertex colours must be a 4-byte aligned device pointer");
+    if (mvlm_mesh_wait_ready(ctx, mesh, ctx->stream)) return 1;
+    return mvlm_launch_landmark_view(ctx, mesh, rot_host, n_views, size, frames.data(), landmarks_host, n_lm, radius, lm_rgb_host,
+                                     out_dev, lm_pixels_dev, vert_rgba_dev);
+}
+
+// Bytes of the context's grow-only scratch whose names start with `prefix` ("backproject": the surface heat's; "": all of it).
+extern "C" int mvlm_scratch_bytes(mvlm_ctx* ctx, const char* prefix, size_t* bytes) {
+    if (!ctx) return 1;
+    MVLM_ENTER(ctx);
+    MVLM_REQUIRE(ctx, prefix && bytes, "scratch_bytes: null pointer");
+    size_t total = 0;
+    for (const auto& kv : ctx->scratch)
+        if (kv.first.rfind(prefix, 0) == 0 && kv.second.first) total += kv.second.second;
+    *bytes = total;
+    return 0;
+}
+
 // The same with the rays: the shared arguments are checked the same, the rays' own under "ray view:"; hands over to raster_rays.hip.
 extern "C" int mvlm_render_ray_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot_host, int n_views, int size,
                                     const float* frame_host, const double* landmarks_host, int n_lm, float radius,

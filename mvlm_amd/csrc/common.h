@@ -381,6 +381,10 @@ struct mvlm_ctx {
     // (mvlm_heat_sheet_stage_ms)
     std::vector<hipEvent_t> heat_events;
     bool heat_events_valid = false;
+    // surface heat (surface_backproject.hip): the four events around peak, score and paint while render_profiling is on
+    // (mvlm_surface_heat_stage_ms)
+    std::vector<hipEvent_t> backproject_events;
+    bool backproject_events_valid = false;
     // device buffers of freed meshes, reused by the next upload: a folder of scans would otherwise pay
     // four hipMalloc + four (device-synchronising) hipFree per scan
     struct PoolEntry {
@@ -459,6 +463,9 @@ int mvlm_view_sheet_draw(mvlm_ctx* ctx, const float* images_dev, int n_views, co
                          const double* landmarks_host, const uint8_t* lm_rgb_host, const uint8_t* used_host, int background, int cols_in,
                          int scale, int gap, double marker_radius, uint8_t* out_dev);
 
+// heat_sheet.hip: the launch of the kernel behind mvlm_heat_plane_peaks, for an entry point that holds the context
+void mvlm_heat_launch_peaks(mvlm_ctx* ctx, const float* heat_dev, int n_planes, float* peaks_dev);
+
 // conv_mfma.hip
 constexpr long MVLM_KPARTS_MAX_TILES = 2048;  // output tiles of a launch that divides K over workgroups
 constexpr long MVLM_KPARTS_MAX_PARTS = 4096;  // tiles x parts (4 KB of partial sums each)
@@ -507,10 +514,12 @@ inline bool mvlm_conv_wino4_pad_serves_slot(int ksize, int cin_pad, int cout_pad
 constexpr int MVLM_CONV_VARIANT_FAST = 62;    // id reported for launches of the bf16x3 kernel
 constexpr int MVLM_CONV_VARIANT_FAST16 = 61;  // ... of the f16x2 kernel
 
-// raster_view.hip: the launch set of mvlm_render_landmark_view (api.hip checks the arguments and holds the context)
+// raster_view.hip: the launch set of mvlm_render_landmark_view (api.hip checks the arguments and holds the context); with
+// vert_rgba_dev u8[V,4] (mvlm_render_landmark_view_colored) the tile kernel shades with those colours: no texture, shading 0
 int mvlm_launch_landmark_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot_host, int n_views, int size,
                               const float* frames_host, const double* landmarks_host, int n_lm, float radius,
-                              const uint8_t* lm_rgb_host, uint8_t* out_dev, int32_t* lm_pixels_dev);
+                              const uint8_t* lm_rgb_host, uint8_t* out_dev, int32_t* lm_pixels_dev,
+                              const uint8_t* vert_rgba_dev = nullptr);
 
 // raster_rays.hip: the launch set of mvlm_render_ray_view (likewise)
 int mvlm_launch_ray_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot_host, int n_views, int size,

@@ -112,14 +112,20 @@ int heat_events(mvlm_ctx* ctx, hipEvent_t** ev) {
 
 }  // namespace
 
+// The peak kernel's launch on the context's stream, for an entry point that holds the context and has checked its arguments (this
+// file's two, and the surface heat: surface_backproject.hip).
+void mvlm_heat_launch_peaks(mvlm_ctx* ctx, const float* heat_dev, int n_planes, float* peaks_dev) {
+    hipLaunchKernelGGL(heat_peak_kernel, dim3(unsigned(n_planes)), dim3(256), 0, ctx->stream, reinterpret_cast<const float4*>(heat_dev),
+                       peaks_dev);
+}
+
 extern "C" int mvlm_heat_plane_peaks(mvlm_ctx* ctx, const float* heat_dev, int n_planes, float* peaks_dev) {
     if (!ctx) return 1;
     MVLM_ENTER(ctx);
     MVLM_REQUIRE(ctx, heat_dev && peaks_dev, "heat sheet: null pointer");
     MVLM_REQUIRE(ctx, reinterpret_cast<uintptr_t>(heat_dev) % 16 == 0, "heat sheet: the heatmaps must be 16-byte aligned");
     MVLM_REQUIRE(ctx, n_planes >= 1 && n_planes <= HS_MAX_PLANES, "heat sheet: 1..32768 planes per call (" + std::to_string(n_planes) + " given)");
-    hipLaunchKernelGGL(heat_peak_kernel, dim3(unsigned(n_planes)), dim3(256), 0, ctx->stream, reinterpret_cast<const float4*>(heat_dev),
-                       peaks_dev);
+    mvlm_heat_launch_peaks(ctx, heat_dev, n_planes, peaks_dev);
     MVLM_CHECK_HIP(ctx, hipGetLastError());
     return 0;
 }
@@ -167,7 +173,7 @@ extern "C" int mvlm_render_heat_sheet(mvlm_ctx* ctx, const float* images_dev, co
     if (sel) MVLM_CHECK_HIP(ctx, hipMemcpyAsync(sel, sel_host, size_t(n_lm), hipMemcpyHostToDevice, st));
     if (lm_rgb) MVLM_CHECK_HIP(ctx, hipMemcpyAsync(lm_rgb, lm_rgb_host, size_t(n_lm) * 3, hipMemcpyHostToDevice, st));
     if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[1], st));
-    hipLaunchKernelGGL(heat_peak_kernel, dim3(unsigned(n_planes)), dim3(256), 0, st, reinterpret_cast<const float4*>(heat_dev), peaks);
+    mvlm_heat_launch_peaks(ctx, heat_dev, int(n_planes), peaks);
     if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[2], st));
     hipLaunchKernelGGL(heat_compose_kernel, dim3(RM_SIZE, unsigned(n_views)), dim3(256), 0, st, heat_dev, peaks, sel, lm_rgb, n_lm, cols,
                        scale, gap, width, floor_, opacity, reinterpret_cast<uint32_t*>(out_dev));

@@ -254,15 +254,18 @@ int mvlm_view_launch_stages(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* 
 // mvlm_render_landmark_view).  frames_host f32[n_views,4]: cx, cy, half, k = rv_scale(size, half).
 int mvlm_launch_landmark_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot_host, int n_views, int size,
                               const float* frames_host, const double* landmarks_host, int n_lm, float radius,
-                              const uint8_t* lm_rgb_host, uint8_t* out_dev, int32_t* lm_pixels_dev) {
+                              const uint8_t* lm_rgb_host, uint8_t* out_dev, int32_t* lm_pixels_dev, const uint8_t* vert_rgba_dev) {
     mvlm_view_stages s;
     if (mvlm_view_launch_stages(ctx, mesh, rot_host, n_views, size, frames_host, landmarks_host, n_lm, radius, lm_rgb_host,
                                 lm_pixels_dev, "landmark view", &s))
         return 1;
     const int tiles_x = size / RM_TILE, tiles = tiles_x * tiles_x;
-    hipLaunchKernelGGL(view_tile_kernel, dim3(view_chunk_grid(tiles, n_views)), dim3(256), 0, ctx->stream, s.tv, mesh->tris, mesh->uvs,
-                       mesh->tex, mesh->tex_w, mesh->tex_h, reinterpret_cast<const uchar4*>(s.vcol), mesh->n_verts, s.bins.counts,
-                       s.bins.offsets, s.bins.bins, s.bins.cap, s.keys, s.frames, ctx->render_shading, n_views, size, s.spheres, n_lm,
+    // the caller's colours: what a mesh uploaded with them as its vertex colours and no texture is drawn with under shading 0
+    const bool given = vert_rgba_dev != nullptr;
+    hipLaunchKernelGGL(view_tile_kernel, dim3(view_chunk_grid(tiles, n_views)), dim3(256), 0, ctx->stream, s.tv, mesh->tris,
+                       given ? nullptr : mesh->uvs, given ? nullptr : mesh->tex, mesh->tex_w, mesh->tex_h,
+                       reinterpret_cast<const uchar4*>(given ? vert_rgba_dev : s.vcol), mesh->n_verts, s.bins.counts,
+                       s.bins.offsets, s.bins.bins, s.bins.cap, s.keys, s.frames, given ? 0 : ctx->render_shading, n_views, size, s.spheres, n_lm,
                        lm_pixels_dev, s.bins.overflow, ctx->render_overflow_host, reinterpret_cast<uint32_t*>(out_dev));
     if (s.ev) MVLM_CHECK_HIP(ctx, hipEventRecord(s.ev[7], ctx->stream));
     MVLM_CHECK_HIP(ctx, hipGetLastError());

@@ -90,7 +90,7 @@ class _Stage:
 
 class Pipeline(abc.ABC):
     # (also for an object that never went through __init__: the picture rules and predict_mesh_device read them)
-    visualize_heat = _keep_ray_view = False
+    visualize_heat = visualize_surface = _keep_ray_view = False
     heat_landmarks = None
 
     def __init__(self, render_image_stack: bool = False, offscreen: bool = True, n_views: int = 8,
@@ -101,7 +101,7 @@ class Pipeline(abc.ABC):
                  visualize_rays_img: bool = False, visualize_rays_poses=((0, 0, 0), (0, 60, 0), (0, -60, 0)),
                  view_png_encoder: str = "host", point_radius: float | None = None, visualize_sheet: bool = False,
                  sheet_scale: int = 1, visualize_heat: bool = False, heat_landmarks=None, heat_floor: float = 0.25,
-                 point_normals: str = "file"):
+                 point_normals: str = "file", visualize_surface: bool = False, surface_depth_tol: int = 2):
         self.render_image_stack = render_image_stack
         self.render_image_folder = render_image_folder
         self.n_views = n_views
@@ -127,9 +127,11 @@ class Pipeline(abc.ABC):
         self.view_png_encoder = check_png_encoder(view_png_encoder)
         self.visualize_sheet = bool(visualize_sheet)
         self.visualize_heat = bool(visualize_heat)
+        self.visualize_surface, self.surface_depth_tol = bool(visualize_surface), surface_depth_tol
         self.sheet_scale, self.heat_floor, self.heat_landmarks = sheet_scale, heat_floor, None  # (sheet_scale: of both sheets)
         pictures.check_options(self, n_views, heat_landmarks, visualize_size)
-        self.last_view_path = self.last_sheet_path = self.last_heat_path = None
+        self.last_view_path = self.last_sheet_path = self.last_heat_path = self.last_surface_path = None
+        self.last_surface_heat = self._surface_mesh = None
         self.last_ray_view_paths: list = []
         # the pictures.Pass of the current call, kept only between a prediction made by predict_one_file / predict_files
         # (_keep_ray_view) and the _after_prediction that draws its ray view
@@ -182,8 +184,9 @@ class Pipeline(abc.ABC):
         (utils3d.py:26-36) and renders RGB + depth; a depth or geometry(+depth) model then never looks at the colours.
         Kept: whenever the views are written out (render_image_stack), the scan is drawn (visualize_img) or the views go to a predictor whose planes are unknown."""
         sel = getattr(self.predictor_2d, "chan_sel", None)
-        if self.render_image_stack or self.visualize_img or sel is None or not isinstance(self.renderer_3d, HipRenderer3D):
-            return True  # (visualize_img draws the scan itself: with its texture)
+        if (self.render_image_stack or self.visualize_img or self.visualize_surface or sel is None
+                or not isinstance(self.renderer_3d, HipRenderer3D)):
+            return True  # (visualize_img and visualize_surface draw the scan itself: with its texture)
         if self.renderer_3d.shading == "geometry":
             return False  # planes 0..2 carry the build-defined geometry shading
         return any(int(c) < 3 for c in sel)
@@ -200,6 +203,9 @@ class Pipeline(abc.ABC):
             raise ValueError(f"{name} is a point cloud: visualize_img is not supported (the landmark view draws triangles)")
         if self.visualize_rays_img:
             raise ValueError(f"{name} is a point cloud: visualize_rays_img is not supported (the ray view draws triangles)")
+        if getattr(self, "visualize_surface", False):
+            raise ValueError(f"{name} is a point cloud: visualize_surface is not supported (the surface heat colours a mesh's vertices "
+                             "and draws its triangles)")
         r3 = self.renderer_3d
         if getattr(r3, "multisamples", 0):
             raise ValueError(f"{name} is a point cloud: multisampled rendering (render_multisamples=4) is not supported")
@@ -432,7 +438,7 @@ class Pipeline(abc.ABC):
                     maxima = torch.empty((p2.get_lm_count(), 0, 3), dtype=torch.float32,
                                          device=torch.device("cuda", self.device))
                 # (the stack stays where it is until the sheets are drawn)
-                sheet_images = images if drawing and (self.visualize_sheet or self.visualize_heat) else None
+                sheet_images = images if drawing and pictures.keeps_images(self) else None
                 del images
                 if sharded:
                     maxima = parallel.all_gather_views(maxima, n_total)
@@ -528,6 +534,10 @@ class Pipeline(abc.ABC):
         """``visualize_img`` (pictures.draw_landmark_view); ``report``: the LandmarkReport of THIS prediction or None."""
         return pictures.draw_landmark_view(self, mesh, landmarks, report)
 
+    def write_surface_mesh(self, path):
+        """``visualize_surface``: the last scan's mesh with the surface heat's colours per vertex, as an OBJ (pictures.write_surface_mesh)."""
+        return pictures.write_surface_mesh(self, path)
+
     def _groupable(self, n_scans: int) -> bool:
         """Can ``n_scans`` scans share one network pass (predict_meshes_device)?"""
         p2, e3 = self.predictor_2d, self.estimator_3d
@@ -539,7 +549,7 @@ class Pipeline(abc.ABC):
             return False
         if self.landmark_report:
             return False  # one report per scan, made by the scan's own pass
-        if self.visualize_img or self.visualize_rays_img or self.visualize_sheet or self.visualize_heat:
+        if self.visualize_img or self.visualize_rays_img or self.visualize_sheet or self.visualize_heat or self.visualize_surface:
             return False  # one picture per scan, drawn by the scan's own pass while its mesh (its views) are resident
         n = int(self.renderer_3d.n_views)
         return e3.expected_counts(p2.get_lm_count(), n) is not None and n_scans * n <= (p2.device_batch or 128)

@@ -26,6 +26,15 @@ visualize_heat      the view sheet's cells, no markers, with the network's heatm
                     not kept by the prediction: the predictor's heatmaps_device runs once more on this pass's image stack, which
                     costs about one network pass more per scan, and its tensor ([N,NL,256,256] float32: 2 GB at 96 views x 84
                     landmarks) lives until the picture is drawn.
+visualize_surface   all views' heatmaps laid on the scan itself (HipRenderer3D.surface_heat): every vertex takes, from every view that
+                    sees it (at most surface_depth_tol depth steps behind that view's depth plane), the share its heatmap value there
+                    has of its plane's peak; the mesh is drawn with the winning landmark's colour per vertex - heat_landmarks and
+                    heat_floor as for the heat sheet - and the final landmarks as spheres, front view, frame="fit", visualize_size
+                    pixels a side, into visualization/<stem>_<visualize_name>_surface.png.  It leaves last_surface_path and
+                    last_surface_heat = {peak_vertex, peak_score, distance}: per landmark the vertex where the views together put
+                    it, its score, and the distance from there to the final landmark (NaN where either is missing) - a second
+                    opinion beside rays + RANSAC.  Costs the heat sheet's second network pass; with visualize_heat as well the
+                    heatmaps are made once for both pictures.
 view_png_encoder    who makes the PNG files.  "host" (the default): the picture is copied to the host and Pillow encodes it.
                     "device": it stays where render_*_device left it and HipRenderer3D.encode_png filters and compresses it there
                     (mvlm_png_encode; the ray view's pictures in one call) - the same pixels in a file of other bytes, and only
@@ -41,10 +50,12 @@ import numpy as np
 from .. import parallel
 from ..utils.render3d import HipRenderer3D
 from ..utils.report import LandmarkReport
-from ..utils.viewer import heat_colours, heat_sheet_path, render_to_png, select_rays, view_path, view_sheet_path
+from ..utils.viewer import heat_colours, heat_sheet_path, render_to_png, select_rays, surface_path, view_path, view_sheet_path
 
-FLAGS = ("visualize_heat", "visualize_sheet", "visualize_rays_img", "visualize_img")  # in the order their rules are checked
-ALL_VIEWS = FLAGS[:2]  # the sheets: they draw the views, and need every view in one process
+FLAGS = ("visualize_heat", "visualize_surface", "visualize_sheet", "visualize_rays_img", "visualize_img")  # in the order their rules are checked
+SHEETS = ("visualize_heat", "visualize_sheet")  # they draw the views
+ALL_VIEWS = SHEETS + ("visualize_surface",)  # they read every view, and need them all in one process
+HEATMAPS = ("visualize_heat", "visualize_surface")  # they show the network's heatmaps
 
 
 @dataclass
@@ -67,7 +78,12 @@ class Pass:
 
 def wanted(pipe) -> bool:
     """Does the pass now running have a picture to draw (or rays to keep for one)?"""
-    return pipe.visualize_img or pipe.visualize_sheet or pipe.visualize_heat or pipe._keep_ray_view
+    return pipe.visualize_img or pipe.visualize_sheet or pipe.visualize_heat or pipe.visualize_surface or pipe._keep_ray_view
+
+
+def keeps_images(pipe) -> bool:
+    """Does a picture of the pass now running read the image stack behind the prediction?"""
+    return pipe.visualize_sheet or pipe.visualize_heat or pipe.visualize_surface
 
 
 def check_options(pipe, n_views, heat_landmarks, visualize_size) -> None:
@@ -80,7 +96,12 @@ def check_options(pipe, n_views, heat_landmarks, visualize_size) -> None:
         pipe.sheet_scale = int(scale)
     if pipe.visualize_sheet and n_views is not None:  # (a sheet beyond 4096 pixels a side: said here, with the scale that fits)
         HipRenderer3D.view_sheet_layout(int(n_views), None, pipe.sheet_scale)
-    if pipe.visualize_heat:
+    if pipe.visualize_surface:
+        tol = pipe.surface_depth_tol
+        if isinstance(tol, bool) or not isinstance(tol, (int, np.integer)) or not 0 <= tol <= 255:
+            raise ValueError(f"surface_depth_tol must be an integer in 0..255, not {tol!r}")
+        pipe.surface_depth_tol = int(tol)
+    if pipe.visualize_heat or pipe.visualize_surface:
         if isinstance(floor, bool) or not isinstance(floor, (int, float, np.integer, np.floating)) \
                 or not (np.isfinite(floor) and 0.0 <= floor < 1.0):
             raise ValueError(f"heat_floor must be a finite number in [0, 1), not {floor!r}")
@@ -91,10 +112,10 @@ def check_options(pipe, n_views, heat_landmarks, visualize_size) -> None:
                     or len(set(int(k) for k in picked)) != len(picked):
                 raise ValueError(f"heat_landmarks must be None or a sequence of distinct landmark indices, not {heat_landmarks!r}")
             pipe.heat_landmarks = [int(k) for k in picked]  # (the upper end: check(), once the predictor is there)
-        if n_views is not None:  # (as for the view sheet)
+        if pipe.visualize_heat and n_views is not None:  # (as for the view sheet)
             HipRenderer3D._sheet_layout("heat sheet", int(n_views), None, pipe.sheet_scale, 2)
     size = pipe.visualize_size
-    if (pipe.visualize_img or pipe.visualize_rays_img) and (size < 64 or size > 2048 or size % 16):
+    if (pipe.visualize_img or pipe.visualize_rays_img or pipe.visualize_surface) and (size < 64 or size > 2048 or size % 16):
         raise ValueError(f"visualize_size must be a multiple of 16 in 64..2048, not {visualize_size}")
 
 
@@ -105,15 +126,15 @@ def check(pipe) -> None:
     for flag in FLAGS:
         if not getattr(pipe, flag):
             continue
-        reason = "it draws the sheet" if flag in ALL_VIEWS else "it draws the mesh resident on the device"
-        if flag == "visualize_heat" and not callable(getattr(pipe.predictor_2d, "heatmaps_device", None)):
-            raise ValueError("visualize_heat needs a predictor with heatmaps_device (HipPaulsenModel): "
+        reason = "it draws the sheet" if flag in SHEETS else "it draws the mesh resident on the device"
+        if flag in HEATMAPS and not callable(getattr(pipe.predictor_2d, "heatmaps_device", None)):
+            raise ValueError(f"{flag} needs a predictor with heatmaps_device (HipPaulsenModel): "
                              f"{type(pipe.predictor_2d).__name__} has no heatmaps to show")
         if not isinstance(pipe.renderer_3d, HipRenderer3D):
             raise ValueError(f"{flag} needs a HipRenderer3D in the renderer slot ({reason}), not {type(pipe.renderer_3d).__name__}")
         if flag in ALL_VIEWS and pipe.shard_views and parallel.is_distributed():
             raise ValueError(f"{flag} is not supported with shard_views in a distributed run: a rank holds only its slice of the views")
-        if flag == "visualize_heat" and pipe.heat_landmarks is not None:
+        if flag in HEATMAPS and pipe.heat_landmarks is not None:
             nl = int(pipe.predictor_2d.get_lm_count())
             if any(k >= nl for k in pipe.heat_landmarks):
                 raise ValueError(f"heat_landmarks must lie in 0..{nl - 1}, not {pipe.heat_landmarks!r}")
@@ -170,20 +191,63 @@ def draw_view_sheet(pipe, p: Pass):
     pipe._say(f"[Pipeline] view sheet written to {pipe.last_sheet_path}")
 
 
-def draw_heat_sheet(pipe, p: Pass):
-    """``visualize_heat``: the views of the pass with the heatmaps the predictor makes of them - a second forward pass -, drawn by
-    ``HipRenderer3D.render_heat_sheet``."""
+def pass_heatmaps(pipe, p: Pass) -> tuple:
+    """(the pass's image stack on the device, the heatmaps the predictor makes of it - a second forward pass): made once per pass,
+    for the heat sheet and the surface heat alike."""
     import torch
 
+    images = p.images
+    if not hasattr(images, "data_ptr"):
+        images = torch.from_numpy(np.ascontiguousarray(images, dtype=np.float32)).to(torch.device("cuda", pipe.renderer_3d.ctx.device))
+    return images, pipe.predictor_2d.heatmaps_device(images)
+
+
+def draw_heat_sheet(pipe, p: Pass, images, heat):
+    """``visualize_heat``: the views of the pass with the heatmaps the predictor made of them (``pass_heatmaps``), drawn by
+    ``HipRenderer3D.render_heat_sheet``."""
     with pipe._timer.stage("visualize_heat"):
-        images = p.images
-        if not hasattr(images, "data_ptr"):
-            images = torch.from_numpy(np.ascontiguousarray(images, dtype=np.float32)).to(torch.device("cuda", pipe.renderer_3d.ctx.device))
-        heat = pipe.predictor_2d.heatmaps_device(images)
         _, pipe.last_heat_path = render_to_png(
             pipe.renderer_3d, "heat_sheet", pipe.view_png_encoder, heat_sheet_path(_mesh_name(p.mesh), pipe.visualize_name), images, heat,
             landmarks=pipe.heat_landmarks, colors=heat_colours(int(heat.shape[1])), floor=pipe.heat_floor, **_sheet_look(pipe))
     pipe._say(f"[Pipeline] heat sheet written to {pipe.last_heat_path}")
+
+
+def draw_surface_heat(pipe, p: Pass, images, heat):
+    """``visualize_surface``: the heatmaps of the pass laid on the resident mesh (``HipRenderer3D.surface_heat``), the mesh drawn
+    with those colours and the final landmarks as spheres (the report's branch colours, else blue).  Leaves ``last_surface_path``,
+    ``last_surface_heat`` and, for ``write_surface_mesh``, the mesh and its colours on the device."""
+    with pipe._timer.stage("visualize_surface"):
+        r3 = pipe.renderer_3d
+        nl = int(heat.shape[1])
+        res = r3.surface_heat(p.mesh, images, heat, np.asarray(p.rot, dtype=np.float64), landmarks=pipe.heat_landmarks,
+                              colors=heat_colours(nl), floor=pipe.heat_floor, depth_tol=pipe.surface_depth_tol)
+        landmarks, colours = finite_landmarks(p.landmarks, p.report.branch_colours() if p.report is not None else None)
+        _, pipe.last_surface_path = render_to_png(r3, "landmark_view", pipe.view_png_encoder,
+                                                  surface_path(_mesh_name(p.mesh), pipe.visualize_name), p.mesh, landmarks, first=True,
+                                                  size=pipe.visualize_size, colors=colours, vertex_colors=res["colors"])
+        peak_vertex = res["peak_vertex"].cpu().numpy()
+        final = np.asarray(p.landmarks, dtype=np.float64).reshape(-1, 3)
+        distance = np.full(nl, np.nan)
+        found = np.nonzero(peak_vertex >= 0)[0]
+        found = found[found < len(final)]
+        at = np.asarray(p.mesh.verts, dtype=np.float64).reshape(-1, 3)[peak_vertex[found]]
+        distance[found] = np.linalg.norm(final[found] - at, axis=1)  # (NaN where the final landmark is not finite)
+        pipe.last_surface_heat = {"peak_vertex": peak_vertex, "peak_score": res["peak_score"].cpu().numpy(), "distance": distance}
+        pipe._surface_mesh = (p.mesh, res["colors"])
+    pipe._say(f"[Pipeline] surface heat written to {pipe.last_surface_path}")
+
+
+def write_surface_mesh(pipe, path) -> Path:
+    """The mesh of the last ``visualize_surface`` picture with its colours as an OBJ with per-vertex colours (``write_obj``): only
+    the V x 4 colour bytes cross from the device."""
+    from ..utils.mesh_io import write_obj
+
+    if getattr(pipe, "_surface_mesh", None) is None:
+        raise ValueError("write_surface_mesh: no surface heat has been drawn (visualize_surface)")
+    mesh, colours = pipe._surface_mesh
+    path = Path(path)
+    write_obj(path, np.asarray(mesh.verts), np.asarray(mesh.tris), colors=colours.cpu().numpy()[:, :3])
+    return path
 
 
 def draw_ray_view(pipe, p: Pass, file_name, landmark_indices=None, view_indices=None, clip_to_mesh: bool = True):
@@ -218,7 +282,7 @@ def draw_ray_view(pipe, p: Pass, file_name, landmark_indices=None, view_indices=
 
 
 def draw(pipe, p: Pass) -> None:
-    """The one hook both paths call behind a prediction: landmark view, view sheet, heat sheet, in this order, and the pass kept
+    """The one hook both paths call behind a prediction: landmark view, view sheet, heat sheet, surface heat, in this order, and the pass kept
     for the ray view, which ``_after_prediction`` draws."""
     check(pipe)
     if p.landmarks is not None:
@@ -226,7 +290,11 @@ def draw(pipe, p: Pass) -> None:
             pipe._draw_landmark_view(p.mesh, p.landmarks, p.report)
         if pipe.visualize_sheet and p.images is not None:
             draw_view_sheet(pipe, p)
-        if pipe.visualize_heat and p.images is not None:
-            draw_heat_sheet(pipe, p)
+        if (pipe.visualize_heat or pipe.visualize_surface) and p.images is not None:
+            images, heat = pass_heatmaps(pipe, p)  # once, for both pictures
+            if pipe.visualize_heat:
+                draw_heat_sheet(pipe, p, images, heat)
+            if pipe.visualize_surface and p.draws:
+                draw_surface_heat(pipe, p, images, heat)
     if pipe._keep_ray_view and p.draws:
         pipe._ray_view = p

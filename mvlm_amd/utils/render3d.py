@@ -388,7 +388,7 @@ class HipRenderer3D:
         return poses, np.ascontiguousarray(frames, dtype=np.float32), lm, float(radius)
 
     def render_landmark_view_device(self, mesh: Mesh, landmarks, poses=None, size: int = 1024, frame="fit", radius=None,
-                                    colors=None, return_pixels: bool = False):
+                                    colors=None, return_pixels: bool = False, vertex_colors=None):
         """``render_landmark_view`` with the results left on the device: uint8 [n,S,S,4] RGBA (and int32 [n,NL] with
         ``return_pixels``).  Only enqueues work; ``check()`` reports a deferred failure."""
         import torch
@@ -397,26 +397,57 @@ class HipRenderer3D:
         n, nl = poses.shape[0], lm.shape[0]
         rgb, size = self._view_colours_and_size(colors, nl, size)
         dev = torch.device("cuda", self.ctx.device)
+        if vertex_colors is not None:
+            vertex_colors = self._vertex_colours(vertex_colors, mesh, dev)
         out = torch.empty((n, size, size, 4), dtype=torch.uint8, device=dev)
         pixels = torch.empty((n, nl), dtype=torch.int32, device=dev) if return_pixels else None
         rot = np.ascontiguousarray(view_rotations(poses), dtype=np.float64)
         handle = upload_mesh(self.ctx, mesh)
         self.ctx.bind_current_stream(torch, dev)
         self._push_render_mode()  # (the view reads the shading and the sub-pixel bits)
-        self.ctx.check(self.ctx.lib.mvlm_render_landmark_view(
-            self.ctx.handle, handle, _lib.as_ptr(rot, C.c_double), n, size, _lib.as_ptr(frames, C.c_float),
-            _lib.as_ptr(lm, C.c_double) if nl else None, nl, C.c_float(radius), None if rgb is None or nl == 0 else _lib.as_ptr(rgb, C.c_uint8),
-            C.c_void_p(out.data_ptr()), C.c_void_p(pixels.data_ptr()) if pixels is not None and nl else None), ValueError)
+        args = (self.ctx.handle, handle, _lib.as_ptr(rot, C.c_double), n, size, _lib.as_ptr(frames, C.c_float),
+                _lib.as_ptr(lm, C.c_double) if nl else None, nl, C.c_float(radius), None if rgb is None or nl == 0 else _lib.as_ptr(rgb, C.c_uint8),
+                C.c_void_p(out.data_ptr()), C.c_void_p(pixels.data_ptr()) if pixels is not None and nl else None)
+        if vertex_colors is None:
+            self.ctx.check(self.ctx.lib.mvlm_render_landmark_view(*args), ValueError)
+        else:
+            self.ctx.check(self.ctx.lib.mvlm_render_landmark_view_colored(*args, C.c_void_p(vertex_colors.data_ptr())), ValueError)
+            self._view_keepalive = vertex_colors  # (read by the enqueued kernels)
         return (out, pixels) if return_pixels else out
 
+    @staticmethod
+    def _vertex_colours(vertex_colors, mesh: Mesh, dev):
+        """``vertex_colors`` of the landmark view on the renderer's device: uint8 [V,4] (r g b and a byte that is not read, the layout
+        ``surface_heat`` leaves) or [V,3]; a numpy array is uploaded."""
+        import torch
+
+        if not hasattr(vertex_colors, "data_ptr"):
+            try:
+                vertex_colors = torch.from_numpy(np.ascontiguousarray(vertex_colors, dtype=np.uint8))
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"landmark view: vertex_colors is not a numeric array ({e})") from None
+        t = vertex_colors
+        if t.dtype != torch.uint8 or t.dim() != 2 or int(t.shape[0]) != mesh.n_verts or int(t.shape[1]) not in (3, 4):
+            raise ValueError(f"landmark view: vertex_colors must be uint8 [{mesh.n_verts},4] (or [{mesh.n_verts},3]), not "
+                             f"{t.dtype} {tuple(t.shape)}")
+        if t.is_cuda and t.device != dev:
+            raise ValueError(f"landmark view: vertex_colors live on {t.device}, the renderer on {dev}")
+        t = t.to(dev)
+        if int(t.shape[1]) == 3:
+            t = torch.cat([t, torch.full((mesh.n_verts, 1), 255, dtype=torch.uint8, device=dev)], dim=1)
+        return t.contiguous()
+
     def render_landmark_view(self, mesh: Mesh, landmarks, poses=None, size: int = 1024, frame="fit", radius=None, colors=None,
-                             return_pixels: bool = False):
+                             return_pixels: bool = False, vertex_colors=None):
         """The mesh with a shaded sphere at every landmark, as the reference's offscreen viewer draws it (utils/viewer.py with
         ``save=True``): uint8 [n,S,S,3], and with ``return_pixels`` also int32 [n,NL], the pixels each landmark's sphere won in
         each view (0: hidden there).  ``poses`` [n,3] degrees (rx, ry, rz), default one front view (viewer.py:45-55);
         ``landmarks`` [NL,3] in the mesh's coordinates; ``colors`` uint8 [NL,3], default blue; ``frame`` / ``radius``: see
-        ``landmark_view_arguments``.  One sample per pixel, whatever ``multisamples`` is ("Landmark view")."""
-        res = self.render_landmark_view_device(mesh, landmarks, poses, size, frame, radius, colors, return_pixels)
+        ``landmark_view_arguments``.  One sample per pixel, whatever ``multisamples`` is ("Landmark view").
+        ``vertex_colors`` uint8 [V,4] or [V,3] (a device tensor, e.g. ``surface_heat(...)["colors"]``, or a numpy array): the mesh is
+        drawn with these colours instead of its own colours or texture, unlit - byte for byte the view of a ``Mesh`` of the same
+        vertices and triangles with these colours and no texture."""
+        res = self.render_landmark_view_device(mesh, landmarks, poses, size, frame, radius, colors, return_pixels, vertex_colors)
         out, pixels = res if return_pixels else (res, None)
         image = out.cpu().numpy()[..., :3].copy()
         counts = pixels.cpu().numpy() if pixels is not None else None
@@ -723,6 +754,131 @@ class HipRenderer3D:
         ms = np.zeros(3, np.float32)
         self.ctx.check(self.ctx.lib.mvlm_heat_sheet_stage_ms(self.ctx.handle, _lib.as_ptr(ms, C.c_float)))
         return ms
+
+    # ---- surface heat (all views' heatmaps laid on the scan) ---------------------------------------------------
+    def surface_heat(self, mesh: Mesh, images, heat, rot, landmarks=None, colors=None, floor: float = 0.25, opacity: float = 0.75,
+                     depth_tol: int = 2, return_scores: bool = False) -> dict:
+        """All views' heatmaps laid on the scan (mvlm_surface_heat; DESIGN.md 5.1, "Surface heat").  ``images`` float32
+        [N,256,256,4] (``render_device``'s stack of ``mesh``), ``heat`` float32 [N,NL,256,256] (``HipPaulsenModel.heatmaps_device``'s)
+        - tensors on the renderer's device, or numpy arrays, which are uploaded; ``rot`` the views' rotations: float64 [N,3,3] /
+        [N,9] as a tensor or an array (``view_rotations``), or ``rotations_device()``'s handle.  Every vertex is carried into every
+        view as the render carried it; a view sees it when it lies at most ``depth_tol`` depth steps (0..255; one is 5.9 model units)
+        behind the view's depth plane, and then adds the share its heatmap value there has of its plane's peak.  A vertex's score
+        for a landmark is the mean of those shares over the views that see it.  Returns a dict of device tensors: ``colors`` uint8
+        [V,4] - per vertex the landmark of ``landmarks`` (None: all; else distinct ints in 0..NL-1) with the largest score, the
+        lowest index on a tie, laid over the vertex's own colour (its colour, else its texel, else grey 200) in its colour of
+        ``colors`` uint8 [NL,3] (default red) with opacity ``opacity`` * (score - ``floor``) / (1 - ``floor``), nothing at a score
+        <= ``floor``: what ``render_landmark_view(vertex_colors=)`` takes -, ``peak_vertex`` int32 [NL] (per landmark the vertex
+        of the largest score above 0, -1: none), ``peak_score`` float32 [NL], ``n_visible`` int32 [V], and with ``return_scores``
+        ``scores`` float32 [V,NL].  Only enqueues work; every bad argument is a ValueError that starts with "surface heat:",
+        raised before any launch."""
+        import torch
+
+        label = "surface heat"
+        picked = None
+        if landmarks is not None:
+            try:
+                picked = [operator.index(k) for k in landmarks]
+            except TypeError:
+                raise ValueError(f"{label}: landmarks must be None or a sequence of integers, not {landmarks!r}") from None
+            if any(isinstance(k, (bool, np.bool_)) for k in landmarks):
+                raise ValueError(f"{label}: landmarks must be None or a sequence of integers, not {landmarks!r}")
+            if len(set(picked)) != len(picked):
+                raise ValueError(f"{label}: landmarks must be distinct, not {picked!r}")
+        try:
+            floor, opacity = float(floor), float(opacity)
+        except (TypeError, ValueError):
+            raise ValueError(f"{label}: floor and opacity must be numbers, not {floor!r} and {opacity!r}") from None
+        if not (np.isfinite(floor) and 0.0 <= floor < 1.0):
+            raise ValueError(f"{label}: floor must be finite and in [0, 1), not {floor}")
+        if not (np.isfinite(opacity) and 0.0 < opacity <= 1.0):
+            raise ValueError(f"{label}: opacity must be finite and in (0, 1], not {opacity}")
+        if isinstance(depth_tol, (bool, np.bool_)) or not isinstance(depth_tol, (int, np.integer)) or not 0 <= depth_tol <= 255:
+            raise ValueError(f"{label}: depth_tol must be an integer in 0..255, not {depth_tol!r}")
+        if not isinstance(mesh, Mesh):
+            raise ValueError(f"{label}: mesh must be a Mesh, not {type(mesh).__name__}")
+        if mesh.n_tris == 0:
+            raise ValueError(f"{label}: a point cloud is not supported here (the mesh has no triangles)")
+        dev = torch.device("cuda", self.ctx.device)
+        images = self._sheet_tensor(images, "images", torch.float32, dev, lambda s: len(s) == 4 and s[0] >= 1 and tuple(s[1:]) == (256, 256, 4),
+                                    "float32 [N,256,256,4]", label)
+        n = int(images.shape[0])
+        heat = self._sheet_tensor(heat, "heat", torch.float32, dev,
+                                  lambda s: len(s) == 4 and s[0] == n and s[1] >= 1 and tuple(s[2:]) == (256, 256),
+                                  f"float32 [{n},NL,256,256]", label)
+        nl, nv = int(heat.shape[1]), int(mesh.n_verts)
+        if nl > 65536 or n * nl > 32768:
+            raise ValueError(f"{label}: at most 65536 landmarks and 32768 planes (views x landmarks) per call, not {n} x {nl}")
+        if nv * nl > 1 << 28:
+            raise ValueError(f"{label}: at most 268435456 scores (vertices x landmarks) per call, not {nv} x {nl}")
+        if heat.data_ptr() % 16 or images.data_ptr() % 16:
+            raise ValueError(f"{label}: images and heat must be 16-byte aligned on the device")
+        if isinstance(rot, _DevicePointer):
+            rot_keep = rot
+        else:
+            if hasattr(rot, "data_ptr"):
+                if rot.dtype != torch.float64 or rot.numel() != n * 9:
+                    raise ValueError(f"{label}: rot must be float64 [{n},3,3], not {rot.dtype} {tuple(rot.shape)}")
+                rot_host = rot.detach().cpu().numpy()
+            else:
+                try:
+                    rot_host = np.ascontiguousarray(rot, dtype=np.float64)
+                except (TypeError, ValueError) as e:
+                    raise ValueError(f"{label}: rot is not a numeric array ({e})") from None
+                if rot_host.size != n * 9:
+                    raise ValueError(f"{label}: rot must be float64 [{n},3,3], not {rot_host.shape}")
+            if not np.isfinite(rot_host).all():
+                raise ValueError(f"{label}: non-finite rotation")
+            rot_keep = rot.to(dev).contiguous() if hasattr(rot, "data_ptr") else torch.from_numpy(rot_host.reshape(n, 9).copy()).to(dev)
+        sel = None
+        if picked is not None:
+            if any(not 0 <= k < nl for k in picked):
+                raise ValueError(f"{label}: landmarks must lie in 0..{nl - 1}, not {picked!r}")
+            sel = np.zeros(nl, np.uint8)
+            sel[picked] = 1
+        if colors is not None:
+            if hasattr(colors, "data_ptr"):
+                colors = colors.detach().cpu().numpy()
+            try:
+                colors = np.ascontiguousarray(colors, dtype=np.uint8)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"{label}: colors is not a numeric array ({e})") from None
+            if colors.shape != (nl, 3):
+                raise ValueError(f"{label}: colors must be uint8 [{nl},3], not {colors.shape}")
+        out = {"colors": torch.empty((nv, 4), dtype=torch.uint8, device=dev),
+               "peak_vertex": torch.empty((nl,), dtype=torch.int32, device=dev),
+               "peak_score": torch.empty((nl,), dtype=torch.float32, device=dev),
+               "n_visible": torch.empty((nv,), dtype=torch.int32, device=dev)}
+        if return_scores:
+            out["scores"] = torch.empty((nv, nl), dtype=torch.float32, device=dev)
+        self.ctx.bind_current_stream(torch, dev)
+        handle = upload_mesh(self.ctx, mesh)
+        self._push_render_mode()  # (the positions are the render's: its sub-pixel bits)
+        self.ctx.check(self.ctx.lib.mvlm_surface_heat(
+            self.ctx.handle, handle, C.c_void_p(rot_keep.data_ptr()), C.c_void_p(images.data_ptr()), C.c_void_p(heat.data_ptr()), n, nl,
+            _lib.as_ptr(sel, C.c_uint8) if sel is not None else None, _lib.as_ptr(colors, C.c_uint8) if colors is not None else None,
+            C.c_double(floor), C.c_double(opacity), int(depth_tol), C.c_void_p(out["colors"].data_ptr()),
+            C.c_void_p(out["scores"].data_ptr()) if return_scores else None, C.c_void_p(out["n_visible"].data_ptr()),
+            C.c_void_p(out["peak_vertex"].data_ptr()), C.c_void_p(out["peak_score"].data_ptr())), ValueError)
+        self._surface_keepalive = (images, heat, rot_keep)  # (read by the enqueued kernels)
+        return out
+
+    def surface_heat_stage_ms(self) -> np.ndarray:
+        """Milliseconds of the last surface heat's stages under render profiling: peak, back-projection, paint."""
+        ms = np.zeros(3, np.float32)
+        self.ctx.check(self.ctx.lib.mvlm_surface_heat_stage_ms(self.ctx.handle, _lib.as_ptr(ms, C.c_float)))
+        return ms
+
+    def release_surface_heat(self) -> None:
+        """Free the scratch ``surface_heat`` keeps in the context (its score table above all: 4 bytes per vertex and landmark);
+        waits for the stream.  The next call allocates again."""
+        self.ctx.check(self.ctx.lib.mvlm_surface_heat_release(self.ctx.handle))
+
+    def scratch_bytes(self, prefix: str = "") -> int:
+        """Bytes of the context's internal scratch whose names start with ``prefix`` ("backproject": the surface heat's)."""
+        n = C.c_size_t()
+        self.ctx.check(self.ctx.lib.mvlm_scratch_bytes(self.ctx.handle, prefix.encode(), C.byref(n)))
+        return int(n.value)
 
     # ---- PNG on the device -------------------------------------------------------------------
     @staticmethod

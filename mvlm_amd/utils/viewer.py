@@ -12,7 +12,7 @@ from pathlib import Path
 
 import numpy as np
 
-__all__ = ["LandmarkViewer", "RayVisualizer", "RayVisualizerConfig", "view_path", "view_sheet_path", "heat_sheet_path", "HEAT_PALETTE",
+__all__ = ["LandmarkViewer", "RayVisualizer", "RayVisualizerConfig", "view_path", "view_sheet_path", "heat_sheet_path", "surface_path", "HEAT_PALETTE",
            "heat_colours", "write_view_png"]
 
 
@@ -34,6 +34,11 @@ def view_sheet_path(filename, pname: str | None = None) -> Path:
 def heat_sheet_path(filename, pname: str | None = None) -> Path:
     """``visualization/<stem>[_<pname>]_heat.png`` relative to the working directory: the heat sheet beside the view sheet."""
     return _picture_path(filename, pname, "_heat")
+
+
+def surface_path(filename, pname: str | None = None) -> Path:
+    """``visualization/<stem>[_<pname>]_surface.png`` relative to the working directory: the surface heat beside the heat sheet."""
+    return _picture_path(filename, pname, "_surface")
 
 
 def select_rays(n_landmarks: int, n_views: int, landmark_indices=None, view_indices=None) -> tuple:
