@@ -120,7 +120,9 @@ int mvlm_mesh_upload_colors(mvlm_ctx* ctx, mvlm_mesh* mesh, const uint8_t* rgb_h
  *   - mvlm_project_to_surface returns the NEAREST POINT's own coordinates (float64 distances, lowest id on ties, non-finite
  *     points never, a non-finite landmark passed through).
  *   - refused with an argument error before anything is launched: mvlm_render with shading 1 (geometry) or 4 multisamples,
- *     mvlm_render_landmark_view, mvlm_render_ray_view, mvlm_clip_rays_to_mesh, mvlm_surface_attach.
+ *     mvlm_render_landmark_view, mvlm_render_ray_view, mvlm_clip_rays_to_mesh, mvlm_surface_attach.  These refusals stand for
+ *     every point mesh; the way round them is to give the cloud triangles first (mvlm_mesh_triangulate_points, below) and to
+ *     upload the result as an ordinary mesh.
  * The radius r (model units) is per mesh: at upload the automatic one, mvlm_points_auto_radius of the uploaded points;
  * mvlm_mesh_set_point_radius replaces it - an error outside 0.75..8 pixels (0.87890625..9.375 model units) or on a mesh with
  * triangles; mvlm_mesh_point_radius reads it (non-zero for a mesh with triangles). */
@@ -163,6 +165,31 @@ int mvlm_mesh_estimate_normals(mvlm_ctx* ctx, mvlm_mesh* mesh, int32_t* neighbor
 int mvlm_mesh_copy_normals(mvlm_ctx* ctx, const mvlm_mesh* mesh, float* normals_host);
 int mvlm_normals_stage_ms(mvlm_ctx* ctx, float* ms3);
 int mvlm_normals_get_stats(mvlm_ctx* ctx, unsigned long long* stats3);
+/* ---- a triangle surface for a point cloud (csrc/cloud_mesh_math.h, DESIGN.md 5.1 "Point clouds") -------------------------------
+ * The refusals above stand for every cloud.  The way round them is to give the cloud triangles: mvlm_mesh_triangulate_points
+ * computes, on the device, a triangle list over the cloud's points, which the caller uploads as an ordinary mesh (the same points,
+ * these triangles) - and that mesh has everything a mesh has (HipRenderer3D.triangulate_point_cloud, Pipeline(point_surface="mesh")).
+ *   mvlm_mesh_triangulate_points  cloud: a point mesh WITH normals (mvlm_mesh_upload_normals or mvlm_mesh_estimate_normals);
+ *                             neighbors_dev i32[V,16]: the table mvlm_mesh_estimate_normals left for THIS cloud.  All in float64:
+ *                             every point is shifted by 1/256 of its nearest-neighbour distance in a direction hashed from its id
+ *                             (exact ties of a regular grid break the same way everywhere); the star of a point p is the set of
+ *                             pairs {a, b} of its neighbours that are a hull edge of the neighbours' tangent-plane positions
+ *                             inverted about p (w = q / |q|^2: "empty circle through p" becomes "hull edge"), at most 16; the triangle
+ *                             {i < j < k} is emitted iff {j,k} is in i's star, {i,k} in j's, {i,j} in k's and, on the unshifted
+ *                             points, |cross|^2 * 1024 > (longest edge^2)^2 (height above 1/32 of the longest edge).  Rows (i, j, k)
+ *                             ascending, the winding unspecified, no row touches a non-finite point; the sign of a normal does not
+ *                             matter and the bytes are the same from run to run (no atomics).  n_tris_dev i32[1] always receives
+ *                             the full count; tris_dev i32[cap,3] receives the rows below cap, none beyond; tris_dev == NULL only
+ *                             counts.  Only enqueues work; leaves the cloud's device copy and the render's key plane as they were.
+ *                             A mesh with triangles, a cloud without normals, NULL neighbors_dev or n_tris_dev, a negative cap or
+ *                             more than 67108864 points set an error that starts with "triangulate points:" and launch nothing.
+ *                             Meant for scanner-like sampling (a depth camera's grid, a structured-light scan), not a general
+ *                             surface reconstruction: where 16 neighbours do not surround a point, its star has gaps.
+ *   mvlm_cloud_mesh_stage_ms  ms3: star (with the shift), count + scan, emit of the last triangulation made while
+ *                             mvlm_render_set_profiling was on; waits for the stream. */
+int mvlm_mesh_triangulate_points(mvlm_ctx* ctx, const mvlm_mesh* cloud, const int32_t* neighbors_dev, int32_t* tris_dev, long long cap,
+                                 int32_t* n_tris_dev);
+int mvlm_cloud_mesh_stage_ms(mvlm_ctx* ctx, float* ms3);
 void mvlm_mesh_free(mvlm_ctx* ctx, mvlm_mesh* mesh);
 
 /* ---- JPEG texture decoded on the device (replaces vtkJPEGReader in obj_to_actor, utils3d.py:28-34 / :42-48, and in

@@ -103,6 +103,12 @@ def build_parser() -> argparse.ArgumentParser:
                         help="where a point cloud's normals come from under a geometry image mode: 'file' takes the scan's own (a "
                              "cloud without is refused), 'estimate' has the GPU estimate them from each point's 16 nearest neighbours "
                              "(DESIGN.md 5.1)")
+    parser.add_argument("--point-surface", choices=("splats", "mesh"), default="splats",
+                        help="what a scan without faces (a point cloud) is to the pipeline: 'splats' renders it as splats, snaps "
+                             "to its nearest point and refuses what needs triangles (--report, --visualize-img, --visualize-rays, "
+                             "--visualize-surface, --multisamples 4); 'mesh' has the GPU give it triangles first - a local Delaunay "
+                             "surface over each point's 16 nearest neighbours, for scanner-like sampling - and then treats it as any "
+                             "mesh; --point-radius and --point-normals are then not consulted (DESIGN.md 5.1)")
     parser.add_argument("--png-encoder", choices=("host", "device"), default="host",
                         help="who makes the PNG files of --visualize-img and --visualize-rays: 'host' copies the picture to the host "
                              "and encodes it with Pillow; 'device' filters and compresses it on the GPU and copies only the file's "
@@ -171,6 +177,8 @@ def main(argv=None) -> int:
         extra["point_radius"] = args.point_radius
     if args.point_normals != "file":
         extra["point_normals"] = args.point_normals
+    if args.point_surface != "splats":
+        extra["point_surface"] = args.point_surface
     if args.png_encoder != "host":
         extra["view_png_encoder"] = args.png_encoder
     if args.config is not None:

@@ -53,6 +53,8 @@ SIGNATURES = {
     "mvlm_mesh_copy_normals": (C.c_int, [C.c_void_p, C.c_void_p, c_float_p]),
     "mvlm_normals_stage_ms": (C.c_int, [C.c_void_p, c_float_p]),
     "mvlm_normals_get_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "mvlm_mesh_triangulate_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "mvlm_cloud_mesh_stage_ms": (C.c_int, [C.c_void_p, c_float_p]),
     "mvlm_mesh_free": (None, [C.c_void_p, C.c_void_p]),
     "mvlm_jpeg_info": (C.c_int, [c_uint8_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_int]),
     "mvlm_mesh_upload_jpeg": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_int, c_int32_p, C.c_int, c_uint8_p, C.c_size_t,

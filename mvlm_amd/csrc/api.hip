@@ -93,6 +93,8 @@ extern "C" void mvlm_ctx_destroy(mvlm_ctx* ctx) {
         if (e) hipEventDestroy(e);
     for (auto e : ctx->normals_events)
         if (e) hipEventDestroy(e);
+    for (auto e : ctx->cloudmesh_events)
+        if (e) hipEventDestroy(e);
     for (auto e : ctx->cnn.sync_events)
         if (e) hipEventDestroy(e);
     ctx->cnn.drop_graphs();

@@ -365,6 +365,9 @@ struct mvlm_ctx {
     // likewise round the three stages of a cloud's normal estimate (cloud_normals.hip: grid build, search, solve; mvlm_normals_stage_ms)
     std::vector<hipEvent_t> normals_events;
     bool normals_events_valid = false;
+    // likewise round the three stages of a cloud's triangulation (cloud_mesh.hip: star, count + scan, emit; mvlm_cloud_mesh_stage_ms)
+    std::vector<hipEvent_t> cloudmesh_events;
+    bool cloudmesh_events_valid = false;
     bool render_profiling = false;        // mvlm_render_set_profiling: HIP events around each render's kernels
     std::vector<RenderProfileRec> render_prof;
     std::vector<hipEvent_t> render_events;

@@ -92,6 +92,7 @@ class Pipeline(abc.ABC):
     # (also for an object that never went through __init__: the picture rules and predict_mesh_device read them)
     visualize_heat = visualize_surface = _keep_ray_view = False
     heat_landmarks = None
+    point_surface = "splats"
 
     def __init__(self, render_image_stack: bool = False, offscreen: bool = True, n_views: int = 8,
                  render_image_folder: Path | None = None, visualize_rays: bool = False,
@@ -101,7 +102,15 @@ class Pipeline(abc.ABC):
                  visualize_rays_img: bool = False, visualize_rays_poses=((0, 0, 0), (0, 60, 0), (0, -60, 0)),
                  view_png_encoder: str = "host", point_radius: float | None = None, visualize_sheet: bool = False,
                  sheet_scale: int = 1, visualize_heat: bool = False, heat_landmarks=None, heat_floor: float = 0.25,
-                 point_normals: str = "file", visualize_surface: bool = False, surface_depth_tol: int = 2):
+                 point_normals: str = "file", visualize_surface: bool = False, surface_depth_tol: int = 2,
+                 point_surface: str = "splats"):
+        from ..utils.render3d import check_point_surface
+
+        # point_surface: what a scan without faces - a point cloud - is to every entry that takes scans: "splats" (the default) - it
+        # is rendered as splats, snapped to its nearest point, and what needs triangles is refused (_check_cloud); "mesh" - it is
+        # replaced by its triangulation (HipRenderer3D.triangulate_point_cloud; DESIGN.md 5.1, "Point clouds") after pre-alignment,
+        # and everything downstream sees an ordinary mesh; point_radius and point_normals are then not consulted
+        self.point_surface = check_point_surface(point_surface)
         self.render_image_stack = render_image_stack
         self.render_image_folder = render_image_folder
         self.n_views = n_views
@@ -158,7 +167,7 @@ class Pipeline(abc.ABC):
         # "estimate" (a cloud without gets them estimated on the device) (HipRenderer3D)
         self.renderer_3d = HipRenderer3D(image_size=(256, 256), offscreen=offscreen, n_views=n_views, device=device,
                                          verbose=verbose, multisamples=render_multisamples, point_radius=point_radius,
-                                         point_normals=point_normals)
+                                         point_normals=point_normals, point_surface=point_surface)
         self.estimator_3d = HipEstimator3D(device=device, verbose=verbose)
         self.predictor_2d = None  # will be assigned externally
 
@@ -196,6 +205,8 @@ class Pipeline(abc.ABC):
         not have is said here, before the GPU section, instead of by the call that would meet it."""
         if mesh is None or getattr(mesh, "n_tris", 1) != 0:
             return
+        if getattr(self, "point_surface", "splats") == "mesh":
+            return  # (the GPU section replaces the cloud by its triangulation, _surface: nothing downstream meets a cloud)
         name = getattr(mesh, "path", None) or "the mesh"
         if self.landmark_report:
             raise ValueError(f"{name} is a point cloud: landmark_report is not supported (the surface attachment needs triangles)")
@@ -214,6 +225,16 @@ class Pipeline(abc.ABC):
                 and getattr(r3, "point_normals", "file") != "estimate"):
             raise ValueError(f"{name} is a point cloud without normals: a geometry image mode needs them (geometry shading of a point "
                              'cloud: point_normals="estimate" / --point-normals estimate has them estimated)')
+
+    def _surface(self, mesh):
+        """``mesh`` itself, or - a point cloud under ``point_surface="mesh"`` - its triangulation (made on the launch stream, so in
+        the GPU section and never on a reader thread; kept on the cloud object)."""
+        if self.point_surface != "mesh" or mesh is None or getattr(mesh, "n_tris", 1) != 0:
+            return mesh
+        make = getattr(self.renderer_3d, "triangulate_point_cloud", None)
+        if not callable(make):
+            raise ValueError('point_surface="mesh" needs a renderer that triangulates a point cloud (HipRenderer3D.triangulate_point_cloud)')
+        return make(mesh)
 
     def _to_original(self, mesh, landmarks):
         """Landmarks found on a pre-aligned mesh -> the file's own coordinates (utils3d.py:505-527)."""
@@ -369,6 +390,7 @@ class Pipeline(abc.ABC):
         import torch
 
         r3, p2, e3 = self.renderer_3d, self.predictor_2d, self.estimator_3d
+        mesh = self._surface(mesh)
         self._check_cloud(mesh)
         drawing = pictures.wanted(self)  # (the one question the hot path asks about the pictures)
         if drawing:
@@ -575,7 +597,7 @@ class Pipeline(abc.ABC):
         k = len(meshes)
         from ..utils.prealign import aligned
 
-        meshes = [aligned(m, self.pre_align) for m in meshes]
+        meshes = [self._surface(aligned(m, self.pre_align)) for m in meshes]
         # (a point cloud among them: the scans go one by one - grouping clouds is not built)
         if not self._groupable(k) or any(m.n_tris == 0 for m in meshes):
             out = []
@@ -734,6 +756,7 @@ class Pipeline(abc.ABC):
             mesh = self.renderer_3d.load_mesh(file_name, load_texture=self._texture_needed())
         else:
             mesh = aligned(mesh, self.pre_align)
+        mesh = self._surface(mesh)
         sharded = self.shard_views and parallel.is_distributed()
         if sharded:
             rank, _ = parallel.rank_world()

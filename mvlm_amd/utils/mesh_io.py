@@ -49,6 +49,9 @@ class Mesh:
     # have them estimated on the device (HipRenderer3D(point_normals="estimate"), estimate_point_normals), which fills this
     # field.  A mesh with triangles keeps them and renders as ever: its geometry plane comes from the triangles.
     normals: np.ndarray | None = None
+    # [V] int32, on the triangle mesh that HipRenderer3D.triangulate_point_cloud makes of a point cloud: the cloud's point each
+    # vertex is (the cloud's non-finite points are left out, the others keep their order).  None on every other mesh.
+    point_ids: np.ndarray | None = None
 
     @property
     def n_verts(self) -> int:

@@ -75,6 +75,14 @@ def _view_rotations_uncached(t: np.ndarray, n: int) -> np.ndarray:
 
 
 POINT_NORMALS = ("file", "estimate")
+POINT_SURFACES = ("splats", "mesh")
+
+
+def check_point_surface(value) -> str:
+    """``point_surface`` of a renderer or a pipeline: "splats" or "mesh"."""
+    if value not in POINT_SURFACES:
+        raise ValueError(f"point_surface must be 'splats' or 'mesh', not {value!r}")
+    return value
 
 
 def upload_mesh(ctx: "_lib.Context", mesh: Mesh, normals: str | None = None) -> C.c_void_p:
@@ -234,7 +242,7 @@ class HipRenderer3D:
                  min_z_angle: int = -20, max_z_angle: int = 20, min_scale: float = 1.4, max_scale: float = 1.9,
                  min_tx: int = -20, max_tx: int = 20, min_ty: int = -20, max_ty: int = 20, device: int = 0,
                  verbose: bool = True, shading: str = "texture", subpixel_bits: int = 8, multisamples: int = 0,
-                 point_radius: float | None = None, point_normals: str = "file"):
+                 point_radius: float | None = None, point_normals: str = "file", point_surface: str = "splats"):
         if tuple(image_size) != (256, 256):
             raise ValueError("the HIP renderer is built for 256x256 views (general_pipeline.py:57)")
         self.n_views = n_views
@@ -270,6 +278,9 @@ class HipRenderer3D:
         if point_normals not in POINT_NORMALS:
             raise ValueError(f"point_normals must be 'file' or 'estimate', not {point_normals!r}")
         self.point_normals = point_normals
+        # what the file entries (multiview_render, multiview_render_device) make of a point cloud: "splats" - the cloud as it is;
+        # "mesh" - its triangulation (triangulate_point_cloud), an ordinary mesh.  render_device draws the Mesh it is handed.
+        self.point_surface = check_point_surface(point_surface)
         # "pre-align" block of a Deep-MVLM config (utils/prealign.py; utils3d.py:465-503): applied to every mesh this
         # renderer loads, the mesh handle it returns carries the matrix (Mesh.to_original)
         self.pre_align: dict | None = None
@@ -950,6 +961,70 @@ class HipRenderer3D:
         self.ctx.check(self.ctx.lib.mvlm_normals_stage_ms(self.ctx.handle, _lib.as_ptr(ms, C.c_float)))
         return ms
 
+    # ---- a triangle surface for a point cloud ---------------------------------------------------
+    def triangulate_point_cloud(self, mesh: Mesh) -> Mesh:
+        """A point cloud -> a new ``Mesh`` with triangles over its points (mvlm_mesh_triangulate_points; DESIGN.md 5.1, "Point
+        clouds"): every point votes for the Delaunay triangles of its 16 nearest neighbours in its tangent plane, a triangle is
+        kept where its three corners agree and it is no sliver.  The neighbour table is the device's (mvlm_mesh_estimate_normals);
+        the normals are ``mesh.normals`` where the cloud has them, else that estimate's.  The result holds the cloud's finite points
+        in their order (triangle indices renumbered), their colours, the cloud's ``path`` and ``to_original``, and ``point_ids``,
+        int32: the cloud's point behind every vertex.  It has no ``point_radius`` and no ``normals`` - a mesh with triangles takes
+        neither.  Made once per cloud object and kept on it.  Meant for scanner-like sampling, not a general reconstruction.
+        ValueError for a mesh with triangles."""
+        import torch
+
+        if mesh.n_tris != 0:
+            raise ValueError("triangulate_point_cloud: the mesh has triangles (a surface is built for a point cloud)")
+        kept = getattr(mesh, "_triangulation", None)
+        if kept is not None:
+            return kept
+        dev = torch.device("cuda", self.ctx.device)
+        ctx = self.ctx
+        handle = upload_mesh(ctx, mesh)
+        ctx.bind_current_stream(torch, dev)
+        n_points = mesh.n_verts
+        table = torch.empty((n_points, 16), dtype=torch.int32, device=dev)
+        ctx.check(ctx.lib.mvlm_mesh_estimate_normals(ctx.handle, handle, C.c_void_p(table.data_ptr())), ValueError)
+        key = id(ctx)
+        mesh._device[key] = mesh._device[key][:4] + ("estimated",)
+        if mesh.normals is not None:  # the cloud's own normals replace the estimate (the table stays)
+            mesh._device[key] = mesh._device[key][:4] + (_send_point_normals(ctx, handle, mesh, "file"),)
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+        cap = 3 * n_points + 1024
+        tris = torch.empty((cap, 3), dtype=torch.int32, device=dev)
+        for _ in range(2):
+            ctx.check(ctx.lib.mvlm_mesh_triangulate_points(ctx.handle, handle, C.c_void_p(table.data_ptr()), C.c_void_p(tris.data_ptr()),
+                                                           C.c_longlong(cap), C.c_void_p(count.data_ptr())), ValueError)
+            n_tris = int(count.item())
+            if n_tris <= cap:
+                break
+            cap = n_tris  # (more than three triangles a point: once more, with room for all of them)
+            tris = torch.empty((cap, 3), dtype=torch.int32, device=dev)
+        tris = tris[:n_tris].cpu().numpy()
+        verts = np.ascontiguousarray(mesh.verts, dtype=np.float32).reshape(-1, 3)
+        finite = np.isfinite(verts).all(axis=1)
+        point_ids = np.nonzero(finite)[0].astype(np.int32)
+        renumber = (np.cumsum(finite) - 1).astype(np.int32)  # (no triangle touches a non-finite point)
+        out = Mesh(np.ascontiguousarray(verts[finite]), np.ascontiguousarray(renumber[tris].reshape(-1, 3), dtype=np.int32), path=mesh.path,
+                   to_original=mesh.to_original,
+                   colors=None if mesh.colors is None else np.ascontiguousarray(np.asarray(mesh.colors)[finite]), point_ids=point_ids)
+        if hasattr(mesh, "_colors_wanted"):
+            out._colors_wanted = mesh._colors_wanted
+        mesh._triangulation = out
+        return out
+
+    def surface_of(self, mesh: Mesh) -> Mesh:
+        """``mesh`` itself, or - for a point cloud under ``point_surface="mesh"`` - its triangulation."""
+        if self.point_surface == "mesh" and mesh is not None and getattr(mesh, "n_tris", 1) == 0:
+            return self.triangulate_point_cloud(mesh)
+        return mesh
+
+    def cloud_mesh_stage_ms(self) -> np.ndarray:
+        """Milliseconds of the last triangulation's stages under render profiling: star (with the shift), count + scan, emit."""
+        ms = np.zeros(3, np.float32)
+        self.ctx.check(self.ctx.lib.mvlm_cloud_mesh_stage_ms(self.ctx.handle, _lib.as_ptr(ms, C.c_float)))
+        return ms
+
     def rotations_device(self):
         """The last render's rotation table where the rasteriser keeps it on the device (f64[N,9]; valid until this context's
         next render): an object with ``data_ptr()`` that ``HipEstimator3D.lines_device(rot_dev=...)`` takes - the rays of the
@@ -993,7 +1068,7 @@ class HipRenderer3D:
         if self.verbose:
             print("Render [0] - Prepare", f"{time.time() - t:08.6f} s")
         transformation_stack = self.generate_3d_transformations()
-        mesh = self.load_mesh(file_name, load_texture=load_texture)
+        mesh = self.surface_of(self.load_mesh(file_name, load_texture=load_texture))
         image_stack = self.render_device(mesh, transformation_stack).cpu().numpy()
         self.check()
         return image_stack, transformation_stack, mesh
@@ -1058,7 +1133,7 @@ class HipRenderer3D:
 
     def multiview_render_device(self, file_or_mesh, transformation_stack=None):
         """Same, but the image stack stays in HBM (used by the fused pipeline path)."""
-        mesh = file_or_mesh if isinstance(file_or_mesh, Mesh) else self.load_mesh(self._check_file(file_or_mesh))
+        mesh = file_or_mesh if isinstance(file_or_mesh, Mesh) else self.surface_of(self.load_mesh(self._check_file(file_or_mesh)))
         if transformation_stack is None:
             transformation_stack = self.generate_3d_transformations()
         return self.render_device(mesh, transformation_stack), transformation_stack, mesh

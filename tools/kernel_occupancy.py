@@ -9,7 +9,8 @@
                                          kernel_occupancy_view.json, kernel_occupancy_rays.json,
                                          kernel_occupancy_png.json, kernel_occupancy_points.json,
                                          kernel_occupancy_sheet.json, kernel_occupancy_heat.json,
-                                         kernel_occupancy_normals.json, kernel_occupancy_backproject.json) from the build
+                                         kernel_occupancy_normals.json, kernel_occupancy_backproject.json,
+                                         kernel_occupancy_cloudmesh.json) from the build
 
 A convolution tile's rate depends on how many workgroups a CU holds, i.e. on which side of 168 / 128 / 102 ... registers the
 compiler lands - and every epilogue kind compiled into a tile moves that number (round 4: two new kinds took the 80-row tile
@@ -32,7 +33,8 @@ kernels of the view sheet (build/sheet/, tests/golden/kernel_occupancy_sheet.jso
 kernels of the heat sheet (build/heat/, tests/golden/kernel_occupancy_heat.json, tests/test_heat_occupancy.py) and the kernels of a
 cloud's normals - the estimate and the tile stage that shades with them - (build/normals/,
 tests/golden/kernel_occupancy_normals.json, tests/test_normals_occupancy.py) and the three kernels of the surface heat
-(build/backproject/, tests/golden/kernel_occupancy_backproject.json, tests/test_backproject_occupancy.py)."""
+(build/backproject/, tests/golden/kernel_occupancy_backproject.json, tests/test_backproject_occupancy.py) and the kernels of a
+cloud's triangulation (build/cloudmesh/, tests/golden/kernel_occupancy_cloudmesh.json, tests/test_cloudmesh_occupancy.py)."""
 import json
 import re
 import subprocess
@@ -57,6 +59,7 @@ SHEET_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_sheet.json"
 HEAT_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_heat.json"
 NORMALS_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_normals.json"
 BACKPROJECT_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_backproject.json"
+CLOUDMESH_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_cloudmesh.json"
 BUILD = REPO / "mvlm_amd" / "csrc" / "build"
 
 
@@ -105,10 +108,11 @@ if __name__ == "__main__":
                                 (WINO_TABLE, BUILD / "wino"), (WINO4_TABLE, BUILD / "wino4"), (WINO4W_TABLE, BUILD / "wino4w"), (REPORT_TABLE, BUILD / "report"),
                                 (VIEW_TABLE, BUILD / "view"), (RAYS_TABLE, BUILD / "rays"), (PNG_TABLE, BUILD / "png"),
                                 (POINTS_TABLE, BUILD / "points"), (SHEET_TABLE, BUILD / "sheet"), (HEAT_TABLE, BUILD / "heat"),
-                                (NORMALS_TABLE, BUILD / "normals"), (BACKPROJECT_TABLE, BUILD / "backproject")):
+                                (NORMALS_TABLE, BUILD / "normals"), (BACKPROJECT_TABLE, BUILD / "backproject"),
+                                (CLOUDMESH_TABLE, BUILD / "cloudmesh")):
         t = build_table(objdir)
         if "--write" in sys.argv:
-            fields = ("waves_per_simd", "spilled", "scratch") if table_path in (VIEW_TABLE, RAYS_TABLE, PNG_TABLE, POINTS_TABLE, SHEET_TABLE, HEAT_TABLE, NORMALS_TABLE, BACKPROJECT_TABLE) else ("waves_per_simd", "spilled")
+            fields = ("waves_per_simd", "spilled", "scratch") if table_path in (VIEW_TABLE, RAYS_TABLE, PNG_TABLE, POINTS_TABLE, SHEET_TABLE, HEAT_TABLE, NORMALS_TABLE, BACKPROJECT_TABLE, CLOUDMESH_TABLE) else ("waves_per_simd", "spilled")
             table_path.write_text(json.dumps({k: {f: v[f] for f in fields} for k, v in t.items()}, indent=1) + "\n")
             print(f"{len(t)} kernels -> {table_path}")
         else:
