@@ -83,24 +83,12 @@ extern "C" void mvlm_ctx_destroy(mvlm_ctx* ctx) {
         if (e) hipEventDestroy(e);
     for (auto e : ctx->render_events)
         if (e) hipEventDestroy(e);
-    for (auto e : ctx->view_events)
-        if (e) hipEventDestroy(e);
-    for (auto e : ctx->png_events)
-        if (e) hipEventDestroy(e);
-    for (auto e : ctx->heat_events)
-        if (e) hipEventDestroy(e);
-    for (auto e : ctx->points_events)
-        if (e) hipEventDestroy(e);
-    for (auto e : ctx->normals_events)
-        if (e) hipEventDestroy(e);
-    for (auto e : ctx->cloudmesh_events)
-        if (e) hipEventDestroy(e);
     for (auto e : ctx->cnn.sync_events)
         if (e) hipEventDestroy(e);
     ctx->cnn.drop_graphs();
     if (ctx->cnn.side_stream) hipStreamDestroy(ctx->cnn.side_stream);
     if (ctx->cnn.capture_stream) hipStreamDestroy(ctx->cnn.capture_stream);
-    delete ctx;
+    delete ctx;  // (and with it every feature's StageClock and its events: the device is current, above)
 }
 
 // The calling thread's last failure on this context (valid until that thread's next failing call); a thread without
@@ -678,11 +666,7 @@ extern "C" int mvlm_points_get_stats(mvlm_ctx* ctx, unsigned long long* covered,
 extern "C" int mvlm_points_stage_ms(mvlm_ctx* ctx, float* ms2) {
     MVLM_ENTER(ctx);
     MVLM_REQUIRE(ctx, ms2, "points_stage_ms: null pointer");
-    MVLM_REQUIRE(ctx, ctx->points_events_valid && ctx->points_events.size() >= 3,
-                 "points_stage_ms: no point cloud was rendered with render profiling on");
-    MVLM_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 2; ++k) MVLM_CHECK_HIP(ctx, hipEventElapsedTime(&ms2[k], ctx->points_events[k], ctx->points_events[k + 1]));
-    return 0;
+    return ctx->points_clock.read(ctx, 2, ms2, "points_stage_ms: no point cloud was rendered with render profiling on");
 }
 
 // Buffers go back to the context's pool together with an event on the launch stream: whatever was enqueued for this
@@ -822,20 +806,12 @@ extern "C" int mvlm_render_ray_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const 
 extern "C" int mvlm_landmark_view_stage_ms(mvlm_ctx* ctx, float* ms7) {
     MVLM_ENTER(ctx);
     MVLM_REQUIRE(ctx, ms7, "landmark_view_stage_ms: null pointer");
-    MVLM_REQUIRE(ctx, ctx->view_events_valid && ctx->view_events.size() >= 8,
-                 "landmark_view_stage_ms: no landmark view was drawn with render profiling on");
-    MVLM_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 7; ++k) MVLM_CHECK_HIP(ctx, hipEventElapsedTime(&ms7[k], ctx->view_events[k], ctx->view_events[k + 1]));
-    return 0;
+    return ctx->view_clock.read(ctx, 7, ms7, "landmark_view_stage_ms: no landmark view was drawn with render profiling on");
 }
 
 // Likewise the last ray view's eight stages: the landmark view's first six, the ray projection, the tile kernel.
 extern "C" int mvlm_ray_view_stage_ms(mvlm_ctx* ctx, float* ms8) {
     MVLM_ENTER(ctx);
     MVLM_REQUIRE(ctx, ms8, "ray_view_stage_ms: null pointer");
-    MVLM_REQUIRE(ctx, ctx->ray_events_valid && ctx->view_events.size() >= 9,
-                 "ray_view_stage_ms: no ray view was drawn with render profiling on");
-    MVLM_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 8; ++k) MVLM_CHECK_HIP(ctx, hipEventElapsedTime(&ms8[k], ctx->view_events[k], ctx->view_events[k + 1]));
-    return 0;
+    return ctx->view_clock.read(ctx, 8, ms8, "ray_view_stage_ms: no ray view was drawn with render profiling on");
 }

@@ -280,33 +280,25 @@ extern "C" int mvlm_mesh_triangulate_points(mvlm_ctx* ctx, const mvlm_mesh* clou
     auto* sums = static_cast<int*>(ctx->get_scratch("cloudmesh.sums", size_t(n_blocks) * sizeof(int)));
     MVLM_REQUIRE(ctx, shifted && star && star_n && mask && counts && starts && sums, "triangulate points: scratch allocation failed");
     if (mvlm_mesh_wait_ready(ctx, cloud, ctx->stream)) return 1;
-    hipEvent_t* ev = nullptr;  // (profiling: events round the three stages, mvlm_cloud_mesh_stage_ms)
-    ctx->cloudmesh_events_valid = false;
-    if (ctx->render_profiling) {
-        ctx->cloudmesh_events.resize(4, nullptr);
-        for (hipEvent_t& e : ctx->cloudmesh_events)
-            if (!e) MVLM_CHECK_HIP(ctx, hipEventCreate(&e));
-        ev = ctx->cloudmesh_events.data();
-        MVLM_CHECK_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
-    }
+    StageClock& clock = ctx->cloudmesh_clock;  // (profiling: events round the three stages, mvlm_cloud_mesh_stage_ms)
+    clock.invalidate();
+    if (clock.arm(ctx, 4) || clock.record(ctx, 0, ctx->stream)) return 1;
     const dim3 per_point(unsigned((V + 255) / 256)), wg(256);
     hipLaunchKernelGGL(cloudmesh_perturb_kernel, per_point, wg, 0, ctx->stream, cloud->verts, V, neighbors_dev, shifted);
     hipLaunchKernelGGL(cloudmesh_star_kernel, dim3(unsigned((V + STAR_WG - 1) / STAR_WG)), dim3(STAR_WG), 0, ctx->stream, cloud->normals, V,
                        neighbors_dev, shifted, star, star_n);
-    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[1], ctx->stream));
+    if (clock.record(ctx, 1, ctx->stream)) return 1;
     if (n_ctr > size_t(V))  // the last scan block's counters past the points
         MVLM_CHECK_HIP(ctx, hipMemsetAsync(counts + V, 0, (n_ctr - size_t(V)) * sizeof(int), ctx->stream));
     hipLaunchKernelGGL(cloudmesh_count_kernel, per_point, wg, 0, ctx->stream, cloud->verts, V, star, star_n, mask, counts);
     hipLaunchKernelGGL(cloudmesh_scan_sums_kernel, dim3(n_blocks), wg, 0, ctx->stream, counts, sums);
     hipLaunchKernelGGL(cloudmesh_scan_top_kernel, dim3(1), wg, 0, ctx->stream, sums, n_blocks, n_tris_dev);
     hipLaunchKernelGGL(cloudmesh_scan_apply_kernel, dim3(n_blocks), wg, 0, ctx->stream, counts, sums, starts);
-    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[2], ctx->stream));
+    if (clock.record(ctx, 2, ctx->stream)) return 1;
     if (tris_dev && cap > 0)
         hipLaunchKernelGGL(cloudmesh_emit_kernel, per_point, wg, 0, ctx->stream, V, star, mask, starts, tris_dev, cap);
-    if (ev) {
-        MVLM_CHECK_HIP(ctx, hipEventRecord(ev[3], ctx->stream));
-        ctx->cloudmesh_events_valid = true;
-    }
+    if (clock.record(ctx, 3, ctx->stream)) return 1;
+    clock.mark(4);
     MVLM_CHECK_HIP(ctx, hipGetLastError());
     return 0;
 }
@@ -316,9 +308,5 @@ extern "C" int mvlm_mesh_triangulate_points(mvlm_ctx* ctx, const mvlm_mesh* clou
 extern "C" int mvlm_cloud_mesh_stage_ms(mvlm_ctx* ctx, float* ms3) {
     MVLM_ENTER(ctx);
     MVLM_REQUIRE(ctx, ms3, "cloud_mesh_stage_ms: null pointer");
-    MVLM_REQUIRE(ctx, ctx->cloudmesh_events_valid && ctx->cloudmesh_events.size() >= 4,
-                 "cloud_mesh_stage_ms: no cloud was triangulated with render profiling on");
-    MVLM_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 3; ++k) MVLM_CHECK_HIP(ctx, hipEventElapsedTime(&ms3[k], ctx->cloudmesh_events[k], ctx->cloudmesh_events[k + 1]));
-    return 0;
+    return ctx->cloudmesh_clock.read(ctx, 3, ms3, "cloud_mesh_stage_ms: no cloud was triangulated with render profiling on");
 }

@@ -420,15 +420,9 @@ extern "C" int mvlm_mesh_estimate_normals(mvlm_ctx* ctx, mvlm_mesh* mesh, int32_
     }
     float* const normals = mvlm_mesh_normals_buffer(ctx, mesh);
     MVLM_REQUIRE(ctx, normals, "mesh_estimate_normals: device allocation failed");
-    hipEvent_t* ev = nullptr;  // (profiling: events round the three stages, mvlm_normals_stage_ms)
-    ctx->normals_events_valid = false;
-    if (ctx->render_profiling) {
-        ctx->normals_events.resize(4, nullptr);
-        for (hipEvent_t& e : ctx->normals_events)
-            if (!e) MVLM_CHECK_HIP(ctx, hipEventCreate(&e));
-        ev = ctx->normals_events.data();
-        MVLM_CHECK_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
-    }
+    StageClock& clock = ctx->normals_clock;  // (profiling: events round the three stages, mvlm_normals_stage_ms)
+    clock.invalidate();
+    if (clock.arm(ctx, 4) || clock.record(ctx, 0, ctx->stream)) return 1;
     const dim3 per_point(unsigned((V + 255) / 256)), wg(256);
     int* const counts = ctr;
     int* const cursors = ctr + n_ctr;
@@ -442,17 +436,15 @@ extern "C" int mvlm_mesh_estimate_normals(mvlm_ctx* ctx, mvlm_mesh* mesh, int32_
     hipLaunchKernelGGL(normals_scan_top_kernel, dim3(1), wg, 0, ctx->stream, sums, n_blocks);
     hipLaunchKernelGGL(normals_scan_apply_kernel, dim3(n_blocks), wg, 0, ctx->stream, counts, sums, starts);
     hipLaunchKernelGGL(normals_scatter_kernel, per_point, wg, 0, ctx->stream, mesh->verts, V, cell_of, starts, cursors, sorted);
-    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[1], ctx->stream));
+    if (clock.record(ctx, 1, ctx->stream)) return 1;
     if (stats)
         hipLaunchKernelGGL(normals_search_kernel<true>, per_point, wg, 0, ctx->stream, sorted, starts, grid, nbr, stats);
     else
         hipLaunchKernelGGL(normals_search_kernel<false>, per_point, wg, 0, ctx->stream, sorted, starts, grid, nbr, stats);
-    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[2], ctx->stream));
+    if (clock.record(ctx, 2, ctx->stream)) return 1;
     hipLaunchKernelGGL(normals_solve_kernel, per_point, wg, 0, ctx->stream, mesh->verts, V, nbr, normals);
-    if (ev) {
-        MVLM_CHECK_HIP(ctx, hipEventRecord(ev[3], ctx->stream));
-        ctx->normals_events_valid = true;
-    }
+    if (clock.record(ctx, 3, ctx->stream)) return 1;
+    clock.mark(4);
     MVLM_CHECK_HIP(ctx, hipGetLastError());
     mesh->normals = normals;
     return 0;
@@ -486,9 +478,5 @@ extern "C" int mvlm_normals_get_stats(mvlm_ctx* ctx, unsigned long long* stats3)
 extern "C" int mvlm_normals_stage_ms(mvlm_ctx* ctx, float* ms3) {
     MVLM_ENTER(ctx);
     MVLM_REQUIRE(ctx, ms3, "normals_stage_ms: null pointer");
-    MVLM_REQUIRE(ctx, ctx->normals_events_valid && ctx->normals_events.size() >= 4,
-                 "normals_stage_ms: no normals were estimated with render profiling on");
-    MVLM_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 3; ++k) MVLM_CHECK_HIP(ctx, hipEventElapsedTime(&ms3[k], ctx->normals_events[k], ctx->normals_events[k + 1]));
-    return 0;
+    return ctx->normals_clock.read(ctx, 3, ms3, "normals_stage_ms: no normals were estimated with render profiling on");
 }

@@ -297,6 +297,34 @@ inline const void*& mvlm_thread_error_ctx() {
     return c;
 }
 
+struct mvlm_ctx;
+
+// The HIP events round one feature's stages while mvlm_render_set_profiling is on, and how many of them the last call that ran
+// through recorded (0: none).  Host only; a plain member of mvlm_ctx per feature, freed with the context by its destructor
+// (mvlm_ctx_destroy has made the device current by then).  A launch function invalidates, arms, records between its stages and
+// marks at its end; the feature's mvlm_*_stage_ms entry point reads.  (The bodies follow mvlm_ctx::fail below.)
+struct StageClock {
+    StageClock() = default;
+    StageClock(const StageClock&) = delete;
+    StageClock& operator=(const StageClock&) = delete;
+    ~StageClock() {
+        for (hipEvent_t e : events) hipEventDestroy(e);
+    }
+    void invalidate() { recorded = 0; }  // nothing recorded from here on
+    // Profiling off: off, and record() enqueues nothing until the next arm().  On: n events exist (those it has are kept).
+    int arm(mvlm_ctx* ctx, int n);
+    int record(mvlm_ctx* ctx, int k, hipStream_t stream);              // event k behind what the stream holds; a no-op when off
+    hipEvent_t event(int k) const { return armed ? events[k] : nullptr; }  // for a launcher that records it itself; null when off
+    void mark(int n) { recorded = armed ? n : 0; }                     // the end of a call that ran through
+    // the m stage times between the m + 1 events of the last call; refuses with `none` unless that call marked m + 1; waits for the stream
+    int read(mvlm_ctx* ctx, int m, float* ms, const char* none);
+
+private:
+    std::vector<hipEvent_t> events;
+    int recorded = 0;
+    bool armed = false;
+};
+
 struct mvlm_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -359,35 +387,20 @@ struct mvlm_ctx {
     int render_shading = 0;  // 0: unlit nearest-texel RGB (reference), 1: build-defined geometry shading
     int* render_overflow_host = nullptr;  // pinned; written asynchronously by mvlm_render
     bool points_counting = false;  // mvlm_points_set_counting: a cloud's splat kernel also counts covered pixels and atomics
-    // under render profiling, round the two kernels of a cloud's render: before the splats, between, behind the tile stage
-    std::vector<hipEvent_t> points_events;
-    bool points_events_valid = false;
-    // likewise round the three stages of a cloud's normal estimate (cloud_normals.hip: grid build, search, solve; mvlm_normals_stage_ms)
-    std::vector<hipEvent_t> normals_events;
-    bool normals_events_valid = false;
-    // likewise round the three stages of a cloud's triangulation (cloud_mesh.hip: star, count + scan, emit; mvlm_cloud_mesh_stage_ms)
-    std::vector<hipEvent_t> cloudmesh_events;
-    bool cloudmesh_events_valid = false;
     bool render_profiling = false;        // mvlm_render_set_profiling: HIP events around each render's kernels
     std::vector<RenderProfileRec> render_prof;
     std::vector<hipEvent_t> render_events;
     size_t render_event_cursor = 0;
-    // landmark view (raster_view.hip): the eight events around its seven stages (copies and fills first) while render_profiling is on, and whether the
-    // last view recorded them (mvlm_landmark_view_stage_ms)
-    std::vector<hipEvent_t> view_events;
-    bool view_events_valid = false;
-    bool ray_events_valid = false;  // likewise the last ray view (raster_rays.hip: nine events, mvlm_ray_view_stage_ms)
-    // PNG encoder (png_encode.hip): the five events around its four stages while render_profiling is on (mvlm_png_stage_ms)
-    std::vector<hipEvent_t> png_events;
-    bool png_events_valid = false;
-    // heat sheet (heat_sheet.hip): the four events around background, peak and compose while render_profiling is on
-    // (mvlm_heat_sheet_stage_ms)
-    std::vector<hipEvent_t> heat_events;
-    bool heat_events_valid = false;
-    // surface heat (surface_backproject.hip): the four events around peak, score and paint while render_profiling is on
-    // (mvlm_surface_heat_stage_ms)
-    std::vector<hipEvent_t> backproject_events;
-    bool backproject_events_valid = false;
+    // under render profiling, one clock per feature (a new feature: a member here, its calls in the launch function, one read)
+    StageClock points_clock;     // a cloud's render (raster.hip): splat, tile; mvlm_points_stage_ms
+    StageClock normals_clock;    // a cloud's normal estimate (cloud_normals.hip): grid build, search, solve; mvlm_normals_stage_ms
+    StageClock cloudmesh_clock;  // a cloud's triangulation (cloud_mesh.hip): star, count + scan, emit; mvlm_cloud_mesh_stage_ms
+    // the landmark view (raster_view.hip: seven stages, copies and fills first, eight events; mvlm_landmark_view_stage_ms) and the
+    // ray view (raster_rays.hip: eight stages, nine events; mvlm_ray_view_stage_ms) share one: each reader refuses after the other's call
+    StageClock view_clock;
+    StageClock png_clock;          // the PNG encoder (png_encode.hip): its four stages; mvlm_png_stage_ms
+    StageClock heat_clock;         // the heat sheet (heat_sheet.hip): background, peak, compose; mvlm_heat_sheet_stage_ms
+    StageClock backproject_clock;  // the surface heat (surface_backproject.hip): peak, score, paint; mvlm_surface_heat_stage_ms
     // device buffers of freed meshes, reused by the next upload: a folder of scans would otherwise pay
     // four hipMalloc + four (device-synchronising) hipFree per scan
     struct PoolEntry {
@@ -436,6 +449,28 @@ inline int mvlm_ctx::fail(const std::string& m) {
     mvlm_thread_error() = m;
     mvlm_thread_error_ctx() = this;
     return 1;
+}
+
+inline int StageClock::arm(mvlm_ctx* ctx, int n) {
+    armed = false;
+    if (!ctx->render_profiling) return 0;
+    while (int(events.size()) < n) {
+        hipEvent_t e = nullptr;
+        MVLM_CHECK_HIP(ctx, hipEventCreate(&e));
+        events.push_back(e);
+    }
+    armed = true;
+    return 0;
+}
+inline int StageClock::record(mvlm_ctx* ctx, int k, hipStream_t stream) {
+    if (armed) MVLM_CHECK_HIP(ctx, hipEventRecord(events[k], stream));
+    return 0;
+}
+inline int StageClock::read(mvlm_ctx* ctx, int m, float* ms, const char* none) {
+    if (recorded != m + 1) return ctx->fail(none);
+    MVLM_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < m; ++k) MVLM_CHECK_HIP(ctx, hipEventElapsedTime(&ms[k], events[k], events[k + 1]));
+    return 0;
 }
 
 // End of every entry point (declared by MVLM_ENTER, destroyed before the context's mutex is released): once a context has

@@ -97,19 +97,6 @@ __global__ __launch_bounds__(256) void heat_compose_kernel(const float* __restri
         for (int dx = 0; dx < scale; ++dx) out[(py + dy) * size_t(width) + px + dx] = rgba;
 }
 
-// the four events of a profiled call, or nullptr with profiling off
-int heat_events(mvlm_ctx* ctx, hipEvent_t** ev) {
-    *ev = nullptr;
-    if (!ctx->render_profiling) return 0;
-    while (ctx->heat_events.size() < 4) {
-        hipEvent_t e = nullptr;
-        MVLM_CHECK_HIP(ctx, hipEventCreate(&e));
-        ctx->heat_events.push_back(e);
-    }
-    *ev = ctx->heat_events.data();
-    return 0;
-}
-
 }  // namespace
 
 // The peak kernel's launch on the context's stream, for an entry point that holds the context and has checked its arguments (this
@@ -136,7 +123,7 @@ extern "C" int mvlm_render_heat_sheet(mvlm_ctx* ctx, const float* images_dev, co
                                       double floor_, double opacity, uint8_t* out_dev) {
     if (!ctx) return 1;
     MVLM_ENTER(ctx);
-    ctx->heat_events_valid = false;
+    ctx->heat_clock.invalidate();
     MVLM_REQUIRE(ctx, images_dev && heat_dev && out_dev, "heat sheet: null pointer");
     MVLM_REQUIRE(ctx, reinterpret_cast<uintptr_t>(heat_dev) % 16 == 0, "heat sheet: the heatmaps must be 16-byte aligned");
     int cols = 0, rows = 0, width = 0, height = 0;
@@ -162,24 +149,24 @@ extern "C" int mvlm_render_heat_sheet(mvlm_ctx* ctx, const float* images_dev, co
         lm_rgb = static_cast<uint8_t*>(ctx->get_scratch("heat.lm_rgb", size_t(n_lm) * 3));
         MVLM_REQUIRE(ctx, lm_rgb, "heat sheet: scratch allocation failed");
     }
-    hipEvent_t* ev = nullptr;
-    if (heat_events(ctx, &ev)) return 1;
+    StageClock& clock = ctx->heat_clock;
+    if (clock.arm(ctx, 4)) return 1;
     hipStream_t st = ctx->stream;
-    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[0], st));
+    if (clock.record(ctx, 0, st)) return 1;
     // the views alone: the view sheet's own code (the marker radius is not read without maxima)
     if (mvlm_view_sheet_draw(ctx, images_dev, n_views, nullptr, 0, nullptr, nullptr, nullptr, nullptr, background, cols_in, scale, gap,
                              VS_RADIUS_MIN, out_dev))
         return 1;
     if (sel) MVLM_CHECK_HIP(ctx, hipMemcpyAsync(sel, sel_host, size_t(n_lm), hipMemcpyHostToDevice, st));
     if (lm_rgb) MVLM_CHECK_HIP(ctx, hipMemcpyAsync(lm_rgb, lm_rgb_host, size_t(n_lm) * 3, hipMemcpyHostToDevice, st));
-    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[1], st));
+    if (clock.record(ctx, 1, st)) return 1;
     mvlm_heat_launch_peaks(ctx, heat_dev, int(n_planes), peaks);
-    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[2], st));
+    if (clock.record(ctx, 2, st)) return 1;
     hipLaunchKernelGGL(heat_compose_kernel, dim3(RM_SIZE, unsigned(n_views)), dim3(256), 0, st, heat_dev, peaks, sel, lm_rgb, n_lm, cols,
                        scale, gap, width, floor_, opacity, reinterpret_cast<uint32_t*>(out_dev));
-    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[3], st));
+    if (clock.record(ctx, 3, st)) return 1;
     MVLM_CHECK_HIP(ctx, hipGetLastError());
-    ctx->heat_events_valid = ev != nullptr;
+    clock.mark(4);
     return 0;
 }
 
@@ -188,9 +175,5 @@ extern "C" int mvlm_heat_sheet_stage_ms(mvlm_ctx* ctx, float* ms3) {
     if (!ctx) return 1;
     MVLM_ENTER(ctx);
     MVLM_REQUIRE(ctx, ms3, "heat_sheet_stage_ms: null pointer");
-    MVLM_REQUIRE(ctx, ctx->heat_events_valid && ctx->heat_events.size() >= 4,
-                 "heat_sheet_stage_ms: no heat sheet was drawn with render profiling on");
-    MVLM_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 3; ++k) MVLM_CHECK_HIP(ctx, hipEventElapsedTime(&ms3[k], ctx->heat_events[k], ctx->heat_events[k + 1]));
-    return 0;
+    return ctx->heat_clock.read(ctx, 3, ms3, "heat_sheet_stage_ms: no heat sheet was drawn with render profiling on");
 }

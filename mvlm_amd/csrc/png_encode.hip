@@ -527,7 +527,7 @@ extern "C" int mvlm_png_encode(mvlm_ctx* ctx, const uint8_t* rgba_dev, int n_ima
                                uint8_t* png_host, size_t stride_bytes, size_t* png_bytes_out) {
     if (!ctx) return 1;
     MVLM_ENTER(ctx);
-    ctx->png_events_valid = false;
+    ctx->png_clock.invalidate();
     MVLM_REQUIRE(ctx, rgba_dev && png_host && png_bytes_out, "png: null pointer");
     MVLM_REQUIRE(ctx, n_images >= 1 && n_images <= 128, "png: n_images must be 1..128 (" + std::to_string(n_images) + " given)");
     MVLM_REQUIRE(ctx, filter_mode >= -1 && filter_mode <= 4, "png: filter_mode must be -1..4 (" + std::to_string(filter_mode) + " given)");
@@ -553,29 +553,22 @@ extern "C" int mvlm_png_encode(mvlm_ctx* ctx, const uint8_t* rgba_dev, int n_ima
     uint32_t* const seg_adler = meta + 2 * n_slots;
     uint32_t* const totals = meta + 4 * n_slots;
 
-    hipEvent_t* ev = nullptr;
-    if (ctx->render_profiling) {
-        while (ctx->png_events.size() < 5) {
-            hipEvent_t e = nullptr;
-            MVLM_CHECK_HIP(ctx, hipEventCreate(&e));
-            ctx->png_events.push_back(e);
-        }
-        ev = ctx->png_events.data();
-    }
+    StageClock& clock = ctx->png_clock;
+    if (clock.arm(ctx, 5)) return 1;
     hipStream_t st = ctx->stream;
-    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[0], st));
+    if (clock.record(ctx, 0, st)) return 1;
     hipLaunchKernelGGL(png_filter_kernel, dim3(unsigned(size_t(n_images) * height)), dim3(WG), 0, st,
                        reinterpret_cast<const uchar4*>(rgba_dev), height, width, filter_mode, stream);
-    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[1], st));
+    if (clock.record(ctx, 1, st)) return 1;
     MVLM_CHECK_HIP(ctx, hipMemsetAsync(slots, 0, n_slots * SLOT, st));  // (the deflate kernel ORs its bits in)
     hipLaunchKernelGGL(png_deflate_kernel, dim3(unsigned(n_slots)), dim3(WG), 0, st, stream, lay.stream_bytes, lay.n_segments,
                        int(lay.last_bytes), slots, seg_size, seg_adler);
-    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[2], st));
+    if (clock.record(ctx, 2, st)) return 1;
     hipLaunchKernelGGL(png_offsets_kernel, dim3(unsigned((n_images + WG - 1) / WG)), dim3(WG), 0, st, seg_size, n_images, lay.n_segments,
                        seg_off, totals);
     hipLaunchKernelGGL(png_gather_kernel, dim3(unsigned(n_slots)), dim3(WG), 0, st, slots, seg_size, seg_off, lay.n_segments,
                        payload_stride, payload);
-    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[3], st));
+    if (clock.record(ctx, 3, st)) return 1;
     MVLM_CHECK_HIP(ctx, hipGetLastError());
 
     std::vector<uint32_t> host_meta(meta_words);
@@ -587,14 +580,14 @@ extern "C" int mvlm_png_encode(mvlm_ctx* ctx, const uint8_t* rgba_dev, int n_ima
         MVLM_CHECK_HIP(ctx, hipMemcpyAsync(png_host + size_t(i) * stride_bytes + mvlm_png::HEAD_BYTES, payload + size_t(i) * payload_stride,
                                            h_totals[i], hipMemcpyDeviceToHost, st));
     }
-    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[4], st));
+    if (clock.record(ctx, 4, st)) return 1;
     MVLM_CHECK_HIP(ctx, hipStreamSynchronize(st));
     for (int i = 0; i < n_images; ++i) {
         const uint32_t adler = mvlm_png_adler_combine(lay, host_meta.data() + 2 * n_slots + 2 * size_t(i) * lay.n_segments);
         if (mvlm_png_finish(png_host + size_t(i) * stride_bytes, stride_bytes, lay, h_totals[i], adler, &png_bytes_out[i], why))
             return ctx->fail(why);
     }
-    ctx->png_events_valid = ev != nullptr;
+    clock.mark(5);
     return 0;
 }
 
@@ -602,9 +595,5 @@ extern "C" int mvlm_png_stage_ms(mvlm_ctx* ctx, float* ms4) {
     if (!ctx) return 1;
     MVLM_ENTER(ctx);
     MVLM_REQUIRE(ctx, ms4, "png_stage_ms: null pointer");
-    MVLM_REQUIRE(ctx, ctx->png_events_valid && ctx->png_events.size() >= 5,
-                 "png_stage_ms: no picture was encoded with render profiling on");
-    MVLM_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 4; ++k) MVLM_CHECK_HIP(ctx, hipEventElapsedTime(&ms4[k], ctx->png_events[k], ctx->png_events[k + 1]));
-    return 0;
+    return ctx->png_clock.read(ctx, 4, ms4, "png_stage_ms: no picture was encoded with render profiling on");
 }

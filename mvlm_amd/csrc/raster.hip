@@ -247,29 +247,21 @@ extern "C" int mvlm_render(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* r
         MVLM_CHECK_HIP(ctx, hipEventRecord(e0, ctx->stream));
     }
     if (cloud) {
-        hipEvent_t* pev = nullptr;  // (profiling: events of the cloud's own round its two kernels, mvlm_points_stage_ms)
-        ctx->points_events_valid = false;
-        if (ctx->render_profiling) {
-            ctx->points_events.resize(3, nullptr);
-            for (hipEvent_t& e : ctx->points_events)
-                if (!e) MVLM_CHECK_HIP(ctx, hipEventCreate(&e));
-            pev = ctx->points_events.data();
-            MVLM_CHECK_HIP(ctx, hipEventRecord(pev[0], ctx->stream));
-        }
+        StageClock& clock = ctx->points_clock;  // (profiling: events of the cloud's own round its two kernels, mvlm_points_stage_ms)
+        clock.invalidate();
+        if (clock.arm(ctx, 3) || clock.record(ctx, 0, ctx->stream)) return 1;
         // per-point colours shade the RGB planes (white without them); a texture or uvs on a faceless mesh are ignored
         if (ctx->render_shading == 1) {  // the same splats, then the tile stage that shades with the normals (cloud_normals.hip)
             raster_points_splat_launch(ctx->stream, mesh->verts, V, rot, n_views, ctx->render_subpixel_bits, mesh->point_R, mesh->point_c,
                                        keys, point_stats);
-            if (pev) (void)hipEventRecord(pev[1], ctx->stream);
+            if (clock.record(ctx, 1, ctx->stream)) return 1;
             cloud_normals_tile_launch(ctx->stream, mesh->normals, rot, n_views, keys, overflow_host, out_dev);
         } else {
             raster_points_launch(ctx->stream, mesh->verts, mesh->colors, V, rot, n_views, ctx->render_subpixel_bits, mesh->point_R,
-                                 mesh->point_c, keys, point_stats, overflow_host, out_dev, pev ? pev[1] : nullptr);
+                                 mesh->point_c, keys, point_stats, overflow_host, out_dev, clock.event(1));
         }
-        if (pev) {
-            MVLM_CHECK_HIP(ctx, hipEventRecord(pev[2], ctx->stream));
-            ctx->points_events_valid = true;
-        }
+        if (clock.record(ctx, 2, ctx->stream)) return 1;
+        clock.mark(3);
     } else {
         hipLaunchKernelGGL(transform_kernel, dim3(view_chunk_grid((V + 255) / 256, n_views)), dim3(256), 0, ctx->stream,
                            mesh->verts, V, rot, n_views, ctx->render_subpixel_bits, tv);

@@ -167,15 +167,15 @@ int mvlm_launch_ray_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot
         hipLaunchKernelGGL(rays_project_kernel, dim3(unsigned((total + 255) / 256)), dim3(256), 0, st, starts_dev, ends_dev, ray_rgb,
                            n_rays, s.rot, s.frames, n_views, size, ray_radius, rays);
     }
-    if (s.ev) MVLM_CHECK_HIP(ctx, hipEventRecord(s.ev[7], st));
+    if (ctx->view_clock.record(ctx, 7, st)) return 1;
     const int tiles_x = size / RM_TILE, tiles = tiles_x * tiles_x;
     hipLaunchKernelGGL(rays_tile_kernel, dim3(view_chunk_grid(tiles, n_views)), dim3(256), 0, st, s.tv, mesh->tris, mesh->uvs, mesh->tex,
                        mesh->tex_w, mesh->tex_h, reinterpret_cast<const uchar4*>(s.vcol), mesh->n_verts, s.bins.counts, s.bins.offsets, s.bins.bins,
                        s.bins.cap, s.keys, s.frames, ctx->render_shading, n_views, size, s.spheres, n_lm, lm_pixels_dev, rays, n_rays,
                        n_rays > 0 ? ray_pixels_dev : nullptr, s.bins.overflow, ctx->render_overflow_host,
                        reinterpret_cast<uint32_t*>(out_dev));
-    if (s.ev) MVLM_CHECK_HIP(ctx, hipEventRecord(s.ev[8], st));
+    if (ctx->view_clock.record(ctx, 8, st)) return 1;
     MVLM_CHECK_HIP(ctx, hipGetLastError());
-    ctx->ray_events_valid = s.ev != nullptr;
+    ctx->view_clock.mark(9);
     return 0;
 }

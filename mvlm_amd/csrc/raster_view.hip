@@ -203,17 +203,11 @@ int mvlm_view_launch_stages(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* 
     }
     hipStream_t st = ctx->stream;
     // mvlm_render_set_profiling: events between the stages, the first in front of the copies and fills (mvlm_landmark_view_stage_ms,
-    // mvlm_ray_view_stage_ms)
-    hipEvent_t* ev = nullptr;
-    if (ctx->render_profiling) {
-        if (ctx->view_events.size() < 9) ctx->view_events.resize(9, nullptr);
-        for (hipEvent_t& e : ctx->view_events)
-            if (!e) MVLM_CHECK_HIP(ctx, hipEventCreate(&e));
-        ev = ctx->view_events.data();
-    }
-    ctx->view_events_valid = false;
-    ctx->ray_events_valid = false;
-    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[0], st));
+    // mvlm_ray_view_stage_ms); the caller records the rest on the same clock and marks it
+    StageClock& clock = ctx->view_clock;
+    if (clock.arm(ctx, 9)) return 1;
+    clock.invalidate();
+    if (clock.record(ctx, 0, st)) return 1;
     MVLM_CHECK_HIP(ctx, hipMemcpyAsync(rot, rot_host, size_t(n_views) * 9 * sizeof(double), hipMemcpyHostToDevice, st));
     MVLM_CHECK_HIP(ctx, hipMemcpyAsync(frames, frames_host, size_t(n_views) * sizeof(view_frame), hipMemcpyHostToDevice, st));
     if (n_lm > 0) {
@@ -224,29 +218,28 @@ int mvlm_view_launch_stages(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* 
     MVLM_CHECK_HIP(ctx, hipMemsetAsync(b.counts, 0, b.ctr_ints * sizeof(int), st));
     MVLM_CHECK_HIP(ctx, hipMemsetAsync(keys, 0xFF, key_bytes, st));  // RM_KEY_EMPTY everywhere, in every call
     MVLM_REQUIRE(ctx, render_overflow_word(ctx), std::string(what) + ": pinned allocation failed");
-    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[1], st));
+    if (clock.record(ctx, 1, st)) return 1;
     hipLaunchKernelGGL(view_transform_kernel, dim3(view_chunk_grid((V + 255) / 256, n_views)), dim3(256), 0, st, mesh->verts, V, rot,
                        frames, n_views, ctx->render_subpixel_bits, tv);
-    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[2], st));
+    if (clock.record(ctx, 2, st)) return 1;
     hipLaunchKernelGGL(view_classify_kernel, dim3(view_chunk_grid((T + 255) / 256, n_views)), dim3(256), 0, st, tv, mesh->tris, V, T,
                        n_views, size, keys, b.counts, b.n_big, b.big_list);
-    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[3], st));
+    if (clock.record(ctx, 3, st)) return 1;
     hipLaunchKernelGGL(view_scan_kernel, dim3(n_views), dim3(256), 0, st, b.counts, b.offsets, tiles, b.cap, b.overflow);
-    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[4], st));
+    if (clock.record(ctx, 4, st)) return 1;
     hipLaunchKernelGGL(view_bin_fill_kernel, dim3(view_chunk_grid(FILL_WGS, n_views)), dim3(256), 0, st, tv, mesh->tris, V, T, n_views,
                        size, b.n_big, b.big_list, b.offsets, b.cursors, b.bins, b.cap, b.overflow);
-    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[5], st));
+    if (clock.record(ctx, 5, st)) return 1;
     if (n_lm > 0)
         hipLaunchKernelGGL(view_project_kernel, dim3((n_views * n_lm + 255) / 256), dim3(256), 0, st, lm, lm_rgb, n_lm, rot, frames,
                            n_views, size, radius, spheres);
-    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[6], st));
+    if (clock.record(ctx, 6, st)) return 1;
     out->tv = tv;
     out->frames = frames;
     out->rot = rot;
     out->keys = keys;
     out->spheres = spheres;
     out->vcol = ctx->render_shading == 0 && mesh->colors && !(mesh->tex && mesh->uvs) ? mesh->colors : nullptr;
-    out->ev = ev;
     return 0;
 }
 
@@ -267,8 +260,8 @@ int mvlm_launch_landmark_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double
                        reinterpret_cast<const uchar4*>(given ? vert_rgba_dev : s.vcol), mesh->n_verts, s.bins.counts,
                        s.bins.offsets, s.bins.bins, s.bins.cap, s.keys, s.frames, given ? 0 : ctx->render_shading, n_views, size, s.spheres, n_lm,
                        lm_pixels_dev, s.bins.overflow, ctx->render_overflow_host, reinterpret_cast<uint32_t*>(out_dev));
-    if (s.ev) MVLM_CHECK_HIP(ctx, hipEventRecord(s.ev[7], ctx->stream));
+    if (ctx->view_clock.record(ctx, 7, ctx->stream)) return 1;
     MVLM_CHECK_HIP(ctx, hipGetLastError());
-    ctx->view_events_valid = s.ev != nullptr;
+    ctx->view_clock.mark(8);
     return 0;
 }

@@ -160,10 +160,10 @@ struct mvlm_view_stages {
     const unsigned long long* keys;
     const rv_sphere* spheres;  // null when n_lm == 0
     const uint8_t* vcol;       // the per-vertex colours the tile stage shades with, or null
-    hipEvent_t* ev;            // null unless render profiling is on: [0..6] recorded, the caller records the rest
 };
 // raster_view.hip: scratch, copies, fills and the kernels of the mesh stages (transform, classify, scan, bin fill) and of the
 // landmark projection, for a launch set that holds the context and has checked its arguments; `what` starts its error messages.
+// Under render profiling it arms ctx->view_clock and records its events 0..6; the caller records the rest and marks the clock.
 int mvlm_view_launch_stages(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot_host, int n_views, int size,
                             const float* frames_host, const double* landmarks_host, int n_lm, float radius,
                             const uint8_t* lm_rgb_host, int32_t* lm_pixels_dev, const char* what, mvlm_view_stages* out);

@@ -159,7 +159,7 @@ extern "C" int mvlm_surface_heat(mvlm_ctx* ctx, const mvlm_mesh* mesh, const dou
                                  int32_t* n_vis_dev, int32_t* peak_vertex_dev, float* peak_score_dev) {
     if (!ctx) return 1;
     MVLM_ENTER(ctx);
-    ctx->backproject_events_valid = false;
+    ctx->backproject_clock.invalidate();
     MVLM_REQUIRE(ctx, mesh && rot_dev && images_dev && heat_dev && vert_rgba_dev && peak_vertex_dev && peak_score_dev,
                  "surface heat: null pointer");
     MVLM_REQUIRE(ctx, mesh->n_verts > 0, "surface heat: empty mesh");
@@ -196,34 +196,29 @@ extern "C" int mvlm_surface_heat(mvlm_ctx* ctx, const mvlm_mesh* mesh, const dou
         lm_rgb = static_cast<uint8_t*>(ctx->get_scratch("backproject.lm_rgb", size_t(n_lm) * 3));
         MVLM_REQUIRE(ctx, lm_rgb, "surface heat: scratch allocation failed");
     }
-    hipEvent_t* ev = nullptr;
-    if (ctx->render_profiling) {
-        if (ctx->backproject_events.size() < 4) ctx->backproject_events.resize(4, nullptr);
-        for (hipEvent_t& e : ctx->backproject_events)
-            if (!e) MVLM_CHECK_HIP(ctx, hipEventCreate(&e));
-        ev = ctx->backproject_events.data();
-    }
+    StageClock& clock = ctx->backproject_clock;
+    if (clock.arm(ctx, 4)) return 1;
     if (mvlm_mesh_wait_ready(ctx, mesh, ctx->stream)) return 1;  // the upload runs on a stream of its own
     hipStream_t st = ctx->stream;
     if (sel) MVLM_CHECK_HIP(ctx, hipMemcpyAsync(sel, sel_host, size_t(n_lm), hipMemcpyHostToDevice, st));
     if (lm_rgb) MVLM_CHECK_HIP(ctx, hipMemcpyAsync(lm_rgb, lm_rgb_host, size_t(n_lm) * 3, hipMemcpyHostToDevice, st));
     MVLM_CHECK_HIP(ctx, hipMemsetAsync(keys, 0, size_t(n_lm) * sizeof(unsigned long long), st));  // SB_KEY_NONE
-    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[0], st));
+    if (clock.record(ctx, 0, st)) return 1;
     mvlm_heat_launch_peaks(ctx, heat_dev, int(n_planes), peaks);
-    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[1], st));
+    if (clock.record(ctx, 1, st)) return 1;
     hipLaunchKernelGGL(backproject_score_kernel, dim3(unsigned((V + 255) / 256), unsigned((n_lm + BP_LM - 1) / BP_LM)), dim3(256), 0, st,
                        mesh->verts, V, rot_dev, images_dev, heat_dev, peaks, n_views, n_lm, ctx->render_subpixel_bits, depth_tol, score,
                        n_vis_dev);
-    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[2], st));
+    if (clock.record(ctx, 2, st)) return 1;
     const bool textured = mesh->tex && mesh->uvs;
     hipLaunchKernelGGL(backproject_paint_kernel, dim3(unsigned((V + 255) / 256)), dim3(256), 0, st, score, V, n_lm, sel, lm_rgb,
                        reinterpret_cast<const uchar4*>(mesh->colors), textured ? mesh->uvs : nullptr, textured ? mesh->tex : nullptr,
                        mesh->tex_w, mesh->tex_h, floor_, opacity, reinterpret_cast<uint32_t*>(vert_rgba_dev), keys);
     hipLaunchKernelGGL(backproject_peaks_kernel, dim3(unsigned((n_lm + 255) / 256)), dim3(256), 0, st, keys, n_lm, peak_vertex_dev,
                        peak_score_dev);
-    if (ev) MVLM_CHECK_HIP(ctx, hipEventRecord(ev[3], st));
+    if (clock.record(ctx, 3, st)) return 1;
     MVLM_CHECK_HIP(ctx, hipGetLastError());
-    ctx->backproject_events_valid = ev != nullptr;
+    clock.mark(4);
     return 0;
 }
 
@@ -250,10 +245,5 @@ extern "C" int mvlm_surface_heat_stage_ms(mvlm_ctx* ctx, float* ms3) {
     if (!ctx) return 1;
     MVLM_ENTER(ctx);
     MVLM_REQUIRE(ctx, ms3, "surface_heat_stage_ms: null pointer");
-    MVLM_REQUIRE(ctx, ctx->backproject_events_valid && ctx->backproject_events.size() >= 4,
-                 "surface_heat_stage_ms: no surface heat was computed with render profiling on");
-    MVLM_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 3; ++k)
-        MVLM_CHECK_HIP(ctx, hipEventElapsedTime(&ms3[k], ctx->backproject_events[k], ctx->backproject_events[k + 1]));
-    return 0;
+    return ctx->backproject_clock.read(ctx, 3, ms3, "surface_heat_stage_ms: no surface heat was computed with render profiling on");
 }

@@ -760,11 +760,15 @@ class HipRenderer3D:
         self.check()
         return image
 
+    def _stage_ms(self, entry: str, n: int) -> np.ndarray:
+        """The ``n`` stage times, float32 milliseconds, that the library's reader ``entry`` gives for its feature's last call."""
+        ms = np.zeros(n, np.float32)
+        self.ctx.check(getattr(self.ctx.lib, entry)(self.ctx.handle, _lib.as_ptr(ms, C.c_float)))
+        return ms
+
     def heat_sheet_stage_ms(self) -> np.ndarray:
         """Milliseconds of the last heat sheet's stages under render profiling: background, peak, compose."""
-        ms = np.zeros(3, np.float32)
-        self.ctx.check(self.ctx.lib.mvlm_heat_sheet_stage_ms(self.ctx.handle, _lib.as_ptr(ms, C.c_float)))
-        return ms
+        return self._stage_ms("mvlm_heat_sheet_stage_ms", 3)
 
     # ---- surface heat (all views' heatmaps laid on the scan) ---------------------------------------------------
     def surface_heat(self, mesh: Mesh, images, heat, rot, landmarks=None, colors=None, floor: float = 0.25, opacity: float = 0.75,
@@ -876,9 +880,7 @@ class HipRenderer3D:
 
     def surface_heat_stage_ms(self) -> np.ndarray:
         """Milliseconds of the last surface heat's stages under render profiling: peak, back-projection, paint."""
-        ms = np.zeros(3, np.float32)
-        self.ctx.check(self.ctx.lib.mvlm_surface_heat_stage_ms(self.ctx.handle, _lib.as_ptr(ms, C.c_float)))
-        return ms
+        return self._stage_ms("mvlm_surface_heat_stage_ms", 3)
 
     def release_surface_heat(self) -> None:
         """Free the scratch ``surface_heat`` keeps in the context (its score table above all: 4 bytes per vertex and landmark);
@@ -929,9 +931,7 @@ class HipRenderer3D:
 
     def png_stage_ms(self) -> np.ndarray:
         """Milliseconds of the last ``encode_png``'s stages under render profiling: filter, deflate, gather, copy to host."""
-        ms = np.zeros(4, dtype=np.float32)
-        self.ctx.check(self.ctx.lib.mvlm_png_stage_ms(self.ctx.handle, _lib.as_ptr(ms, C.c_float)))
-        return ms
+        return self._stage_ms("mvlm_png_stage_ms", 4)
 
     # ---- normals of a point cloud ---------------------------------------------------------------
     def estimate_point_normals(self, mesh: Mesh, return_neighbors: bool = False):
@@ -957,9 +957,7 @@ class HipRenderer3D:
 
     def normals_stage_ms(self) -> np.ndarray:
         """Milliseconds of the last normal estimate's stages under render profiling: grid build, search, solve."""
-        ms = np.zeros(3, np.float32)
-        self.ctx.check(self.ctx.lib.mvlm_normals_stage_ms(self.ctx.handle, _lib.as_ptr(ms, C.c_float)))
-        return ms
+        return self._stage_ms("mvlm_normals_stage_ms", 3)
 
     # ---- a triangle surface for a point cloud ---------------------------------------------------
     def triangulate_point_cloud(self, mesh: Mesh) -> Mesh:
@@ -1021,9 +1019,7 @@ class HipRenderer3D:
 
     def cloud_mesh_stage_ms(self) -> np.ndarray:
         """Milliseconds of the last triangulation's stages under render profiling: star (with the shift), count + scan, emit."""
-        ms = np.zeros(3, np.float32)
-        self.ctx.check(self.ctx.lib.mvlm_cloud_mesh_stage_ms(self.ctx.handle, _lib.as_ptr(ms, C.c_float)))
-        return ms
+        return self._stage_ms("mvlm_cloud_mesh_stage_ms", 3)
 
     def rotations_device(self):
         """The last render's rotation table where the rasteriser keeps it on the device (f64[N,9]; valid until this context's

@@ -41,6 +41,7 @@ hipError_t hipGetLastError() { return hipSuccess; }
 hipError_t hipMalloc(void**, size_t) { return hipErrorOutOfMemory; }
 hipError_t hipMemset(void*, int, size_t) { return hipSuccess; }
 hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
+hipError_t hipEventDestroy(hipEvent_t) { return hipSuccess; }  // (mvlm_ctx's stage clocks: none has an event here)
 hipError_t hipGraphExecDestroy(hipGraphExec_t) { return hipSuccess; }
 
 namespace {
