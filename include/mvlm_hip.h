@@ -424,6 +424,47 @@ int mvlm_surface_heat_release(mvlm_ctx* ctx);
 /* Bytes of the context's grow-only internal scratch whose names start with `prefix` ("backproject": the surface heat's; "": all). */
 int mvlm_scratch_bytes(mvlm_ctx* ctx, const char* prefix, size_t* bytes);
 
+/* ---- surface distances between landmarks (csrc/geodesic_math.h, DESIGN.md 5.1 "Surface distances") ---- */
+/* The distance along the scan's triangles - the "tape-measure" distance - between landmarks, beside the straight one.  One distance
+ * field per source landmark: the first-order fast-marching update (Hopf-Lax over a triangle's edge, Kimmel-Sethian / Bornemann-Rasch),
+ * swept Jacobi-fashion until a sweep changes nothing.  It is NOT an exact polyhedral geodesic: it overestimates by a few per cent
+ * (DESIGN.md 5.1 has the measured figures).  csrc/geodesic_math.h states the rule and every operation's order; all of it is
+ * float64 on the mesh's float32 vertices, and no value depends on scheduling or on the order of a vertex's triangle list.
+ *   pts_dev      f64[n,3]           the landmarks; each is attached as mvlm_surface_attach attaches it
+ *   init_rings   0..8               the source triangle's corners are widened by this many rings of triangles, each vertex of the
+ *                                   set starting at its straight distance from the snapped point (2 is the Python default)
+ *   max_sweeps   1..1048576, 0 = 4096: a source that has not settled by then is an error that names it; the outputs are then
+ *                                   filled with NaN / -1, never with a partial result
+ *   max_scratch_bytes  0 = 512 MiB: the sources are processed in groups whose two field buffers (16 bytes per vertex and source,
+ *                                   plus the context scratch's headroom: a quarter and 256 bytes) stay under it; a cap that cannot
+ *                                   hold one source is an error
+ *   pairs_host   i32[n_pairs,2] or NULL: with pairs only the landmarks named in one get a field, and only D[i,j] and D[j,i] of
+ *                                   every pair (i, j) are computed; the other entries of D are NaN
+ *   snapped_dev  f64[n,3], tri_dev i32[n]   the attachment (tri -1: no finite distance to any triangle)
+ *   D_dev        f64[n,n]           D[i,j]: from source i to target j, read over the three edges of j's triangle; the straight
+ *                                   distance where both lie in one triangle; 0 on the diagonal; +inf in another connected
+ *                                   component; NaN in the row and column of a landmark that is not attached (tri -1, a triangle
+ *                                   with a non-finite vertex, a non-finite point).  Directed: D[i,j] and D[j,i] differ by
+ *                                   discretisation; the reported distance is their mean, their difference says how far to trust it
+ *   E_dev        f64[n,n]           |P_i - P_j| of the snapped points, always all of it
+ *   sweeps_dev   i32[n]             per source the index of the first sweep that changed nothing; -1 without a field
+ *   field_dev    f64[n,n_verts] or NULL   the fields themselves; a row of NaN for a landmark without one
+ * The adjacency (vertex -> incident triangles), the field buffers and the small tables live in the context's grow-only scratch
+ * under "geodesic." (mvlm_scratch_bytes); mvlm_geodesic_release frees them.  n 1..65536.  A point cloud ("point cloud" is in the
+ * message), a NULL or misaligned pointer, a value out of range or a pair index outside 0..n-1 set an error that starts with
+ * "geodesics:" and launch nothing.  The sweep boundary is a kernel boundary: no workgroup ever waits for another.
+ * WAITS FOR THE STREAM: the work is enqueued on the launch stream, but after every batch of 32 sweeps the host reads the
+ * per-source settled flags, so the call returns only when the distances are final. */
+int mvlm_landmark_geodesics(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* pts_dev, int n, int init_rings, int max_sweeps,
+                            long long max_scratch_bytes, const int32_t* pairs_host, int n_pairs, double* snapped_dev,
+                            int32_t* tri_dev, double* D_dev, double* E_dev, int32_t* sweeps_dev, double* field_dev);
+/* With mvlm_render_set_profiling on, the last call's stages in milliseconds (HIP events), f32[4]: adjacency (with the attachment
+ * and the straight distances), init, sweeps (with the host's reads), targets - the last three added up over the call's source
+ * groups.  Waits for the stream. */
+int mvlm_geodesic_stage_ms(mvlm_ctx* ctx, float* ms4);
+/* Frees the "geodesic." scratch.  Waits for the stream; the next mvlm_landmark_geodesics allocates again. */
+int mvlm_geodesic_release(mvlm_ctx* ctx);
+
 /* ---- PNG on the device (the views' files without the picture crossing to the host) ---- */
 /* Bytes that hold any file mvlm_png_encode writes for a picture of height x width (each 1..4096): the filtered stream
  * height * (1 + 3 * width), 10 bytes per 32 768-byte segment of it (5 of a stored block's header, 5 of the flush), and 63 of

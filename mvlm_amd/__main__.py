@@ -3,7 +3,8 @@
 Same behaviour as the reference's ``main.py`` (:9-67): collect ``*.obj`` files, run every
 available pipeline over them and write ``<stem>_<pipeline>.txt`` (comma-separated [NL,3]
 landmarks, ``np.savetxt(..., delimiter=",")``, main.py:62; with ``--report`` also ``<stem>_<pipeline>_report.csv``, the
-per-landmark quality report of mvlm_amd/utils/report.py).  Only the pipelines whose 2-D
+per-landmark quality report of mvlm_amd/utils/report.py; with ``--distances`` also ``<stem>_<pipeline>_distances.csv``, the
+straight and surface distances between the landmarks, mvlm_amd/utils/distances.py).  Only the pipelines whose 2-D
 predictor this build ships are looped ("bu3dfe", "dtu3d").  ``--visualize-img`` (main.py:66-67) writes
 ``visualization/<stem>_<pipeline>.png`` under the working directory: the scan with a sphere at every landmark, drawn on the GPU
 (mvlm_amd/utils/viewer.py); the interactive viewer flag of the reference (``--visualize-iter``) needs VTK and is not available.
@@ -26,6 +27,16 @@ def shard_files(files, rank: int, world: int):
 def _index_list(text: str) -> list:
     """"3,17,40" -> [3, 17, 40] (argparse reports what is no such list)."""
     return [int(k) for k in text.split(",")]
+
+
+def _pairs(text: str):
+    """"0-16,8-27" -> [(0, 16), (8, 27)] (argparse reports what is no such list)."""
+    from .utils.distances import parse_pairs
+
+    try:
+        return parse_pairs(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -109,6 +120,14 @@ def build_parser() -> argparse.ArgumentParser:
                              "--visualize-surface, --multisamples 4); 'mesh' has the GPU give it triangles first - a local Delaunay "
                              "surface over each point's 16 nearest neighbours, for scanner-like sampling - and then treats it as any "
                              "mesh; --point-radius and --point-normals are then not consulted (DESIGN.md 5.1)")
+    parser.add_argument("--distances", action="store_true",
+                        help="write <stem>_<pipeline>_distances.csv beside every landmark file: one row per pair of landmarks i < j with "
+                             "the straight distance and the distance along the scan's surface (geodesic: the mean of the two directions "
+                             "geodesic_ij and geodesic_ji, whose difference says how far to trust it), in the scan's own units; inf: the "
+                             "landmarks lie on separate pieces of the scan.  The surface distance is a first-order fast-marching "
+                             "estimate, a few per cent above the true one (DESIGN.md 5.1); a point cloud needs --point-surface mesh")
+    parser.add_argument("--distance-pairs", type=_pairs, default=None, metavar="I-J,I-J",
+                        help="with --distances: only these pairs of landmark indices, e.g. 0-16,8-27 (default: every pair)")
     parser.add_argument("--png-encoder", choices=("host", "device"), default="host",
                         help="who makes the PNG files of --visualize-img and --visualize-rays: 'host' copies the picture to the host "
                              "and encodes it with Pillow; 'device' filters and compresses it on the GPU and copies only the file's "
@@ -117,7 +136,8 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def main(argv=None) -> int:
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
     if args.out is None:
         args.out = args.path
     input_path, path_to_out = Path(args.path), Path(args.out)
@@ -173,6 +193,11 @@ def main(argv=None) -> int:
         extra["surface_depth_tol"] = args.surface_depth_tol
         extra["heat_landmarks"] = args.heat_landmarks
         extra["heat_floor"] = args.heat_floor
+    if args.distance_pairs is not None and not args.distances:
+        parser.error("--distance-pairs needs --distances")
+    if args.distances:
+        extra["landmark_distances"] = True
+        extra["distance_pairs"] = args.distance_pairs
     if args.point_radius is not None:
         extra["point_radius"] = args.point_radius
     if args.point_normals != "file":
@@ -207,6 +232,8 @@ def main(argv=None) -> int:
             np.savetxt((path_to_out / f"{file.stem}_{pname}.txt").as_posix(), landmarks, delimiter=",")
             if args.report:
                 dm.last_report.to_csv(path_to_out / f"{file.stem}_{pname}_report.csv")
+            if args.distances:
+                dm.last_distances.to_csv(path_to_out / f"{file.stem}_{pname}_distances.csv")
             if args.surface_mesh:
                 dm.write_surface_mesh(path_to_out / f"{file.stem}_{pname}_surface.obj")
     return 0

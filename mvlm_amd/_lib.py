@@ -89,6 +89,10 @@ SIGNATURES = {
     "mvlm_render_landmark_view_colored": (C.c_int, [C.c_void_p, C.c_void_p, c_double_p, C.c_int, C.c_int, c_float_p, c_double_p, C.c_int,
                                                     C.c_float, c_uint8_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mvlm_scratch_bytes": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_size_t)]),
+    "mvlm_landmark_geodesics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_longlong, c_int32_p, C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mvlm_geodesic_stage_ms": (C.c_int, [C.c_void_p, c_float_p]),
+    "mvlm_geodesic_release": (C.c_int, [C.c_void_p]),
     "mvlm_png_bound": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "mvlm_png_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                   C.POINTER(C.c_size_t)]),

@@ -401,6 +401,10 @@ struct mvlm_ctx {
     StageClock png_clock;          // the PNG encoder (png_encode.hip): its four stages; mvlm_png_stage_ms
     StageClock heat_clock;         // the heat sheet (heat_sheet.hip): background, peak, compose; mvlm_heat_sheet_stage_ms
     StageClock backproject_clock;  // the surface heat (surface_backproject.hip): peak, score, paint; mvlm_surface_heat_stage_ms
+    // the surface distances (geodesic.hip): attachment + adjacency first, then init, sweeps and targets of each of the last call's
+    // geodesic_groups source groups (2 + 3 groups events); mvlm_geodesic_stage_ms adds the groups up
+    StageClock geodesic_clock;
+    int geodesic_groups = 0;
     // device buffers of freed meshes, reused by the next upload: a folder of scans would otherwise pay
     // four hipMalloc + four (device-synchronising) hipFree per scan
     struct PoolEntry {
@@ -569,6 +573,10 @@ int mvlm_launch_ray_view(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* rot
 // for an entry point that holds the context; its final kernel follows (mvlm_project_to_surface, mvlm_surface_attach)
 int mvlm_project_partials(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* pts_dev, int n_points, int* n_chunks_out,
                           const double** part_d_out, const int** part_t_out);
+
+// surface_attach.hip: mvlm_surface_attach behind its MVLM_ENTER, for an entry point that holds the context (geodesic.hip)
+int mvlm_launch_surface_attach(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* pts_dev, int n_points, double* snapped_dev,
+                               int32_t* tri_dev, double* bary_dev, double* uv_dev);
 
 // surface_points.hip: the snap of a point mesh (n_tris == 0) - the nearest point - for mvlm_project_to_surface, which holds the context
 int mvlm_points_nearest(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* pts_dev, int n_points, double* out_dev);

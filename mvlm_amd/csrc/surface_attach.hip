@@ -106,9 +106,8 @@ __global__ __launch_bounds__(64) void attach_final_kernel(const float* __restric
 
 }  // namespace
 
-extern "C" int mvlm_surface_attach(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* pts_dev, int n_points,
-                                   double* snapped_dev, int32_t* tri_dev, double* bary_dev, double* uv_dev) {
-    MVLM_ENTER(ctx);
+int mvlm_launch_surface_attach(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* pts_dev, int n_points, double* snapped_dev,
+                               int32_t* tri_dev, double* bary_dev, double* uv_dev) {
     MVLM_REQUIRE(ctx, mesh && pts_dev && snapped_dev && tri_dev && bary_dev && uv_dev && n_points > 0,
                  "surface_attach: bad arguments");
     MVLM_REQUIRE(ctx, mesh->n_tris > 0, "surface_attach: the surface attachment of a point cloud is not supported (the mesh has no triangles)");
@@ -120,4 +119,10 @@ extern "C" int mvlm_surface_attach(mvlm_ctx* ctx, const mvlm_mesh* mesh, const d
                        pts_dev, n_chunks, part_d, part_t, snapped_dev, tri_dev, bary_dev, uv_dev);
     MVLM_CHECK_HIP(ctx, hipGetLastError());
     return 0;
+}
+
+extern "C" int mvlm_surface_attach(mvlm_ctx* ctx, const mvlm_mesh* mesh, const double* pts_dev, int n_points,
+                                   double* snapped_dev, int32_t* tri_dev, double* bary_dev, double* uv_dev) {
+    MVLM_ENTER(ctx);
+    return mvlm_launch_surface_attach(ctx, mesh, pts_dev, n_points, snapped_dev, tri_dev, bary_dev, uv_dev);
 }

@@ -93,6 +93,8 @@ class Pipeline(abc.ABC):
     visualize_heat = visualize_surface = _keep_ray_view = False
     heat_landmarks = None
     point_surface = "splats"
+    landmark_distances = False
+    distance_pairs = None
 
     def __init__(self, render_image_stack: bool = False, offscreen: bool = True, n_views: int = 8,
                  render_image_folder: Path | None = None, visualize_rays: bool = False,
@@ -103,8 +105,21 @@ class Pipeline(abc.ABC):
                  view_png_encoder: str = "host", point_radius: float | None = None, visualize_sheet: bool = False,
                  sheet_scale: int = 1, visualize_heat: bool = False, heat_landmarks=None, heat_floor: float = 0.25,
                  point_normals: str = "file", visualize_surface: bool = False, surface_depth_tol: int = 2,
-                 point_surface: str = "splats"):
+                 point_surface: str = "splats", landmark_distances: bool = False, distance_pairs=None):
+        from ..utils.distances import check_pairs
         from ..utils.render3d import check_point_surface
+
+        # landmark_distances: every prediction leaves a LandmarkDistances (mvlm_amd/utils/distances.py) in ``last_distances``: the
+        # straight distance and the distance along the scan's triangles between the landmarks - all pairs, or ``distance_pairs``,
+        # a sequence of (i, j).  Measured where the mesh is resident, in the space it was uploaded in, and divided by a pre-align
+        # block's scale: the numbers are in the scan's own units.  Off (the default): nothing of it is launched, allocated or copied.
+        if not isinstance(landmark_distances, (bool, np.bool_)):
+            raise ValueError(f"landmark_distances must be True or False, not {landmark_distances!r}")
+        self.landmark_distances = bool(landmark_distances)
+        self.distance_pairs = check_pairs(distance_pairs)
+        if self.distance_pairs is not None and not self.landmark_distances:
+            raise ValueError("distance_pairs needs landmark_distances=True")
+        self.last_distances = None
 
         # point_surface: what a scan without faces - a point cloud - is to every entry that takes scans: "splats" (the default) - it
         # is rendered as splats, snapped to its nearest point, and what needs triangles is refused (_check_cloud); "mesh" - it is
@@ -210,6 +225,9 @@ class Pipeline(abc.ABC):
         name = getattr(mesh, "path", None) or "the mesh"
         if self.landmark_report:
             raise ValueError(f"{name} is a point cloud: landmark_report is not supported (the surface attachment needs triangles)")
+        if getattr(self, "landmark_distances", False):
+            raise ValueError(f"{name} is a point cloud: landmark_distances is not supported (a surface distance needs triangles; "
+                             'point_surface="mesh" / --point-surface mesh gives the cloud some)')
         if self.visualize_img:
             raise ValueError(f"{name} is a point cloud: visualize_img is not supported (the landmark view draws triangles)")
         if self.visualize_rays_img:
@@ -235,6 +253,25 @@ class Pipeline(abc.ABC):
         if not callable(make):
             raise ValueError('point_surface="mesh" needs a renderer that triangulates a point cloud (HipRenderer3D.triangulate_point_cloud)')
         return make(mesh)
+
+    def _check_distances(self) -> None:
+        """``landmark_distances`` needs the renderer that holds the mesh on the device: said before anything is launched."""
+        if self.landmark_distances and not isinstance(self.renderer_3d, HipRenderer3D):
+            raise ValueError("landmark_distances needs a renderer that measures them (HipRenderer3D.landmark_geodesics), not "
+                             f"{type(self.renderer_3d).__name__}")
+        if self.landmark_distances and self.distance_pairs is not None and self.predictor_2d is not None:
+            from ..utils.distances import check_pairs
+
+            check_pairs(self.distance_pairs, int(self.predictor_2d.get_lm_count()))
+
+    def _measure_distances(self, mesh, landmarks):
+        """``landmark_distances``: the distances between ``landmarks`` (in the space of ``mesh``, as the snap left them) on ``mesh``,
+        in the scan's own units, into ``last_distances``."""
+        found = self.renderer_3d.landmark_geodesics(mesh, np.asarray(landmarks, dtype=np.float64), pairs=self.distance_pairs)
+        block = self.pre_align
+        scale = float(block.get("scale", 1)) if block and getattr(mesh, "to_original", None) is not None else 1.0
+        self.last_distances = found.scaled(scale) if scale != 1.0 else found
+        return self.last_distances
 
     def _to_original(self, mesh, landmarks):
         """Landmarks found on a pre-aligned mesh -> the file's own coordinates (utils3d.py:505-527)."""
@@ -390,6 +427,7 @@ class Pipeline(abc.ABC):
         import torch
 
         r3, p2, e3 = self.renderer_3d, self.predictor_2d, self.estimator_3d
+        self._check_distances()
         mesh = self._surface(mesh)
         self._check_cloud(mesh)
         drawing = pictures.wanted(self)  # (the one question the hot path asks about the pictures)
@@ -540,6 +578,9 @@ class Pipeline(abc.ABC):
                     return p2.repeat_without_fp16(lambda: self.predict_mesh_device(mesh, transform_stack))
             self._say("Landmarks [Error]: ", f"{error:08.6f}", " mm")
             self.last_error = error
+            if self.landmark_distances and (not sharded or rank == 0):  # (sharded: every rank holds the landmarks, one measures)
+                with tm.stage("distances"):
+                    self._measure_distances(mesh, landmarks)
             if drawing:
                 if kept_views is not None and sheet_images is not None:  # the views a detector's ``valid`` mask left
                     sheet_images = sheet_images.index_select(0, torch.from_numpy(np.asarray(kept_views)).to(sheet_images.device))
@@ -571,6 +612,8 @@ class Pipeline(abc.ABC):
             return False
         if self.landmark_report:
             return False  # one report per scan, made by the scan's own pass
+        if self.landmark_distances:
+            return False  # likewise the distances: measured while the scan's mesh is resident
         if self.visualize_img or self.visualize_rays_img or self.visualize_sheet or self.visualize_heat or self.visualize_surface:
             return False  # one picture per scan, drawn by the scan's own pass while its mesh (its views) are resident
         n = int(self.renderer_3d.n_views)
@@ -788,6 +831,7 @@ class Pipeline(abc.ABC):
     # ---- the reference's numpy slot protocol (general_pipeline.py:83-108) ----------------
     def _predict_slots(self, file_name: Path):
         tm = self._timer
+        self._check_distances()
         with tm.stage("render"):
             if isinstance(self.renderer_3d, HipRenderer3D):
                 image_stack, transform_stack, pd = self.renderer_3d.multiview_render(file_name, load_texture=self._texture_needed())
@@ -825,6 +869,9 @@ class Pipeline(abc.ABC):
         self.last_error = error
         self._dump_pre_aligned(pd, file_name)
         drawn = landmarks  # (the picture: in the space the mesh was rendered in)
+        if self.landmark_distances:
+            with tm.stage("distances"):
+                self._measure_distances(pd, drawn)
         # a mesh handle that went through the config's pre-align block carries its matrix: results go back to
         # the file's coordinates (the rays kept for visualisation stay in the aligned space, with the mesh handle)
         landmarks = self._to_original(pd, landmarks)

@@ -893,6 +893,66 @@ class HipRenderer3D:
         self.ctx.check(self.ctx.lib.mvlm_scratch_bytes(self.ctx.handle, prefix.encode(), C.byref(n)))
         return int(n.value)
 
+    # ---- surface distances between landmarks ----------------------------------------------------
+    def landmark_geodesics(self, mesh: Mesh, points, *, init_rings: int = 2, pairs=None, return_fields: bool = False,
+                           max_sweeps: int = 4096, max_scratch_bytes: int = 0):
+        """The distances between landmarks, straight and along the scan's triangles (mvlm_landmark_geodesics; DESIGN.md 5.1,
+        "Surface distances").  ``points`` float64 [n,3], host or device, in the space of ``mesh``; each is attached to the surface as
+        the landmark report attaches it.  ``pairs``: None for every pair, else a sequence of (i, j) - only the landmarks named get a
+        distance field and only those entries are computed.  ``init_rings`` 0..8: rings of triangles round the source triangle that
+        start at their straight distance.  Returns a ``LandmarkDistances`` (utils/distances.py); with ``return_fields`` its
+        ``fields`` is the float64 [n,V] device tensor of the distance fields.  The surface distance is the first-order fast-marching
+        discretisation, an overestimate of a few per cent, not an exact geodesic.  Waits for the stream.  ValueError for a point
+        cloud, bad values, or a source that does not settle within ``max_sweeps`` sweeps."""
+        import torch
+
+        from .distances import LandmarkDistances, check_pairs
+
+        label = "landmark_geodesics"
+        if not isinstance(mesh, Mesh):
+            raise ValueError(f"{label}: mesh must be a Mesh, not {type(mesh).__name__}")
+        if mesh.n_tris == 0:
+            raise ValueError(f"{label}: a point cloud is not supported here (the mesh has no triangles; triangulate_point_cloud gives it some)")
+        for name, value, lo, hi in (("init_rings", init_rings, 0, 8), ("max_sweeps", max_sweeps, 1, 1 << 20),
+                                    ("max_scratch_bytes", max_scratch_bytes, 0, 1 << 62)):
+            if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or not lo <= value <= hi:
+                raise ValueError(f"{label}: {name} must be an integer in {lo}..{hi}, not {value!r}")
+        dev = torch.device("cuda", self.ctx.device)
+        if hasattr(points, "data_ptr"):
+            pts = points.detach().to(device=dev, dtype=torch.float64).contiguous()
+        else:
+            try:
+                pts = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float64)).to(dev)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"{label}: points is not a numeric array ({e})") from None
+        if pts.dim() != 2 or pts.shape[1] != 3 or not 1 <= pts.shape[0] <= 65536:
+            raise ValueError(f"{label}: points must be float64 [n,3] with n in 1..65536, not {tuple(pts.shape)}")
+        n, nv = int(pts.shape[0]), int(mesh.n_verts)
+        pairs = check_pairs(pairs, n, f"{label}: pairs")
+        snapped = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        tri = torch.empty((n,), dtype=torch.int32, device=dev)
+        directed = torch.empty((n, n), dtype=torch.float64, device=dev)
+        euclid = torch.empty((n, n), dtype=torch.float64, device=dev)
+        sweeps = torch.empty((n,), dtype=torch.int32, device=dev)
+        fields = torch.empty((n, nv), dtype=torch.float64, device=dev) if return_fields else None
+        self.ctx.bind_current_stream(torch, dev)
+        handle = upload_mesh(self.ctx, mesh)
+        self.ctx.check(self.ctx.lib.mvlm_landmark_geodesics(
+            self.ctx.handle, handle, C.c_void_p(pts.data_ptr()), n, int(init_rings), int(max_sweeps), C.c_longlong(int(max_scratch_bytes)),
+            _lib.as_ptr(pairs, C.c_int32) if pairs is not None else None, 0 if pairs is None else int(pairs.shape[0]),
+            C.c_void_p(snapped.data_ptr()), C.c_void_p(tri.data_ptr()), C.c_void_p(directed.data_ptr()), C.c_void_p(euclid.data_ptr()),
+            C.c_void_p(sweeps.data_ptr()), C.c_void_p(fields.data_ptr()) if return_fields else None), ValueError)
+        return LandmarkDistances(snapped.cpu().numpy(), tri.cpu().numpy(), euclid.cpu().numpy(), directed.cpu().numpy(),
+                                 sweeps.cpu().numpy(), pairs, fields)
+
+    def geodesic_stage_ms(self) -> np.ndarray:
+        """Milliseconds of the last ``landmark_geodesics``'s stages under render profiling: adjacency, init, sweeps, targets."""
+        return self._stage_ms("mvlm_geodesic_stage_ms", 4)
+
+    def release_geodesics(self) -> None:
+        """Free the scratch ``landmark_geodesics`` keeps in the context (adjacency, field buffers); waits for the stream."""
+        self.ctx.check(self.ctx.lib.mvlm_geodesic_release(self.ctx.handle))
+
     # ---- PNG on the device -------------------------------------------------------------------
     @staticmethod
     def png_bound(height: int, width: int) -> int:

@@ -10,7 +10,7 @@
                                          kernel_occupancy_png.json, kernel_occupancy_points.json,
                                          kernel_occupancy_sheet.json, kernel_occupancy_heat.json,
                                          kernel_occupancy_normals.json, kernel_occupancy_backproject.json,
-                                         kernel_occupancy_cloudmesh.json) from the build
+                                         kernel_occupancy_cloudmesh.json, kernel_occupancy_geodesic.json) from the build
 
 A convolution tile's rate depends on how many workgroups a CU holds, i.e. on which side of 168 / 128 / 102 ... registers the
 compiler lands - and every epilogue kind compiled into a tile moves that number (round 4: two new kinds took the 80-row tile
@@ -34,7 +34,9 @@ kernels of the heat sheet (build/heat/, tests/golden/kernel_occupancy_heat.json,
 cloud's normals - the estimate and the tile stage that shades with them - (build/normals/,
 tests/golden/kernel_occupancy_normals.json, tests/test_normals_occupancy.py) and the three kernels of the surface heat
 (build/backproject/, tests/golden/kernel_occupancy_backproject.json, tests/test_backproject_occupancy.py) and the kernels of a
-cloud's triangulation (build/cloudmesh/, tests/golden/kernel_occupancy_cloudmesh.json, tests/test_cloudmesh_occupancy.py)."""
+cloud's triangulation (build/cloudmesh/, tests/golden/kernel_occupancy_cloudmesh.json, tests/test_cloudmesh_occupancy.py) and the
+kernels of the surface distances between landmarks (build/geodesic/, tests/golden/kernel_occupancy_geodesic.json,
+tests/test_geodesic_occupancy.py)."""
 import json
 import re
 import subprocess
@@ -60,6 +62,7 @@ HEAT_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_heat.json"
 NORMALS_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_normals.json"
 BACKPROJECT_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_backproject.json"
 CLOUDMESH_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_cloudmesh.json"
+GEODESIC_TABLE = REPO / "tests" / "golden" / "kernel_occupancy_geodesic.json"
 BUILD = REPO / "mvlm_amd" / "csrc" / "build"
 
 
@@ -109,10 +112,10 @@ if __name__ == "__main__":
                                 (VIEW_TABLE, BUILD / "view"), (RAYS_TABLE, BUILD / "rays"), (PNG_TABLE, BUILD / "png"),
                                 (POINTS_TABLE, BUILD / "points"), (SHEET_TABLE, BUILD / "sheet"), (HEAT_TABLE, BUILD / "heat"),
                                 (NORMALS_TABLE, BUILD / "normals"), (BACKPROJECT_TABLE, BUILD / "backproject"),
-                                (CLOUDMESH_TABLE, BUILD / "cloudmesh")):
+                                (CLOUDMESH_TABLE, BUILD / "cloudmesh"), (GEODESIC_TABLE, BUILD / "geodesic")):
         t = build_table(objdir)
         if "--write" in sys.argv:
-            fields = ("waves_per_simd", "spilled", "scratch") if table_path in (VIEW_TABLE, RAYS_TABLE, PNG_TABLE, POINTS_TABLE, SHEET_TABLE, HEAT_TABLE, NORMALS_TABLE, BACKPROJECT_TABLE, CLOUDMESH_TABLE) else ("waves_per_simd", "spilled")
+            fields = ("waves_per_simd", "spilled", "scratch") if table_path in (VIEW_TABLE, RAYS_TABLE, PNG_TABLE, POINTS_TABLE, SHEET_TABLE, HEAT_TABLE, NORMALS_TABLE, BACKPROJECT_TABLE, CLOUDMESH_TABLE, GEODESIC_TABLE) else ("waves_per_simd", "spilled")
             table_path.write_text(json.dumps({k: {f: v[f] for f in fields} for k, v in t.items()}, indent=1) + "\n")
             print(f"{len(t)} kernels -> {table_path}")
         else:
